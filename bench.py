@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark of the biHomE training hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one full training iteration of BASELINE.json configs[1]: s-coco Zeng backbone + biHomE head,
 batch 64 per GPU, 128x128 grayscale synthetic COCO-style pairs, fp32: model.train(), zero_grad, forward,
 backward, (N>1: RCCL all-reduce SUM of the flat gradient), Adam step, MultiStepLR step
-(train.py:296-387).  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line with
-the whole-job image-pairs/s, the roofline of the dominant kernel (per-launch HIP-event timing inside this
-process) and, at N=1, the CPU baseline (the oracle = PyTorch-CPU restatement, timed on the host cores).
+(train.py:296-387).  Inputs are resident in HBM before the timed region.  The timed region starts from the seeded
+initial weights with a fresh optimizer state, and the last timed step starts from them again (seeded_state), so that
+what that step computes depends on the arguments alone.  Rank 0 prints ONE JSON line with the whole-job
+image-pairs/s and ms_per_step.  A plain run does nothing else: set-up, W warm-up steps, K timed steps, the outputs
+of the last timed step (--dump-outputs), the line.  --full adds the secondary legs after the timed steps: the eval
+leg, the roofline of the dominant kernel (per-launch HIP-event timing inside this process) with the measured peaks,
+the exact-arithmetic (f32x3) step time, at N>1 the exchange diagnostics and, at N=1, the CPU baseline (the oracle =
+PyTorch-CPU restatement, timed on the host cores).
 """
 import argparse
 import json
@@ -86,7 +91,58 @@ def parse():
                     help="capture the whole training step in a HIP graph (bihome_amd.graph.GraphedStep) and time replays")
     ap.add_argument("--hook", action="append", default=[], metavar="A,B",
                     help="tuning experiments: call bh_debug_force_tile(A, B) before the run (see csrc/conv_gemm.hip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary legs: eval, roofline + measured peaks (--no-roofline), the f32x3 "
+                         "step time (--no-alt), the CPU baseline (--no-cpu-baseline) and, at N>1, the exchange diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0): loss, delta_gt, delta_hat, and a fixed "
+                         "seeded sample of the updated parameters and of the floating-point buffers (BatchNorm running statistics)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def seeded_state(model, opt):
+    """Returns restore(): puts the weights and the BatchNorm running statistics back to what they are now (the seeded initial state) and
+    the optimizer to a fresh state (Adam moments and step count zero, as before its first step).  A step taken from there computes (on
+    the resident batch, with the DSAC indices of the seeded generator) a function of the arguments alone, up to rounding.  Chained steps do
+    not: the fp32 atomics sum in a different order from run to run, and training amplifies those last-bit differences to percents of the
+    loss within a few steps.  main() restores before the timed steps and before the last of them, whose outputs --dump-outputs writes;
+    a restore before every step would add its copy of the weights and moments (~0.07 ms, 0.6 % of a step) to each."""
+    params = list(model.parameters())
+    bufs = [b for b in model.buffers() if b.is_floating_point()]
+    saved = [t.detach().clone() for t in params + bufs]
+
+    def restore():
+        with torch.no_grad():
+            torch._foreach_copy_([p.data for p in params] + bufs, saved)
+            state = [v for st in opt.state.values() for v in st.values() if torch.is_tensor(v)]
+            if state:
+                torch._foreach_zero_(state)
+    return restore
+
+
+DUMP_SAMPLE = 1 << 22          # elements kept of a larger parameter / buffer vector (16 MB each as float32)
+
+
+def dump_outputs(outdir, model, loss, delta_gt, delta_hat):
+    """The arrays a caller of the timed step receives - its return values and the model state it updated - as float32 .npy files.
+    Parameters and buffers are concatenated in name order; above DUMP_SAMPLE elements, a fixed sample (seed 0, sorted indices) is kept."""
+    os.makedirs(outdir, exist_ok=True)
+
+    def flat(named):
+        ts = [t.detach().reshape(-1).float() for _, t in sorted(named, key=lambda kv: kv[0]) if t.is_floating_point()]
+        v = torch.cat(ts) if ts else torch.zeros(0, device=loss.device)
+        if v.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            v = v[idx.to(v.device)]
+        return v
+
+    arrays = {"loss": loss, "delta_gt": delta_gt, "delta_hat": delta_hat,
+              "params_sample": flat(model.named_parameters()), "buffers_sample": flat(model.named_buffers())}
+    for name, t in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def cpu_baseline(cfg, seed=42, batch=8, steps=20, warmup=1):
@@ -496,6 +552,7 @@ def main():
     use_graph = args.graph and world == 1 and not args.gpu_datagen
     opt, sched = build_optimizer(model, cfg["SOLVER"], capturable=use_graph)
     reducer = attach_reducer(model) if world > 1 else None
+    restore = seeded_state(model, opt)
 
     B = args.batch or cfg["DATA"]["BATCH_SIZE"]
     # each rank owns its contiguous shard of the global batch; synthetic data generated on the host
@@ -541,6 +598,7 @@ def main():
         torch.cuda.set_stream(_main)
     for _ in range(args.warmup):
         loss, dgt, dh = one_step()
+    restore()                                         # (outside the timed region: its first launches load their kernels)
     sync()
     # (one event per step on the launch stream: no host synchronisation inside the timed region; the gaps between consecutive
     #  events are the per-step times the percentiles below come from)
@@ -548,6 +606,8 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
+        if i == args.steps - 1:
+            restore()                                 # the step whose outputs --dump-outputs writes: from the seeded state
         loss, dgt, dh = one_step()
         marks[i + 1].record()
     sync()
@@ -560,6 +620,8 @@ def main():
         dt = t.item()
     ms = 1e3 * dt / args.steps
     value = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, dgt, dh)
     if args.host_profile and rank == 0:
         # host side of the step (tools/: where does Python spend the launch time?): enqueue time per step against the device time, then cProfile
         import cProfile, pstats
@@ -579,14 +641,19 @@ def main():
     final_loss, final_mace = float(loss.item()), mace(dgt, dh)
 
     # inference leg (eval.py:80-112): eval-mode forward + DLT on fresh batches, BatchNorms folded into the convs
-    from bihome_amd.step import evaluate
-    ev = [{k: torch.tensor(v).cuda() for k, v in synth.make_pairs(B, patch=P, rho=D["RHO"], seed=1000 + rank + 7 * i,
-                                                                   channels=CH, target=CH == 1).items() if k in KEYS}
-          for i in range(2)]
-    eval_mace, eval_ms = evaluate(model, [ev[i % 2] for i in range(6)])
+    eval_info = None
+    if args.full:
+        from bihome_amd.step import evaluate
+        ev = [{k: torch.tensor(v).cuda() for k, v in synth.make_pairs(B, patch=P, rho=D["RHO"], seed=1000 + rank + 7 * i,
+                                                                       channels=CH, target=CH == 1).items() if k in KEYS}
+              for i in range(2)]
+        eval_mace, eval_ms = evaluate(model, [ev[i % 2] for i in range(6)])
+        eval_info = {"mace": eval_mace, "ms_per_batch": eval_ms, "pairs_per_s_per_gpu": 1e3 * B / eval_ms,
+                     "note": "predict_homography in eval mode (BatchNorm folded), held-out synthetic pairs, random-init "
+                             "weights after the timed steps"}
 
     roof, rows = (None, None)
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roof, rows = roofline_leg(model, data, opt, sched, reducer)
         if dist is not None:
             dist.barrier()                 # the probe below (2 GiB, synchronising) runs on rank 0 only: keep the ranks together around it
@@ -602,7 +669,7 @@ def main():
         if dist is not None:
             dist.barrier()
     dist_info = None
-    if dist is not None:
+    if args.full and dist is not None:
         # The N-GPU line proves itself (round-4 VERDICT item 8): backend and RCCL version, ranks counted by an all-reduce, the buckets, the
         # exchange alone (event-timed around the bucket sequence: launch -> Work.wait() puts the RCCL stream's completion on the timed
         # stream) and the SAME ranks stepping WITHOUT the exchange in the same run - what each replica costs alone, warm, on this node.
@@ -651,9 +718,9 @@ def main():
                                                 "ms/step with it; weak scaling, so value = n_gpus x pairs per GPU / ms"}
     # The headline's 'f32' is the fp16-piece arithmetic (22-bit operands, fp32 accumulate): the SAME run also times the exact form - three
     # bf16 pieces per operand, six products, bit-exact operand cut ('f32x3', the default of rounds 2-3) - on a second model of the same
-    # config, so that the line always carries the exact-arithmetic number next to the headline (round-4 VERDICT item 7).
+    # config, so that the --full line carries the exact-arithmetic number next to the headline (round-4 VERDICT item 7).
     alt = None
-    if rank == 0 and world == 1 and args.precision in ("f32", "f16x2") and not args.no_alt and not use_graph:
+    if args.full and rank == 0 and world == 1 and args.precision in ("f32", "f16x2") and not args.no_alt and not use_graph:
         import copy
         cfg2 = copy.deepcopy(cfg)
         cfg2["MODEL"]["BACKBONE"]["PRECISION"] = "f32x3"
@@ -677,7 +744,7 @@ def main():
                "note": "same config, same resident batch, same run; a second model instance (the timed model is not touched)"}
         del m2, o2, s2
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and CH == 1:    # the reference (and so the oracle) has no RGB path
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and CH == 1:    # the reference (and so the oracle) has no RGB path
         cpu = cpu_baseline(cfg)
     if dist is not None:
         dist.barrier()
@@ -711,9 +778,7 @@ def main():
                        "hip_graph": bool(use_graph),
                        "global_batch": world * B, "parallelism": "dp%d" % world, "optimizer": "Adam lr 1e-3"},
             "final_loss": final_loss, "final_mace": final_mace,
-            "eval": {"mace": eval_mace, "ms_per_batch": eval_ms, "pairs_per_s_per_gpu": 1e3 * B / eval_ms,
-                     "note": "predict_homography in eval mode (BatchNorm folded), held-out synthetic pairs, random-init "
-                             "weights after the timed steps"},
+            "eval": eval_info,
             "step_ms_percentiles": {"p10": pct(0.10), "p50": pct(0.50), "p90": pct(0.90), "min": round(step_ms[0], 4), "max": round(step_ms[-1], 4),
                                     "note": "rank 0, gaps between per-step events on the launch stream"},
             "roofline": roof, "cpu_baseline": cpu, "distributed": dist_info, "alt_arithmetic": alt,

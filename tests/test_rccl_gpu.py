@@ -78,7 +78,7 @@ def test_bench_eight_ranks_over_gloo_prints_the_eight_gpu_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(BIHOME_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-roofline", "--config", "zeng-bihome-pds"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--no-roofline", "--full", "--config", "zeng-bihome-pds"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -107,8 +107,8 @@ def test_bench_json_line_contract():
     peaks of the same run) and `cpu_baseline` (value, unit, cores, kind, sample)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"], env=env, capture_output=True,
-                       text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full"], env=env,
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -136,3 +136,37 @@ def test_bench_json_line_contract():
     assert rf["measured_peaks"]["bf16_mfma_random_operands_TFLOPs"] < rf["measured_peaks"]["bf16_mfma_constant_operands_TFLOPs"] <= 2600
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "sample" in cb
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --steps K` without --full: the headline only (no secondary leg in the line), and --dump-outputs writes the last
+    timed step's loss, deltas and seeded samples of the updated parameters / buffers as float32 .npy files, 64 MB at most.  Two runs with
+    the same arguments dump the same arrays up to rounding: the last timed step starts from the seeded state (chained steps part by
+    percents within a few steps, from the run-to-run order of the fp32 atomics)."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    runs = []
+    for n in range(2):
+        out = tmp_path / ("dump%d" % n)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--dump-outputs", str(out)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 6 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "image-pairs/s" and d["dtype"] == "f32"
+        assert abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert all(d[k] is None for k in ("roofline", "cpu_baseline", "alt_arithmetic", "eval", "distributed"))
+        got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+        assert set(got) == {"loss", "delta_gt", "delta_hat", "params_sample", "buffers_sample"}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64 << 20
+        assert got["delta_gt"].shape == got["delta_hat"].shape == (64, 4, 2) and got["params_sample"].size >= 1 << 20
+        assert np.isclose(float(got["loss"]), d["final_loss"], rtol=1e-6)
+        runs.append(got)
+    a, b = runs
+    assert np.array_equal(a["delta_gt"], b["delta_gt"])
+    assert np.allclose(a["loss"], b["loss"], rtol=1e-5, atol=0)
+    assert np.allclose(a["delta_hat"], b["delta_hat"], rtol=0, atol=1e-4)
+    assert np.allclose(a["params_sample"], b["params_sample"], rtol=0, atol=1e-5)
+    assert np.allclose(a["buffers_sample"], b["buffers_sample"], rtol=1e-5, atol=1e-6)
