@@ -83,6 +83,8 @@ SIGNATURES = {
     "bh_zhang_triplet_bwd": [P] * 12 + [c_int, c_int, c_int] + [P] * 6 + [P],
     "bh_zhang_triplet_bwd_m": [P] * 12 + [c_int, c_int, c_int] + [P] * 8 + [P],
     "bh_warp_bwd_img_f": [P, P, c_int, c_int, c_int, c_int, P, P, c_int, P],
+    "bh_photo_warp_fwd_f": [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
+    "bh_photo_warp_bwd_f": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
     "bh_mask_fwd": [P, P, c_int, c_int, c_float, P, P, P, P, P],
     "bh_mask_bwd": [P] * 7 + [c_int, c_int, c_float, P, P, P],
     "bh_conv3x3_pack": [P, c_int, P],
@@ -133,6 +135,7 @@ SIGNATURES = {
     "bh_tail_bwd": [P] * 17 + [c_int] * 6 + [c_float, c_int, P],
     "bh_tail_bwd_f": [P] * 17 + [c_int] * 6 + [c_float, c_int, c_int, P],
     "bh_synth_pairs": [P] * 5 + [c_int] * 5 + [c_float, c_float, P, P, P],
+    "bh_synth_image": [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_gap_fwd": [P, P, c_int, c_int, c_int, P],

@@ -85,6 +85,37 @@ DETONE_ORIG = {
 }
 
 
+# Nguyen et al.'s unsupervised photometric baseline (config/s-coco/nguyen-orig-lr-5e-3.yaml): the DeTone regressor (OneLine) + the
+# PhotometricHead, L1Loss between patch_2 and the crop of image_1 warped by the predicted homography.  The batch carries the whole
+# grayscale, standardised image_1 and the patch corners as well (DATA IMAGE_KEYS: what batch producers emit on top of the patches).
+NGUYEN_ORIG = {
+    "MODEL": {
+        "BACKBONE": {
+            "NAME": "ResNet34", "VARIANT": "OneLine", "IMAGE_SIZE": 128, "PRETRAINED_RESNET": False,      # reference: True
+            "IMAGE_KEY": ["image"], "PATCH_KEYS": ["patch_1", "patch_2"], "TARGET_KEYS": ["delta_hat_12"],
+        },
+        "HEAD": {"NAME": "PhotometricHead", "LEARNING_KEYS": ["patch_2", "image_1", "delta", "delta_hat_12"]},
+    },
+    "SOLVER": {"OPTIMIZER": "Adam", "MOMENTUM_1": 0.9, "MOMENTUM_2": 0.999, "LR": 0.005,
+               "MILESTONES": [30000, 60000, 90000], "LR_DECAY": 0.1, "LOSS": "L1Loss"},
+    "DATA": {"BATCH_SIZE": 64, "RHO": 32, "PATCH_SIZE": 128, "PHOTOMETRIC_MAX_DELTA": 0, "TARGET_GEN": "4_points",
+             "IMAGE_KEYS": ["image_1"]},
+}
+
+# config/pds-coco/nguyen-orig-lr-5e-3.yaml is NOT the photometric head on distorted data: it is the supervised DeTone regressor
+# (NoOpHead, '4_points') under L1Loss with photometric max_delta 32 - its own values, not the generic '-pds' rule applied to NGUYEN_ORIG
+NGUYEN_ORIG_PDS = {
+    "MODEL": {
+        "BACKBONE": copy.deepcopy(NGUYEN_ORIG["MODEL"]["BACKBONE"]),
+        "HEAD": {"NAME": "NoOpHead", "TARGET_GEN": "4_points",
+                 "LEARNING_KEYS": ["delta", "delta_hat_12", "delta", "delta_hat_12"]},
+    },
+    "SOLVER": copy.deepcopy(NGUYEN_ORIG["SOLVER"]),
+    # (TARGET_GEN as the yaml's HomographyNetPrep: the batch carries the 'all_points' target, which the '4_points' head does not read)
+    "DATA": {"BATCH_SIZE": 64, "RHO": 32, "PATCH_SIZE": 128, "PHOTOMETRIC_MAX_DELTA": 32, "TARGET_GEN": "all_points"},
+}
+
+
 # Zhang et al. "Content-Aware" baselines (config/s-coco/zhang-orig-lr-1e-2.yaml: ContentAware backbone + TripletHead;
 # zhang-bihome-lr-1e-2.yaml: the same backbone under the biHomE PerceptualHead with directly regressed offsets)
 ZHANG_ORIG = {
@@ -138,7 +169,8 @@ def get(name):
     """'zeng-bihome' / 'detone-bihome' = config/s-coco/*; the '-pds' variants = config/pds-coco/* (the two trees differ
     only in HomographyNetPrep's photometric max_delta, 0 vs 32, and the log dir).  'zeng-bihome-rgb256' is the
     build-side extension BASELINE.json configs[4] names (256x256 RGB patches, 6-channel stem; no upstream
-    counterpart - SURVEY.md 0)."""
+    counterpart - SURVEY.md 0).  'nguyen-orig' = config/s-coco/nguyen-orig-lr-5e-3.yaml (PhotometricHead); 'nguyen-orig-pds' =
+    config/pds-coco/nguyen-orig-lr-5e-3.yaml, which upstream made a different experiment (NoOpHead + L1Loss), not a data variant."""
     if name == "zeng-bihome-rgb256":
         cfg = copy.deepcopy(ZENG_BIHOME)
         cfg["MODEL"]["BACKBONE"].update(IMAGE_SIZE=256, PATCH_CHANNELS=3)
@@ -147,6 +179,8 @@ def get(name):
         return cfg
     if name in ("zeng-multihead", "detone-multihead"):
         return _multihead(ZENG_BIHOME if name == "zeng-multihead" else DETONE_BIHOME)
+    if name in ("nguyen-orig", "nguyen-orig-pds"):
+        return copy.deepcopy(NGUYEN_ORIG if name == "nguyen-orig" else NGUYEN_ORIG_PDS)
     if name in ("zeng-ihome", "detone-ihome"):
         return _ihome(ZENG_BIHOME if name == "zeng-ihome" else DETONE_BIHOME)
     base = name[:-4] if name.endswith("-pds") else name

@@ -111,7 +111,46 @@ __global__ void __launch_bounds__(256) synth_pairs_kernel(const float* __restric
     }
 }
 
+// image_1 of the photometric head's batch (config/s-coco/nguyen-orig-lr-5e-3.yaml: DictToGrayscale / DictStandardize also on 'image_1'):
+// the whole base image under image 1's photometric record, grayscale, standardised - the plane patch_1 is cropped from, with the same
+// per-pixel arithmetic as synth_pairs_kernel's patch_1 (its crop at `origin` equals patch_1 bitwise).  grid (ceil(Ws/16), ceil(Hs/16), B)
+__global__ void __launch_bounds__(256) synth_image_kernel(const float* __restrict__ images, const int* __restrict__ img_idx,
+                                                          const float* __restrict__ photo, int Hs, int Ws, float mean, float inv_std,
+                                                          float* __restrict__ out) {
+    const int b = blockIdx.z;
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= Ws || y >= Hs) return;
+    const size_t plane = (size_t)Hs * Ws;
+    const float* q = images + (size_t)img_idx[b] * 3 * plane + (size_t)y * Ws + x;
+    float g;
+    if (!photo) {
+        g = q[0] * 0.299f + q[plane] * 0.587f + q[2 * plane] * 0.114f;                                  // transforms.py:351-353
+    } else {
+        const float* p = photo + (size_t)b * 12;                                                         // image 1's record
+        const PhotoRec r1 = {p[0], p[1], p[2], p[3], p[4], (int)p[5]};
+        g = photo_gray(q[0], q[plane], q[2 * plane], r1);
+    }
+    // transforms.py:377, as a product, a difference and a product: in synth_pairs_kernel the in-image select between the grayscale and
+    // the standardisation keeps the compiler from fusing g * (1/255) - mean, and patch_1 must come out bitwise the same
+    float v;
+    {
+#pragma clang fp contract(off)
+        v = (g * (1.0f / 255.0f) - mean) * inv_std;
+    }
+    out[(size_t)b * plane + (size_t)y * Ws + x] = v;
+}
+
 extern "C" {
+
+int bh_synth_image(const float* images, const int* img_idx, const float* photo, int B, int n_images, int Hs, int Ws, float mean,
+                   float std, float* image1, void* stream) {
+    if (!images || !img_idx || !image1 || B < 0 || n_images < 1 || Hs < 1 || Ws < 1 || std == 0.f) return BH_E_BADARG;
+    if (B == 0) return BH_OK;
+    hipLaunchKernelGGL(synth_image_kernel, dim3((Ws + 15) / 16, (Hs + 15) / 16, B), dim3(256), 0, bh_stream(stream), images, img_idx,
+                       photo, Hs, Ws, mean, 1.0f / std, image1);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
 
 int bh_synth_pairs(const float* images, const int* img_idx, const float* origin, const double* Hpatch, const float* photo,
                    int B, int n_images, int Hs, int Ws, int P, float mean, float std, float* patch1, float* patch2,

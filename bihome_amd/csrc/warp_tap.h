@@ -52,6 +52,41 @@ __device__ __forceinline__ Tap4 make_tap4(const Hf& H, int x, int y, int w, int 
     return t;
 }
 
+// The photometric head's tap (csrc/photo.hip): the map is written in PATCH coordinates, (x, y) -> origin + Hp.(x, y, 1), and gathers
+// from a source plane of its own size wi x hi (the full image, larger than the patch grid).  u / v are the patch-relative coordinates
+// qx / qz, qy / qz (what the adjoint w.r.t. Hp needs); the tap position is origin + (u, v), one add each.  Coordinates, guard, clamping
+// and the out-of-range offsets follow make_tap4; forward and adjoint both call this one helper, so they agree bitwise on which side of an
+// integer coordinate a pixel falls.
+__device__ __forceinline__ Tap4 make_tap4_o(const Hf& H, int x, int y, float ox, float oy, int wi, int hi) {
+#pragma clang fp contract(off)
+    Tap4 t;
+    const float fxp = (float)x, fyp = (float)y;
+    const float qx = __builtin_fmaf(H.h0, fxp, __builtin_fmaf(H.h1, fyp, H.h2)), qy = __builtin_fmaf(H.h3, fxp, __builtin_fmaf(H.h4, fyp, H.h5)),
+                qz = __builtin_fmaf(H.h6, fxp, __builtin_fmaf(H.h7, fyp, H.h8));
+    t.guard = !(fabsf(qz) > 1e-8f);
+    float r = __builtin_amdgcn_rcpf(qz);
+    r = __builtin_fmaf(__builtin_fmaf(-qz, r, 1.0f), r, r);
+    t.iz = t.guard ? 1.0f : r;
+    t.u = qx * t.iz;
+    t.v = qy * t.iz;
+    const float su = ox + t.u, sv = oy + t.v;
+    const float x0f = floorf(su), y0f = floorf(sv);
+    t.fx = su - x0f;
+    t.fy = sv - y0f;
+    const int x0 = (int)fminf(fmaxf(x0f, -2.0f), (float)wi), y0 = (int)fminf(fmaxf(y0f, -2.0f), (float)hi);
+    t.vx0 = (unsigned)x0 < (unsigned)wi; t.vx1 = (unsigned)(x0 + 1) < (unsigned)wi;
+    t.vy0 = (unsigned)y0 < (unsigned)hi; t.vy1 = (unsigned)(y0 + 1) < (unsigned)hi;
+    t.wx0 = t.vx0 ? 1.0f - t.fx : 0.0f; t.wx1 = t.vx1 ? t.fx : 0.0f;
+    t.wy0 = t.vy0 ? 1.0f - t.fy : 0.0f; t.wy1 = t.vy1 ? t.fy : 0.0f;
+    const int w4 = 4 * wi;
+    const int o = y0 * w4 + 4 * x0;
+    t.o00 = (t.vx0 && t.vy0) ? (unsigned)o : 0xFFFFFFFFu;
+    t.o01 = (t.vx1 && t.vy0) ? (unsigned)(o + 4) : 0xFFFFFFFFu;
+    t.o10 = (t.vx0 && t.vy1) ? (unsigned)(o + w4) : 0xFFFFFFFFu;
+    t.o11 = (t.vx1 && t.vy1) ? (unsigned)(o + w4 + 4) : 0xFFFFFFFFu;
+    return t;
+}
+
 // the blend of the four taps, spelled out for the same reason: warp_fwd4_kernel and the stem forward that makes its own warped pixels
 // (stem7_fwd_f16_kernel<1, true>) produce bitwise the same image
 __device__ __forceinline__ void tap_weights(const Tap4& t, float& w00, float& w01, float& w10, float& w11, float& wsum) {

@@ -329,6 +329,38 @@ def warp_bwd(img, H64, g_out, g_cov, pool=4, gH=None):
     return gH
 
 
+def _photo_shapes(B, Hp64, origin):
+    if Hp64.numel() != B * 9 or tuple(origin.shape) != (B, 2):
+        raise ValueError("photo warp: Hp64 must hold [%d,9] and origin be [%d,2] (got %s, %s)" % (B, B, tuple(Hp64.shape), tuple(origin.shape)))
+
+
+def photo_warp_fwd(img, Hp64, origin, P):
+    """Photometric head (PhotometricHead.py:29-42): img [B,C,Hi,Wi], Hp64 [B,9] (bh_h4pt_fwd in patch coordinates), origin [B,2] float
+    (integer top-left patch corners) -> out [B,C,P,P] = bilinear img(origin + Hp.(x, y, 1)), the crop of the full-image warp."""
+    _chk(img); _chk(Hp64, torch.float64); _chk(origin)
+    B, C, Hi, Wi = img.shape
+    _photo_shapes(B, Hp64, origin)
+    out = torch.empty(B, C, P, P, dtype=torch.float32, device=img.device)
+    with _Timed("photo_warp_fwd_kernel", 0.0, 4.0 * 5 * out.numel()):        # four gathered taps + one write per output pixel
+        check(lib.bh_photo_warp_fwd_f(_p(img), _p(Hp64), _p(origin), B, C, Hi, Wi, int(P), _p(out), _fdet(), _stream()), "bh_photo_warp_fwd_f")
+    return out
+
+
+def photo_warp_bwd(img, Hp64, origin, g_out, P, gH=None):
+    """Adjoint of photo_warp_fwd w.r.t. Hp: g_out [B,C,P,P] -> gH [B,9] float64 (added into gH when given, else a zeroed one)."""
+    _chk(img); _chk(Hp64, torch.float64); _chk(origin); _chk(g_out); _chk(gH, torch.float64)
+    B, C, Hi, Wi = img.shape
+    _photo_shapes(B, Hp64, origin)
+    if tuple(g_out.shape) != (B, C, P, P) or (gH is not None and tuple(gH.shape) != (B, 9)):
+        raise ValueError("photo_warp_bwd: g_out must be [%d,%d,%d,%d] and gH [%d,9]" % (B, C, P, P, B))
+    if gH is None:
+        gH = torch.zeros(B, 9, dtype=torch.float64, device=img.device)
+    with _Timed("photo_warp_bwd_kernel", 0.0, 4.0 * 5 * g_out.numel()):
+        check(lib.bh_photo_warp_bwd_f(_p(img), _p(Hp64), _p(origin), _p(g_out), B, C, Hi, Wi, int(P), _p(gH), _fdet(), _stream()),
+              "bh_photo_warp_bwd_f")
+    return gH
+
+
 def warp_bwd_img(H64, g_out):
     """Adjoint of warp_fwd w.r.t. the image (the trained masks of the Zhang baseline, TripletHead.py:60,69): g_out[B,C,h,w] -> g_img."""
     _chk(H64, torch.float64); _chk(g_out)

@@ -192,9 +192,14 @@ def gray_standardize(patch, mean=0.443, std=0.129):
     return ((g[None].astype(np.float32) / 255) - mean) / std
 
 
-def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, channels=1, pool=4, target=False):
+def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, channels=1, pool=4, target=False, image=False):
     """Return dict of float32 arrays: patch_1, patch_2 [B,C,P,P] (standardised), delta [B,4,2]
-    (ground-truth 4-point offsets, integers in [-rho, rho-1]), corners [B,4,2], homography [B,3,3]."""
+    (ground-truth 4-point offsets, integers in [-rho, rho-1]), corners [B,4,2], homography [B,3,3].
+    image=True (channels 1 only): also image_1 [B,1,h,w], the whole standardised grayscale image 1 that patch_1 is cropped from
+    (the photometric head's input, config/s-coco/nguyen-orig-lr-5e-3.yaml); no extra random draws, every other output unchanged."""
+    want_image = bool(image)          # (the loop below names the base image `image`)
+    if want_image and channels != 1:
+        raise ValueError("make_pairs(image=True) produces the grayscale image_1 of the photometric head: channels must be 1")
     rng = np.random.Generator(np.random.PCG64(seed))
     h = max(240, patch + 2 * rho + 48)
     w = max(320, patch + 2 * rho + 128)
@@ -204,6 +209,7 @@ def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, chann
     deltas = np.zeros((batch, 4, 2), np.float32)
     corners_all = np.zeros((batch, 4, 2), np.float32)
     Hs = np.zeros((batch, 3, 3), np.float32)
+    image_1 = np.zeros((batch, 1, h, w), np.float32) if want_image else None
     half = patch // 2
     for b in range(batch):
         image = images[b % len(images)]
@@ -223,7 +229,7 @@ def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, chann
         T = np.array([[1, 0, x0], [0, 1, y0], [0, 0, 1.0]])
         crop2 = warp_bilinear(im2, H @ T, patch, patch)
         crop1 = im1[y0:y0 + patch, x0:x0 + patch]
-        for dst, crop in ((p1, crop1), (p2, crop2)):
+        for dst, crop in ((p1, crop1), (p2, crop2)) + (((image_1, im1),) if want_image else ()):
             if channels == 1:
                 g = crop[..., 0] * 0.299 + crop[..., 1] * 0.587 + crop[..., 2] * 0.114   # :351-353
                 dst[b, 0] = ((g.astype(np.float32) / 255) - 0.443) / 0.129              # :377
@@ -231,6 +237,8 @@ def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, chann
                 dst[b] = ((crop.astype(np.float32) / 255) - 0.443).transpose(2, 0, 1) / 0.129
         deltas[b], corners_all[b], Hs[b] = delta, corners, H
     out = {"patch_1": p1, "patch_2": p2, "delta": deltas, "corners": corners_all, "homography": Hs}
+    if want_image:
+        out["image_1"] = image_1
     if target:      # HomographyNetPrep 'all_points' (transforms.py:635-685): pf(x) = H x - x over the patch of image 1
         c = np.array([[0, 0], [patch, 0], [patch, patch], [0, patch]], np.float64)
         out["target"] = np.stack([perspective_field(four_point_homography(c, c + deltas[b].astype(np.float64)), patch)

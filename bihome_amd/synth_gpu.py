@@ -45,7 +45,9 @@ class GpuPairGenerator:
             photo = torch.tensor(recs, dtype=torch.float32, device=dev).contiguous()
         return idx, origin, delta, photo
 
-    def make(self, idx, origin, delta, photo=None):
+    def make(self, idx, origin, delta, photo=None, image=False):
+        """image=True: also image_1 [B,1,h,w] (the whole standardised grayscale image 1 under its photometric record, bh_synth_image:
+        its crop at the corners is patch_1 bitwise) and corners [B,4,2] - the batch of the photometric head (nguyen-orig)."""
         B, P = delta.shape[0], self.patch
         H64, _ = K.h4pt_fwd(delta, P)
         p1 = torch.empty(B, 1, P, P, dtype=torch.float32, device=self.device)
@@ -55,7 +57,16 @@ class GpuPairGenerator:
                                  pv(photo.data_ptr()) if photo is not None else None, B, self.images.shape[0], self.h,
                                  self.w, P, 0.443, 0.129, pv(p1.data_ptr()), pv(p2.data_ptr()),
                                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_synth_pairs")
-        return {"patch_1": p1, "patch_2": p2, "delta": delta}
+        out = {"patch_1": p1, "patch_2": p2, "delta": delta}
+        if image:
+            im = torch.empty(B, 1, self.h, self.w, dtype=torch.float32, device=self.device)
+            check(lib.bh_synth_image(pv(self.images.data_ptr()), pv(idx.data_ptr()), pv(photo.data_ptr()) if photo is not None else None,
+                                     B, self.images.shape[0], self.h, self.w, 0.443, 0.129, pv(im.data_ptr()),
+                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_synth_image")
+            # corners in HomographyNetPrep's order (top-left, top-right, bottom-right, bottom-left; transforms.py:510-513)
+            sq = torch.tensor([[0, 0], [P, 0], [P, P], [0, P]], dtype=torch.float32, device=self.device)
+            out["image_1"], out["corners"] = im, (origin[:, None, :] + sq).contiguous()
+        return out
 
-    def next(self, B):
-        return self.make(*self.draw(B))
+    def next(self, B, image=False):
+        return self.make(*self.draw(B), image=image)

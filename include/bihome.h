@@ -123,6 +123,18 @@ int bh_warp_bwd(const float* img, const double* H64, const float* g_out, const f
                 int B, int C, int h, int w, int pool, double* gH, void* stream);
 int bh_warp_bwd_f(const float* img, const double* H64, const float* g_out, const float* g_cov,
                   int B, int C, int h, int w, int pool, double* gH, int flags, void* stream);
+/* Photometric head (src/heads/PhotometricHead.py:29-41, Nguyen et al.'s unsupervised baseline): H_hat = four_point_to_homography(corners,
+ * delta_hat, crop=False) (:29-30, src/data/utils.py:7-33), image_warped = warp_image(image_1, H_hat) (:33-35, utils.py:54-59) and the
+ * per-sample crop image_warped[b, :, c[0,1]:c[3,1], c[0,0]:c[1,0]] (:38-42) in ONE gather over the crop window only.  Written in patch
+ * coordinates: Hp64[B,9] = bh_h4pt_fwd(delta_hat) for the corners [[0,0],[P,0],[P,P],[0,P]], origin[B,2] float = the integer top-left
+ * corner (x, y) of each patch; then H_hat.(o + u) = o + Hp.u and out[b,c,j,i] = bilinear img[b,c](origin_b + Hp_b.(i, j, 1)), zero padding
+ * outside the Hi x Wi image (kornia.warp_perspective, align_corners=True).  img[B,C,Hi,Wi], out[B,C,P,P]; P a multiple of 16. */
+int bh_photo_warp_fwd_f(const float* img, const double* Hp64, const float* origin, int B, int C, int Hi, int Wi, int P, float* out,
+                        int flags, void* stream);
+/* adjoint w.r.t. Hp only (image_1 is data): g_out[B,C,P,P] -> gH[B,9] double += (the caller zeroes it; feed to bh_h4pt_bwd).
+ * flags & BH_F_DETERMINISTIC: one workgroup per sample is the only writer of gH[b]; otherwise workgroup sums are added with atomics. */
+int bh_photo_warp_bwd_f(const float* img, const double* Hp64, const float* origin, const float* g_out, int B, int C, int Hi, int Wi,
+                        int P, double* gH, int flags, void* stream);
 /* adjoint w.r.t. the IMAGE (the trained masks of the Zhang baseline are warped, src/heads/TripletHead.py:60,69, and their gradient must
  * reach the mask predictor): g_out[B,C,h,w] -> g_img[B,C,h,w] (overwritten) = transpose of the bilinear gather with the same taps and
  * zero padding.  flags & BH_F_DETERMINISTIC: scratch = bh_warp_bwd_img_scratch_doubles(...) doubles (integer-limb entries); else NULL. */
@@ -608,6 +620,13 @@ int bh_tail_bwd_f(const float* gout, const float* x, const float* w1, const floa
 int bh_synth_pairs(const float* images, const int* img_idx, const float* origin, const double* Hpatch, const float* photo,
                    int B, int n_images, int Hs, int Ws, int P, float mean, float std, float* patch1, float* patch2,
                    void* stream);
+
+/* image_1 for the photometric head (config/s-coco/nguyen-orig-lr-5e-3.yaml: HomographyNetPrep's image_1 after DictToGrayscale and
+ * DictStandardize, transforms.py:344-378): image1[B,1,Hs,Ws] = the whole base image images[img_idx[b]] under image 1's photometric record
+ * (photo[b,0,:] of bh_synth_pairs' layout, NULL = none), grayscale, standardised - the same per-pixel arithmetic as bh_synth_pairs'
+ * patch1, whose crop at origin it equals bitwise. */
+int bh_synth_image(const float* images, const int* img_idx, const float* photo, int B, int n_images, int Hs, int Ws, float mean,
+                   float std, float* image1, void* stream);
 
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation). */
