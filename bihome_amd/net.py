@@ -14,7 +14,6 @@ MI355X-first choices:
     in a HIP graph.
 """
 import os
-import sys
 import weakref
 
 import torch
@@ -340,10 +339,9 @@ def run_forward(prog, x, groups, training, save, precision=0, fold_cache=None, p
     # (the packer is named by its serial number, not by id(): an id can be reused by another packer after garbage collection)
     fw_key = (bool(training), int(groups), int(precision), packer.serial if packer is not None else 0,
               len(packer.entries) if packer is not None else 0, bool(packer.f16) if packer is not None else False,
-              os.environ.get("BIHOME_BN_ON_LOAD_1X1", "1"), os.environ.get("BIHOME_BN_ON_LOAD", "1"), os.environ.get("BIHOME_BN_JOIN", "1"),
               tuple(op.mod.weight.requires_grad for op in prog.ops if op.kind == "conv"))
     fw_plans = prog.__dict__.setdefault("_fw_plans", {})
-    fw_cached = fw_plans.get(fw_key) if os.environ.get("BIHOME_PLAN_CACHE", "1") != "0" else None
+    fw_cached = fw_plans.get(fw_key)
     consumer = None
     if fw_cached is None:
         fused_stats = {}                                      # conv op index -> bn op index
@@ -365,7 +363,7 @@ def run_forward(prog, x, groups, training, save, precision=0, fold_cache=None, p
         # residual unit).  Needs the sums from the producer's epilogue (fused_stats) and a table of <= 4 KB.
         bn_on_load = set()
         bn_on_load_1x1 = set()
-        if training and os.environ.get("BIHOME_BN_ON_LOAD_1X1", "1") != "0" and groups <= 2 and int(precision) != 1:      # (not the bf16-operand mode)
+        if training and groups <= 2 and int(precision) != 1:      # (not the bf16-operand mode)
             # round 4: the same for a 1x1 / stride-1 conv consumer with <= 32 channels on one side (the 1x1 conv of the decoder units behind
             # BatchNorm + ReLU at 64 x 64 and 128 x 128): generic forward kernel and small-channel weight-gradient kernel transform on load
             consumer_ = {}
@@ -381,7 +379,7 @@ def run_forward(prog, x, groups, training, save, precision=0, fold_cache=None, p
                         and prog.ops[j].mod.in_channels % 32 == 0 and prog.ops[j].mod.out_channels % 4 == 0
                         and min(prog.ops[j].mod.in_channels, prog.ops[j].mod.out_channels) <= 32 and prog.ops[j].mod.weight.requires_grad):
                     bn_on_load_1x1.add(i)
-        if training and packer is not None and int(precision) in K.SPLIT_PIECES and os.environ.get("BIHOME_BN_ON_LOAD", "1") != "0":
+        if training and packer is not None and int(precision) in K.SPLIT_PIECES:
             consumer = {}
             for j, op in enumerate(prog.ops):
                 consumer.setdefault(op.src, j)
@@ -397,7 +395,7 @@ def run_forward(prog, x, groups, training, save, precision=0, fold_cache=None, p
         # nobody else reads (the lower branch of ResNet50DeconvBlock / the strided ResNet34ConvBlock): the lower BatchNorm is not applied
         # on its own - both are applied, added and rectified in ONE pass (kernels.bn_join_fwd), the adjoint is one reduce + one apply
         joins = {}                                            # join bn op index -> lower bn op index
-        if training and os.environ.get("BIHOME_BN_JOIN", "1") != "0":
+        if training:
             producer_ = {op.dst: j for j, op in enumerate(prog.ops)}
             for i, op in enumerate(prog.ops):
                 j = producer_.get(op.res) if (op.kind == "bn" and op.res is not None) else None
@@ -507,8 +505,7 @@ def run_forward(prog, x, groups, training, save, precision=0, fold_cache=None, p
                 res = slots[op.res] = lo
             nxt = prog.ops[i + 1] if i + 1 < len(prog.ops) else None
             if (res is None and nxt is not None and nxt.kind == "maxpool" and nxt.src == op.dst and src.dim() == 4 and src.shape[0] % groups == 0
-                    and m.num_features % 4 == 0 and m.num_features > 1 and sum(1 for o_ in prog.ops if o_.src == op.dst or o_.res == op.dst) == 1
-                    and os.environ.get("BIHOME_BN_POOL", "1") != "0"):
+                    and m.num_features % 4 == 0 and m.num_features > 1 and sum(1 for o_ in prog.ops if o_.src == op.dst or o_.res == op.dst) == 1):
                 # BatchNorm (+ReLU) -> MaxPool2d(3, 2, 1), its only consumer: one pass, the activation in between is never stored
                 st = arena[bn_off[i]:bn_off[i] + K.bn_stats_doubles(groups, m.num_features)]
                 slots[op.dst] = K.bn_maxpool_fwd(src, m.weight, m.bias, m.running_mean, m.running_var, groups, m.eps, _momentum(m), op.relu,
@@ -576,8 +573,7 @@ def side_stream(device):
     consumer inside the backward chain, so they run under the dgrad / BatchNorm kernels of the main stream."""
     key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
     if key not in _SIDE_STREAMS:
-        # (BIHOME_SIDE_PRIORITY: experiments - the stream's priority; lower number = higher priority, out-of-range values are clamped)
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=key, priority=int(os.environ.get("BIHOME_SIDE_PRIORITY", "0")))
+        _SIDE_STREAMS[key] = torch.cuda.Stream(device=key)
     return _SIDE_STREAMS[key]
 
 
@@ -599,16 +595,13 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
     # (the fusion plan below is a pure function of the program, the mode and the shapes: made once and kept on the program - three
     #  backward walks per step used to rebuild it, ~0.4 ms of a host that has ~9 ms of enqueueing to do per 12 ms step)
     # (key: everything the plan reads that can differ between two walks of one program - mode, batch / map geometry via the output
-    #  gradient's shape, the joins made by this forward, the precision, the switches)
     #  gradient's shape, the joins made by this forward and the convs it ran - their CONTENTS, not their counts - the precision, which conv
-    #  weights / biases train (fuse_bias reads the flags: freezing a layer between two steps must not reuse the other plan), the switches)
+    #  weights / biases train (fuse_bias reads the flags: freezing a layer between two steps must not reuse the other plan))
     plan_key = (bool(ctx.training), bool(want_wgrad), int(ctx.groups), tuple(gout.shape), frozenset(ctx.joined.items()), frozenset(ctx.descs),
                 getattr(ctx, "precision", 0),
-                tuple((op.mod.weight.requires_grad, op.mod.bias is not None and op.mod.bias.requires_grad) for op in prog.ops if op.kind == "conv"),
-                os.environ.get("BIHOME_FUSE_BN_REDUCE", "1"), os.environ.get("BIHOME_FUSE_BIAS_GRAD", "1"), os.environ.get("BIHOME_BN_FROM_1X1", "1"),
-                os.environ.get("BIHOME_WGRAD_BNADJ", "0"))
+                tuple((op.mod.weight.requires_grad, op.mod.bias is not None and op.mod.bias.requires_grad) for op in prog.ops if op.kind == "conv"))
     plans = prog.__dict__.setdefault("_bw_plans", {})
-    cached = plans.get(plan_key) if os.environ.get("BIHOME_PLAN_CACHE", "1") != "0" else None
+    cached = plans.get(plan_key)
     consumed_by = {}
     for op in (prog.ops if cached is None else ()):
         consumed_by.setdefault(op.src, 0)
@@ -626,7 +619,7 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
     # slot in backward order) also accumulates that BatchNorm's backward sums in its epilogue (bh_conv_dgrad_bnreduce),
     # so the BatchNorm adjoint is one apply launch instead of reduce + finalize + apply.
     fuse_bn = {}                                          # conv op index -> bn op index
-    if cached is None and ctx.training and os.environ.get("BIHOME_FUSE_BN_REDUCE", "1") != "0":
+    if cached is None and ctx.training:
         producer = {op.dst: j for j, op in enumerate(prog.ops)}
         last_consumer = {}
         for j, op in enumerate(prog.ops):                 # the lowest-index consumer is processed last
@@ -641,7 +634,7 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
     # A 3x3 conv that is the ONLY consumer of a biased (transposed) conv's output: the column sums of its input gradient
     # are that layer's bias gradient - accumulated in the dgrad epilogue instead of a streaming pass over the gradient
     fuse_bias = {}                                        # conv op index -> producer op index
-    if cached is None and want_wgrad and os.environ.get("BIHOME_FUSE_BIAS_GRAD", "1") != "0":
+    if cached is None and want_wgrad:
         producer = {op.dst: j for j, op in enumerate(prog.ops)}
         for j, op in enumerate(prog.ops):
             p = producer.get(op.src)
@@ -654,7 +647,7 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
     # its dgrad is rebuilt inside that BatchNorm's adjoint (bh_bn_bwd_from_1x1) - the full-resolution decoder unit's 268 MB gradient is
     # never written
     from_1x1 = set()
-    if cached is None and ctx.training and os.environ.get("BIHOME_BN_FROM_1X1", "1") != "0":
+    if cached is None and ctx.training:
         producer_ = {op.dst: j for j, op in enumerate(prog.ops)}
         for j, op in enumerate(prog.ops):
             b = producer_.get(op.src)
@@ -665,28 +658,6 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
                     and prog.ops[b].mod.num_features % 4 == 0 and 256 % (prog.ops[b].mod.num_features // 4) == 0
                     and not op.extra["in_nchw"] and not op.extra["out_nchw"]):
                 from_1x1.add(j)
-    # Round 6 (round-5 VERDICT item 2): a fused BatchNorm whose input comes from a 3x3 conv with an fp16-piece weight gradient - that
-    # weight gradient takes the BatchNorm's adjoint ON LOAD (kernels.conv_wgrad_bnadj): it reads the gradient of the BatchNorm's output,
-    # the BatchNorm's input and the sums the dgrad epilogue made, so it is enqueued IN FRONT of the BatchNorm's adjoint pass and runs next
-    # to that HBM-bound pass instead of behind it.  bn op index -> conv op index
-    # MEASURED AND NOT ADOPTED (profiles/r06g_wx3_bnadj_ab.txt, r06g_step_ab_bnadj.txt): the second operand stream and its transform cost
-    # the weight-gradient kernel 6-15 us per launch alone (four waves 45.9 -> 61.4 us on 32 x 32 x 64, eight waves 43.8 -> 49.8) - as much as
-    # the 12-22 us adjoint pass it no longer waits for - and the step gets 0.27 ms SLOWER (13.34 against 13.07 ms, three alternating runs on
-    # one box).  The form stays behind BIHOME_WGRAD_BNADJ=1 (C ABI entry, parity test tests/test_f16x2_gpu.py); the default is off.
-    bnadj = {}
-    if (cached is None and want_wgrad and ctx.training and getattr(ctx, "precision", 0) == K.F16X2
-            and os.environ.get("BIHOME_WGRAD_BNADJ", "0") != "0"):
-        producer_c = {op.dst: j for j, op in enumerate(prog.ops)}
-        for b in fuse_bn.values():
-            c = producer_c.get(prog.ops[b].src)
-            if c is None or prog.ops[c].kind != "conv" or c not in ctx.descs or consumed_by.get(prog.ops[b].src, 0) != 1:
-                continue
-            cm, cd = prog.ops[c].mod, ctx.descs[c]
-            if (isinstance(cm, nn.Conv2d) and cm.kernel_size == (3, 3) and cm.stride == (1, 1) and cm.padding == (1, 1) and cm.weight.requires_grad
-                    and prog.ops[c].extra["weight_fn"] is None and not (cm.bias is not None and cm.bias.requires_grad)
-                    and getattr(cd, "bh_wx3", False) and cd.Ci % 64 == 0 and cd.Co % 64 == 0 and cd.Hi % 8 == 0 and cd.Wi % 8 == 0
-                    and cd.N % ctx.groups == 0):
-                bnadj[b] = c
     red_off, total = {}, 0
     bias_off = {}
     if cached is None:
@@ -696,70 +667,17 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
         for b in fuse_bn.values():
             red_off[b] = total
             total += K.bn_stats_doubles(ctx.groups, prog.ops[b].mod.num_features)
-        plans[plan_key] = (consumed_by, fuse_bn, fuse_bias, from_1x1, red_off, bias_off, total, bnadj)
+        plans[plan_key] = (consumed_by, fuse_bn, fuse_bias, from_1x1, red_off, bias_off, total)
     else:
-        consumed_by, fuse_bn, fuse_bias, from_1x1, red_off, bias_off, total, bnadj = cached
-    if os.environ.get("BIHOME_BN_PLAN") == "1" and not getattr(prog, "_bn_plan_printed", False):
-        # tools/: which BatchNorm adjoints still run their own reduce pass, and what completes their output gradient
-        prog._bn_plan_printed = True
-        lc = {}
-        for j, op in enumerate(prog.ops):
-            for sl in (op.src, op.res):
-                if sl is not None and sl not in lc:
-                    lc[sl] = j
-        for b, op in enumerate(prog.ops):
-            if op.kind != "bn":
-                continue
-            j = lc.get(op.dst)
-            cons = prog.ops[j] if j is not None else None
-            what = "output" if cons is None else cons.kind
-            if cons is not None and cons.kind == "conv":
-                m = cons.mod
-                what = "%s k%s s%s %d->%d" % (type(m).__name__, getattr(m, "kernel_size", "?"), getattr(m, "stride", "?"),
-                                               getattr(m, "in_channels", getattr(m, "in_features", 0)), getattr(m, "out_channels", getattr(m, "out_features", 0)))
-            elif cons is not None and cons.kind == "bn":
-                what = "bn(res)" if cons.res == op.dst else "bn"
-            print("BN_PLAN op %3d C%-4d %s last consumer: op %s %s | fused=%s joined=%s shape=%s" %
-                  (b, op.mod.num_features, "relu" if op.relu else "    ", j, what, b in fuse_bn.values(), b in ctx.joined,
-                   tuple(slots[op.src].shape) if hasattr(slots[op.src], "shape") else "?"), file=sys.stderr)
+        consumed_by, fuse_bn, fuse_bias, from_1x1, red_off, bias_off, total = cached
     bn_reduced = {}
     # precision 4: magnitude records of the BatchNorm input gradients (the gy operand of the fp16-piece dgrad / weight-gradient kernels)
     amax_next = None
-    nrec = (max(1, sum(1 for op in prog.ops if op.kind == "bn")) + len(bnadj)) if getattr(ctx, "precision", 0) == K.F16X2 else 0
+    nrec = max(1, sum(1 for op in prog.ops if op.kind == "bn")) if getattr(ctx, "precision", 0) == K.F16X2 else 0
     red_arena, amax_arena = _zero_arenas(total, nrec * K.AMAX_FLOATS, gout.device)    # (one fill launch for both)
-    bnadj_on = wgrad_stream is not None and bool(bnadj)     # (only where a second stream exists: what the form buys is the earlier start)
-    amax_d_of, wgrad_done = {}, set()
     if nrec:
         amax_iter = iter(amax_arena.split(K.AMAX_FLOATS))
         amax_next = lambda: next(amax_iter)
-
-    # Round 6: consecutive fp16-piece weight gradients of ONE geometry are queued and leave as one launch of up to `wbatch` layers
-    # (kernels.conv_wgrad_batch: one set of split-K partial blocks and one kernel / reduce launch pair per BATCH instead of per layer);
-    # a change of geometry, a full queue or the end of the walk flushes it.
-    # MEASURED AND NOT ADOPTED (profiles/r06i_step_ab_wgrad_batch.txt, three alternating runs on one box): 12.43 ms per step with every
-    # layer its own launch, 12.49 with pairs, 12.51 with batches of four - a batch starts when its LAST layer's gradient exists, and what
-    # the later start costs the two-stream schedule exceeds the launches and the 12 MB of partial blocks per layer it saves.  The default
-    # is 1 (every layer its own launch, as in rounds 2-5); BIHOME_WGRAD_BATCH=2..4 enables the queue.
-    wbatch = max(1, min(4, int(os.environ.get("BIHOME_WGRAD_BATCH", "1")))) if wgrad_stream is not None else 1
-    wpend = []
-
-    def wflush():
-        if not wpend:
-            return
-        items = list(wpend)
-        wpend.clear()
-        ev = torch.cuda.Event()
-        ev.record(main)                                       # the last queued layer's gradient is final here
-        for it in items:
-            it[2].record_stream(wgrad_stream)
-        with torch.cuda.stream(wgrad_stream):
-            wgrad_stream.wait_event(ev)
-            if len(items) == 1 or not K.conv_wgrad_batch([(it[1], it[2], it[3], it[4]) for it in items], x3_ws):
-                for it in items:
-                    K.conv_wgrad(it[1], it[2], it[3], None, it[4], det_ws=x3_ws)
-        if on_param_grad is not None:                         # these layers' gradients are final (enqueued): their buckets may leave
-            for it in items:
-                on_param_grad(it[5].weight)
 
     for i in range(len(prog.ops) - 1, -1, -1):
         op = prog.ops[i]
@@ -771,7 +689,7 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
         if op.kind == "conv":
             d, wk = ctx.descs[i], ctx.weights[i]
             m = op.mod
-            if want_wgrad and m.weight.requires_grad and op.extra["weight_fn"] is None and i not in wgrad_done:
+            if want_wgrad and m.weight.requires_grad and op.extra["weight_fn"] is None:
                 gw = m.weight.grad if m.weight.dim() == 2 else kview(m.weight.grad)
                 gb = m.bias.grad if (m.bias is not None and m.bias.requires_grad) else None
                 has_gb = gb is not None
@@ -788,23 +706,8 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
                     d.route = (d.route | K.ROUTE_WX3_PC) & ~K.ROUTE_WX3_SHARED
                 else:
                     d.route = (d.route & ~K.ROUTE_WX3_PC) | K.ROUTE_WX3_SHARED
-                queued = False
                 if wgrad_stream is None:
                     K.conv_wgrad(x, g, gw, gb, d, det_ws=ws)
-                elif (wbatch > 1 and gb is None and getattr(ctx, "precision", 0) == K.F16X2 and getattr(d, "bh_wx3", False) and ws is not None
-                      and d.Ci % 64 == 0 and d.Co % 64 == 0 and d.Hi >= 8):
-                    # round 6: queued - up to `wbatch` consecutive layers of one geometry leave in ONE launch (kernels.conv_wgrad_batch)
-                    key = (d.N, d.Hi, d.Wi, d.Ci, d.Co, (x.groups, bool(x.relu)) if isinstance(x, K.BnOnLoad) else None)
-                    if wpend and wpend[0][0] != key:
-                        wflush()
-                    K.amax_of(g)                                      # (magnitude records: on the main stream, as below)
-                    K.amax_of(x)
-                    wpend.append((key, x, g, gw, d, m))
-                    if len(wpend) >= wbatch:
-                        wflush()
-                    queued = True
-                    if on_param_grad is not None and has_gb:      # (its column sums came from the consumer's dgrad epilogue: final)
-                        on_param_grad(m.bias)
                 else:
                     if getattr(ctx, "precision", 0) == K.F16X2 and getattr(d, "bh_wx3", False):
                         # magnitude records the fp16-piece weight gradient reads: made (if missing) on the MAIN stream, in front of the
@@ -818,7 +721,7 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
                     with torch.cuda.stream(wgrad_stream):
                         wgrad_stream.wait_event(ev)
                         K.conv_wgrad(x, g, gw, gb, d, det_ws=ws if getattr(d, "bh_wx3", False) else None)     # (one stream: launches serialise on the workspace)
-                if on_param_grad is not None and not queued:       # gradient of this layer is final: its bucket may leave
+                if on_param_grad is not None:                      # gradient of this layer is final: its bucket may leave
                     on_param_grad(m.weight)
                     if has_gb:
                         on_param_grad(m.bias)
@@ -836,8 +739,6 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
                                stats=ctx.stats[b], gamma=bm.weight, beta=bm.bias, eps=bm.eps, relu=bop.relu, sums=sums,
                                groups=ctx.groups)
                     bn_reduced[b] = sums
-                    if bnadj_on and b in bnadj and amax_next is not None:
-                        red["amax_d"] = amax_d_of[b] = amax_next()      # (max |mask(d)|: the bound of the on-load adjoint's fp16 scale)
                 if i in fuse_bias and op.src not in grads and red is None:
                     p = fuse_bias[i]
                     grads[op.src] = K.conv_dgrad(g, wk, d, wpacked=ctx.wpacked.get(i),
@@ -892,26 +793,6 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
                 if need_src_grad:
                     contribute(op.src, gx)
                 continue
-            if bnadj_on and i in amax_d_of and isinstance(g, torch.Tensor):
-                c = bnadj[i]
-                cop, cd, cm = prog.ops[c], ctx.descs[c], prog.ops[c].mod
-                xin = slots[cop.src]
-                if isinstance(xin, (torch.Tensor, K.BnOnLoad)) and x3_ws is not None:
-                    cd.route = (cd.route & ~K.ROUTE_WX3_PC) | K.ROUTE_WX3_SHARED
-                    K.amax_of(xin)                                    # (made - if missing - on the main stream, in front of the event)
-                    ev = torch.cuda.Event()
-                    ev.record(main)                                   # d and its sums are final here; the adjoint pass below has not started
-                    g.record_stream(wgrad_stream)
-                    with torch.cuda.stream(wgrad_stream):
-                        wgrad_stream.wait_event(ev)
-                        done = K.conv_wgrad_bnadj(xin, g, kview(cm.weight.grad), cd, x3_ws,
-                                                  dict(z=x, y=yb if (op.relu and op.res is not None) else None, stats=ctx.stats[i],
-                                                       sums=bn_reduced[i], gamma=m.weight, beta=m.bias, eps=m.eps, relu=op.relu, groups=ctx.groups),
-                                                  amax_d_of[i])
-                    if done:
-                        wgrad_done.add(c)
-                        if on_param_grad is not None:
-                            on_param_grad(cm.weight)
             gx, gres = K.bn_bwd(g, yb, x, m.weight, ctx.stats[i], m.running_mean, m.running_var, ctx.groups,
                                 m.eps, op.relu, ctx.training, op.res is not None and ((op.res != 0) or want_input_grad),
                                 m.weight.grad if train_w else None, m.bias.grad if train_w else None, beta=m.bias,
@@ -948,14 +829,13 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
                 contribute(op.src, gx)
         elif op.kind == "maxpool":
             if need_src_grad:
-                if isinstance(x, K.BnPooled) and op.src not in grads and os.environ.get("BIHOME_BN_POOL_BWD", "1") != "0":
+                if isinstance(x, K.BnPooled) and op.src not in grads:
                     grads[op.src] = K.PooledGrad(g, ctx.stats[i])          # (consumed by the BatchNorm's adjoint: bn_maxpool_bwd)
                 else:
                     contribute(op.src, K.maxpool_bwd(ctx.stats[i], g, tuple(x.shape)))
         elif op.kind == "gap":
             if need_src_grad:
                 contribute(op.src, K.gap_bwd(g, tuple(x.shape)))
-    wflush()
     if wgrad_stream is not None:
         main.wait_stream(wgrad_stream)          # the optimiser (and the release of the activations) follows
     return grads.get(0)
@@ -1102,27 +982,25 @@ class Runner:
         # eval-mode BatchNorm folding cache (run_forward / _folded); Runners over the SAME modules (the extractor's
         # 1- and 3-channel programs) share one dict so that a training forward through either invalidates both
         self._fold = fold_cache if fold_cache is not None else {}
-        self.fold_bn = os.environ.get("BIHOME_FOLD_BN", "1") != "0"
+        self.fold_bn = True                 # (tests switch it off to compare the folded and unfolded eval forwards)
         # second HIP stream for the weight-gradient launches (default since round 4: with three instead of six MFMA products per
         # product the 3x3 kernels are no longer matrix-pipe-bound and two streams fill each other's gaps: 15.5 -> 14.7 ms per step;
         # BIHOME_OVERLAP=0 or bench.py --no-overlap: one stream - per-kernel durations of rocprofv3 / the roofline leg are then those
         # of each kernel alone, which is how profiles/ and bench.py's roofline object are measured)
         self.wgrad_on_side_stream = os.environ.get("BIHOME_OVERLAP", "1") != "0"
-        # fragment-ordered weight copies for the halo-tiled 3x3 kernel (csrc/conv3x3.hip PACKED; BIHOME_PACK_WEIGHTS=0: off)
-        self.use_packer = os.environ.get("BIHOME_PACK_WEIGHTS", "1") != "0"
+        # fragment-ordered weight copies for the halo-tiled 3x3 kernel (csrc/conv3x3.hip PACKED; tests switch it off to compare with
+        # the unpacked path)
+        self.use_packer = True
         self._packer = None
-        self.deterministic_wgrad = os.environ.get("BIHOME_DETERMINISTIC_WGRAD", "0") == "1"
         self._det_ws = None
 
     def det_workspace(self, device):
-        """BIHOME_DETERMINISTIC_WGRAD=1: one 40 MB workspace for the fixed-order split-K reduction of the 3x3 weight
-        gradients (every launch of the stride-1 fast path stores 2048 x 16 KB partial tiles)."""
-        det = K.deterministic()
-        if not (self.deterministic_wgrad or det) or self.flat is None:
+        """Deterministic mode: one workspace for the fixed-order split-K reduction of the weight gradients (every launch of the
+        stride-1 fast path stores 2048 x 16 KB partial tiles)."""
+        if not K.deterministic() or self.flat is None:
             return None
-        size = DET_WS_BYTES if det else X3_WS_BYTES
-        if self._det_ws is None or self._det_ws.device != device or self._det_ws.numel() * 4 < size:
-            self._det_ws = torch.empty(size // 4, dtype=torch.float32, device=device)
+        if self._det_ws is None or self._det_ws.device != device or self._det_ws.numel() * 4 < DET_WS_BYTES:
+            self._det_ws = torch.empty(DET_WS_BYTES // 4, dtype=torch.float32, device=device)
         return self._det_ws
 
     def x3_workspace(self, device):

@@ -152,7 +152,7 @@ def build_optimizer(model, solver, capturable=False):
     params = list(model.parameters())
     # train.py:703-707.  On the device the update runs as torch's fused Adam (one pass over parameters, gradients and both
     # moments instead of the ~5 multi-tensor passes of the default implementation: 0.36 -> ~0.1 ms per step)
-    fused = bool(params) and all(p.is_cuda for p in params) and os.environ.get("BIHOME_FUSED_ADAM", "1") != "0"
+    fused = bool(params) and all(p.is_cuda for p in params)
     kw = {"fused": True} if fused else {}
     lr = solver["LR"]
     if capturable:
@@ -202,7 +202,7 @@ def train_step(model, data, opt, sched, clip=-1.0, reducer=None, loss_fn="biHomE
         loss, delta_gt, delta_hat = model(data)                     # train.py:357
     # train.py:379.  On the calling thread: torch hands a CUDA graph's backward to a device thread, and the hand-over plus the two threads'
     # turns at the interpreter lock cost 1.4 ms of host time per step (bench.py --host-profile) - a fifth of what a 7 ms step leaves the host
-    with torch.autograd.set_multithreading_enabled(os.environ.get("BIHOME_AUTOGRAD_THREAD", "0") == "1"):
+    with torch.autograd.set_multithreading_enabled(False):
         loss.backward()
     if reducer is not None:
         reducer.allreduce()                                         # RCCL SUM over ranks

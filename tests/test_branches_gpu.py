@@ -250,7 +250,7 @@ def test_score_weighted_multi_hypothesis_training_vs_golden(golden, base, loss_n
     # rounding-level difference in the updated weights can hand a sample to another hypothesis (measured: MACE 24.48 against
     # 24.55 with gradient norms equal to 3 digits at step 0); the band is the size of one such flip.  (Round 4: with the two-branch
     # BatchNorm join - one rounding less in four layers, kernel-level equal to float64 to 2e-6, the B = 64 oracle test unchanged - the
-    # one-line config flips a different sample: 6.96 against 7.91, 12 %; with BIHOME_BN_JOIN=0 it is 7.9 again.  Band 15 %; the step-0
+    # one-line config flips a different sample: 6.96 against 7.91, 12 %; without the join it is 7.9 again.  Band 15 %; the step-0
     # assertions above are the tight ones.)
     assert abs(losses[1] - g64["loss"][1]) <= 0.15 * abs(g64["loss"][1]), (losses, g64["loss"], g32["loss"])
     assert abs(maces[1] - g64["mace"][1]) <= 0.15, (maces, g64["mace"], g32["mace"])

@@ -32,10 +32,9 @@ for it in range(3):
     M.append(mace(dgt, dh) - float(g64["mace"][it]))
 print("RESULT %%+.4f %%+.4f %%+.4f" %% tuple(M))
 ''' % (ROOT, ROOT)
-VARIANTS = [("default", {}), ("warp adjoint as its own launch", {"BIHOME_WARP_IN_STEM_DGRAD": "0"}), ("BatchNorm adjoint not rebuilding the 1x1 dgrad", {"BIHOME_BN_FROM_1X1": "0"}),
-            ("join adjoint reading y", {"BIHOME_JOIN_REMASK": "0"}), ("BatchNorm sums not in the dgrad epilogue", {"BIHOME_FUSE_BN_REDUCE": "0"}),
-            ("no BatchNorm-on-load", {"BIHOME_BN_ON_LOAD": "0", "BIHOME_BN_ON_LOAD_1X1": "0"}), ("one stream", {"BIHOME_OVERLAP": "0"}),
-            ("deterministic calls", {"BIHOME_DETERMINISTIC": "1"}), ("no weight packs (LDS-slab 3x3 path)", {"BIHOME_PACK_WEIGHTS": "0"})]
+VARIANTS = [("default", {}), ("warp adjoint as its own launch", {"BIHOME_WARP_IN_STEM_DGRAD": "0"}),
+            ("join adjoint reading y", {"BIHOME_JOIN_REMASK": "0"}), ("one stream", {"BIHOME_OVERLAP": "0"}),
+            ("deterministic calls", {"BIHOME_DETERMINISTIC": "1"})]
 if os.environ.get("PDS_ONLY_PERTURB") == "1":
     VARIANTS = [("inputs x (1 + %d 2^-22)" % k, {"PDS_PERTURB": str(k)}) for k in range(0, 9)]
 for prec in (("f32-mfma", "f16x2") if os.environ.get("PDS_ONLY_PERTURB") == "1" else ("f32x3", "f16x2", "f32-mfma")):
