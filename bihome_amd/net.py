@@ -12,6 +12,9 @@ MI355X-first choices:
     into a flat fp32 buffer whose slices are the parameters' `.grad` views (one contiguous RCCL payload);
   * every launch goes to the current HIP stream with static shapes, so a whole step can be captured
     in a HIP graph.
+
+Which launches are fused into their neighbours is decided in plan.py (ForwardPlan / BackwardPlan, cached on the Program);
+run_forward / run_backward below execute a plan: one arm per op kind, run-time guards only.
 """
 import os
 import weakref
@@ -20,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
+from . import plan as P
 
 
 # -----------------------------------------------------------------------------------------------
@@ -128,6 +132,31 @@ class Program:
     def __init__(self):
         self.ops = []
         self.nslots = 1
+        self._index = None
+        self.fw_plans, self.bw_plans = {}, {}             # plan.forward_plan / backward_plan: key -> plan
+        self.last_forward_plan = self.last_backward_plan = None
+
+    def index(self):
+        """Producer / consumer maps over the op list (plan.ProgramIndex), made once: a program is built in one go and not extended after
+        it first ran (the plans made from a shorter op list are dropped if it is)."""
+        if self._index is None or self._index.nops != len(self.ops):
+            self.fw_plans.clear()
+            self.bw_plans.clear()
+            self._index = P.ProgramIndex(self.ops)
+        return self._index
+
+    def plans(self):
+        """The fusion plans kept on this program and the two that the most recent forward / backward pass ran with."""
+        return {"forward": dict(self.fw_plans), "backward": dict(self.bw_plans),
+                "last_forward": self.last_forward_plan, "last_backward": self.last_backward_plan}
+
+    def invalidate(self):
+        """Drop everything derived from the op list and the conv geometry: the index, the plans and the memoised descriptors."""
+        self._index = None
+        self.fw_plans.clear()
+        self.bw_plans.clear()
+        self.last_forward_plan = self.last_backward_plan = None
+        _GEOM_CACHE.clear()
 
     def _new(self):
         self.nslots += 1
@@ -209,6 +238,7 @@ class Ctx:
     def __init__(self):
         self.slots, self.stats, self.descs, self.weights, self.wkeys, self.wpacked = {}, {}, {}, {}, {}, {}
         self.joined = {}          # join BatchNorm op index -> lower-branch BatchNorm op index (kernels.bn_join_fwd)
+        self.precision = 0
 
 
 _GEOM_CACHE = {}
@@ -298,16 +328,169 @@ def _zero_arenas(n_doubles, n_floats, device):
     return a, b
 
 
+class _FwPass:
+    """What the arms of one run_forward call share (one object per pass)."""
+    __slots__ = ("prog", "plan", "slots", "ready", "arena", "amax_next", "ctx", "save", "groups", "training", "precision", "packer",
+                 "fold_cache", "input_source")
+
+
+def _bn_stats_slice(s, i, C):
+    """The float64 sums of BatchNorm op `i` (C channels) in the pass's zeroed arena."""
+    off = s.plan.bn_off[i]
+    return s.arena[off:off + K.bn_stats_doubles(s.groups, C)]
+
+
+def _count_batch(m, groups):
+    """Flushed to the `num_batches_tracked` buffer lazily (flush_counters): no per-layer launch."""
+    m._bh_pending_batches = getattr(m, "_bh_pending_batches", 0) + groups
+
+
+def _fw_folded_conv(s, i, op):
+    """Inference: the conv deferred to its BatchNorm's position `i`, with the BatchNorm folded into its weights."""
+    cop = s.prog.ops[s.plan.folded[i]]
+    e, slots, fold_cache, precision = cop.extra, s.slots, s.fold_cache, s.precision
+    csrc = slots[cop.src]
+    d = _conv_geometry(cop.mod, csrc.shape, e["in_nchw"], e["out_nchw"], precision)
+    wf, bf = _folded(fold_cache, cop.mod, op.mod, e["weight_fn"])
+    pf = None
+    if precision in K.SPLIT_PIECES and d.bh_packs and e["weight_fn"] is None:
+        # f32x3 inference: the folded weights in cut fragment order (packed once per fold)
+        ent = fold_cache[(id(cop.mod), id(op.mod))]
+        if len(ent) < 4 or ent[3] is None:
+            pk = K.packer_for_precision(precision)
+            pf, _ = pk.get(wf, need_dgrad=False)
+            pk.refresh()
+            fold_cache[(id(cop.mod), id(op.mod))] = (ent[0], ent[1], ent[2], pf)
+        else:
+            pf = ent[3]
+    return K.conv_fwd(csrc, kview(wf), bf, d, res=slots[op.res] if op.res is not None else None, relu=op.relu, wpacked=pf,
+                      warp_src=s.input_source if cop.src == 0 else None)
+
+
+def _fw_conv(s, i, op, src):
+    e, packer, groups, amax_next = op.extra, s.packer, s.groups, s.amax_next
+    d = _conv_geometry(op.mod, src.shape, e["in_nchw"], e["out_nchw"], s.precision)
+    w = e["weight_fn"](op.mod.weight) if e["weight_fn"] else op.mod.weight
+    wk = kview(w)
+    pk = None
+    if packer is not None and e["weight_fn"] is None and d.bh_packs and id(op.mod.weight) in packer.entries:
+        pk = packer.entries[id(op.mod.weight)]
+    wsrc = s.input_source if op.src == 0 else None
+    fused_stats = s.plan.fused_stats
+    if i in fused_stats and d.N % groups == 0:
+        b = fused_stats[i]
+        out = K.conv_fwd(src, wk, op.mod.bias, d, bn_sums=_bn_stats_slice(s, b, d.Co), groups=groups,
+                         wpacked=pk[1] if pk else None, warp_src=wsrc)
+        s.ready.add(b)
+    elif amax_next and pk is None and isinstance(op.mod, nn.ConvTranspose2d) and not e["out_nchw"]:
+        # a transposed conv in front of a packed fp16-piece 3x3 conv (the decoder units): the magnitude record of its output from
+        # its own epilogue instead of a bh_absmax pass over the (up to 268 MB) tensor
+        out = K.conv_fwd(src, wk, op.mod.bias, d, amax=amax_next(), warp_src=wsrc)
+    else:
+        out = K.conv_fwd(src, wk, op.mod.bias, d, wpacked=pk[1] if pk else None, warp_src=wsrc)
+    if s.save:
+        ctx = s.ctx
+        ctx.descs[i], ctx.weights[i] = d, wk
+        ctx.wpacked[i] = pk[2] if pk else None
+        ctx.wkeys[i] = (op.mod.weight, op.mod.weight._version)
+    return out
+
+
+def _bn_on_load_ok(s, i, op, src):
+    """Run-time half of the BatchNorm-on-load decisions (plan.plan_bn_on_load / plan_bn_on_load_1x1): the sums came from the producer's
+    epilogue, the batch divides into the statistics groups, and the consumer can take the un-materialised operand."""
+    m, groups, plan = op.mod, s.groups, s.plan
+    if i in plan.bn_on_load_1x1 and i in s.ready and src.shape[0] % groups == 0 and (src.numel() // (m.num_features * groups)) % 128 == 0:
+        return True
+    if i in plan.bn_on_load and i in s.ready and src.shape[0] % groups == 0:
+        cop = s.prog.ops[plan.consumer[op.dst]]
+        cd = _conv_geometry(cop.mod, src.shape, False, cop.extra["out_nchw"], s.precision)
+        # (the consumer's weight gradient must fit the fixed f32x3 workspace, else its backward could not take the
+        #  un-materialised operand: decided here, before the BatchNorm output is elided)
+        return bool(cd.bh_packs and cd.bh_wx3 and 0 < cd.bh_wx3_bytes <= (DET_WS_BYTES if K.deterministic() else X3_WS_BYTES))
+    return False
+
+
+def _fw_bn(s, i, op, src):
+    m, plan, groups, training, amax_next = op.mod, s.plan, s.groups, s.training, s.amax_next
+    res = s.slots[op.res] if op.res is not None else None
+    if i in plan.join_lower and src.shape[0] % groups == 0:
+        # the lower branch of a join: statistics only (from the producer's epilogue, else one pass); applied inside the join
+        st = _bn_stats_slice(s, i, m.num_features)
+        if i not in s.ready:
+            K.bn_stats(src, st, groups, m.num_features)
+        out = K.BnJoinPending(src, st, m)
+    elif i in plan.joins and isinstance(res, K.BnJoinPending) and src.shape[0] % groups == 0:
+        st = _bn_stats_slice(s, i, m.num_features)
+        if i not in s.ready:
+            K.bn_stats(src, st, groups, m.num_features)
+        out = K.bn_join_fwd(src, res.x, m, res.mod, st, res.stats, groups, op.relu, _momentum(m), _momentum(res.mod),
+                            amax=amax_next() if amax_next else None)
+        if s.save:
+            s.ctx.joined[i] = plan.joins[i]
+    else:
+        if isinstance(res, K.BnJoinPending):          # (a join that could not be formed after all: apply the lower BatchNorm now)
+            lo, _ = K.bn_fwd(res.x, res.mod.weight, res.mod.bias, res.mod.running_mean, res.mod.running_var, None, groups, res.mod.eps,
+                             _momentum(res.mod), False, training, stats=res.stats, stats_ready=True)
+            res = s.slots[op.res] = lo
+        st = _bn_stats_slice(s, i, m.num_features)
+        if i in plan.bn_pool and src.dim() == 4 and src.shape[0] % groups == 0:
+            out = K.bn_maxpool_fwd(src, m.weight, m.bias, m.running_mean, m.running_var, groups, m.eps, _momentum(m), op.relu,
+                                   training, st, i in s.ready, want_index=s.save, amax=amax_next() if amax_next else None)
+        elif _bn_on_load_ok(s, i, op, src):
+            rec = amax_next() if amax_next else None
+            table = K.bn_fwd_coeffs(st, m.weight, m.bias, m.running_mean, m.running_var, groups,
+                                    src.numel() // (m.num_features * groups), m.num_features, m.eps, _momentum(m), amax=rec)
+            out = K.BnOnLoad(src, table, groups, op.relu, amax=rec)
+        else:
+            out, st = K.bn_fwd(src, m.weight, m.bias, m.running_mean, m.running_var, res, groups, m.eps, _momentum(m), op.relu, training,
+                               stats=st, stats_ready=i in s.ready, amax=amax_next() if (amax_next and m.num_features > 1) else None)
+    if training:            # (joins are planned in training mode only)
+        _count_batch(m, groups)
+    if s.save:
+        s.ctx.stats[i] = st
+    return out
+
+
+def _fw_tail(s, i, op, src):
+    c1, bn, c2 = op.mod
+    N, h, w, _ = src.shape
+    out, ws = K.tail_fwd(src, kview(c1.weight), c1.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                         kview(c2.weight), c2.bias, s.groups, h * w, bn.eps, _momentum(bn), s.training)
+    if s.training:
+        _count_batch(bn, s.groups)
+    if s.save:
+        s.ctx.stats[i] = ws
+    return out
+
+
+def _fw_maxpool(s, i, op, src):
+    if isinstance(src, K.BnPooled):               # pooled by the fused BatchNorm kernel already
+        out, idx = src.pooled, src.idx
+    else:
+        out, idx = K.maxpool_fwd(src, want_index=s.save)
+    if s.save:
+        s.ctx.stats[i] = idx
+    return out
+
+
+def _fw_gap(s, i, op, src):
+    return K.gap_fwd(src)
+
+
+_FW_ARMS = {"conv": _fw_conv, "bn": _fw_bn, "tail": _fw_tail, "maxpool": _fw_maxpool, "gap": _fw_gap}
+
+
 def run_forward(prog, x, groups, training, save, precision=0, fold_cache=None, packer=None, input_source=None):
     """packer: kernels.WeightPacker holding fragment-ordered copies of the 3x3 weights (refreshed here, one launch, when
     a parameter changed): the halo-tiled 3x3 kernel then streams its B operand straight into registers.
     x: NHWC (or NCHW when the first conv is flagged in_nchw). Returns (out, ctx|None).
     fold_cache (inference only: not training, nothing saved): a dict - every conv whose only consumer is a BatchNorm
     runs with that BatchNorm folded into its weights and the ReLU / residual add fused into its epilogue.
-    input_source (round 6): x is an unfilled buffer - the homography warp of input_source["src"], which the conv that reads the input
+    input_source: x is an unfilled buffer - the homography warp of input_source["src"], which the conv that reads the input
     makes on the way (kernels.conv_fwd warp_src) or has made in front of it."""
-    ctx = Ctx() if save else None
-    if int(precision) == K.F16X2 and (packer is None or not packer.f16):
+    precision = int(precision)
+    if precision == K.F16X2 and (packer is None or not packer.f16):
         # the fp16-piece kernels exist for packed weights with magnitude records of their operands (the BatchNorm kernels of a
         # training-style pass leave them); the BatchNorm-folded inference pass runs the exact three-piece arithmetic
         precision = 2
@@ -315,251 +498,25 @@ def run_forward(prog, x, groups, training, save, precision=0, fold_cache=None, p
         # a forward that saves for backward is (probably) followed by an optimizer step, whatever module.training says
         # (frozen-BatchNorm fine-tuning runs the backbone in eval() mode): fused optimizers do not bump version counters
         packer.refresh(training or save)
-    slots = {0: x}
+    plan = P.forward_plan(prog, training, groups, precision, packer, fold_cache is not None and not training and not save)
+    s = _FwPass()
+    s.prog, s.plan, s.groups, s.training, s.save, s.precision = prog, plan, groups, training, save, precision
+    s.packer, s.fold_cache, s.input_source = packer, fold_cache, input_source
+    s.slots = slots = {0: x}
+    s.ready = set()
+    s.ctx = ctx = Ctx() if save else None
     if save:
-        ctx.groups, ctx.training, ctx.precision = groups, training, int(precision)
-    # precision 4: one zeroed arena of magnitude records, one per BatchNorm output (the operands of the fp16-piece 3x3 kernels)
-    amax_next = None
-    nrec = 0
-    if int(precision) == K.F16X2:
-        nrec = max(1, sum(1 for op in prog.ops if op.kind == "bn" or (op.kind == "conv" and isinstance(op.mod, nn.ConvTranspose2d))))
-    # BatchNorm sums: one zeroed float64 arena for the whole pass (the kernels accumulate with atomics); a conv whose
-    # only consumer is a training-mode BatchNorm accumulates that layer's statistics in its own epilogue
-    bn_off, total = {}, 0
-    for i, op in enumerate(prog.ops):
-        if op.kind == "bn":
-            bn_off[i] = total
-            total += K.bn_stats_doubles(groups, op.mod.num_features)
-    arena, amax_arena = _zero_arenas(total, nrec * K.AMAX_FLOATS, x.device)          # (one fill launch for both)
-    if nrec:
-        amax_iter = iter(amax_arena.split(K.AMAX_FLOATS))
-        amax_next = lambda: next(amax_iter)
-    # the fusion plan below (which conv feeds which BatchNorm's sums, which BatchNorms are applied on load or joined) depends on the program, the
-    # mode and the weight packer only: computed once per (mode, groups, arithmetic, packer) and kept on the program, as run_backward's
-    # (the packer is named by its serial number, not by id(): an id can be reused by another packer after garbage collection)
-    fw_key = (bool(training), int(groups), int(precision), packer.serial if packer is not None else 0,
-              len(packer.entries) if packer is not None else 0, bool(packer.f16) if packer is not None else False,
-              tuple(op.mod.weight.requires_grad for op in prog.ops if op.kind == "conv"))
-    fw_plans = prog.__dict__.setdefault("_fw_plans", {})
-    fw_cached = fw_plans.get(fw_key)
-    consumer = None
-    if fw_cached is None:
-        fused_stats = {}                                      # conv op index -> bn op index
-        if training:
-            users = {}
-            for op in prog.ops:
-                users[op.src] = users.get(op.src, 0) + 1
-                if op.res is not None:
-                    users[op.res] = users.get(op.res, 0) + 1
-            producer = {op.dst: j for j, op in enumerate(prog.ops)}
-            for i, op in enumerate(prog.ops):
-                j = producer.get(op.src)
-                if (op.kind == "bn" and j is not None and prog.ops[j].kind == "conv" and users.get(op.src, 0) == 1
-                        and not prog.ops[j].extra["out_nchw"] and prog.ops[j].mod.weight.dim() == 4):
-                    fused_stats[j] = i
-        # BatchNorm-on-load: a training-mode BatchNorm(+ReLU) without residual whose ONLY consumer is a 3x3 conv that runs the packed
-        # f32x3 forward and the f32x3 weight gradient is not applied at all - the consumer transforms the BatchNorm's INPUT while
-        # staging it (kernels.BnOnLoad): one launch and two tensor passes per such layer gone (the inner BatchNorm of every
-        # residual unit).  Needs the sums from the producer's epilogue (fused_stats) and a table of <= 4 KB.
-        bn_on_load = set()
-        bn_on_load_1x1 = set()
-        if training and groups <= 2 and int(precision) != 1:      # (not the bf16-operand mode)
-            # round 4: the same for a 1x1 / stride-1 conv consumer with <= 32 channels on one side (the 1x1 conv of the decoder units behind
-            # BatchNorm + ReLU at 64 x 64 and 128 x 128): generic forward kernel and small-channel weight-gradient kernel transform on load
-            consumer_ = {}
-            for j, op in enumerate(prog.ops):
-                consumer_.setdefault(op.src, j)
-            fused_bn_ = set(fused_stats.values())
-            for i, op in enumerate(prog.ops):
-                j = consumer_.get(op.dst)
-                if (op.kind == "bn" and op.res is None and i in fused_bn_ and users.get(op.dst, 0) == 1 and j is not None
-                        and prog.ops[j].kind == "conv" and prog.ops[j].src == op.dst and prog.ops[j].extra["weight_fn"] is None
-                        and not prog.ops[j].extra["in_nchw"] and not prog.ops[j].extra["out_nchw"] and isinstance(prog.ops[j].mod, nn.Conv2d)
-                        and prog.ops[j].mod.kernel_size == (1, 1) and prog.ops[j].mod.stride == (1, 1) and prog.ops[j].mod.padding == (0, 0)
-                        and prog.ops[j].mod.in_channels % 32 == 0 and prog.ops[j].mod.out_channels % 4 == 0
-                        and min(prog.ops[j].mod.in_channels, prog.ops[j].mod.out_channels) <= 32 and prog.ops[j].mod.weight.requires_grad):
-                    bn_on_load_1x1.add(i)
-        if training and packer is not None and int(precision) in K.SPLIT_PIECES:
-            consumer = {}
-            for j, op in enumerate(prog.ops):
-                consumer.setdefault(op.src, j)
-            fused_bn = set(fused_stats.values())
-            for i, op in enumerate(prog.ops):
-                j = consumer.get(op.dst)
-                if (op.kind == "bn" and op.res is None and i in fused_bn and users.get(op.dst, 0) == 1 and j is not None
-                        and prog.ops[j].kind == "conv" and prog.ops[j].src == op.dst and prog.ops[j].extra["weight_fn"] is None
-                        and not prog.ops[j].extra["in_nchw"] and id(prog.ops[j].mod.weight) in packer.entries
-                        and groups * op.mod.num_features * 8 <= 4096):
-                    bn_on_load.add(i)
-        # Two-branch join (round 4): a training-mode BatchNorm whose residual input is itself the output of a training-mode BatchNorm that
-        # nobody else reads (the lower branch of ResNet50DeconvBlock / the strided ResNet34ConvBlock): the lower BatchNorm is not applied
-        # on its own - both are applied, added and rectified in ONE pass (kernels.bn_join_fwd), the adjoint is one reduce + one apply
-        joins = {}                                            # join bn op index -> lower bn op index
-        if training:
-            producer_ = {op.dst: j for j, op in enumerate(prog.ops)}
-            for i, op in enumerate(prog.ops):
-                j = producer_.get(op.res) if (op.kind == "bn" and op.res is not None) else None
-                if (j is not None and prog.ops[j].kind == "bn" and prog.ops[j].res is None and not prog.ops[j].relu
-                        and users.get(op.res, 0) == 1 and j not in bn_on_load and i not in bn_on_load
-                        and op.mod.num_features == prog.ops[j].mod.num_features and op.mod.num_features % 4 == 0
-                        and op.mod.weight is not None and prog.ops[j].mod.weight is not None):
-                    joins[i] = j
-        join_lower = set(joins.values())
-        if len(fw_plans) > 16:
-            fw_plans.clear()
-        fw_plans[fw_key] = (fused_stats, bn_on_load, bn_on_load_1x1, joins, join_lower, consumer)
-    else:
-        fused_stats, bn_on_load, bn_on_load_1x1, joins, join_lower, consumer = fw_cached
-    folded = {}                                           # bn op index -> conv op index (conv deferred to the bn's position)
-    if fold_cache is not None and not training and not save:
-        users = {}
-        for op in prog.ops:
-            users[op.src] = users.get(op.src, 0) + 1
-            if op.res is not None:
-                users[op.res] = users.get(op.res, 0) + 1
-        producer = {op.dst: j for j, op in enumerate(prog.ops)}
-        for i, op in enumerate(prog.ops):
-            j = producer.get(op.src)
-            if (op.kind == "bn" and j is not None and prog.ops[j].kind == "conv" and users.get(op.src, 0) == 1
-                    and not prog.ops[j].extra["out_nchw"]):
-                folded[i] = j
-    deferred = set(folded.values())
-    ready = set()
+        ctx.groups, ctx.training, ctx.precision = groups, training, precision
+    s.arena, amax_arena = _zero_arenas(plan.total, plan.nrec * K.AMAX_FLOATS, x.device)          # (one fill launch for both)
+    s.amax_next = iter(amax_arena.split(K.AMAX_FLOATS)).__next__ if plan.nrec else None
+    folded, deferred, arms = plan.folded, plan.deferred, _FW_ARMS
     for i, op in enumerate(prog.ops):
         if i in deferred:
             continue
-        src = slots.get(op.src)
         if i in folded:
-            cop = prog.ops[folded[i]]
-            e = cop.extra
-            csrc = slots[cop.src]
-            d = _conv_geometry(cop.mod, csrc.shape, e["in_nchw"], e["out_nchw"], precision)
-            wf, bf = _folded(fold_cache, cop.mod, op.mod, e["weight_fn"])
-            pf = None
-            if int(precision) in K.SPLIT_PIECES and d.bh_packs and e["weight_fn"] is None:
-                # f32x3 inference: the folded weights in cut fragment order (packed once per fold)
-                ent = fold_cache[(id(cop.mod), id(op.mod))]
-                if len(ent) < 4 or ent[3] is None:
-                    pk = K.packer_for_precision(precision)
-                    pf, _ = pk.get(wf, need_dgrad=False)
-                    pk.refresh()
-                    fold_cache[(id(cop.mod), id(op.mod))] = (ent[0], ent[1], ent[2], pf)
-                else:
-                    pf = ent[3]
-            out = K.conv_fwd(csrc, kview(wf), bf, d, res=slots[op.res] if op.res is not None else None, relu=op.relu, wpacked=pf,
-                             warp_src=input_source if cop.src == 0 else None)
-        elif op.kind == "conv":
-            e = op.extra
-            d = _conv_geometry(op.mod, src.shape, e["in_nchw"], e["out_nchw"], precision)
-            w = e["weight_fn"](op.mod.weight) if e["weight_fn"] else op.mod.weight
-            wk = kview(w)
-            pk = None
-            if packer is not None and e["weight_fn"] is None and d.bh_packs and id(op.mod.weight) in packer.entries:
-                pk = packer.entries[id(op.mod.weight)]
-            wsrc = input_source if op.src == 0 else None
-            if i in fused_stats and d.N % groups == 0:
-                b = fused_stats[i]
-                out = K.conv_fwd(src, wk, op.mod.bias, d,
-                                 bn_sums=arena[bn_off[b]:bn_off[b] + K.bn_stats_doubles(groups, d.Co)], groups=groups,
-                                 wpacked=pk[1] if pk else None, warp_src=wsrc)
-                ready.add(b)
-            elif amax_next and pk is None and isinstance(op.mod, nn.ConvTranspose2d) and not e["out_nchw"]:
-                # a transposed conv in front of a packed fp16-piece 3x3 conv (the decoder units): the magnitude record of its output from
-                # its own epilogue instead of a bh_absmax pass over the (up to 268 MB) tensor
-                out = K.conv_fwd(src, wk, op.mod.bias, d, amax=amax_next(), warp_src=wsrc)
-            else:
-                out = K.conv_fwd(src, wk, op.mod.bias, d, wpacked=pk[1] if pk else None, warp_src=wsrc)
-            if save:
-                ctx.descs[i], ctx.weights[i] = d, wk
-                ctx.wpacked[i] = pk[2] if pk else None
-                ctx.wkeys[i] = (op.mod.weight, op.mod.weight._version)
-        elif op.kind == "bn":
-            m = op.mod
-            res = slots[op.res] if op.res is not None else None
-            lazy = False
-            if i in join_lower and src.shape[0] % groups == 0:
-                # the lower branch of a join: statistics only (from the producer's epilogue, else one pass); applied inside the join
-                st = arena[bn_off[i]:bn_off[i] + K.bn_stats_doubles(groups, m.num_features)]
-                if i not in ready:
-                    K.bn_stats(src, st, groups, m.num_features)
-                m._bh_pending_batches = getattr(m, "_bh_pending_batches", 0) + groups
-                if save:
-                    ctx.stats[i] = st
-                slots[op.dst] = K.BnJoinPending(src, st, m)
-                continue
-            if i in joins and isinstance(res, K.BnJoinPending) and src.shape[0] % groups == 0:
-                st = arena[bn_off[i]:bn_off[i] + K.bn_stats_doubles(groups, m.num_features)]
-                if i not in ready:
-                    K.bn_stats(src, st, groups, m.num_features)
-                out = K.bn_join_fwd(src, res.x, m, res.mod, st, res.stats, groups, op.relu, _momentum(m), _momentum(res.mod),
-                                    amax=amax_next() if amax_next else None)
-                m._bh_pending_batches = getattr(m, "_bh_pending_batches", 0) + groups
-                if save:
-                    ctx.stats[i] = st
-                    ctx.joined[i] = joins[i]
-                slots[op.dst] = out
-                continue
-            if isinstance(res, K.BnJoinPending):          # (a join that could not be formed after all: apply the lower BatchNorm now)
-                lo, _ = K.bn_fwd(res.x, res.mod.weight, res.mod.bias, res.mod.running_mean, res.mod.running_var, None, groups, res.mod.eps,
-                                 _momentum(res.mod), False, training, stats=res.stats, stats_ready=True)
-                res = slots[op.res] = lo
-            nxt = prog.ops[i + 1] if i + 1 < len(prog.ops) else None
-            if (res is None and nxt is not None and nxt.kind == "maxpool" and nxt.src == op.dst and src.dim() == 4 and src.shape[0] % groups == 0
-                    and m.num_features % 4 == 0 and m.num_features > 1 and sum(1 for o_ in prog.ops if o_.src == op.dst or o_.res == op.dst) == 1):
-                # BatchNorm (+ReLU) -> MaxPool2d(3, 2, 1), its only consumer: one pass, the activation in between is never stored
-                st = arena[bn_off[i]:bn_off[i] + K.bn_stats_doubles(groups, m.num_features)]
-                slots[op.dst] = K.bn_maxpool_fwd(src, m.weight, m.bias, m.running_mean, m.running_var, groups, m.eps, _momentum(m), op.relu,
-                                                 training, st, i in ready, want_index=save, amax=amax_next() if amax_next else None)
-                if training:
-                    m._bh_pending_batches = getattr(m, "_bh_pending_batches", 0) + groups
-                if save:
-                    ctx.stats[i] = st
-                continue
-            if i in bn_on_load_1x1 and i in ready and src.shape[0] % groups == 0 and (src.numel() // (m.num_features * groups)) % 128 == 0:
-                lazy = True
-            elif i in bn_on_load and i in ready and src.shape[0] % groups == 0:
-                cop = prog.ops[consumer[op.dst]]
-                cd = _conv_geometry(cop.mod, src.shape, False, cop.extra["out_nchw"], precision)
-                # (the consumer's weight gradient must fit the fixed f32x3 workspace, else its backward could not take the
-                #  un-materialised operand: decided here, before the BatchNorm output is elided)
-                lazy = bool(cd.bh_packs and cd.bh_wx3 and 0 < cd.bh_wx3_bytes <= (DET_WS_BYTES if K.deterministic() else X3_WS_BYTES))
-            if lazy:
-                st = arena[bn_off[i]:bn_off[i] + K.bn_stats_doubles(groups, m.num_features)]
-                rec = amax_next() if amax_next else None
-                table = K.bn_fwd_coeffs(st, m.weight, m.bias, m.running_mean, m.running_var, groups,
-                                        src.numel() // (m.num_features * groups), m.num_features, m.eps, _momentum(m), amax=rec)
-                out = K.BnOnLoad(src, table, groups, op.relu, amax=rec)
-            else:
-                out, st = K.bn_fwd(src, m.weight, m.bias, m.running_mean, m.running_var, res, groups, m.eps,
-                                   _momentum(m), op.relu, training,
-                                   stats=arena[bn_off[i]:bn_off[i] + K.bn_stats_doubles(groups, m.num_features)],
-                                   stats_ready=i in ready, amax=amax_next() if (amax_next and m.num_features > 1) else None)
-            if training:        # flushed to the `num_batches_tracked` buffer lazily (flush_counters): no per-layer launch
-                m._bh_pending_batches = getattr(m, "_bh_pending_batches", 0) + groups
-            if save:
-                ctx.stats[i] = st
-        elif op.kind == "tail":
-            c1, bn, c2 = op.mod
-            N, h, w, _ = src.shape
-            out, ws = K.tail_fwd(src, kview(c1.weight), c1.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                 kview(c2.weight), c2.bias, groups, h * w, bn.eps,
-                                 _momentum(bn), training)
-            if training:
-                bn._bh_pending_batches = getattr(bn, "_bh_pending_batches", 0) + groups
-            if save:
-                ctx.stats[i] = ws
-        elif op.kind == "maxpool":
-            if isinstance(src, K.BnPooled):               # pooled by the fused BatchNorm kernel already
-                out, idx = src.pooled, src.idx
-            else:
-                out, idx = K.maxpool_fwd(src, want_index=save)
-            if save:
-                ctx.stats[i] = idx
-        elif op.kind == "gap":
-            out = K.gap_fwd(src)
+            slots[op.dst] = _fw_folded_conv(s, i, op)
         else:
-            raise RuntimeError(op.kind)
-        slots[op.dst] = out
+            slots[op.dst] = arms[op.kind](s, i, op, slots.get(op.src))
     if save:
         ctx.slots = slots
     return slots[prog.ops[-1].dst], ctx
@@ -577,7 +534,181 @@ def side_stream(device):
     return _SIDE_STREAMS[key]
 
 
-_FROM_1X1_KC = (16,)      # output channels of the 1x1 convs whose dgrad the BatchNorm in front rebuilds (run_backward)
+class _BwPass:
+    """What the arms of one run_backward call share (one object per pass)."""
+    __slots__ = ("prog", "plan", "ctx", "slots", "grads", "bn_reduced", "red_arena", "amax_next", "want_wgrad", "want_input_grad",
+                 "on_param_grad", "wgrad_stream", "main", "det_ws", "x3_ws", "input_sink")
+
+
+def _contribute(grads, slot, g):
+    if slot in grads:
+        K.add_(grads[slot], g)
+    else:
+        grads[slot] = g
+
+
+def _params_ready(s, *params):
+    """The gradients of these parameters are final: their bucket may leave."""
+    if s.on_param_grad is not None:
+        for p in params:
+            if p is not None:
+                s.on_param_grad(p)
+
+
+def _enqueue_wgrad(s, i, op, g, x, d):
+    """Weight (and bias) gradient of conv op `i`: on the side stream behind an event when there is one (g is final here)."""
+    m, wgrad_stream, red_arena, bias_off = op.mod, s.wgrad_stream, s.red_arena, s.plan.bias_off
+    gw = m.weight.grad if m.weight.dim() == 2 else kview(m.weight.grad)
+    gb = m.bias.grad if (m.bias is not None and m.bias.requires_grad) else None
+    has_gb = gb is not None
+    if i in bias_off and has_gb:              # column sums already taken by the consumer's dgrad epilogue
+        K.bias_grad_from_sums(red_arena[bias_off[i]:bias_off[i] + K.bn_stats_doubles(1, d.Co)], gb, 1, d.Co)
+        gb = None
+    ws = s.det_ws if s.det_ws is not None else (s.x3_ws if d.bh_wx3 else None)
+    # the fp16-piece weight gradient's eight-wave form is the faster launch alone, the four-wave form the better neighbour: it
+    # leaves ~200 registers per SIMD lane, so the main stream's BatchNorm kernels run ON the same CUs (same-box A/B:
+    # two streams 13.30 ms with the four-wave form against 13.49; one stream 14.13 against 14.02)
+    # and with 160 instead of 256 workgroups the side stream leaves CUs to the main stream's next launch (and writes fewer partial
+    # blocks): two streams 12.60 against 12.79 ms (ROUTE_WX3_SHARED)
+    if wgrad_stream is None:
+        d.route = (d.route | K.ROUTE_WX3_PC) & ~K.ROUTE_WX3_SHARED
+    else:
+        d.route = (d.route & ~K.ROUTE_WX3_PC) | K.ROUTE_WX3_SHARED
+    if wgrad_stream is None:
+        K.conv_wgrad(x, g, gw, gb, d, det_ws=ws)
+    else:
+        if s.ctx.precision == K.F16X2 and d.bh_wx3:
+            # magnitude records the fp16-piece weight gradient reads: made (if missing) on the MAIN stream, in front of the
+            # event - a record first measured on the side stream would be read by the main stream's dgrad without a wait
+            # (a still-zero record scales by 2^100)
+            K.amax_of(g)
+            K.amax_of(x)
+        ev = torch.cuda.Event()
+        ev.record(s.main)                                 # g is final here
+        g.record_stream(wgrad_stream)
+        with torch.cuda.stream(wgrad_stream):
+            wgrad_stream.wait_event(ev)
+            K.conv_wgrad(x, g, gw, gb, d, det_ws=ws if d.bh_wx3 else None)     # (one stream: launches serialise on the workspace)
+    _params_ready(s, m.weight, m.bias if has_gb else None)
+
+
+def _bw_conv(s, i, op, g, x, need_src_grad):
+    ctx, plan, grads = s.ctx, s.plan, s.grads
+    d, wk = ctx.descs[i], ctx.weights[i]
+    if s.want_wgrad and op.mod.weight.requires_grad and op.extra["weight_fn"] is None:
+        _enqueue_wgrad(s, i, op, g, x, d)
+    if not need_src_grad:
+        return
+    if i in plan.from_1x1 and op.src not in grads:
+        # the BatchNorm in front rebuilds this dgrad per element in its own adjoint (bn_bwd_from_1x1): nothing is launched here
+        grads[op.src] = K.GradFrom1x1(g, wk)
+        return
+    red = None
+    if i in plan.fuse_bn:
+        b = plan.fuse_bn[i]
+        bop, bm = s.prog.ops[b], s.prog.ops[b].mod
+        sums = s.red_arena[plan.red_off[b]:plan.red_off[b] + K.bn_stats_doubles(ctx.groups, bm.num_features)]
+        red = dict(z=s.slots[bop.src], y=s.slots[bop.dst] if (bop.relu and bop.res is not None) else None,
+                   stats=ctx.stats[b], gamma=bm.weight, beta=bm.bias, eps=bm.eps, relu=bop.relu, sums=sums,
+                   groups=ctx.groups)
+        s.bn_reduced[b] = sums
+    if i in plan.fuse_bias and op.src not in grads and red is None:
+        p = plan.fuse_bias[i]
+        grads[op.src] = K.conv_dgrad(g, wk, d, wpacked=ctx.wpacked.get(i),
+                                     colsum=s.red_arena[plan.bias_off[p]:plan.bias_off[p] + K.bn_stats_doubles(1, d.Ci)])
+    elif op.src in grads:
+        K.conv_dgrad(g, wk, d, out=grads[op.src], bn_reduce=red, wkey=ctx.wkeys[i], wpacked=ctx.wpacked.get(i))
+    else:
+        # (input_sink: the consumer of the INPUT's gradient folded into the first conv's dgrad - the warp's adjoint)
+        gsrc = K.conv_dgrad(g, wk, d, bn_reduce=red, wkey=ctx.wkeys[i], wpacked=ctx.wpacked.get(i),
+                            warp_sink=s.input_sink if (op.src == 0 and red is None) else None)
+        if gsrc is not None:
+            grads[op.src] = gsrc
+
+
+def _bw_bn_join(s, i, op, g, x, need_src_grad):
+    ctx, slots, amax_next = s.ctx, s.slots, s.amax_next
+    j = ctx.joined[i]
+    lop, m, lm = s.prog.ops[j], op.mod, s.prog.ops[j].mod
+    train_a = s.want_wgrad and m.weight.requires_grad
+    train_b = s.want_wgrad and lm.weight.requires_grad
+    xb = slots[lop.src]
+    gxa, gxb = K.bn_join_bwd(g, slots[op.dst], x, xb, m, lm, ctx.stats[i], ctx.stats[j], ctx.groups, op.relu, train_a, train_b,
+                             amax_a=amax_next() if amax_next else None, amax_b=amax_next() if amax_next else None)
+    if train_a:
+        _params_ready(s, m.weight, m.bias)
+    if train_b:
+        _params_ready(s, lm.weight, lm.bias)
+    if need_src_grad:
+        _contribute(s.grads, op.src, gxa)
+    if (lop.src != 0) or s.want_input_grad:
+        _contribute(s.grads, lop.src, gxb)
+
+
+def _bw_bn(s, i, op, g, x, need_src_grad):
+    m, ctx, amax_next = op.mod, s.ctx, s.amax_next
+    train_w = s.want_wgrad and m.weight is not None and m.weight.requires_grad
+    ggamma, gbeta = (m.weight.grad, m.bias.grad) if train_w else (None, None)
+    amax = amax_next() if (amax_next and m.num_features > 1) else None
+    gres = None
+    if isinstance(g, K.GradFrom1x1):             # the 1x1 conv behind this BatchNorm left its dgrad to this call
+        gx = K.bn_bwd_from_1x1(g, x, m.weight, m.bias, ctx.stats[i], ctx.groups, m.eps, op.relu, ggamma, gbeta, amax=amax)
+    elif isinstance(g, K.PooledGrad):            # BatchNorm (+ReLU) + MaxPool in one pass: its adjoint in one call too
+        gx = K.bn_maxpool_bwd(g, x, m.weight, m.bias, ctx.stats[i], m.running_mean, m.running_var, ctx.groups, m.eps, op.relu,
+                              ctx.training, ggamma, gbeta, amax=amax)
+    else:
+        yb = s.slots[op.dst]
+        if isinstance(yb, (K.BnOnLoad, K.BnPooled)):  # applied on load by its consumer / fused with the pooling: no output tensor (the mask comes from x)
+            yb = None
+        gx, gres = K.bn_bwd(g, yb, x, m.weight, ctx.stats[i], m.running_mean, m.running_var, ctx.groups,
+                            m.eps, op.relu, ctx.training, op.res is not None and ((op.res != 0) or s.want_input_grad),
+                            ggamma, gbeta, beta=m.bias, had_res=op.res is not None, sums_ready=s.bn_reduced.get(i), amax=amax)
+    if train_w and s.on_param_grad is not None:
+        s.on_param_grad(m.weight)
+        s.on_param_grad(m.bias)
+    if need_src_grad:
+        _contribute(s.grads, op.src, gx)
+    if gres is not None:
+        _contribute(s.grads, op.res, gres)
+
+
+def _bw_tail(s, i, op, g, x, need_src_grad):
+    ctx = s.ctx
+    c1, bn, c2 = op.mod
+    tr = s.want_wgrad and c1.weight.requires_grad
+    N, h, w, _ = x.shape
+    eval_b1 = tr and not ctx.training and c1.bias is not None and c1.bias.requires_grad
+    gbeta0 = bn.bias.grad.clone() if eval_b1 else None
+    gx = K.tail_bwd(g, x, kview(c1.weight), c1.bias, bn.weight, bn.bias, kview(c2.weight), ctx.stats[i],
+                    bn.running_mean, bn.running_var, ctx.groups, h * w, bn.eps, ctx.training, need_src_grad,
+                    kview(c1.weight.grad) if tr else None, bn.weight.grad if tr else None,
+                    bn.bias.grad if tr else None, kview(c2.weight.grad) if tr else None,
+                    c2.bias.grad if (tr and c2.bias is not None) else None)
+    if eval_b1:
+        # eval-mode BatchNorm is a fixed affine map, so layer8.0.bias has a gradient (with batch statistics it is
+        # exactly zero and the fused kernel never forms it): g_b1 = g_beta * gamma / sqrt(running_var + eps)
+        with torch.no_grad():
+            c1.bias.grad.add_((bn.bias.grad - gbeta0) * bn.weight * torch.rsqrt(bn.running_var + bn.eps))
+    if tr:
+        _params_ready(s, c2.weight, c2.bias, bn.weight, bn.bias, c1.weight, c1.bias)
+    if need_src_grad:
+        _contribute(s.grads, op.src, gx)
+
+
+def _bw_maxpool(s, i, op, g, x, need_src_grad):
+    if need_src_grad:
+        if isinstance(x, K.BnPooled) and op.src not in s.grads:
+            s.grads[op.src] = K.PooledGrad(g, s.ctx.stats[i])          # (consumed by the BatchNorm's adjoint: bn_maxpool_bwd)
+        else:
+            _contribute(s.grads, op.src, K.maxpool_bwd(s.ctx.stats[i], g, tuple(x.shape)))
+
+
+def _bw_gap(s, i, op, g, x, need_src_grad):
+    if need_src_grad:
+        _contribute(s.grads, op.src, K.gap_bwd(g, tuple(x.shape)))
+
+
+_BW_ARMS = {"conv": _bw_conv, "bn": _bw_bn, "tail": _bw_tail, "maxpool": _bw_maxpool, "gap": _bw_gap}
 
 
 def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=None, wgrad_stream=None, det_ws=None, x3_ws=None, input_sink=None):
@@ -590,252 +721,23 @@ def run_backward(prog, ctx, gout, want_wgrad, want_input_grad, on_param_grad=Non
     main = torch.cuda.current_stream() if wgrad_stream is not None else None
     if wgrad_stream is not None:
         wgrad_stream.wait_stream(main)          # activations, zeroed gradient buffer
-    grads = {prog.ops[-1].dst: gout}
-    slots = ctx.slots
-    # (the fusion plan below is a pure function of the program, the mode and the shapes: made once and kept on the program - three
-    #  backward walks per step used to rebuild it, ~0.4 ms of a host that has ~9 ms of enqueueing to do per 12 ms step)
-    # (key: everything the plan reads that can differ between two walks of one program - mode, batch / map geometry via the output
-    #  gradient's shape, the joins made by this forward and the convs it ran - their CONTENTS, not their counts - the precision, which conv
-    #  weights / biases train (fuse_bias reads the flags: freezing a layer between two steps must not reuse the other plan))
-    plan_key = (bool(ctx.training), bool(want_wgrad), int(ctx.groups), tuple(gout.shape), frozenset(ctx.joined.items()), frozenset(ctx.descs),
-                getattr(ctx, "precision", 0),
-                tuple((op.mod.weight.requires_grad, op.mod.bias is not None and op.mod.bias.requires_grad) for op in prog.ops if op.kind == "conv"))
-    plans = prog.__dict__.setdefault("_bw_plans", {})
-    cached = plans.get(plan_key)
-    consumed_by = {}
-    for op in (prog.ops if cached is None else ()):
-        consumed_by.setdefault(op.src, 0)
-        consumed_by[op.src] += 1
-        if op.res is not None:
-            consumed_by[op.res] = consumed_by.get(op.res, 0) + 1
-
-    def contribute(slot, g):
-        if slot in grads:
-            K.add_(grads[slot], g)
-        else:
-            grads[slot] = g
-
-    # A conv dgrad that COMPLETES the gradient of a training-mode BatchNorm's output (it is the last consumer of that
-    # slot in backward order) also accumulates that BatchNorm's backward sums in its epilogue (bh_conv_dgrad_bnreduce),
-    # so the BatchNorm adjoint is one apply launch instead of reduce + finalize + apply.
-    fuse_bn = {}                                          # conv op index -> bn op index
-    if cached is None and ctx.training:
-        producer = {op.dst: j for j, op in enumerate(prog.ops)}
-        last_consumer = {}
-        for j, op in enumerate(prog.ops):                 # the lowest-index consumer is processed last
-            for sl in (op.src, op.res):
-                if sl is not None and sl not in last_consumer:
-                    last_consumer[sl] = j
-        for j, op in enumerate(prog.ops):
-            b = producer.get(op.src)
-            if (op.kind == "conv" and b is not None and prog.ops[b].kind == "bn" and last_consumer.get(op.src) == j
-                    and j in ctx.descs and ctx.descs[j].bh_reduce_ok and ctx.descs[j].N % ctx.groups == 0 and b not in ctx.joined):
-                fuse_bn[j] = b
-    # A 3x3 conv that is the ONLY consumer of a biased (transposed) conv's output: the column sums of its input gradient
-    # are that layer's bias gradient - accumulated in the dgrad epilogue instead of a streaming pass over the gradient
-    fuse_bias = {}                                        # conv op index -> producer op index
-    if cached is None and want_wgrad:
-        producer = {op.dst: j for j, op in enumerate(prog.ops)}
-        for j, op in enumerate(prog.ops):
-            p = producer.get(op.src)
-            if (op.kind == "conv" and j not in fuse_bn and p is not None and prog.ops[p].kind == "conv" and consumed_by.get(op.src, 0) == 1
-                    and j in ctx.descs and p in ctx.descs and ctx.descs[j].bh_reduce_ok):
-                pm = prog.ops[p].mod
-                if pm.bias is not None and pm.bias.requires_grad and pm.weight.requires_grad and prog.ops[p].extra["weight_fn"] is None:
-                    fuse_bias[j] = p
-    # A 1x1 / stride-1 conv with 16 output channels that is the ONLY consumer of a training-mode BatchNorm (+ReLU, no residual, not joined):
-    # its dgrad is rebuilt inside that BatchNorm's adjoint (bh_bn_bwd_from_1x1) - the full-resolution decoder unit's 268 MB gradient is
-    # never written
-    from_1x1 = set()
-    if cached is None and ctx.training:
-        producer_ = {op.dst: j for j, op in enumerate(prog.ops)}
-        for j, op in enumerate(prog.ops):
-            b = producer_.get(op.src)
-            m_ = op.mod
-            if (op.kind == "conv" and b is not None and prog.ops[b].kind == "bn" and prog.ops[b].res is None and b not in ctx.joined
-                    and consumed_by.get(op.src, 0) == 1 and j not in fuse_bn and isinstance(m_, nn.Conv2d) and m_.kernel_size == (1, 1)
-                    and m_.stride == (1, 1) and m_.padding == (0, 0) and op.extra["weight_fn"] is None and m_.out_channels in _FROM_1X1_KC
-                    and prog.ops[b].mod.num_features % 4 == 0 and 256 % (prog.ops[b].mod.num_features // 4) == 0
-                    and not op.extra["in_nchw"] and not op.extra["out_nchw"]):
-                from_1x1.add(j)
-    red_off, total = {}, 0
-    bias_off = {}
-    if cached is None:
-        for j, p in fuse_bias.items():
-            bias_off[p] = total
-            total += K.bn_stats_doubles(1, ctx.descs[j].Ci)
-        for b in fuse_bn.values():
-            red_off[b] = total
-            total += K.bn_stats_doubles(ctx.groups, prog.ops[b].mod.num_features)
-        plans[plan_key] = (consumed_by, fuse_bn, fuse_bias, from_1x1, red_off, bias_off, total)
-    else:
-        consumed_by, fuse_bn, fuse_bias, from_1x1, red_off, bias_off, total = cached
-    bn_reduced = {}
-    # precision 4: magnitude records of the BatchNorm input gradients (the gy operand of the fp16-piece dgrad / weight-gradient kernels)
-    amax_next = None
-    nrec = max(1, sum(1 for op in prog.ops if op.kind == "bn")) if getattr(ctx, "precision", 0) == K.F16X2 else 0
-    red_arena, amax_arena = _zero_arenas(total, nrec * K.AMAX_FLOATS, gout.device)    # (one fill launch for both)
-    if nrec:
-        amax_iter = iter(amax_arena.split(K.AMAX_FLOATS))
-        amax_next = lambda: next(amax_iter)
-
-    for i in range(len(prog.ops) - 1, -1, -1):
-        op = prog.ops[i]
+    plan = P.backward_plan(prog, ctx, gout.shape, want_wgrad)
+    s = _BwPass()
+    s.prog, s.plan, s.ctx, s.slots, s.main, s.wgrad_stream = prog, plan, ctx, ctx.slots, main, wgrad_stream
+    s.want_wgrad, s.want_input_grad, s.on_param_grad = want_wgrad, want_input_grad, on_param_grad
+    s.det_ws, s.x3_ws, s.input_sink = det_ws, x3_ws, input_sink
+    s.grads = grads = {prog.ops[-1].dst: gout}
+    s.bn_reduced = {}
+    s.red_arena, amax_arena = _zero_arenas(plan.total, plan.nrec * K.AMAX_FLOATS, gout.device)    # (one fill launch for both)
+    s.amax_next = iter(amax_arena.split(K.AMAX_FLOATS)).__next__ if plan.nrec else None
+    ops, slots, joined, arms = prog.ops, ctx.slots, ctx.joined, _BW_ARMS
+    for i in range(len(ops) - 1, -1, -1):
+        op = ops[i]
         g = grads.pop(op.dst, None)
         if g is None:
             continue
-        need_src_grad = (op.src != 0) or want_input_grad
-        x = slots[op.src]
-        if op.kind == "conv":
-            d, wk = ctx.descs[i], ctx.weights[i]
-            m = op.mod
-            if want_wgrad and m.weight.requires_grad and op.extra["weight_fn"] is None:
-                gw = m.weight.grad if m.weight.dim() == 2 else kview(m.weight.grad)
-                gb = m.bias.grad if (m.bias is not None and m.bias.requires_grad) else None
-                has_gb = gb is not None
-                if i in bias_off and has_gb:              # column sums already taken by the consumer's dgrad epilogue
-                    K.bias_grad_from_sums(red_arena[bias_off[i]:bias_off[i] + K.bn_stats_doubles(1, d.Co)], gb, 1, d.Co)
-                    gb = None
-                ws = det_ws if det_ws is not None else (x3_ws if getattr(d, "bh_wx3", False) else None)
-                # the fp16-piece weight gradient's eight-wave form is the faster launch alone, the four-wave form the better neighbour: it
-                # leaves ~200 registers per SIMD lane, so the main stream's BatchNorm kernels run ON the same CUs (same-box A/B, round 5:
-                # two streams 13.30 ms with the four-wave form against 13.49; one stream 14.13 against 14.02)
-                # and with 160 instead of 256 workgroups the side stream leaves CUs to the main stream's next launch (and writes fewer partial
-                # blocks): two streams 12.60 against 12.79 ms (ROUTE_WX3_SHARED)
-                if wgrad_stream is None:
-                    d.route = (d.route | K.ROUTE_WX3_PC) & ~K.ROUTE_WX3_SHARED
-                else:
-                    d.route = (d.route & ~K.ROUTE_WX3_PC) | K.ROUTE_WX3_SHARED
-                if wgrad_stream is None:
-                    K.conv_wgrad(x, g, gw, gb, d, det_ws=ws)
-                else:
-                    if getattr(ctx, "precision", 0) == K.F16X2 and getattr(d, "bh_wx3", False):
-                        # magnitude records the fp16-piece weight gradient reads: made (if missing) on the MAIN stream, in front of the
-                        # event - a record first measured on the side stream would be read by the main stream's dgrad without a wait
-                        # (round-4 ADVICE: a still-zero record scales by 2^100)
-                        K.amax_of(g)
-                        K.amax_of(x)
-                    ev = torch.cuda.Event()
-                    ev.record(main)                                   # g is final here
-                    g.record_stream(wgrad_stream)
-                    with torch.cuda.stream(wgrad_stream):
-                        wgrad_stream.wait_event(ev)
-                        K.conv_wgrad(x, g, gw, gb, d, det_ws=ws if getattr(d, "bh_wx3", False) else None)     # (one stream: launches serialise on the workspace)
-                if on_param_grad is not None:                      # gradient of this layer is final: its bucket may leave
-                    on_param_grad(m.weight)
-                    if has_gb:
-                        on_param_grad(m.bias)
-            if need_src_grad and i in from_1x1 and op.src not in grads:
-                # the BatchNorm in front rebuilds this dgrad per element in its own adjoint (bn_bwd_from_1x1): nothing is launched here
-                grads[op.src] = K.GradFrom1x1(g, wk)
-                continue
-            if need_src_grad:
-                red = None
-                if i in fuse_bn:
-                    b = fuse_bn[i]
-                    bop, bm = prog.ops[b], prog.ops[b].mod
-                    sums = red_arena[red_off[b]:red_off[b] + K.bn_stats_doubles(ctx.groups, bm.num_features)]
-                    red = dict(z=slots[bop.src], y=slots[bop.dst] if (bop.relu and bop.res is not None) else None,
-                               stats=ctx.stats[b], gamma=bm.weight, beta=bm.bias, eps=bm.eps, relu=bop.relu, sums=sums,
-                               groups=ctx.groups)
-                    bn_reduced[b] = sums
-                if i in fuse_bias and op.src not in grads and red is None:
-                    p = fuse_bias[i]
-                    grads[op.src] = K.conv_dgrad(g, wk, d, wpacked=ctx.wpacked.get(i),
-                                                 colsum=red_arena[bias_off[p]:bias_off[p] + K.bn_stats_doubles(1, d.Ci)])
-                elif op.src in grads:
-                    K.conv_dgrad(g, wk, d, out=grads[op.src], bn_reduce=red, wkey=ctx.wkeys[i], wpacked=ctx.wpacked.get(i))
-                else:
-                    # (input_sink: the consumer of the INPUT's gradient folded into the first conv's dgrad - the warp's adjoint, round 6)
-                    gsrc = K.conv_dgrad(g, wk, d, bn_reduce=red, wkey=ctx.wkeys[i], wpacked=ctx.wpacked.get(i),
-                                        warp_sink=input_sink if (op.src == 0 and red is None) else None)
-                    if gsrc is not None:
-                        grads[op.src] = gsrc
-        elif op.kind == "bn" and i in ctx.joined:
-            j = ctx.joined[i]
-            lop, m, lm = prog.ops[j], op.mod, prog.ops[j].mod
-            train_a = want_wgrad and m.weight.requires_grad
-            train_b = want_wgrad and lm.weight.requires_grad
-            xb = slots[lop.src]
-            gxa, gxb = K.bn_join_bwd(g, slots[op.dst], x, xb, m, lm, ctx.stats[i], ctx.stats[j], ctx.groups, op.relu, train_a, train_b,
-                                     amax_a=amax_next() if amax_next else None, amax_b=amax_next() if amax_next else None)
-            if on_param_grad is not None:
-                for p_, tr_ in ((m.weight, train_a), (m.bias, train_a), (lm.weight, train_b), (lm.bias, train_b)):
-                    if tr_:
-                        on_param_grad(p_)
-            if need_src_grad:
-                contribute(op.src, gxa)
-            if (lop.src != 0) or want_input_grad:
-                contribute(lop.src, gxb)
-        elif op.kind == "bn":
-            m = op.mod
-            train_w = want_wgrad and m.weight is not None and m.weight.requires_grad
-            yb = slots[op.dst]
-            if isinstance(yb, (K.BnOnLoad, K.BnPooled)):  # applied on load by its consumer / fused with the pooling: no output tensor (the mask comes from x)
-                yb = None
-            if isinstance(g, K.GradFrom1x1):             # the 1x1 conv behind this BatchNorm left its dgrad to this call
-                gx = K.bn_bwd_from_1x1(g, x, m.weight, m.bias, ctx.stats[i], ctx.groups, m.eps, op.relu,
-                                       m.weight.grad if train_w else None, m.bias.grad if train_w else None,
-                                       amax=amax_next() if (amax_next and m.num_features > 1) else None)
-                if train_w and on_param_grad is not None:
-                    on_param_grad(m.weight)
-                    on_param_grad(m.bias)
-                if need_src_grad:
-                    contribute(op.src, gx)
-                continue
-            if isinstance(g, K.PooledGrad):              # BatchNorm (+ReLU) + MaxPool in one pass: its adjoint in one call too
-                gx = K.bn_maxpool_bwd(g, x, m.weight, m.bias, ctx.stats[i], m.running_mean, m.running_var, ctx.groups, m.eps, op.relu,
-                                      ctx.training, m.weight.grad if train_w else None, m.bias.grad if train_w else None,
-                                      amax=amax_next() if (amax_next and m.num_features > 1) else None)
-                if train_w and on_param_grad is not None:
-                    on_param_grad(m.weight)
-                    on_param_grad(m.bias)
-                if need_src_grad:
-                    contribute(op.src, gx)
-                continue
-            gx, gres = K.bn_bwd(g, yb, x, m.weight, ctx.stats[i], m.running_mean, m.running_var, ctx.groups,
-                                m.eps, op.relu, ctx.training, op.res is not None and ((op.res != 0) or want_input_grad),
-                                m.weight.grad if train_w else None, m.bias.grad if train_w else None, beta=m.bias,
-                                had_res=op.res is not None, sums_ready=bn_reduced.get(i),
-                                amax=amax_next() if (amax_next and m.num_features > 1) else None)
-            if train_w and on_param_grad is not None:
-                on_param_grad(m.weight)
-                on_param_grad(m.bias)
-            if need_src_grad:
-                contribute(op.src, gx)
-            if gres is not None:
-                contribute(op.res, gres)
-        elif op.kind == "tail":
-            c1, bn, c2 = op.mod
-            tr = want_wgrad and c1.weight.requires_grad
-            N, h, w, _ = x.shape
-            eval_b1 = tr and not ctx.training and c1.bias is not None and c1.bias.requires_grad
-            gbeta0 = bn.bias.grad.clone() if eval_b1 else None
-            gx = K.tail_bwd(g, x, kview(c1.weight), c1.bias, bn.weight, bn.bias, kview(c2.weight), ctx.stats[i],
-                            bn.running_mean, bn.running_var, ctx.groups, h * w, bn.eps, ctx.training, need_src_grad,
-                            kview(c1.weight.grad) if tr else None, bn.weight.grad if tr else None,
-                            bn.bias.grad if tr else None, kview(c2.weight.grad) if tr else None,
-                            c2.bias.grad if (tr and c2.bias is not None) else None)
-            if eval_b1:
-                # eval-mode BatchNorm is a fixed affine map, so layer8.0.bias has a gradient (with batch statistics it is
-                # exactly zero and the fused kernel never forms it): g_b1 = g_beta * gamma / sqrt(running_var + eps)
-                with torch.no_grad():
-                    c1.bias.grad.add_((bn.bias.grad - gbeta0) * bn.weight * torch.rsqrt(bn.running_var + bn.eps))
-            if tr and on_param_grad is not None:
-                for p_ in (c2.weight, c2.bias, bn.weight, bn.bias, c1.weight, c1.bias):
-                    if p_ is not None:
-                        on_param_grad(p_)
-            if need_src_grad:
-                contribute(op.src, gx)
-        elif op.kind == "maxpool":
-            if need_src_grad:
-                if isinstance(x, K.BnPooled) and op.src not in grads:
-                    grads[op.src] = K.PooledGrad(g, ctx.stats[i])          # (consumed by the BatchNorm's adjoint: bn_maxpool_bwd)
-                else:
-                    contribute(op.src, K.maxpool_bwd(ctx.stats[i], g, tuple(x.shape)))
-        elif op.kind == "gap":
-            if need_src_grad:
-                contribute(op.src, K.gap_bwd(g, tuple(x.shape)))
+        arm = _bw_bn_join if (op.kind == "bn" and i in joined) else arms[op.kind]
+        arm(s, i, op, g, slots[op.src], (op.src != 0) or want_input_grad)
     if wgrad_stream is not None:
         main.wait_stream(wgrad_stream)          # the optimiser (and the release of the activations) follows
     return grads.get(0)
@@ -1020,11 +922,8 @@ class Runner:
         if self._packer is None or self._packer_dev != device:
             pk = K.packer_for_precision(self.precision)
             for op in self.prog.ops:
-                m = op.mod
-                if (op.kind == "conv" and isinstance(m, nn.Conv2d) and op.extra["weight_fn"] is None and m.kernel_size == (3, 3)
-                        and m.stride == (1, 1) and m.padding == (1, 1) and m.in_channels % 32 == 0 and m.out_channels % 32 == 0
-                        and m.weight.device == device):
-                    pk.get(m.weight)
+                if P.packs_weight(op, device):
+                    pk.get(op.mod.weight)
             self._packer, self._packer_dev = pk, device
         return self._packer
 

@@ -169,6 +169,38 @@ def test_zeng_train_step_vs_golden(zeng, golden):
     assert all(np.isfinite(losses))
 
 
+def test_training_step_runs_the_plans_the_cpu_planner_makes(zeng):
+    """The fusion plans a B=8 training step actually ran with (Program.plans()) are the ones bihome_amd.plan makes on the host for the
+    same program and key - what tests/test_plan_cpu.py pins without a GPU is what runs."""
+    from bihome_amd import plan as P
+    from bihome_amd.step import build_optimizer, train_step
+    from test_plan_cpu import _saved_ctx
+    cfg, model = zeng
+    load_synthetic(model[0], 0)
+    opt, sched = build_optimizer(model, cfg["SOLVER"])
+    d = synth.make_pairs(8, seed=42)
+    data = {k: cuda(d[k]) for k in ("patch_1", "patch_2", "delta")}
+    model.train()
+    train_step(model, data, opt, sched)
+    runner = model[0]._runner
+    prog = runner.prog
+    used = prog.plans()
+    fw, bw = used["last_forward"], used["last_backward"]
+    packer = runner.packer_for(torch.device("cuda", torch.cuda.current_device()))
+    assert fw is used["forward"][P.forward_key(prog, True, 2, runner.precision, packer, False)]
+    assert set(packer.entries) == P.packed_weight_ids(prog)
+    want = P.make_forward_plan(prog, True, 2, runner.precision, P.packed_weight_ids(prog))
+    for f in P.ForwardPlan.__slots__:
+        assert getattr(fw, f) == getattr(want, f), f
+    assert len(fw.bn_on_load) == 19 and len(fw.joins) == 6 and fw.bn_pool == {1}          # (as pinned in test_plan_cpu.py)
+    ctx = _saved_ctx(prog, (16, 2, 128, 128), 2, True, runner.precision, fw.joins)
+    assert bw is used["backward"][P.backward_key(prog, ctx, (16, 2, 128, 128), True)]
+    want = P.make_backward_plan(prog, ctx, True)
+    for f in P.BackwardPlan.__slots__:
+        assert getattr(bw, f) == getattr(want, f), f
+    assert bw.fuse_bn and bw.fuse_bias and bw.from_1x1 == {109}
+
+
 def test_predict_homography_eval_mode(zeng):
     from bihome_amd.step import predict
     cfg, model = zeng
