@@ -2,39 +2,7 @@
 // correspondences (one wavefront per problem: shuffle reductions for the Hartley statistics and the
 // A^T A blocks, a 9x9 Jacobi eigen-solve in LDS), their adjoints, and DSAC reprojection scoring.
 // All arithmetic in double: these problems are tiny (B*n <= a few hundred) and latency-bound.
-#include "common.h"
-
-// ---------------------------------------------------------------------------------------------
-// 8x8 solve with partial pivoting; S is an 8x9 augmented system in LDS, row stride 9
-// ---------------------------------------------------------------------------------------------
-__device__ static void solve8(double* S, double* x) {
-    for (int k = 0; k < 8; ++k) {
-        int r = k;
-        double best = fabs(S[k * 9 + k]);
-        for (int i = k + 1; i < 8; ++i) {
-            double v = fabs(S[i * 9 + k]);
-            if (v > best) { best = v; r = i; }
-        }
-        if (r != k)
-            for (int j = k; j < 9; ++j) { double t = S[k * 9 + j]; S[k * 9 + j] = S[r * 9 + j]; S[r * 9 + j] = t; }
-        double inv = 1.0 / S[k * 9 + k];
-        for (int i = k + 1; i < 8; ++i) {
-            double f = S[i * 9 + k] * inv;
-            for (int j = k + 1; j < 9; ++j) S[i * 9 + j] -= f * S[k * 9 + j];
-        }
-    }
-    for (int k = 7; k >= 0; --k) {
-        double acc = S[k * 9 + 8];
-        for (int j = k + 1; j < 8; ++j) acc -= S[k * 9 + j] * x[j];
-        x[k] = acc / S[k * 9 + k];
-    }
-}
-
-__device__ static void corner_xy(int i, double W, double H, double& x, double& y) {
-    // image_shape_to_corners: [[0,0],[W,0],[W,H],[0,H]]
-    x = (i == 1 || i == 2) ? W : 0.0;
-    y = (i >= 2) ? H : 0.0;
-}
+#include "geometry_dev.h"
 
 __global__ void __launch_bounds__(64) h4pt_fwd_kernel(const float* __restrict__ delta, int B, float W, float H,
                                                       double* __restrict__ H64, float* __restrict__ H32) {
@@ -93,10 +61,6 @@ __global__ void __launch_bounds__(64) h4pt_bwd_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // DLT: one wave per (sample, hypothesis)
 // ---------------------------------------------------------------------------------------------
-struct Hartley {
-    double mx, my, s, dbar;
-};
-
 // statistics of the P points held by this wave (each lane passes its partial sums)
 __device__ static Hartley hartley_stats(const double* px, const double* py, int cnt, int P) {
     double sx = 0, sy = 0;
@@ -113,55 +77,6 @@ __device__ static Hartley hartley_stats(const double* px, const double* py, int 
 }
 
 #define DLT_MAXPTS 8   // points per lane: P <= 512
-
-// Jacobi eigen-decomposition of the symmetric 9x9 matrix in LDS A (destroyed); V gets eigenvectors in columns.
-// Parallel (round-robin) ordering: round r of a sweep rotates the four disjoint pairs {(r+k) mod 9, (r-k) mod 9},
-// k = 1..4 (index r sits out; every pair {a, b} occurs once per sweep, in the round with 2r = a+b mod 9), so a sweep is
-// 9 dependent steps instead of 36.  The rotations of a round commute (disjoint index pairs): first A J and V J
-// (lane = (row, pair), columns p and q), then J^T (A J) (lane = (column, pair), rows p and q).
-__device__ static void jacobi9(double* A, double* V, int lane) {
-    if (lane < 9)
-        for (int j = 0; j < 9; ++j) V[lane * 9 + j] = (lane == j) ? 1.0 : 0.0;
-    __syncthreads();
-    const int k = lane >> 2, pr = lane & 3;       // lanes 0..35: row / column k, pair pr
-    for (int sweep = 0; sweep < 16; ++sweep) {
-        // convergence: off-diagonal mass vs diagonal mass
-        double off = 0, dia = 0;
-        if (lane < 9)
-            for (int j = 0; j < 9; ++j) { double v = A[lane * 9 + j]; if (j == lane) dia += v * v; else off += v * v; }
-        off = wave_sum(off); dia = wave_sum(dia);
-        if (off <= 1e-30 * dia || off == 0.0) break;      // off-diagonal Frobenius mass below 1e-15 of the diagonal: converged in double
-        for (int r = 0; r < 9; ++r) {
-            int ia = r + pr + 1, ib = r + 8 - pr;
-            ia = ia >= 9 ? ia - 9 : ia; ib = ib >= 9 ? ib - 9 : ib;
-            const int p = min(ia, ib), q = max(ia, ib);
-            const double apq = A[p * 9 + q], app = A[p * 9 + p], aqq = A[q * 9 + q];
-            double c = 1.0, s = 0.0;
-            if (fabs(apq) > 1e-300) {
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                c = 1.0 / sqrt(t * t + 1.0); s = t * c;
-            }
-            __syncthreads();                      // every lane has read its pair's entries
-            if (k < 9) {
-                const double akp = A[k * 9 + p], akq = A[k * 9 + q];
-                A[k * 9 + p] = c * akp - s * akq;
-                A[k * 9 + q] = s * akp + c * akq;
-                const double vkp = V[k * 9 + p], vkq = V[k * 9 + q];
-                V[k * 9 + p] = c * vkp - s * vkq;
-                V[k * 9 + q] = s * vkp + c * vkq;
-            }
-            __syncthreads();
-            if (k < 9) {
-                const double apk = A[p * 9 + k], aqk = A[q * 9 + k];
-                A[p * 9 + k] = c * apk - s * aqk;
-                A[q * 9 + k] = s * apk + c * aqk;
-            }
-            __syncthreads();
-        }
-    }
-    __syncthreads();
-}
 
 // loads this wave's points; returns count for this lane
 __device__ static int load_points(const float* pf, const int64_t* choice, int b, int j, int n, int P, int h, int w, int lane,
@@ -197,33 +112,15 @@ __global__ void __launch_bounds__(64) dlt_fwd_kernel(const float* __restrict__ p
     double acc[24];
     for (int i = 0; i < 24; ++i) acc[i] = 0;
     for (int k = 0; k < cnt; ++k) {
-        double a0 = t1.s * (x1[k] - t1.mx), a1 = t1.s * (y1[k] - t1.my), a2 = 1.0;
-        double u = t2.s * (x2[k] - t2.mx), v = t2.s * (y2[k] - t2.my);
-        double aa[6] = {a0 * a0, a0 * a1, a0 * a2, a1 * a1, a1 * a2, a2 * a2};
-        double r = u * u + v * v;
-        for (int i = 0; i < 6; ++i) {
-            acc[i] += aa[i]; acc[6 + i] += u * aa[i]; acc[12 + i] += v * aa[i]; acc[18 + i] += r * aa[i];
-        }
+        dlt_accumulate(acc, t1, t2, x1[k], y1[k], x2[k], y2[k]);
     }
     for (int i = 0; i < 24; ++i) acc[i] = wave_sum(acc[i]);
-    if (lane == 0) {
-        // symmetric 3x3 from 6 uniques: index map
-        const int sym[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) {
-                int s = sym[r][c];
-                A[(r) * 9 + c] = acc[s];                 // M00  (ay: [a,0,-x2 a])
-                A[(3 + r) * 9 + 3 + c] = acc[s];         // M11  (ax: [0,-a,y2 a])
-                A[(r) * 9 + 3 + c] = 0; A[(3 + r) * 9 + c] = 0;
-                A[(r) * 9 + 6 + c] = -acc[6 + s]; A[(6 + r) * 9 + c] = -acc[6 + s];         // M02 = -Sx
-                A[(3 + r) * 9 + 6 + c] = -acc[12 + s]; A[(6 + r) * 9 + 3 + c] = -acc[12 + s]; // M12 = -Sy
-                A[(6 + r) * 9 + 6 + c] = acc[18 + s];    // M22 = Sr
-            }
-    }
+    if (lane == 0) dlt_normal_matrix(A, acc);
     __syncthreads();
     // keep a copy of the diagonal? Jacobi leaves eigenvalues on the diagonal of A.
     jacobi9(A, V, lane);
     if (lane == 0) {
+        // (dlt_epilogue of geometry_dev.h spelled out, with the eigen-system saved for the adjoint on the way)
         int m = 0;
         for (int i = 1; i < 9; ++i) if (A[i * 9 + i] < A[m * 9 + m]) m = i;
         double* e = eig + (size_t)prob * 96;

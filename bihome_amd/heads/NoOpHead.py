@@ -7,10 +7,24 @@ predicted perspective field (NoOpHead.py:33-50).  All indexing runs on the devic
   * '4_points'  (NoOpHead.py:59-73): H = four_point_to_homography(corners, delta_hat, crop=False) - the 8x8 solve on
     the gfx950 kernel (bh_h4pt_fwd) in patch coordinates, conjugated by the translation to the patch corner.
   * 'all_points' (NoOpHead.py:75-110): upstream fits cv2.findHomography(RANSAC, 10 px) to all P*P correspondences of
-    the field on the host (cv2 is not available here, also not to the oracle).  Here a uniform 32 x 16 lattice of those
-    correspondences goes through the DLT kernel (bh_dlt_fwd, no sampling): the least-squares homography, the same
-    estimate as upstream's inlier refit when every residual is below the 10 px threshold; a stated difference otherwise
-    (exact for a field that is a homography's, tests/test_model_gpu.py).
+    the field on the host (cv2 is not available here, also not to the oracle).  Two estimators, kwarg ALL_POINTS_FIT:
+      'lattice' (default): a uniform 32 x 16 lattice of those correspondences goes through the DLT kernel (bh_dlt_fwd, no
+        sampling): the least-squares homography, the same estimate as upstream's inlier refit when every residual is
+        below the 10 px threshold; a stated difference otherwise (exact for a field that is a homography's,
+        tests/test_model_gpu.py).
+      'ransac': upstream's estimator on the device (bh_ransac_homography, csrc/ransac.hip): RANSAC_ITERS minimal
+        samples of four correspondences, inliers of each counted over ALL h*w points against RANSAC_THRESHOLD (10 px,
+        upstream's literal; cv2's squared-distance measure), the first hypothesis with the most inliers, and the
+        Hartley-normalised least-squares refit on its inliers.  What still differs from upstream: cv2 follows its refit
+        with ten Levenberg-Marquardt steps on the reprojection error (not built: no cv2 anywhere to pin it against), and
+        the minimal samples are our draws, not cv2's RNG stream.
+        RANSAC_ITERS = 256: cv2 stops after ln(1 - 0.995) / ln(1 - s^4) draws for an inlier share s; 256 draws reach that
+        confidence for every s >= 0.38 (ln 0.005 / ln(1 - 0.38^4) = 251), and evaluating a fixed number of draws never
+        finds fewer inliers than stopping early on the same draws.  The draws come from a device generator that is
+        re-seeded with a constant on every call (cv2's RANSAC is deterministic per call for the same reason), unless
+        data['ransac_choice'] [B,K,4] supplies them; the counts are integer atomics, so two calls agree bit for bit.
+        Evaluation only (no gradient; the field is detached).  The call does not sync, except for the host range check
+        of supplied indices.
 """
 import torch
 import torch.nn as nn
@@ -27,6 +41,13 @@ class Model(nn.Module):
         self.learning_keys = kwargs['LEARNING_KEYS']             # ground_truth, network_output, delta_gt, delta_hat
         if self.target_gen not in ('4_points', 'all_points'):
             raise ValueError("TARGET_GEN must be '4_points' or 'all_points'")
+        self.all_points_fit = kwargs.get('ALL_POINTS_FIT', 'lattice')
+        if self.all_points_fit not in ('lattice', 'ransac'):
+            raise ValueError("ALL_POINTS_FIT must be 'lattice' or 'ransac'")
+        self.ransac_iters = int(kwargs.get('RANSAC_ITERS', 256))
+        self.ransac_threshold = float(kwargs.get('RANSAC_THRESHOLD', 10.0))
+        if self.ransac_iters < 1 or not self.ransac_threshold >= 0:
+            raise ValueError("RANSAC_ITERS must be >= 1 and RANSAC_THRESHOLD >= 0")
 
     def forward(self, data):
         ret = [data[key] for key in self.learning_keys[:-1]]
@@ -47,7 +68,26 @@ class Model(nn.Module):
                 raise KeyError("predict_homography('4_points') needs data['corners'] (NoOpHead.py:62-65)")
             delta_hat = data[self.learning_keys[3]]
             return delta_hat, self._h_from_corners(data['corners'], delta_hat)
+        if self.all_points_fit == 'ransac':
+            return self._postprocess_ransac(data[self.learning_keys[1]], data.get('ransac_choice'))
         return self._postprocess(data[self.learning_keys[1]])
+
+    RANSAC_SEED = 0x5eed
+
+    def _postprocess_ransac(self, perspective_field, choice=None):
+        pf = perspective_field.detach().to(torch.float32).contiguous()
+        if not pf.is_cuda:
+            raise RuntimeError("bihome_amd heads run on the MI355X only; no CPU fallback (use oracle/ for CPU checks)")
+        B, _, h, w = pf.shape
+        supplied = choice is not None
+        if not supplied:
+            gen = torch.Generator(device=pf.device).manual_seed(self.RANSAC_SEED)      # the same draws on every call
+            choice = torch.randint(0, h * w, (B, self.ransac_iters, 4), generator=gen, device=pf.device)
+        else:
+            choice = choice.to(device=pf.device, dtype=torch.int64).reshape(B, -1, 4).contiguous()
+        with torch.no_grad():
+            dh, Hd = K.ransac_homography(pf, choice, self.ransac_threshold, check_range=supplied)[:2]
+        return dh, Hd
 
     @staticmethod
     def _h_from_corners(corners, delta_hat):

@@ -297,6 +297,40 @@ def dsac_score(pf, Hd, n):
     return err, best
 
 
+def ransac_homography(pf, choice, thr=10.0, want_mask=False, check_range=True):
+    """RANSAC + inlier refit of one homography per perspective field (bh_ransac_homography: upstream's
+    cv2.findHomography(src, dst, cv2.RANSAC, 10) of NoOpHead.py:75-109 without its LM polish; evaluation only).
+    pf [B,2,h,w] f32, choice [B,K,4] i64 (pixel indices y*w + x of the K minimal samples)
+    -> (delta_hat [B,4,2], H [B,3,3], best [B] i64, n_inl [B] i32, count [B,K] i32, mask [B,h,w] u8 or None).
+    count is -1 for an invalid hypothesis; n_inl = 0 flags a sample that fell back to the least-squares fit of all points.
+    check_range: the indices are range-checked on the host (one device sync, skipped inside a graph capture) - for caller-supplied
+    indices; a caller that drew them in range itself passes False and the call only enqueues five launches.  (The kernel treats an
+    index outside the field as an invalid hypothesis and never dereferences it.)"""
+    _chk(pf); _chk(choice, torch.int64)
+    if pf.requires_grad:
+        raise RuntimeError("ransac_homography is an evaluation path without a gradient: call it under torch.no_grad() on a detached field")
+    if pf.dim() != 4 or pf.shape[1] != 2:
+        raise ValueError("pf must be [B,2,h,w], got %s" % (tuple(pf.shape),))
+    B, _, h, w = pf.shape
+    if choice.dim() != 3 or choice.shape[0] != B or choice.shape[2] != 4 or choice.shape[1] < 1:
+        raise ValueError("choice must be [B,K,4] with K >= 1, got %s for B = %d" % (tuple(choice.shape), B))
+    K = choice.shape[1]
+    if check_range and choice.numel() and not torch.cuda.is_current_stream_capturing() and not bool(((choice >= 0) & (choice < h * w)).all()):
+        raise ValueError("bihome_amd: ransac_homography choice holds indices outside [0, %d)" % (h * w))
+    dev = pf.device
+    hyp = torch.empty(B, K, 9, dtype=torch.float32, device=dev)
+    count = torch.empty(B, K, dtype=torch.int32, device=dev)
+    best = torch.empty(B, dtype=torch.int64, device=dev)
+    n_inl = torch.empty(B, dtype=torch.int32, device=dev)
+    mask = torch.empty(B, h, w, dtype=torch.uint8, device=dev) if want_mask else None
+    work = torch.empty(B, 32, dtype=torch.float64, device=dev)
+    Hd = torch.empty(B, 3, 3, dtype=torch.float32, device=dev)
+    dh = torch.empty(B, 4, 2, dtype=torch.float32, device=dev)
+    check(lib.bh_ransac_homography(_p(pf), _p(choice), B, K, h, w, float(thr), _p(hyp), _p(count), _p(best), _p(n_inl), _p(mask),
+                                   _p(work), _p(Hd), _p(dh), _stream()), "bh_ransac_homography")
+    return dh, Hd, best, n_inl, count, mask
+
+
 # ------------------------------------------------------------------------------------------------
 # warp
 # ------------------------------------------------------------------------------------------------

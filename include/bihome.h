@@ -106,6 +106,34 @@ int bh_dsac_scores_bwd(const float* pf, const float* Hdlt, const float* scores, 
 int bh_dsac_scores_bwd_f(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h,
                          int w, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream);
 
+/* Robust homography of a perspective field: RANSAC over K minimal samples + least-squares refit on the inliers of the winner - the
+ * estimator of upstream's NoOpHead._postprocess, cv2.findHomography(src, dst, cv2.RANSAC, 10) over all h*w correspondences
+ * (src/heads/NoOpHead.py:75-109), batched on the device (csrc/ransac.hip).  Not included: cv2's Levenberg-Marquardt polish after the
+ * refit, and its sampler - the minimal samples are an input.  Forward only.
+ *   pf[B,2,h,w]      the field; pixel (x, y) corresponds to (x + pf[b,0,y,x], y + pf[b,1,y,x]) as in bh_dsac_score
+ *   choice[B,K,4]    int64 pixel indices y*w + x of the K minimal samples of every field
+ *   thr              inlier threshold in pixels (upstream: 10)
+ *   hyp[B,K,9]       out: the hypotheses, H22 = 1 (8x8 solve with partial pivoting in double, stored fp32); all NaN when INVALID:
+ *                      - an index outside [0, h*w) (never dereferenced), or two equal indices;
+ *                      - three collinear points among the four source or among the four destination points: for every triple
+ *                        i < j < k, d1 = p_i - p_k, d2 = p_j - p_k: |d2.x d1.y - d2.y d1.x| <= FLT_EPSILON (|d1.x| + |d1.y| + |d2.x| +
+ *                        |d2.y|), evaluated in double without contraction (cv2's minimal-sample check);
+ *                      - an elimination pivot with |pivot| <= 1e-12 (or NaN), or a non-finite coefficient
+ *   count[B,K]       out: inliers of every hypothesis, -1 for an invalid one.  A pixel is an inlier when (qx/qz - x')^2 + (qy/qz - y')^2
+ *                    <= thr^2 with q = hyp.(x, y, 1) (cv2's measure), qz > 0 and finite; fp32, evaluated as (qx - x' qz)^2 + (qy - y' qz)^2
+ *                    <= (thr qz)^2.  Integer atomics: independent of the order of execution
+ *   best[B]          out: the FIRST k with the maximal count (cv2 replaces its model on strictly more inliers only)
+ *   n_inl[B]         out: count[b, best[b]], or 0 when that is below 4 (every hypothesis invalid, or nothing to refit on): the sample is
+ *                    FLAGGED and its result is the least-squares fit of all h*w points
+ *   mask[B,h,w]      out, NULL ok: 1 where the pixel is an inlier of hypothesis best[b] (the same decision, bit for bit, that was
+ *                    counted: sum(mask[b]) == n_inl[b]); all ones for a flagged sample
+ *   work[B,32]       scratch (doubles)
+ *   H[B,9], delta_hat[B,4,2]   out: the Hartley-normalised DLT over all inliers, /(H22 + 1e-8), and H.corners - corners - the
+ *                    arithmetic and the corner convention of bh_dlt_fwd
+ * BH_E_BADARG: K < 1, h*w < 4, thr negative or NaN, a NULL pointer other than mask.  BH_E_UNSUPPORTED: B > 65535 or h*w, B*K > 2^30. */
+int bh_ransac_homography(const float* pf, const int64_t* choice, int B, int K, int h, int w, float thr, float* hyp, int32_t* count,
+                         int64_t* best, int32_t* n_inl, uint8_t* mask, double* work, float* H, float* delta_hat, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Homography warp (warp_image, src/data/utils.py:54-59 -> kornia.warp_perspective(bilinear, zeros,
  * align_corners=True); net map out(x,y) = bilinear img(H.(x,y,1)))  and the warped all-ones mask
