@@ -64,6 +64,7 @@ SIGNATURES = {
     "bh_scale_samples_bwd_f": [P, P, P, c_int, c_int64, c_int, P, P, c_int, P],
     "bh_dsac_score": [P, P, c_int, c_int, c_int, c_int, P, P, P],
     "bh_ransac_homography": [P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P],
+    "bh_homography_refine_lm": [P, P, c_int, c_int, c_int, c_int, P, P, P, P],
     "bh_warp_fwd": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P],
     "bh_warp_fwd_f": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P],
     "bh_warp_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P],

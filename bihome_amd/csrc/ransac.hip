@@ -1,6 +1,7 @@
 // Robust homography of a perspective field: batched RANSAC on the device (bh_ransac_homography, include/bihome.h) - what upstream's
 // NoOpHead._postprocess does per sample on the host with cv2.findHomography(src, dst, cv2.RANSAC, 10) (src/heads/NoOpHead.py:75-109),
-// without cv2's Levenberg-Marquardt polish and with the minimal samples as an INPUT.
+// with the minimal samples as an INPUT - and the Levenberg-Marquardt polish cv2 runs after its refit as a call of its own
+// (bh_homography_refine_lm, at the end of this file).
 //
 //   ransac_hyp_kernel     one THREAD per (sample, hypothesis): the 8x8 solve of its four correspondences in double -> nine fp32
 //                         coefficients (NaN for an invalid hypothesis) and count = 0 / -1
@@ -9,6 +10,7 @@
 //   ransac_select_kernel  first hypothesis with the most inliers
 //   ransac_sums_kernel    inlier mask of the winner + the Hartley statistics and the 24 sums of the normal matrix over ALL inliers
 //   ransac_solve_kernel   9x9 Jacobi eigen-solve, denormalisation, corner transform - dlt_fwd_kernel's epilogue
+//   homography_refine_lm_kernel   the polish: all Levenberg-Marquardt steps of a sample in one launch, one workgroup per sample
 #include <math.h>
 #include "geometry_dev.h"
 
@@ -273,6 +275,211 @@ __global__ void __launch_bounds__(64) ransac_solve_kernel(const double* __restri
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------
+// Levenberg-Marquardt polish (bh_homography_refine_lm; the specification is in include/bihome.h).  grid B, block 512, ONE launch for
+// all steps: pass 0 evaluates the start, pass it >= 1 the trial of step it - each pass is one sweep over the sample's field (it stays
+// in L2: 128 KB at 128 x 128; the next pixel's three loads are issued before the current pixel's arithmetic), a fixed-order workgroup
+// reduction of LM_NS sums in double, and the accept / reject decision + the damped 8x8 solve of the next step by thread 0.  No early
+// exit: every sample runs iters + 1 passes whatever it decides, and a sample that is not (or no longer) live re-evaluates its own
+// parameters.  512 threads, not the 1024 of ransac_sums_kernel: the 30 double accumulators and the temporaries of the division want
+// ~170 vector registers, and a 1024-thread workgroup leaves 128 per thread (it spilled); 8 waves per CU keep no scratch.
+//
+// The sums.  With a = (x, y, 1) / qz and p = (qx, qy) / qz the two rows of the Jacobian of a correspondence are
+//     d rx / d h = [a0 a1 a2  0  0  0  -a0 px  -a1 px],    d ry / d h = [ 0  0  0 a0 a1 a2  -a0 py  -a1 py]
+// so the 36 unique entries of J^T J are 19 distinct sums (a a^T: 6, px a a^T and py a a^T without their last column: 5 each,
+// (px^2 + py^2) a a^T without its last row and column: 3); with the 8 of J^T r, the cost, the number of correspondences and the number
+// of them with qz <= 0 that is LM_NS = 30.
+// ---------------------------------------------------------------------------------------------
+#define LM_THREADS 512
+#define LM_NS 30
+#define LM_COST 0
+#define LM_N 1
+#define LM_BAD 2
+#define LM_AA 3        // a0a0 a0a1 a0a2 a1a1 a1a2 a2a2
+#define LM_X 9         // px * (a0a0 a0a1 a1a1 a2a0 a2a1)
+#define LM_Y 14        // py * (the same)
+#define LM_R 19        // (px^2 + py^2) * (a0a0 a0a1 a1a1)
+#define LM_G 22        // J^T r
+
+__device__ __forceinline__ bool lm_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }      // (NaN fails)
+
+// a workgroup-uniform double into scalar registers: the eight parameters stay out of the vector register budget of the sweep
+__device__ __forceinline__ double lm_uniform(double v) {
+    const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+__device__ __forceinline__ void lm_accumulate(double* s, const double* __restrict__ par, double x, double y, double u, double v) {
+    const double qx = par[0] * x + par[1] * y + par[2], qy = par[3] * x + par[4] * y + par[5], qz = par[6] * x + par[7] * y + 1.0;
+    const double iz = 1.0 / qz;
+    const double px = qx * iz, py = qy * iz, rx = px - u, ry = py - v;
+    const double a0 = x * iz, a1 = y * iz, a2 = iz;
+    const double a00 = a0 * a0, a01 = a0 * a1, a11 = a1 * a1, a20 = a2 * a0, a21 = a2 * a1;
+    s[LM_COST] += rx * rx + ry * ry;
+    s[LM_N] += 1.0;
+    s[LM_BAD] += qz > 0.0 ? 0.0 : 1.0;                    // (a NaN qz counts)
+    s[LM_AA] += a00; s[LM_AA + 1] += a01; s[LM_AA + 2] += a20; s[LM_AA + 3] += a11; s[LM_AA + 4] += a21; s[LM_AA + 5] += a2 * a2;
+    s[LM_X] += px * a00; s[LM_X + 1] += px * a01; s[LM_X + 2] += px * a11; s[LM_X + 3] += px * a20; s[LM_X + 4] += px * a21;
+    s[LM_Y] += py * a00; s[LM_Y + 1] += py * a01; s[LM_Y + 2] += py * a11; s[LM_Y + 3] += py * a20; s[LM_Y + 4] += py * a21;
+    const double rr = px * px + py * py, pr = px * rx + py * ry;
+    s[LM_R] += rr * a00; s[LM_R + 1] += rr * a01; s[LM_R + 2] += rr * a11;
+    s[LM_G] += a0 * rx; s[LM_G + 1] += a1 * rx; s[LM_G + 2] += a2 * rx;
+    s[LM_G + 3] += a0 * ry; s[LM_G + 4] += a1 * ry; s[LM_G + 5] += a2 * ry;
+    s[LM_G + 6] -= a0 * pr; s[LM_G + 7] -= a1 * pr;
+}
+
+// (J^T J + lambda diag(J^T J)) d = -J^T r as the 8x9 augmented system of solve8; one lane
+__device__ static void lm_system(double* S, const double* c, double lambda) {
+    const int sym3[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+    const int xy[3][2] = {{0, 1}, {1, 2}, {3, 4}};
+    const int sym2[2][2] = {{0, 1}, {1, 2}};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) {
+            S[i * 9 + j] = c[LM_AA + sym3[i][j]]; S[(3 + i) * 9 + 3 + j] = c[LM_AA + sym3[i][j]];
+            S[i * 9 + 3 + j] = 0; S[(3 + i) * 9 + j] = 0;
+        }
+        for (int j = 0; j < 2; ++j) {
+            S[i * 9 + 6 + j] = -c[LM_X + xy[i][j]]; S[(6 + j) * 9 + i] = -c[LM_X + xy[i][j]];
+            S[(3 + i) * 9 + 6 + j] = -c[LM_Y + xy[i][j]]; S[(6 + j) * 9 + 3 + i] = -c[LM_Y + xy[i][j]];
+        }
+    }
+    for (int i = 0; i < 2; ++i)
+        for (int j = 0; j < 2; ++j) S[(6 + i) * 9 + 6 + j] = c[LM_R + sym2[i][j]];
+    for (int i = 0; i < 8; ++i) {
+        S[i * 9 + i] += lambda * S[i * 9 + i];
+        S[i * 9 + 8] = -c[LM_G + i];
+    }
+}
+
+__global__ void __launch_bounds__(LM_THREADS) homography_refine_lm_kernel(const float* __restrict__ pf, const uint8_t* __restrict__ mask,
+                                                                          int h, int w, int iters, float* __restrict__ H,
+                                                                          float* __restrict__ delta_hat, double* __restrict__ work) {
+    __shared__ double red[(LM_THREADS / 64) * LM_NS];
+    __shared__ double cur[LM_NS];          // the sums at the current parameters
+    __shared__ double S[72];
+    __shared__ double par[8];              // what the next pass evaluates: the start, then the trial of every step
+    __shared__ double pc[8];               // the current parameters
+    __shared__ double dstep[8];            // thread 0: the step of the solve
+    __shared__ double st[2];               // thread 0: lambda, the start's cost
+    __shared__ int fl[4];                  // thread 0: accepted steps, live, stepped, failed
+    const int b = blockIdx.x, N = h * w, tid = threadIdx.x;
+    const float* pfx = pf + (size_t)b * 2 * N;
+    const float* pfy = pfx + N;
+    const uint8_t* mk = mask ? mask + (size_t)b * N : nullptr;
+    float* Hb = H + (size_t)b * 9;
+    const int x0 = tid % w, y0 = tid / w, sx = LM_THREADS % w, sy = LM_THREADS / w;
+    if (tid == 0) {
+        const double h8 = (double)Hb[8];
+        for (int k = 0; k < 8; ++k) par[k] = pc[k] = (double)Hb[k] / h8;
+        st[0] = 1e-3; st[1] = 0.0;
+        fl[0] = fl[1] = fl[2] = fl[3] = 0;
+    }
+    __syncthreads();
+
+    for (int it = 0; it <= iters; ++it) {
+        double s[LM_NS];
+#pragma unroll
+        for (int i = 0; i < LM_NS; ++i) s[i] = 0.0;
+        {
+            double p[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) p[k] = lm_uniform(par[k]);
+            int i = tid, x = x0, y = y0;
+            bool in = false;
+            float dx = 0.0f, dy = 0.0f;
+            if (i < N) { in = mk ? mk[i] != 0 : true; dx = pfx[i]; dy = pfy[i]; }
+            while (i < N) {
+                const int i2 = i + LM_THREADS;
+                bool in2 = false;
+                float dx2 = 0.0f, dy2 = 0.0f;
+                if (i2 < N) { in2 = mk ? mk[i2] != 0 : true; dx2 = pfx[i2]; dy2 = pfy[i2]; }
+                if (in) lm_accumulate(s, p, (double)x, (double)y, (double)x + (double)dx, (double)y + (double)dy);
+                i = i2; in = in2; dx = dx2; dy = dy2;
+                x += sx; y += sy;
+                if (x >= w) { x -= w; ++y; }
+            }
+        }
+        // fixed order: the pixels of a thread in ascending order, the butterfly of a wave, then the 8 waves in order (thread 0)
+#pragma unroll
+        for (int i = 0; i < LM_NS; ++i) s[i] = wave_sum(s[i]);
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int i = 0; i < LM_NS; ++i) red[(tid >> 6) * LM_NS + i] = s[i];
+        }
+        __syncthreads();
+        if (tid == 0) {                                    // (its state lives in LDS, not in registers the sweep would have to carry)
+            int accepted = fl[0];
+            bool live = fl[1] != 0, stepped = fl[2] != 0, failed = fl[3] != 0;
+            for (int i = 0; i < LM_NS; ++i) {
+                double t = 0;
+                for (int q = 0; q < LM_THREADS / 64; ++q) t += red[q * LM_NS + i];
+                S[i] = t;                                   // (S is free until lm_system)
+            }
+            const bool good = S[LM_BAD] == 0.0 && lm_finite(S[LM_COST]);
+            if (it == 0) {
+                st[1] = S[LM_COST];
+                live = good && S[LM_N] >= 4.0;
+                for (int k = 0; k < 8; ++k) live = live && lm_finite(pc[k]);
+                for (int i = 0; i < LM_NS; ++i) cur[i] = S[i];
+            } else if (stepped) {
+                if (good && S[LM_COST] < cur[LM_COST]) {
+                    for (int k = 0; k < 8; ++k) pc[k] = par[k];
+                    for (int i = 0; i < LM_NS; ++i) cur[i] = S[i];
+                    st[0] = fmax(st[0] / 10.0, 1e-12);
+                    ++accepted;
+                } else {
+                    st[0] = fmin(st[0] * 10.0, 1e12);
+                }
+            }
+            stepped = false;
+            if (live && it < iters) {
+                double* d = dstep;
+                lm_system(S, cur, st[0]);
+                solve8(S, d);
+                bool ok = true;
+                for (int k = 0; k < 8; ++k) ok = ok && fabs(S[k * 9 + k]) > 1e-12 && lm_finite(d[k]);      // ransac_hyp_kernel's rule
+                if (ok) {
+                    for (int k = 0; k < 8; ++k) par[k] = pc[k] + d[k];
+                    stepped = true;
+                } else {
+                    live = false; failed = true;
+                }
+            }
+            if (!stepped)
+                for (int k = 0; k < 8; ++k) par[k] = pc[k];
+            fl[0] = accepted; fl[1] = live; fl[2] = stepped; fl[3] = failed;
+        }
+        __syncthreads();
+    }
+
+    if (tid == 0) {
+        double cost1 = cur[LM_COST];
+        int accepted = fl[0];
+        if (fl[3]) {                                      // a failed solve: the sample keeps its START
+            const double h8 = (double)Hb[8];
+            for (int k = 0; k < 8; ++k) pc[k] = (double)Hb[k] / h8;
+            accepted = 0; cost1 = st[1];
+        }
+        if (accepted > 0) {                                // (no accepted step: H stays as it was passed in)
+            for (int k = 0; k < 8; ++k) Hb[k] = (float)pc[k];
+            Hb[8] = 1.0f;
+        }
+        float* dh = delta_hat + (size_t)b * 8;
+        for (int c = 0; c < 4; ++c) {                      // dlt_epilogue's corner transform
+            double x, y;
+            corner_xy(c, (double)w, (double)h, x, y);
+            const double qx = pc[0] * x + pc[1] * y + pc[2], qy = pc[3] * x + pc[4] * y + pc[5], qz = pc[6] * x + pc[7] * y + 1.0;
+            const double sc = fabs(qz) > 1e-8 ? 1.0 / qz : 1.0;
+            dh[2 * c] = (float)(qx * sc - x);
+            dh[2 * c + 1] = (float)(qy * sc - y);
+        }
+        double* wk = work + (size_t)b * 4;
+        wk[0] = st[1]; wk[1] = cost1; wk[2] = (double)accepted; wk[3] = st[0];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -293,6 +500,17 @@ int bh_ransac_homography(const float* pf, const int64_t* choice, int B, int K, i
     hipLaunchKernelGGL(ransac_sums_kernel, dim3(B), dim3(RANSAC_SUMS_THREADS), 0, st, pf, hyp, best, n_inl, K, h, w, thr, mask, work);
     BH_LAUNCH_CHECK();
     hipLaunchKernelGGL(ransac_solve_kernel, dim3(B), dim3(64), 0, st, work, h, w, H, delta_hat);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+int bh_homography_refine_lm(const float* pf, const uint8_t* mask, int B, int h, int w, int iters, float* H, float* delta_hat, double* work,
+                            void* stream) {
+    if (!pf || !H || !delta_hat || !work) return BH_E_BADARG;
+    if (B < 0 || h < 1 || w < 1 || (long long)h * w < 4 || iters < 0) return BH_E_BADARG;
+    if ((long long)h * w > (1ll << 30) || B > 65535) return BH_E_UNSUPPORTED;
+    if (B == 0) return BH_OK;
+    hipLaunchKernelGGL(homography_refine_lm_kernel, dim3(B), dim3(LM_THREADS), 0, bh_stream(stream), pf, mask, h, w, iters, H, delta_hat, work);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

@@ -15,9 +15,12 @@ predicted perspective field (NoOpHead.py:33-50).  All indexing runs on the devic
       'ransac': upstream's estimator on the device (bh_ransac_homography, csrc/ransac.hip): RANSAC_ITERS minimal
         samples of four correspondences, inliers of each counted over ALL h*w points against RANSAC_THRESHOLD (10 px,
         upstream's literal; cv2's squared-distance measure), the first hypothesis with the most inliers, and the
-        Hartley-normalised least-squares refit on its inliers.  What still differs from upstream: cv2 follows its refit
-        with ten Levenberg-Marquardt steps on the reprojection error (not built: no cv2 anywhere to pin it against), and
-        the minimal samples are our draws, not cv2's RNG stream.
+        Hartley-normalised least-squares refit on its inliers.  RANSAC_REFINE = 'lm' (default 'none') then runs what cv2 runs
+        after its refit: RANSAC_LM_ITERS (10) Levenberg-Marquardt steps on the reprojection error of the winner's inliers
+        (bh_homography_refine_lm, one more launch on the same stream; a flagged sample is polished over all points).  What
+        still differs from upstream: the minimal samples are our draws, not cv2's RNG stream; the polish always runs all
+        its steps where cv2 may terminate early; and its constants (H22 fixed, lambda from 1e-3 in factors of 10) are
+        recalled, not read from cv2's source.
         RANSAC_ITERS = 256: cv2 stops after ln(1 - 0.995) / ln(1 - s^4) draws for an inlier share s; 256 draws reach that
         confidence for every s >= 0.38 (ln 0.005 / ln(1 - 0.38^4) = 251), and evaluating a fixed number of draws never
         finds fewer inliers than stopping early on the same draws.  The draws come from a device generator that is
@@ -48,6 +51,12 @@ class Model(nn.Module):
         self.ransac_threshold = float(kwargs.get('RANSAC_THRESHOLD', 10.0))
         if self.ransac_iters < 1 or not self.ransac_threshold >= 0:
             raise ValueError("RANSAC_ITERS must be >= 1 and RANSAC_THRESHOLD >= 0")
+        self.ransac_refine = kwargs.get('RANSAC_REFINE', 'none')
+        if self.ransac_refine not in ('none', 'lm'):
+            raise ValueError("RANSAC_REFINE must be 'none' or 'lm'")
+        self.ransac_lm_iters = int(kwargs.get('RANSAC_LM_ITERS', 10))
+        if self.ransac_lm_iters < 1:
+            raise ValueError("RANSAC_LM_ITERS must be >= 1")
 
     def forward(self, data):
         ret = [data[key] for key in self.learning_keys[:-1]]
@@ -86,7 +95,11 @@ class Model(nn.Module):
         else:
             choice = choice.to(device=pf.device, dtype=torch.int64).reshape(B, -1, 4).contiguous()
         with torch.no_grad():
-            dh, Hd = K.ransac_homography(pf, choice, self.ransac_threshold, check_range=supplied)[:2]
+            if self.ransac_refine == 'none':
+                dh, Hd = K.ransac_homography(pf, choice, self.ransac_threshold, check_range=supplied)[:2]
+            else:
+                r = K.ransac_homography(pf, choice, self.ransac_threshold, want_mask=True, check_range=supplied)
+                dh, Hd = K.homography_refine_lm(pf, r[1], r[5], self.ransac_lm_iters)[:2]
         return dh, Hd
 
     @staticmethod

@@ -299,7 +299,7 @@ def dsac_score(pf, Hd, n):
 
 def ransac_homography(pf, choice, thr=10.0, want_mask=False, check_range=True):
     """RANSAC + inlier refit of one homography per perspective field (bh_ransac_homography: upstream's
-    cv2.findHomography(src, dst, cv2.RANSAC, 10) of NoOpHead.py:75-109 without its LM polish; evaluation only).
+    cv2.findHomography(src, dst, cv2.RANSAC, 10) of NoOpHead.py:75-109; its LM polish is homography_refine_lm; evaluation only).
     pf [B,2,h,w] f32, choice [B,K,4] i64 (pixel indices y*w + x of the K minimal samples)
     -> (delta_hat [B,4,2], H [B,3,3], best [B] i64, n_inl [B] i32, count [B,K] i32, mask [B,h,w] u8 or None).
     count is -1 for an invalid hypothesis; n_inl = 0 flags a sample that fell back to the least-squares fit of all points.
@@ -329,6 +329,32 @@ def ransac_homography(pf, choice, thr=10.0, want_mask=False, check_range=True):
     check(lib.bh_ransac_homography(_p(pf), _p(choice), B, K, h, w, float(thr), _p(hyp), _p(count), _p(best), _p(n_inl), _p(mask),
                                    _p(work), _p(Hd), _p(dh), _stream()), "bh_ransac_homography")
     return dh, Hd, best, n_inl, count, mask
+
+
+def homography_refine_lm(pf, H, mask=None, iters=10):
+    """Levenberg-Marquardt polish of H on the reprojection error of the field's correspondences (bh_homography_refine_lm: the step
+    cv2.findHomography runs after its inlier refit; evaluation only).
+    pf [B,2,h,w] f32, H [B,3,3] f32 (the start, e.g. ransac_homography's; not modified), mask [B,h,w] u8 or None (every pixel)
+    -> (delta_hat [B,4,2], H [B,3,3], info [B,4] f64: cost at the start, cost at the result, accepted steps, final lambda).
+    One launch, no sync."""
+    _chk(pf); _chk(H); _chk(mask, torch.uint8)
+    if pf.requires_grad or H.requires_grad:
+        raise RuntimeError("homography_refine_lm is an evaluation path without a gradient: call it under torch.no_grad() on a detached field")
+    if pf.dim() != 4 or pf.shape[1] != 2:
+        raise ValueError("pf must be [B,2,h,w], got %s" % (tuple(pf.shape),))
+    B, _, h, w = pf.shape
+    if H.numel() != B * 9 or H.shape[0] != B:
+        raise ValueError("H must be [B,3,3], got %s for B = %d" % (tuple(H.shape), B))
+    if mask is not None and tuple(mask.shape) != (B, h, w):
+        raise ValueError("mask must be [B,h,w] = %s, got %s" % ((B, h, w), tuple(mask.shape)))
+    iters = int(iters)
+    if iters < 0:
+        raise ValueError("iters must be >= 0")
+    Hd = H.clone().view(B, 3, 3)
+    dh = torch.empty(B, 4, 2, dtype=torch.float32, device=pf.device)
+    info = torch.empty(B, 4, dtype=torch.float64, device=pf.device)
+    check(lib.bh_homography_refine_lm(_p(pf), _p(mask), B, h, w, iters, _p(Hd), _p(dh), _p(info), _stream()), "bh_homography_refine_lm")
+    return dh, Hd, info
 
 
 # ------------------------------------------------------------------------------------------------

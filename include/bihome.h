@@ -108,8 +108,8 @@ int bh_dsac_scores_bwd_f(const float* pf, const float* Hdlt, const float* scores
 
 /* Robust homography of a perspective field: RANSAC over K minimal samples + least-squares refit on the inliers of the winner - the
  * estimator of upstream's NoOpHead._postprocess, cv2.findHomography(src, dst, cv2.RANSAC, 10) over all h*w correspondences
- * (src/heads/NoOpHead.py:75-109), batched on the device (csrc/ransac.hip).  Not included: cv2's Levenberg-Marquardt polish after the
- * refit, and its sampler - the minimal samples are an input.  Forward only.
+ * (src/heads/NoOpHead.py:75-109), batched on the device (csrc/ransac.hip).  cv2's Levenberg-Marquardt polish after the refit is a call
+ * of its own (bh_homography_refine_lm, below); not included: cv2's sampler - the minimal samples are an input.  Forward only.
  *   pf[B,2,h,w]      the field; pixel (x, y) corresponds to (x + pf[b,0,y,x], y + pf[b,1,y,x]) as in bh_dsac_score
  *   choice[B,K,4]    int64 pixel indices y*w + x of the K minimal samples of every field
  *   thr              inlier threshold in pixels (upstream: 10)
@@ -133,6 +133,40 @@ int bh_dsac_scores_bwd_f(const float* pf, const float* Hdlt, const float* scores
  * BH_E_BADARG: K < 1, h*w < 4, thr negative or NaN, a NULL pointer other than mask.  BH_E_UNSUPPORTED: B > 65535 or h*w, B*K > 2^30. */
 int bh_ransac_homography(const float* pf, const int64_t* choice, int B, int K, int h, int w, float thr, float* hyp, int32_t* count,
                          int64_t* best, int32_t* n_inl, uint8_t* mask, double* work, float* H, float* delta_hat, void* stream);
+
+/* Levenberg-Marquardt polish of a homography on the REPROJECTION error of a perspective field's correspondences - the step
+ * cv2.findHomography(src, dst, cv2.RANSAC, 10) (src/heads/NoOpHead.py:75-109) runs after its inlier refit, which minimises the algebraic
+ * error only.  Chained after bh_ransac_homography with its mask, H and delta_hat.  The specification below is this project's own: cv2's
+ * solver source is not available to this project, so its constants are RECALLED, not copied - 8 free parameters with H22 fixed to 1, at
+ * most 10 iterations, lambda starting at 1e-3 and moved by factors of 10 - and cv2 may stop before its tenth iteration where this call
+ * never does.  Forward only; all arithmetic in double.
+ *   pf[B,2,h,w]      the field, as in bh_ransac_homography
+ *   mask[B,h,w]      NULL ok (every pixel).  The correspondences of sample b: every pixel i with mask[b,i] != 0, (x, y) = (i % w, i / w),
+ *                    (u, v) = (x + pf[b,0,i], y + pf[b,1,i])
+ *   iters            number of steps; every sample runs all of them (fixed work, no early exit, nothing read back by the host).  0 is
+ *                    valid: delta_hat of the start and two equal costs
+ *   H[B,9]           in: the start; out: the refined homography, fp32 of the double parameters with H[8] = 1 - written only for a sample
+ *                    with at least one accepted step, otherwise left as passed in
+ *   delta_hat[B,4,2] out: p.corners - corners for corners [[0,0],[w,0],[w,h],[0,h]] from the double parameters p (the corner
+ *                    transform of bh_dlt_fwd: the quotient is skipped where |qz| <= 1e-8)
+ *   work[B,4]        out (doubles): cost at the start, cost at the result, number of accepted steps, final lambda
+ * Parameters p[0..7] = H[0..7] / H[8].  With q = (p0 x + p1 y + p2, p3 x + p4 y + p5, p6 x + p7 y + 1): residuals r = (qx/qz - u,
+ * qy/qz - v), cost = sum over the correspondences of rx^2 + ry^2, and the analytic Jacobian J: d rx / d p0..2 = (x, y, 1) / qz,
+ * d rx / d p6,7 = -(x, y) (qx/qz) / qz, zero for p3..5; d ry likewise with p3..5 and qy.
+ * One step: solve (J^T J + lambda diag(J^T J)) d = -J^T r (8x8, Gaussian elimination with partial pivoting), trial = p + d.  The trial
+ * is ACCEPTED iff its cost is finite, every correspondence has qz > 0 at the trial, and cost(trial) < cost(p) - then p = trial and
+ * lambda = max(lambda / 10, 1e-12); otherwise p stays and lambda = min(lambda * 10, 1e12).  lambda starts at 1e-3.
+ * A sample KEEPS ITS START (H untouched, delta_hat of the start, both costs the start's, zero accepted steps) when it has fewer than
+ * 4 correspondences, when a start parameter or the start's cost is not finite, when a correspondence has qz <= 0 at the start, or when
+ * the solve of ANY of its steps fails: an elimination pivot with |pivot| <= 1e-12 (or NaN) or a non-finite component of d - the pivot
+ * rule of bh_ransac_homography's hypotheses.
+ * J^T J, J^T r and the cost are accumulated in double and reduced in a fixed order without floating-point atomics (the 36 unique
+ * entries of J^T J are formed from the 19 distinct sums they consist of): two calls agree bit for bit.
+ * A field of any size is handled: it is re-read from memory in each of the iters + 1 passes (one launch, one workgroup per sample).
+ * BH_E_BADARG: NULL pf / H / delta_hat / work, B < 0, h*w < 4, iters < 0.  BH_E_UNSUPPORTED: B > 65535 or h*w > 2^30.  B == 0: BH_OK,
+ * nothing launched.  All checks come before any launch. */
+int bh_homography_refine_lm(const float* pf, const uint8_t* mask, int B, int h, int w, int iters, float* H, float* delta_hat,
+                            double* work, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Homography warp (warp_image, src/data/utils.py:54-59 -> kornia.warp_perspective(bilinear, zeros,

@@ -1,7 +1,9 @@
 """Time bh_ransac_homography (kernels.ransac_homography) at the evaluation shape of zeng-orig: B = 64 fields of 128 x 128, K = 64 / 256 /
 1024 minimal samples, 100 repetitions behind 10 warm-ups with device events around the whole call - next to (a) today's lattice fit
 (NoOpHead._postprocess: bh_dlt_fwd on 512 points) and (b) a numpy float64 restatement of the same algorithm on the host for 8 samples,
-the shape of upstream's per-sample host loop.  Prints one JSON line.
+the shape of upstream's per-sample host loop.  The `ransac+lm` leg is the same call followed by the Levenberg-Marquardt polish
+(kernels.homography_refine_lm on the call's own mask and H: NoOpHead RANSAC_REFINE='lm'), on the same fields and with the same event
+timing; `lm_polish_ms` is the difference of the two medians at each K.  Prints one JSON line.
 
     python tools/ransac_bench.py                  # all of it
     rocprofv3 --kernel-trace --stats -- python tools/ransac_bench.py --no-host --reps 20     # per-kernel times
@@ -97,11 +99,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--host-samples", type=int, default=8)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--lm-iters", type=int, default=10)
     args = ap.parse_args()
     B = args.batch
     pf_np = make_fields(B)
     pf = torch.tensor(pf_np).cuda()
-    res = {"tool": "ransac_bench", "batch": B, "field": [128, 128], "reps": args.reps, "device": torch.cuda.get_device_name(0), "ransac": {}}
+    res = {"tool": "ransac_bench", "batch": B, "field": [128, 128], "reps": args.reps, "device": torch.cuda.get_device_name(0), "ransac": {},
+           "ransac+lm": {}, "lm_iters": args.lm_iters}
+
+    def ransac_lm(choice):
+        r = K.ransac_homography(pf, choice, THR, want_mask=True, check_range=False)
+        return K.homography_refine_lm(pf, r[1], r[5], args.lm_iters)
     with torch.no_grad():
         res["lattice_dlt"] = timed(lambda: NoOpHead.Model._postprocess(pf), args.reps, args.warmup)
         for k in args.iters:
@@ -112,6 +120,12 @@ def main():
             n_inl = K.ransac_homography(pf, choice, THR)[3]
             r["mean_inlier_share"] = float(n_inl.float().mean().item() / (128 * 128))
             res["ransac"][str(k)] = r
+            p = timed(lambda: ransac_lm(choice), args.reps, args.warmup)
+            p["lm_polish_ms"] = p["median_ms"] - r["median_ms"]
+            info = ransac_lm(choice)[2]
+            p["mean_accepted_steps"] = float(info[:, 2].mean().item())
+            p["mean_relative_cost_gain"] = float(((info[:, 0] - info[:, 1]) / info[:, 0]).mean().item())
+            res["ransac+lm"][str(k)] = p
         ks = sorted(args.iters)
         if len(ks) > 1:
             dt = (res["ransac"][str(ks[-1])]["median_ms"] - res["ransac"][str(ks[0])]["median_ms"]) * 1e-3
@@ -123,6 +137,7 @@ def main():
         host_restatement(pf_np[:n].astype(np.float64), choice)
         res["host_numpy_f64"] = {"samples": n, "iters": 256, "ms": (time.perf_counter() - t0) * 1e3}
         res["host_numpy_f64"]["ms_per_sample"] = res["host_numpy_f64"]["ms"] / n
+        res["host_numpy_f64"]["ms_scaled_to_batch"] = res["host_numpy_f64"]["ms_per_sample"] * B
     print(json.dumps(res))
 
 
