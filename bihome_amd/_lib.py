@@ -63,6 +63,8 @@ SIGNATURES = {
     "bh_scale_samples_bwd": [P, P, P, c_int, c_int64, c_int, P, P, P],
     "bh_scale_samples_bwd_f": [P, P, P, c_int, c_int64, c_int, P, P, c_int, P],
     "bh_dsac_score": [P, P, c_int, c_int, c_int, c_int, P, P, P],
+    "bh_dsac_score_m": [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P],
+    "bh_dsac_scores_bwd_m": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, c_int, P],
     "bh_ransac_homography": [P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P],
     "bh_homography_refine_lm": [P, P, c_int, c_int, c_int, c_int, P, P, P, P],
     "bh_warp_fwd": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P],
@@ -172,6 +174,7 @@ lib = _load()
 # (BIHOME_DETERMINISTIC=1 is read by kernels.py: the library holds no mode, every call carries its own bit - include/bihome.h
 #  "Deterministic calls")
 ROUTE_DETERMINISTIC, BN_DETERMINISTIC, F_DETERMINISTIC = 128, 32, 1
+DSAC_METHODS = {"repr_error": 0, "inliers_ratio": 1, "soft_inliers_ratio": 2}      # include/bihome.h BH_DSAC_*
 ROUTE_C3_PC = 512
 ROUTE_WX3_PC = 1024       # include/bihome.h BH_ROUTE_WX3_PC
 ROUTE_WX3_SHARED = 2048   # include/bihome.h BH_ROUTE_WX3_SHARED             # ... the persistent kernel for every launch it supports (default: where it is the faster one)

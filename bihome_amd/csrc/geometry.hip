@@ -405,6 +405,167 @@ __global__ void dsac_best_kernel(const float* __restrict__ err, int B, int n, in
 }
 
 // ---------------------------------------------------------------------------------------------
+// DSAC inlier-count scoring ('inliers_ratio' / 'soft_inliers_ratio', ransac_utils.py:98-111).  Per point and hypothesis
+//   t = H.(x, y) with the guard of dsac_score_kernel, m = (x + pf_x, y + pf_y), e = sqrt((tx - mx)^2 + (ty - my)^2)   (fp32)
+//   hard: score = #{e < thr} / (h*w)  - an integer count, independent of the order of execution
+//   soft: score = sum sigmoid(beta (e - thr)), accumulated in double
+// SIGN: upstream feeds both into softmax(-score) (:126) and evaluates by argmax of that weight = the first MINIMUM of the score.  The soft
+// score therefore counts soft OUTLIERS and the lower one wins - consistent.  The hard ratio counts INLIERS and is negated all the same,
+// so upstream prefers the hypothesis with the FEWEST inliers: an upstream quirk, reproduced as it is, not repaired.
+// Form: a workgroup holds a tile of DSAC_PT (adjoint: DSAC_PTB) points per thread in registers (coordinates and field read once) and loops over up to
+// DSAC_JF (forward) / DSAC_JB (adjoint) homographies of its sample, kept in LDS; grid (B, ceil(n / J)).  Each (b, j) has one writer, so
+// no workspace and no atomics on the scores; the field is read ceil(n / J) times per sample instead of n times, and the adjoint adds
+// into g_pf once per point and workgroup instead of once per point and hypothesis.
+// ---------------------------------------------------------------------------------------------
+#define DSAC_JF 8
+#define DSAC_JB 4
+#define DSAC_PT 4      // points per thread and tile, forward
+#define DSAC_PTB 2     // ... adjoint (its 9 double sums per hypothesis take the registers)
+
+// the tile of thread `tid`: points base + p * 256 + tid; a point past the end is clamped to index 0 and flagged
+template <int PT>
+__device__ __forceinline__ void dsac_load_tile(const float* __restrict__ pfx, const float* __restrict__ pfy, int base, int N, int w,
+                                               int* idx, bool* valid, float* x, float* y, float* mx, float* my) {
+#pragma unroll
+    for (int p = 0; p < PT; ++p) {
+        const int i = base + p * 256 + (int)threadIdx.x;
+        valid[p] = i < N;
+        idx[p] = valid[p] ? i : 0;
+        x[p] = (float)(idx[p] % w); y[p] = (float)(idx[p] / w);
+        mx[p] = x[p] + pfx[idx[p]]; my[p] = y[p] + pfy[idx[p]];
+    }
+}
+
+template <bool SOFT>
+__global__ void __launch_bounds__(256) dsac_score_m_kernel(const float* __restrict__ pf, const float* __restrict__ Hd, int n, int h,
+                                                           int w, float thr, float beta, float* __restrict__ score) {
+    __shared__ float Hs[DSAC_JF * 9];
+    __shared__ double part[4][DSAC_JF];
+    const int b = blockIdx.x, j0 = blockIdx.y * DSAC_JF, nj = min(DSAC_JF, n - j0), N = h * w;
+    if ((int)threadIdx.x < nj * 9) Hs[threadIdx.x] = Hd[((size_t)b * n + j0) * 9 + threadIdx.x];
+    __syncthreads();
+    const float* pfx = pf + (size_t)b * 2 * N;
+    const float* pfy = pfx + N;
+    double acc[DSAC_JF];           // (the hard count goes through the same double: integers below 2^53 add exactly)
+#pragma unroll
+    for (int j = 0; j < DSAC_JF; ++j) acc[j] = 0.0;
+    for (int base = 0; base < N; base += 256 * DSAC_PT) {
+        int idx[DSAC_PT];
+        bool valid[DSAC_PT];
+        float x[DSAC_PT], y[DSAC_PT], mx[DSAC_PT], my[DSAC_PT];
+        dsac_load_tile<DSAC_PT>(pfx, pfy, base, N, w, idx, valid, x, y, mx, my);
+#pragma unroll
+        for (int j = 0; j < DSAC_JF; ++j) {
+            if (j >= nj) break;                                   // (the same in every lane)
+            const float* Hm = Hs + j * 9;
+            const float H0 = Hm[0], H1 = Hm[1], H2 = Hm[2], H3 = Hm[3], H4 = Hm[4], H5 = Hm[5], H6 = Hm[6], H7 = Hm[7], H8 = Hm[8];
+#pragma unroll
+            for (int p = 0; p < DSAC_PT; ++p) {
+                const float qx = H0 * x[p] + H1 * y[p] + H2, qy = H3 * x[p] + H4 * y[p] + H5, qz = H6 * x[p] + H7 * y[p] + H8;
+                const float s = fabsf(qz) > 1e-8f ? 1.0f / qz : 1.0f;
+                const float rx = qx * s - mx[p], ry = qy * s - my[p];
+                const float e = sqrtf(rx * rx + ry * ry);
+                float v;
+                if (SOFT) {
+                    const float u = beta * (e - thr), a = expf(-fabsf(u));      // sigmoid(u) without overflow for either sign
+                    v = (u >= 0.f ? 1.0f : a) / (1.0f + a);                     // (a NaN distance stays NaN, as in torch)
+                } else {
+                    v = e < thr ? 1.0f : 0.0f;
+                }
+                if (valid[p]) acc[j] += (double)v;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < DSAC_JF; ++j) {
+        const double v = wave_sum(acc[j]);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][j] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nj) {
+        const double v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+        score[(size_t)b * n + j0 + threadIdx.x] = SOFT ? (float)v : (float)v / (float)N;
+    }
+}
+
+// adjoint of the soft score: g_sc[B,n] (gradient w.r.t. the scores) -> g_Hd[B*n,9] (double, overwritten) and g_pf[B,2,h,w] +=.
+// grid (B, G) with G = ceil(n / DSAC_JB) hypothesis groups per sample, or (B, 1) in deterministic mode: one workgroup walks the groups of
+// its sample in order, and point i is always handled by thread i % 256, so the adds to g_pf[i] follow the group order.
+__global__ void __launch_bounds__(256) dsac_soft_score_bwd_kernel(const float* __restrict__ pf, const float* __restrict__ Hd,
+                                                                  const float* __restrict__ g_sc, int n, int h, int w, float thr,
+                                                                  float beta, double* __restrict__ g_Hd, float* __restrict__ g_pf) {
+    __shared__ float Hs[DSAC_JB * 9];
+    __shared__ float ges[DSAC_JB];
+    __shared__ double part[4][DSAC_JB * 9];
+    const int b = blockIdx.x, N = h * w, G = (n + DSAC_JB - 1) / DSAC_JB;
+    const float* pfx = pf + (size_t)b * 2 * N;
+    const float* pfy = pfx + N;
+    float* gxp = g_pf + (size_t)b * 2 * N;
+    float* gyp = gxp + N;
+    for (int g = blockIdx.y; g < G; g += gridDim.y) {
+        const int j0 = g * DSAC_JB, nj = min(DSAC_JB, n - j0);
+        if ((int)threadIdx.x < nj * 9) Hs[threadIdx.x] = Hd[((size_t)b * n + j0) * 9 + threadIdx.x];
+        if ((int)threadIdx.x < nj) ges[threadIdx.x] = g_sc[(size_t)b * n + j0 + threadIdx.x];
+        __syncthreads();
+        double s[DSAC_JB][9];
+#pragma unroll
+        for (int j = 0; j < DSAC_JB; ++j)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) s[j][k] = 0.0;
+        for (int base = 0; base < N; base += 256 * DSAC_PTB) {
+            int idx[DSAC_PTB];
+            bool valid[DSAC_PTB];
+            float x[DSAC_PTB], y[DSAC_PTB], mx[DSAC_PTB], my[DSAC_PTB], gx[DSAC_PTB], gy[DSAC_PTB];
+            dsac_load_tile<DSAC_PTB>(pfx, pfy, base, N, w, idx, valid, x, y, mx, my);
+#pragma unroll
+            for (int p = 0; p < DSAC_PTB; ++p) gx[p] = gy[p] = 0.f;
+#pragma unroll
+            for (int j = 0; j < DSAC_JB; ++j) {
+                if (j >= nj) break;
+                const float* Hm = Hs + j * 9;
+                const float H0 = Hm[0], H1 = Hm[1], H2 = Hm[2], H3 = Hm[3], H4 = Hm[4], H5 = Hm[5], H6 = Hm[6], H7 = Hm[7], H8 = Hm[8];
+                const float gb = ges[j] * beta;
+#pragma unroll
+                for (int p = 0; p < DSAC_PTB; ++p) {
+                    const float qx = H0 * x[p] + H1 * y[p] + H2, qy = H3 * x[p] + H4 * y[p] + H5, qz = H6 * x[p] + H7 * y[p] + H8;
+                    const bool ok = fabsf(qz) > 1e-8f;
+                    const float sc = ok ? 1.0f / qz : 1.0f;
+                    const float tx = qx * sc, ty = qy * sc;
+                    const float rx = tx - mx[p], ry = ty - my[p];
+                    const float e = sqrtf(rx * rx + ry * ry);
+                    const float a = expf(-fabsf(beta * (e - thr)));
+                    // d sigmoid(u) = sigmoid(u) (1 - sigmoid(u)) = a / (1 + a)^2 with a = exp(-|u|);  d e / d t = (t - m) / e, 0 at e == 0
+                    const float de = (valid[p] && e > 0.f) ? gb * a / ((1.0f + a) * (1.0f + a)) / e : 0.f;
+                    const float gtx = de * rx, gty = de * ry;
+                    gx[p] -= gtx; gy[p] -= gty;                   // m = coord + pf enters with the opposite sign
+                    const double gqx = (double)(gtx * sc), gqy = (double)(gty * sc);
+                    const double gqz = (ok && de != 0.f) ? -(double)(gtx * tx + gty * ty) * (double)sc : 0.0;
+                    s[j][0] += gqx * x[p]; s[j][1] += gqx * y[p]; s[j][2] += gqx;
+                    s[j][3] += gqy * x[p]; s[j][4] += gqy * y[p]; s[j][5] += gqy;
+                    s[j][6] += gqz * x[p]; s[j][7] += gqz * y[p]; s[j][8] += gqz;
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < DSAC_PTB; ++p) {
+                if (valid[p] && gx[p] != 0.f) atomicAdd(gxp + idx[p], gx[p]);
+                if (valid[p] && gy[p] != 0.f) atomicAdd(gyp + idx[p], gy[p]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < DSAC_JB; ++j)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const double v = wave_sum(s[j][k]);
+                if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][j * 9 + k] = v;
+            }
+        __syncthreads();
+        if ((int)threadIdx.x < nj * 9)
+            g_Hd[((size_t)b * n + j0) * 9 + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 extern "C" {
 
 int bh_h4pt_fwd(const float* delta, int B, float W, float H, double* H64, float* H32, void* stream) {
@@ -494,6 +655,43 @@ int bh_dsac_scores_bwd_f(const float* pf, const float* Hdlt, const float* scores
     BH_LAUNCH_CHECK();
     hipLaunchKernelGGL(dsac_score_bwd_kernel, dim3(B, (flags & BH_F_DETERMINISTIC) ? 1 : n), dim3(256), 0, bh_stream(stream), pf, Hdlt, g_err, h, w,
                        g_Hdlt, g_pf, n);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+int bh_dsac_score_m(const float* pf, const float* Hdlt, int B, int n, int h, int w, int method, float thr, float beta, float* score,
+                    int64_t* best, void* stream) {
+    if (method != BH_DSAC_REPR_ERROR && method != BH_DSAC_INLIERS && method != BH_DSAC_SOFT_INLIERS) return BH_E_BADARG;
+    if (thr != thr || beta != beta || thr < 0.f) return BH_E_BADARG;
+    if (!pf || !Hdlt || !score || B < 0 || n < 1 || h < 1 || w < 1) return BH_E_BADARG;
+    if (method == BH_DSAC_REPR_ERROR) return bh_dsac_score(pf, Hdlt, B, n, h, w, score, best, stream);
+    if ((int64_t)h * w > (1 << 30)) return BH_E_UNSUPPORTED;
+    if (B == 0) return BH_OK;
+    const dim3 grid(B, (n + DSAC_JF - 1) / DSAC_JF);
+    if (method == BH_DSAC_SOFT_INLIERS)
+        hipLaunchKernelGGL(dsac_score_m_kernel<true>, grid, dim3(256), 0, bh_stream(stream), pf, Hdlt, n, h, w, thr, beta, score);
+    else
+        hipLaunchKernelGGL(dsac_score_m_kernel<false>, grid, dim3(256), 0, bh_stream(stream), pf, Hdlt, n, h, w, thr, beta, score);
+    BH_LAUNCH_CHECK();
+    if (best) {
+        hipLaunchKernelGGL(dsac_best_kernel, dim3((B + 63) / 64), dim3(64), 0, bh_stream(stream), score, B, n, best);
+        BH_LAUNCH_CHECK();
+    }
+    return BH_OK;
+}
+
+int bh_dsac_scores_bwd_m(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h, int w,
+                         int method, float thr, float beta, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream) {
+    if (method != BH_DSAC_REPR_ERROR && method != BH_DSAC_SOFT_INLIERS) return BH_E_BADARG;      // the hard count has no adjoint
+    if (thr != thr || beta != beta || thr < 0.f) return BH_E_BADARG;
+    if (!pf || !Hdlt || !scores || !g_scores || !g_err || !g_Hdlt || !g_pf || B < 0 || n < 1 || h < 1 || w < 1) return BH_E_BADARG;
+    if (method == BH_DSAC_REPR_ERROR) return bh_dsac_scores_bwd_f(pf, Hdlt, scores, g_scores, B, n, h, w, g_err, g_Hdlt, g_pf, flags, stream);
+    if ((int64_t)h * w > (1 << 30)) return BH_E_UNSUPPORTED;
+    if (B == 0) return BH_OK;
+    hipLaunchKernelGGL(dsac_softmax_bwd_kernel, dim3((B + 63) / 64), dim3(64), 0, bh_stream(stream), scores, g_scores, B, n, g_err);
+    BH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dsac_soft_score_bwd_kernel, dim3(B, (flags & BH_F_DETERMINISTIC) ? 1 : (n + DSAC_JB - 1) / DSAC_JB), dim3(256), 0,
+                       bh_stream(stream), pf, Hdlt, g_err, n, h, w, thr, beta, g_Hdlt, g_pf);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

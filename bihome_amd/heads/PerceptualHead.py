@@ -150,24 +150,31 @@ class _DltFunction(torch.autograd.Function):
 
 @K.scoped_function
 class _DsacScores(torch.autograd.Function):
-    """DSACSoftmax.__score_hypotheses (ransac_utils.py:76-128): scores[N,n] = softmax(-sum_points |H.coord - map|_1), with
-    its adjoint w.r.t. the perspective field (every point) and the hypotheses' homographies."""
+    """DSACSoftmax.__score_hypotheses (ransac_utils.py:76-128): scores[N,n] = softmax(-raw score) with the raw score of `method`
+    (sum_points |H.coord - map|_1, the inlier ratio, or the soft outlier count), and its adjoint w.r.t. the perspective field (every
+    point) and the hypotheses' homographies.  'inliers_ratio': upstream's comparison cuts the graph - the scores carry no gradient and
+    backward launches nothing."""
 
     @staticmethod
-    def forward(ctx, pf, Hd):
+    def forward(ctx, pf, Hd, method="repr_error", thr=0.0, beta=0.0):
         pf = pf.contiguous()
         N, n = Hd.shape[0], Hd.shape[1]
         Hflat = Hd.reshape(N * n, 9).contiguous()
-        scores, _ = K.dsac_scores_fwd(pf, Hflat, n)
-        ctx.save_for_backward(pf, Hflat, scores)
-        ctx.n = n
+        scores, _ = K.dsac_scores_fwd(pf, Hflat, n, method, thr, beta)
+        ctx.n, ctx.method, ctx.thr, ctx.beta = n, method, thr, beta
+        if method == "inliers_ratio":
+            ctx.mark_non_differentiable(scores)
+        else:
+            ctx.save_for_backward(pf, Hflat, scores)
         return scores
 
     @staticmethod
     def backward(ctx, g_scores):
+        if ctx.method == "inliers_ratio":
+            return None, None, None, None, None
         pf, Hflat, scores = ctx.saved_tensors
-        g_pf, g_Hd = K.dsac_scores_bwd(pf, Hflat, scores, g_scores.contiguous(), ctx.n)
-        return g_pf, g_Hd.to(torch.float32).view(-1, ctx.n, 3, 3)
+        g_pf, g_Hd = K.dsac_scores_bwd(pf, Hflat, scores, g_scores.contiguous(), ctx.n, ctx.method, ctx.thr, ctx.beta)
+        return g_pf, g_Hd.to(torch.float32).view(-1, ctx.n, 3, 3), None, None, None
 
 
 @K.scoped_function
@@ -380,8 +387,18 @@ class Model(nn.Module):
             self.pf_keys = kwargs['PF_KEYS']
             self.hypothesis_no = kwargs['RANSAC_HYPOTHESIS_NO']
             self.point_per_hypothesis = kwargs['POINTS_PER_HYPOTHESIS']
-            if kwargs.get('SCORING_METHOD', 'repr_error') != 'repr_error':
-                raise NotImplementedError("only SCORING_METHOD='repr_error' is built")
+            # DSACSoftmax.__init__ (ransac_utils.py:28-45): a missing threshold / beta is a KeyError, as upstream
+            self.scoring_method = kwargs.get('SCORING_METHOD', 'repr_error')
+            self.scoring_distance_threshold = self.scoring_distance_beta = 0.0
+            if self.scoring_method == 'score_cnn':
+                raise NotImplementedError("SCORING_METHOD='score_cnn' (a ResNet-18 that scores the residual field) is not built; built: "
+                                          "'repr_error', 'inliers_ratio', 'soft_inliers_ratio'")
+            if self.scoring_method not in ('repr_error', 'inliers_ratio', 'soft_inliers_ratio'):
+                raise ValueError("unknown SCORING_METHOD %r" % (self.scoring_method,))
+            if self.scoring_method == 'soft_inliers_ratio':
+                self.scoring_distance_beta = float(kwargs['SCORING_DISTANCE_BETA'])
+            if self.scoring_method != 'repr_error':
+                self.scoring_distance_threshold = float(kwargs['SCORING_DISTANCE_THRESHOLD'])
         self.triplet_version = kwargs['TRIPLET_LOSS']
         self.multihead = self.triplet_version == ''           # PerceptualHead.py:108,:230-235 -> multihead_resnet_loss
         common = ('dual' not in self.triplet_version and kwargs.get('TRIPLET_DISTANCE') == 'l1'
@@ -521,7 +538,11 @@ class Model(nn.Module):
             c12 = self._choices(data, 'choice_12', B, N, pf.device)
             dh, Hd = _DltFunction.apply(pf, c12, n, self.point_per_hypothesis)
             self.last_dlt = Hd
-            scores = _DsacScores.apply(pf, Hd).reshape(B * n) if n > 1 else None
+            scores = None
+            if n > 1:
+                scores = _DsacScores.apply(pf, Hd, self.scoring_method, self.scoring_distance_threshold, self.scoring_distance_beta)
+                self.last_scores = scores.detach()              # [B, n], kept next to last_dlt for inspection
+                scores = scores.reshape(B * n)
             return dh.reshape(B * n, 4, 2), scores
         return data[self.delta_hat_keys[0]].reshape(B, 4, 2), None
 
@@ -586,7 +607,8 @@ class Model(nn.Module):
         Hd, dh, _ = K.dlt_fwd(pf, choice, n, P)
         if n == 1:
             return dh.view(B, 4, 2), None
-        err, best = K.dsac_score(pf, Hd.view(-1, 9), n)         # argmax softmax(-err) == argmin err (:755-757)
+        err, best = K.dsac_score(pf, Hd.view(-1, 9), n, self.scoring_method, self.scoring_distance_threshold,
+                                 self.scoring_distance_beta)          # argmax softmax(-score) == first argmin score (:755-757)
         self.last.update(best=best, repr_error=err)
         return dh.view(B, n, 4, 2)[torch.arange(B, device=pf.device), best], None
 

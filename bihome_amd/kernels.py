@@ -5,7 +5,7 @@ import os
 
 import torch
 
-from ._lib import (AMAX_FLOATS, BN_DETERMINISTIC, F_DETERMINISTIC, GEOMETRY_FIELDS, ROUTE_DETERMINISTIC, ROUTE_WX3_PC, ROUTE_WX3_SHARED, BhBnIn, BhBnReduce, BhConvDesc,
+from ._lib import (AMAX_FLOATS, BN_DETERMINISTIC, DSAC_METHODS, F_DETERMINISTIC, GEOMETRY_FIELDS, ROUTE_DETERMINISTIC, ROUTE_WX3_PC, ROUTE_WX3_SHARED, BhBnIn, BhBnReduce, BhConvDesc,
                    BhPack3x3Job, check, lib)
 
 
@@ -245,26 +245,43 @@ def dlt_bwd(pf, choice, eig, g_delta, n, P, g_H=None):
     return g_pf
 
 
-def dsac_scores_fwd(pf, Hd, n):
-    """scores[B,n] = softmax(-reprojection error) (ransac_utils.py:76-128); returns (scores, err)."""
+def _dsac_method(method, thr, beta):
+    """-> (BH_DSAC_* code, thr, beta) of a DSACSoftmax scoring method; 'repr_error' takes neither parameter."""
+    if method not in DSAC_METHODS:
+        raise ValueError("unknown DSAC scoring method %r (built: %s)" % (method, ", ".join(DSAC_METHODS)))
+    return DSAC_METHODS[method], float(thr), float(beta)
+
+
+def dsac_scores_fwd(pf, Hd, n, method="repr_error", thr=0.0, beta=0.0):
+    """scores[B,n] = softmax(-raw score) (ransac_utils.py:76-128); returns (scores, raw).  raw: the reprojection error ('repr_error'),
+    the inlier ratio ('inliers_ratio', e < thr) or the soft outlier count ('soft_inliers_ratio', sum sigmoid(beta (e - thr)))."""
     _chk(pf); _chk(Hd)
     B, _, h, w = pf.shape
     err = torch.empty(B, n, dtype=torch.float32, device=pf.device)
     scores = torch.empty_like(err)
-    check(lib.bh_dsac_score(_p(pf), _p(Hd), B, n, h, w, _p(err), None, _stream()), "bh_dsac_score")
+    if method == "repr_error":
+        check(lib.bh_dsac_score(_p(pf), _p(Hd), B, n, h, w, _p(err), None, _stream()), "bh_dsac_score")
+    else:
+        m, thr, beta = _dsac_method(method, thr, beta)
+        check(lib.bh_dsac_score_m(_p(pf), _p(Hd), B, n, h, w, m, thr, beta, _p(err), None, _stream()), "bh_dsac_score_m")
     check(lib.bh_dsac_scores_fwd(_p(err), B, n, _p(scores), _stream()), "bh_dsac_scores_fwd")
     return scores, err
 
 
-def dsac_scores_bwd(pf, Hd, scores, g_scores, n):
-    """-> (g_pf [B,2,h,w], g_Hd [B*n,9] float64)."""
+def dsac_scores_bwd(pf, Hd, scores, g_scores, n, method="repr_error", thr=0.0, beta=0.0):
+    """-> (g_pf [B,2,h,w], g_Hd [B*n,9] float64).  'inliers_ratio' has no adjoint (BH_E_BADARG)."""
     _chk(pf); _chk(Hd); _chk(scores); _chk(g_scores)
     B, _, h, w = pf.shape
     g_err = torch.empty_like(scores)
     g_Hd = torch.empty(B * n, 9, dtype=torch.float64, device=pf.device)
     g_pf = torch.zeros_like(pf)
-    check(lib.bh_dsac_scores_bwd_f(_p(pf), _p(Hd), _p(scores), _p(g_scores), B, n, h, w, _p(g_err), _p(g_Hd), _p(g_pf), _fdet(), _stream()),
-          "bh_dsac_scores_bwd")
+    if method == "repr_error":
+        check(lib.bh_dsac_scores_bwd_f(_p(pf), _p(Hd), _p(scores), _p(g_scores), B, n, h, w, _p(g_err), _p(g_Hd), _p(g_pf), _fdet(), _stream()),
+              "bh_dsac_scores_bwd")
+    else:
+        m, thr, beta = _dsac_method(method, thr, beta)
+        check(lib.bh_dsac_scores_bwd_m(_p(pf), _p(Hd), _p(scores), _p(g_scores), B, n, h, w, m, thr, beta, _p(g_err), _p(g_Hd), _p(g_pf),
+                                       _fdet(), _stream()), "bh_dsac_scores_bwd_m")
     return g_pf, g_Hd
 
 
@@ -288,12 +305,17 @@ def scale_samples_bwd(g_y, x, s, rep, want_gx):
     return g_x, g_s
 
 
-def dsac_score(pf, Hd, n):
+def dsac_score(pf, Hd, n, method="repr_error", thr=0.0, beta=0.0):
+    """-> (raw score [B,n], best [B] int64: its first minimum = argmax softmax(-score))."""
     _chk(pf); _chk(Hd)
     B, _, h, w = pf.shape
     err = torch.empty(B, n, dtype=torch.float32, device=pf.device)
     best = torch.empty(B, dtype=torch.int64, device=pf.device)
-    check(lib.bh_dsac_score(_p(pf), _p(Hd), B, n, h, w, _p(err), _p(best), _stream()), "bh_dsac_score")
+    if method == "repr_error":
+        check(lib.bh_dsac_score(_p(pf), _p(Hd), B, n, h, w, _p(err), _p(best), _stream()), "bh_dsac_score")
+    else:
+        m, thr, beta = _dsac_method(method, thr, beta)
+        check(lib.bh_dsac_score_m(_p(pf), _p(Hd), B, n, h, w, m, thr, beta, _p(err), _p(best), _stream()), "bh_dsac_score_m")
     return err, best
 
 

@@ -106,6 +106,31 @@ int bh_dsac_scores_bwd(const float* pf, const float* Hdlt, const float* scores, 
 int bh_dsac_scores_bwd_f(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h,
                          int w, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream);
 
+/* The scoring methods of DSACSoftmax.__score_hypotheses (ransac_utils.py:76-128) behind one pair of calls.  Per point (x, y) of the field
+ * and hypothesis j: t = H_j.(x, y) (scale s = |qz| > 1e-8 ? 1/qz : 1, as in bh_dsac_score), m = (x + pf[b,0,y,x], y + pf[b,1,y,x]),
+ * e = sqrt((tx - mx)^2 + (ty - my)^2), all fp32.
+ *   BH_DSAC_REPR_ERROR     score = sum |t - m|_1: bh_dsac_score / bh_dsac_scores_bwd_f themselves (delegated, bitwise the same); thr and
+ *                          beta are checked and otherwise unused
+ *   BH_DSAC_INLIERS        'inliers_ratio' (:98-103): score = #{points with e < thr} / (h*w); the comparison strict, the count an integer
+ *                          (independent of the order of execution).  No adjoint: upstream's comparison cuts the graph
+ *   BH_DSAC_SOFT_INLIERS   'soft_inliers_ratio' (:105-111): score = sum over the points of sigmoid(beta (e - thr)), accumulated in double
+ * SIGN CONVENTION, upstream's and kept: the weights are softmax(-score) (:126, bh_dsac_scores_fwd, unchanged) and the evaluation pick is
+ * their arg-max = the FIRST MINIMUM of score (best[B] int64, NULL ok).  The soft score thus counts soft OUTLIERS and the lower one wins.
+ * The hard ratio counts INLIERS and is negated too: upstream prefers the hypothesis with the FEWEST inliers.  That is an upstream quirk;
+ * it is reproduced, not repaired.
+ * bh_dsac_scores_bwd_m: adjoint of scoring + softmax for the soft method (method 0: bh_dsac_scores_bwd_f).  scores[B,n] the softmax weights,
+ * g_scores[B,n] -> g_err[B,n] (scratch, overwritten: the gradient w.r.t. the raw scores), g_Hdlt[B*n,9] (double, overwritten) and
+ * g_pf[B,2,h,w] += (atomics).  d score / d e = beta sg (1 - sg) with sg = sigmoid(beta (e - thr)); d e / d t = (t - m) / e and exactly 0 where
+ * e == 0 (torch's sub-gradient of norm); through the quotient as in bh_dsac_scores_bwd.  flags & BH_F_DETERMINISTIC: one workgroup per
+ * sample adds the hypotheses in order - bit-identical from call to call (the contract of bh_dsac_scores_bwd_f).
+ * BH_E_BADARG, checked before any launch: an unknown method, BH_DSAC_INLIERS passed to the adjoint, thr or beta NaN, thr < 0, n < 1,
+ * h or w < 1, a NULL pointer other than best.  BH_E_UNSUPPORTED: h*w > 2^30.  B == 0: BH_OK, nothing launched. */
+enum { BH_DSAC_REPR_ERROR = 0, BH_DSAC_INLIERS = 1, BH_DSAC_SOFT_INLIERS = 2 };
+int bh_dsac_score_m(const float* pf, const float* Hdlt, int B, int n, int h, int w, int method, float thr, float beta,
+                    float* score, int64_t* best, void* stream);
+int bh_dsac_scores_bwd_m(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h, int w,
+                         int method, float thr, float beta, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream);
+
 /* Robust homography of a perspective field: RANSAC over K minimal samples + least-squares refit on the inliers of the winner - the
  * estimator of upstream's NoOpHead._postprocess, cv2.findHomography(src, dst, cv2.RANSAC, 10) over all h*w correspondences
  * (src/heads/NoOpHead.py:75-109), batched on the device (csrc/ransac.hip).  cv2's Levenberg-Marquardt polish after the refit is a call
