@@ -54,44 +54,34 @@ SIGNATURES = {
     "bh_h4pt_fwd": [P, c_int, c_float, c_float, P, P, P],
     "bh_h4pt_bwd": [P, P, P, c_int, c_float, c_float, P, P],
     "bh_dlt_fwd": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P],
-    "bh_dlt_bwd": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P],
-    "bh_dlt_bwd_f": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
+    "bh_dlt_bwd": [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
     "bh_dsac_scores_fwd": [P, c_int, c_int, P, P],
-    "bh_dsac_scores_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P],
-    "bh_dsac_scores_bwd_f": [P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, P],
     "bh_scale_samples_fwd": [P, P, c_int, c_int64, c_int, P, P],
-    "bh_scale_samples_bwd": [P, P, P, c_int, c_int64, c_int, P, P, P],
-    "bh_scale_samples_bwd_f": [P, P, P, c_int, c_int64, c_int, P, P, c_int, P],
-    "bh_dsac_score": [P, P, c_int, c_int, c_int, c_int, P, P, P],
-    "bh_dsac_score_m": [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P],
-    "bh_dsac_scores_bwd_m": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, c_int, P],
+    "bh_scale_samples_bwd": [P, P, P, c_int, c_int64, c_int, P, P, c_int, P],
+    "bh_dsac_score": [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P],
+    "bh_dsac_scores_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, c_int, P],
     "bh_ransac_homography": [P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P],
     "bh_homography_refine_lm": [P, P, c_int, c_int, c_int, c_int, P, P, P, P],
-    "bh_warp_fwd": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, P],
-    "bh_warp_fwd_f": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P],
-    "bh_warp_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P],
-    "bh_warp_bwd_f": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
-    "bh_triplet_l1_fwd": [P] * 8 + [c_int, c_int, c_int, P, P, P, P],
-    "bh_triplet_l1_fwd_f": [P] * 8 + [c_int, c_int, c_int, P, P, P, c_int, P],
+    "bh_warp_fwd": [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P],
+    "bh_warp_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
+    "bh_triplet_l1_fwd": [P] * 8 + [c_int, c_int, c_int, P, P, P, c_int, P],
     "bh_bihome_loss_fwd": [P, P, P, c_int, c_float, P, P],
     "bh_bihome_loss_bwd": [P] * 14 + [c_int, c_int, c_int, c_float] + [P] * 6 + [P],
-    "bh_oneline_loss_fwd": [P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, P, P, P, P, P, P],
-    "bh_oneline_loss_fwd_f": [P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, P, P, P, P, P, c_int, P],
+    "bh_oneline_loss_fwd": [P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, P, P, P, P, P, c_int, P],
     "bh_oneline_loss_bwd": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P],
     "bh_zhang_triplet_fwd": [P] * 8 + [c_int, c_int, c_float, c_int, P, P, P, P],
-    "bh_zhang_triplet_bwd": [P] * 12 + [c_int, c_int, c_int] + [P] * 6 + [P],
-    "bh_zhang_triplet_bwd_m": [P] * 12 + [c_int, c_int, c_int] + [P] * 8 + [P],
-    "bh_warp_bwd_img_f": [P, P, c_int, c_int, c_int, c_int, P, P, c_int, P],
-    "bh_photo_warp_fwd_f": [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
-    "bh_photo_warp_bwd_f": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
+    "bh_zhang_triplet_bwd": [P] * 12 + [c_int, c_int, c_int] + [P] * 8 + [P],
+    "bh_warp_bwd_img": [P, P, c_int, c_int, c_int, c_int, P, P, c_int, P],
+    "bh_photo_warp_fwd": [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
+    "bh_photo_warp_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
     "bh_mask_fwd": [P, P, c_int, c_int, c_float, P, P, P, P, P],
     "bh_mask_bwd": [P] * 7 + [c_int, c_int, c_float, P, P, P],
     "bh_conv3x3_pack": [P, c_int, P],
     "bh_conv3x3_pack_f16": [P, c_int, P],
     "bh_absmax": [P, c_int64, P, P],
-    "bh_bn_fwd_coeffs_amax": [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P],
-    "bh_bn_fwd_amax": [P] * 8 + [c_int, c_int, c_int, c_float, c_float, c_int, c_int, P, P],
-    "bh_bn_bwd_amax": [P] * 11 + [c_int, c_int, c_int, c_float, c_int, c_int, P, P, P, P],
+    "bh_bn_fwd_coeffs": [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P],
+    "bh_bn_fwd": [P] * 8 + [c_int, c_int, c_int, c_float, c_float, c_int, c_int, P, P],
+    "bh_bn_bwd": [P] * 11 + [c_int, c_int, c_int, c_float, c_int, c_int, P, P, P, P],
     "bh_conv_variant": [POINTER(BhConvDesc), c_int, c_int, c_int, c_char_p, c_int],
     "bh_conv_fwd": [P, P, P, P, POINTER(BhConvDesc), P],
     "bh_conv_fwd_act": [P, P, P, P, P, POINTER(BhConvDesc), c_int, P],
@@ -99,7 +89,6 @@ SIGNATURES = {
     "bh_conv_fwd_bnstats": [P, P, P, P, POINTER(BhConvDesc), P, c_int, P],
     "bh_conv_fwd_bnin": [P, P, P, P, POINTER(BhConvDesc), P, c_int, POINTER(BhBnIn), P],
     "bh_conv_wgrad_bnin": [P, P, P, P, POINTER(BhConvDesc), P, c_int64, POINTER(BhBnIn), P],
-    "bh_bn_fwd_coeffs": [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P],
     "bh_conv_dgrad": [P, P, P, POINTER(BhConvDesc), c_int, P],
     "bh_conv_dgrad_colsum": [P, P, P, POINTER(BhConvDesc), P, P],
     "bh_bias_grad_from_sums": [P, P, c_int, c_int, P],
@@ -115,8 +104,6 @@ SIGNATURES = {
     "bh_conv_bias_grad": [P, P, POINTER(BhConvDesc), P],
     "bh_bn_stats_doubles": [c_int, c_int],
     "bh_bn_scratch_doubles": [c_int, c_int],
-    "bh_bn_fwd": [P] * 8 + [c_int, c_int, c_int, c_float, c_float, c_int, c_int, P],
-    "bh_bn_bwd": [P] * 11 + [c_int, c_int, c_int, c_float, c_int, c_int, P, P, P],
     "bh_bn_stats": [P, P, c_int, c_int, c_int, c_int, P],
     "bh_bn_maxpool_fwd": [P] * 8 + [c_int] * 5 + [c_float, c_float, c_int, c_int, P, P],
     "bh_bn_maxpool_bwd": [P] * 10 + [c_int] * 5 + [c_float, c_int, c_int, P, P, P, P],
@@ -127,10 +114,8 @@ SIGNATURES = {
     "bh_bn_join_bwd_remask": [P] * 16 + [c_int, c_int, c_int, c_float, c_float, c_int, P, P, P],
     "bh_tail_ws_doubles": [c_int, c_int, c_int],
     "bh_tail_scratch_floats": [c_int, c_int, c_int],
-    "bh_tail_fwd": [P] * 11 + [c_int] * 6 + [c_float, c_float, c_int, P],
-    "bh_tail_fwd_route": [P] * 11 + [c_int] * 6 + [c_float, c_float, c_int, c_int, P],
-    "bh_tail_bwd": [P] * 17 + [c_int] * 6 + [c_float, c_int, P],
-    "bh_tail_bwd_f": [P] * 17 + [c_int] * 6 + [c_float, c_int, c_int, P],
+    "bh_tail_fwd": [P] * 11 + [c_int] * 6 + [c_float, c_float, c_int, c_int, P],
+    "bh_tail_bwd": [P] * 17 + [c_int] * 6 + [c_float, c_int, c_int, P],
     "bh_synth_pairs": [P] * 5 + [c_int] * 5 + [c_float, c_float, P, P, P],
     "bh_synth_image": [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],

@@ -6,7 +6,7 @@ gfx950 kernels.  State-dict keys `mask_predictor.layerN.*`, `feature_extractor.l
 Every shipped zhang-* config sets FIX_MASK: True - the mask is all ones and the mask predictor never runs.  FIX_MASK: False (round 4):
 the predictor's five Conv3x3 + BatchNorm layers run on the conv executor (statistics per call), csrc/mask.hip applies the Sigmoid, the
 per-sample max normalisation (MASK_NORMALIZATION_STRENGTH > 0) and G = mask * features in one launch, and its adjoint takes the
-mask gradients the TripletHead sends back (direct and through the warp, csrc/warp.hip bh_warp_bwd_img_f).  The last BatchNorm of the
+mask gradients the TripletHead sends back (direct and through the warp, csrc/warp.hip bh_warp_bwd_img).  The last BatchNorm of the
 predictor and of the extractor has ONE channel (csrc/bn1.hip); the tiny-channel convolutions run on the generic implicit-GEMM kernels."""
 import os
 

@@ -785,13 +785,7 @@ int bh_bn_stats_doubles(int groups, int C) { return (int)BH_BN_SUM_DOUBLES(group
 
 int bh_bn_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
               const float* res, float* y, double* stats, int groups, int rows, int C, float eps, float momentum,
-              int flags, int use_running, void* stream) {
-    return bh_bn_fwd_amax(x, gamma, beta, running_mean, running_var, res, y, stats, groups, rows, C, eps, momentum, flags, use_running, nullptr, stream);
-}
-
-int bh_bn_fwd_amax(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
-                   const float* res, float* y, double* stats, int groups, int rows, int C, float eps, float momentum,
-                   int flags, int use_running, float* amax_y, void* stream) {
+              int flags, int use_running, float* amax_y, void* stream) {
     BnGeom g;
     if (!x || !y || !stats) return BH_E_BADARG;
     if (use_running && (!running_mean || !running_var)) return BH_E_BADARG;
@@ -811,12 +805,7 @@ int bh_bn_fwd_amax(const float* x, const float* gamma, const float* beta, float*
 }
 
 int bh_bn_fwd_coeffs(const double* stats, const float* gamma, const float* beta, float* running_mean, float* running_var, int groups,
-                     int rows, int C, float eps, float momentum, float* table, void* stream) {
-    return bh_bn_fwd_coeffs_amax(stats, gamma, beta, running_mean, running_var, groups, rows, C, eps, momentum, table, nullptr, stream);
-}
-
-int bh_bn_fwd_coeffs_amax(const double* stats, const float* gamma, const float* beta, float* running_mean, float* running_var, int groups,
-                          int rows, int C, float eps, float momentum, float* table, float* amax_y, void* stream) {
+                     int rows, int C, float eps, float momentum, float* table, float* amax_y, void* stream) {
     BnGeom g;
     if (!stats || !table) return BH_E_BADARG;
     if (!bn_geom(groups, rows, C, g, -1)) return BH_E_UNSUPPORTED;        // (a reader: looks at the limbs of whatever mode wrote the sums)
@@ -830,14 +819,7 @@ int bh_bn_fwd_coeffs_amax(const double* stats, const float* gamma, const float* 
 
 int bh_bn_bwd(const float* gy, const float* y, const float* x, const float* gamma, const float* beta, const double* stats, float* gx,
               float* gres, float* ggamma, float* gbeta, double* scratch, int groups, int rows, int C, float eps, int flags,
-              int use_running, const float* running_mean, const float* running_var, void* stream) {
-    return bh_bn_bwd_amax(gy, y, x, gamma, beta, stats, gx, gres, ggamma, gbeta, scratch, groups, rows, C, eps, flags, use_running, running_mean,
-                          running_var, nullptr, stream);
-}
-
-int bh_bn_bwd_amax(const float* gy, const float* y, const float* x, const float* gamma, const float* beta, const double* stats, float* gx,
-                   float* gres, float* ggamma, float* gbeta, double* scratch, int groups, int rows, int C, float eps, int flags,
-                   int use_running, const float* running_mean, const float* running_var, float* amax_gx, void* stream) {
+              int use_running, const float* running_mean, const float* running_var, float* amax_gx, void* stream) {
     BnGeom g;
     if (!gy || !x || !gx || !stats || !scratch || ((flags & 1) && !(flags & 4) && !y)) return BH_E_BADARG;
     if ((flags & 4) && (flags & 2)) return BH_E_BADARG;        // the mask can only be recomputed without a residual input

@@ -23,7 +23,7 @@ bool bh_query(const char* fmt, ...) {
 
 extern "C" {
 
-int bh_version(void) { return 1; }
+int bh_version(void) { return 2; }
 
 
 int bh_device_arch(char* buf, int buflen) {

@@ -598,12 +598,7 @@ int bh_dlt_fwd(const float* pf, const int64_t* choice, int B, int n, int P, int 
 }
 
 int bh_dlt_bwd(const float* pf, const int64_t* choice, const double* eig, const float* g_delta, const double* g_Hdlt, int B,
-               int n, int P, int h, int w, float* g_pf, void* stream) {
-    return bh_dlt_bwd_f(pf, choice, eig, g_delta, g_Hdlt, B, n, P, h, w, g_pf, 0, stream);
-}
-
-int bh_dlt_bwd_f(const float* pf, const int64_t* choice, const double* eig, const float* g_delta, const double* g_Hdlt, int B,
-                 int n, int P, int h, int w, float* g_pf, int flags, void* stream) {
+               int n, int P, int h, int w, float* g_pf, int flags, void* stream) {
     if (!pf || !choice || !eig || !g_delta || !g_pf || B < 0 || n < 1 || P < 4) return BH_E_BADARG;
     if (P > 64 * DLT_MAXPTS) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
@@ -621,19 +616,6 @@ int bh_dlt_bwd_f(const float* pf, const int64_t* choice, const double* eig, cons
     return BH_OK;
 }
 
-int bh_dsac_score(const float* pf, const float* Hdlt, int B, int n, int h, int w, float* err, int64_t* best,
-                  void* stream) {
-    if (!pf || !Hdlt || !err || B < 0 || n < 1) return BH_E_BADARG;
-    if (B == 0) return BH_OK;
-    hipLaunchKernelGGL(dsac_score_kernel, dim3(B, n), dim3(256), 0, bh_stream(stream), pf, Hdlt, h, w, err);
-    BH_LAUNCH_CHECK();
-    if (best) {
-        hipLaunchKernelGGL(dsac_best_kernel, dim3((B + 63) / 64), dim3(64), 0, bh_stream(stream), err, B, n, best);
-        BH_LAUNCH_CHECK();
-    }
-    return BH_OK;
-}
-
 int bh_dsac_scores_fwd(const float* err, int B, int n, float* scores, void* stream) {
     if (!err || !scores || B < 0 || n < 1) return BH_E_BADARG;
     if (B == 0) return BH_OK;
@@ -642,33 +624,17 @@ int bh_dsac_scores_fwd(const float* err, int B, int n, float* scores, void* stre
     return BH_OK;
 }
 
-int bh_dsac_scores_bwd(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h,
-                       int w, float* g_err, double* g_Hdlt, float* g_pf, void* stream) {
-    return bh_dsac_scores_bwd_f(pf, Hdlt, scores, g_scores, B, n, h, w, g_err, g_Hdlt, g_pf, 0, stream);
-}
-
-int bh_dsac_scores_bwd_f(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h,
-                         int w, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream) {
-    if (!pf || !Hdlt || !scores || !g_scores || !g_err || !g_Hdlt || !g_pf || B < 0 || n < 1) return BH_E_BADARG;
-    if (B == 0) return BH_OK;
-    hipLaunchKernelGGL(dsac_softmax_bwd_kernel, dim3((B + 63) / 64), dim3(64), 0, bh_stream(stream), scores, g_scores, B, n, g_err);
-    BH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dsac_score_bwd_kernel, dim3(B, (flags & BH_F_DETERMINISTIC) ? 1 : n), dim3(256), 0, bh_stream(stream), pf, Hdlt, g_err, h, w,
-                       g_Hdlt, g_pf, n);
-    BH_LAUNCH_CHECK();
-    return BH_OK;
-}
-
-int bh_dsac_score_m(const float* pf, const float* Hdlt, int B, int n, int h, int w, int method, float thr, float beta, float* score,
-                    int64_t* best, void* stream) {
+int bh_dsac_score(const float* pf, const float* Hdlt, int B, int n, int h, int w, int method, float thr, float beta, float* score,
+                  int64_t* best, void* stream) {
     if (method != BH_DSAC_REPR_ERROR && method != BH_DSAC_INLIERS && method != BH_DSAC_SOFT_INLIERS) return BH_E_BADARG;
     if (thr != thr || beta != beta || thr < 0.f) return BH_E_BADARG;
     if (!pf || !Hdlt || !score || B < 0 || n < 1 || h < 1 || w < 1) return BH_E_BADARG;
-    if (method == BH_DSAC_REPR_ERROR) return bh_dsac_score(pf, Hdlt, B, n, h, w, score, best, stream);
-    if ((int64_t)h * w > (1 << 30)) return BH_E_UNSUPPORTED;
+    if (method != BH_DSAC_REPR_ERROR && (int64_t)h * w > (1 << 30)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
-    const dim3 grid(B, (n + DSAC_JF - 1) / DSAC_JF);
-    if (method == BH_DSAC_SOFT_INLIERS)
+    const dim3 grid(B, (n + DSAC_JF - 1) / DSAC_JF);      // the inlier-count kernels take DSAC_JF hypotheses per workgroup
+    if (method == BH_DSAC_REPR_ERROR)
+        hipLaunchKernelGGL(dsac_score_kernel, dim3(B, n), dim3(256), 0, bh_stream(stream), pf, Hdlt, h, w, score);
+    else if (method == BH_DSAC_SOFT_INLIERS)
         hipLaunchKernelGGL(dsac_score_m_kernel<true>, grid, dim3(256), 0, bh_stream(stream), pf, Hdlt, n, h, w, thr, beta, score);
     else
         hipLaunchKernelGGL(dsac_score_m_kernel<false>, grid, dim3(256), 0, bh_stream(stream), pf, Hdlt, n, h, w, thr, beta, score);
@@ -680,18 +646,21 @@ int bh_dsac_score_m(const float* pf, const float* Hdlt, int B, int n, int h, int
     return BH_OK;
 }
 
-int bh_dsac_scores_bwd_m(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h, int w,
-                         int method, float thr, float beta, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream) {
+int bh_dsac_scores_bwd(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h, int w,
+                       int method, float thr, float beta, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream) {
     if (method != BH_DSAC_REPR_ERROR && method != BH_DSAC_SOFT_INLIERS) return BH_E_BADARG;      // the hard count has no adjoint
     if (thr != thr || beta != beta || thr < 0.f) return BH_E_BADARG;
     if (!pf || !Hdlt || !scores || !g_scores || !g_err || !g_Hdlt || !g_pf || B < 0 || n < 1 || h < 1 || w < 1) return BH_E_BADARG;
-    if (method == BH_DSAC_REPR_ERROR) return bh_dsac_scores_bwd_f(pf, Hdlt, scores, g_scores, B, n, h, w, g_err, g_Hdlt, g_pf, flags, stream);
-    if ((int64_t)h * w > (1 << 30)) return BH_E_UNSUPPORTED;
+    if (method != BH_DSAC_REPR_ERROR && (int64_t)h * w > (1 << 30)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
+    const bool det = flags & BH_F_DETERMINISTIC;
     hipLaunchKernelGGL(dsac_softmax_bwd_kernel, dim3((B + 63) / 64), dim3(64), 0, bh_stream(stream), scores, g_scores, B, n, g_err);
     BH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dsac_soft_score_bwd_kernel, dim3(B, (flags & BH_F_DETERMINISTIC) ? 1 : (n + DSAC_JB - 1) / DSAC_JB), dim3(256), 0,
-                       bh_stream(stream), pf, Hdlt, g_err, n, h, w, thr, beta, g_Hdlt, g_pf);
+    if (method == BH_DSAC_REPR_ERROR)
+        hipLaunchKernelGGL(dsac_score_bwd_kernel, dim3(B, det ? 1 : n), dim3(256), 0, bh_stream(stream), pf, Hdlt, g_err, h, w, g_Hdlt, g_pf, n);
+    else
+        hipLaunchKernelGGL(dsac_soft_score_bwd_kernel, dim3(B, det ? 1 : (n + DSAC_JB - 1) / DSAC_JB), dim3(256), 0, bh_stream(stream), pf, Hdlt,
+                           g_err, n, h, w, thr, beta, g_Hdlt, g_pf);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

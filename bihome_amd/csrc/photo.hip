@@ -72,8 +72,8 @@ __global__ void __launch_bounds__(256) photo_warp_bwd_kernel(const float* __rest
 
 extern "C" {
 
-int bh_photo_warp_fwd_f(const float* img, const double* Hp64, const float* origin, int B, int C, int Hi, int Wi, int P, float* out,
-                        int flags, void* stream) {
+int bh_photo_warp_fwd(const float* img, const double* Hp64, const float* origin, int B, int C, int Hi, int Wi, int P, float* out,
+                      int flags, void* stream) {
     (void)flags;                  // (a gather: one writer per output pixel in either mode)
     if (!img || !Hp64 || !origin || !out || B < 0 || C < 1 || Hi < 1 || Wi < 1 || P < 1) return BH_E_BADARG;
     if ((P % 16) || (size_t)Hi * (size_t)Wi * 4u >= 0xFFFFFFFFull) return BH_E_UNSUPPORTED;
@@ -84,8 +84,8 @@ int bh_photo_warp_fwd_f(const float* img, const double* Hp64, const float* origi
     return BH_OK;
 }
 
-int bh_photo_warp_bwd_f(const float* img, const double* Hp64, const float* origin, const float* g_out, int B, int C, int Hi, int Wi,
-                        int P, double* gH, int flags, void* stream) {
+int bh_photo_warp_bwd(const float* img, const double* Hp64, const float* origin, const float* g_out, int B, int C, int Hi, int Wi,
+                      int P, double* gH, int flags, void* stream) {
     if (!img || !Hp64 || !origin || !g_out || !gH || B < 0 || C < 1 || Hi < 1 || Wi < 1 || P < 1) return BH_E_BADARG;
     if ((P % 16) || (size_t)Hi * (size_t)Wi * 4u >= 0xFFFFFFFFull) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;

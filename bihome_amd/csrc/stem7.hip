@@ -743,7 +743,7 @@ extern "C" int bh_stem7_dgrad_c1(const float* gy, const float* w, float* gx, con
 //   warped = warp(src, H)  (bh_warp_fwd, pool-averaged coverage included when g_cov is given)
 // for the gradient gx = dgrad(gy) of `warped` - what bh_stem7_dgrad_c1 followed by bh_warp_bwd(src, H64, gx, g_cov, ...) computes, without
 // the gradient image.  gx: NULL, or [N][Hi][Wi] written as by bh_stem7_dgrad_c1.  The f64 atomics make the last bits of gH depend on the
-// order of the workgroups: deterministic callers use the two separate calls (bh_warp_bwd_f with BH_F_DETERMINISTIC).
+// order of the workgroups: deterministic callers use the two separate calls (bh_warp_bwd with BH_F_DETERMINISTIC).
 extern "C" int bh_stem7_dgrad_c1_warp(const float* gy, const float* w, float* gx, const bh_conv_desc* d, const float* src, const double* H64,
                                       const float* g_cov, int pool, double* gH, void* stream) {
     if (!gy || !w || !d || !src || !H64 || !gH) return BH_E_BADARG;

@@ -930,14 +930,7 @@ int bh_tail_scratch_floats(int groups, int Ci, int Cm) { return groups * TAIL_CH
 
 int bh_tail_fwd(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta, float* running_mean,
                 float* running_var, const float* w2, const float* b2, float* out, double* ws, int groups, int rows, int hw,
-                int Ci, int Cm, int Co, float eps, float momentum, int use_running, void* stream) {
-    return bh_tail_fwd_route(x, w1, b1, gamma, beta, running_mean, running_var, w2, b2, out, ws, groups, rows, hw, Ci, Cm, Co, eps,
-                             momentum, use_running, 0, stream);
-}
-
-int bh_tail_fwd_route(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta, float* running_mean,
-                      float* running_var, const float* w2, const float* b2, float* out, double* ws, int groups, int rows, int hw,
-                      int Ci, int Cm, int Co, float eps, float momentum, int use_running, int tail_route, void* stream) {
+                int Ci, int Cm, int Co, float eps, float momentum, int use_running, int tail_route, void* stream) {
     TailGeom g;
     if (!x || !w1 || !w2 || !out || !ws) return BH_E_BADARG;
     if (!tail_geom(groups, rows, hw, Ci, Cm, Co, g) || (Ci != 16 && Ci != 32 && Ci != 8)) return BH_E_UNSUPPORTED;
@@ -983,15 +976,7 @@ int bh_tail_fwd_route(const float* x, const float* w1, const float* b1, const fl
 int bh_tail_bwd(const float* gout, const float* x, const float* w1, const float* b1, const float* gamma, const float* beta,
                 const float* w2, const double* ws, const float* running_mean, const float* running_var, float* gx, float* gw1,
                 float* ggamma, float* gbeta, float* gw2, float* gb2, float* scratch, int groups, int rows, int hw, int Ci, int Cm,
-                int Co, float eps, int use_running, void* stream) {
-    return bh_tail_bwd_f(gout, x, w1, b1, gamma, beta, w2, ws, running_mean, running_var, gx, gw1, ggamma, gbeta, gw2, gb2, scratch, groups, rows,
-                         hw, Ci, Cm, Co, eps, use_running, 0, stream);
-}
-
-int bh_tail_bwd_f(const float* gout, const float* x, const float* w1, const float* b1, const float* gamma, const float* beta,
-                  const float* w2, const double* ws, const float* running_mean, const float* running_var, float* gx, float* gw1,
-                  float* ggamma, float* gbeta, float* gw2, float* gb2, float* scratch, int groups, int rows, int hw, int Ci, int Cm,
-                  int Co, float eps, int use_running, int flags, void* stream) {
+                int Co, float eps, int use_running, int flags, void* stream) {
     TailGeom g;
     if (!gout || !x || !w1 || !w2 || !ws || !scratch) return BH_E_BADARG;
     if (!tail_geom(groups, rows, hw, Ci, Cm, Co, g) || (Ci != 16 && Ci != 32 && Ci != 8)) return BH_E_UNSUPPORTED;

@@ -387,15 +387,8 @@ int bh_zhang_triplet_fwd(const float* f1, const float* f2, const float* f1w, con
 
 int bh_zhang_triplet_bwd(const float* g_loss, const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
                          const float* m2w, const float* m1, const float* m2, const float* T1, const float* T2, const double* numden, int B,
-                         int hw, int hinge, float* g_f1, float* g_f2, float* g_f1w, float* g_f2w, float* g_m1w, float* g_m2w, void* stream) {
-    return bh_zhang_triplet_bwd_m(g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, T1, T2, numden, B, hw, hinge, g_f1, g_f2, g_f1w, g_f2w, g_m1w,
-                                  g_m2w, nullptr, nullptr, stream);
-}
-
-int bh_zhang_triplet_bwd_m(const float* g_loss, const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
-                           const float* m2w, const float* m1, const float* m2, const float* T1, const float* T2, const double* numden, int B,
-                           int hw, int hinge, float* g_f1, float* g_f2, float* g_f1w, float* g_f2w, float* g_m1w, float* g_m2w,
-                           float* g_m1, float* g_m2, void* stream) {
+                         int hw, int hinge, float* g_f1, float* g_f2, float* g_f1w, float* g_f2w, float* g_m1w, float* g_m2w,
+                         float* g_m1, float* g_m2, void* stream) {
     if (!g_loss || !f1 || !f2 || !f1w || !m1w || !T1 || !numden || !g_f1 || !g_f2 || !g_f1w || !g_m1w ||
         (f2w && (!m2w || !T2 || !g_f2w || !g_m2w)) || B < 0 || hw < 1)
         return BH_E_BADARG;
@@ -410,13 +403,7 @@ int bh_zhang_triplet_bwd_m(const float* g_loss, const float* f1, const float* f2
 
 int bh_oneline_loss_fwd(const float* f1, const float* f2, const float* f1w, const float* m1w, const float* m2, int B, int hw,
                         int C, float margin, int rep, const float* sample_w, float* T, double* numden, float* per_sample,
-                        float* loss, void* stream) {
-    return bh_oneline_loss_fwd_f(f1, f2, f1w, m1w, m2, B, hw, C, margin, rep, sample_w, T, numden, per_sample, loss, 0, stream);
-}
-
-int bh_oneline_loss_fwd_f(const float* f1, const float* f2, const float* f1w, const float* m1w, const float* m2, int B, int hw,
-                          int C, float margin, int rep, const float* sample_w, float* T, double* numden, float* per_sample,
-                          float* loss, int flags, void* stream) {
+                        float* loss, int flags, void* stream) {
     if (!f1 || !f2 || !f1w || !m1w || !T || !numden || !loss || B < 0 || rep < 1 || B % rep) return BH_E_BADARG;
     if (C % 4 || C < 4 || (C / 4 < 64 && (64 % (C / 4)))) return BH_E_UNSUPPORTED;
     hipStream_t s = bh_stream(stream);
@@ -446,13 +433,7 @@ int bh_oneline_loss_bwd(const float* g_loss, const float* f2, const float* f1w, 
 
 int bh_triplet_l1_fwd(const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
                       const float* m2w, const float* m1, const float* m2, int B, int hw, int C, float* M1, float* M2,
-                      double* numden, void* stream) {
-    return bh_triplet_l1_fwd_f(f1, f2, f1w, f2w, m1w, m2w, m1, m2, B, hw, C, M1, M2, numden, 0, stream);
-}
-
-int bh_triplet_l1_fwd_f(const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
-                        const float* m2w, const float* m1, const float* m2, int B, int hw, int C, float* M1, float* M2,
-                        double* numden, int flags, void* stream) {
+                      double* numden, int flags, void* stream) {
     if (!f1 || !f2 || !f1w || !f2w || !m1w || !m2w || !M1 || !M2 || !numden || B < 0) return BH_E_BADARG;
     if (C % 4 || C < 4 || (C / 4 < 64 && (64 % (C / 4)))) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
@@ -501,12 +482,7 @@ int bh_scale_samples_fwd(const float* x, const float* s, int Bn, long long L, in
 }
 
 int bh_scale_samples_bwd(const float* g_y, const float* x, const float* s, int Bn, long long L, int rep, float* g_x, float* g_s,
-                         void* stream) {
-    return bh_scale_samples_bwd_f(g_y, x, s, Bn, L, rep, g_x, g_s, 0, stream);
-}
-
-int bh_scale_samples_bwd_f(const float* g_y, const float* x, const float* s, int Bn, long long L, int rep, float* g_x, float* g_s,
-                           int flags, void* stream) {
+                         int flags, void* stream) {
     if (!g_y || !x || !s || !g_s || Bn < 0 || rep < 1 || L % 4 || (g_x && rep != 1)) return BH_E_BADARG;
     if (Bn == 0) return BH_OK;
     hipError_t e = hipMemsetAsync(g_s, 0, sizeof(float) * (size_t)Bn, bh_stream(stream));

@@ -375,12 +375,7 @@ void bh_warp_tune(int which, int n) {
 extern "C" {
 
 int bh_warp_fwd(const float* img, const double* H64, int B, int C, int h, int w, int pool, float* out, float* cov,
-                void* stream) {
-    return bh_warp_fwd_f(img, H64, B, C, h, w, pool, out, cov, 0, stream);
-}
-
-int bh_warp_fwd_f(const float* img, const double* H64, int B, int C, int h, int w, int pool, float* out, float* cov,
-                  int flags, void* stream) {
+                int flags, void* stream) {
     if (!H64 || B < 0 || (img && !out) || (!img && !cov)) return BH_E_BADARG;
     if ((h % 16) || (w % 16) || (pool != 1 && pool != 2 && pool != 4 && pool != 8 && pool != 16 && pool != 32) || (h % pool) || (w % pool)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
@@ -409,12 +404,7 @@ int bh_warp_fwd_f(const float* img, const double* H64, int B, int C, int h, int 
 }
 
 int bh_warp_bwd(const float* img, const double* H64, const float* g_out, const float* g_cov, int B, int C, int h, int w,
-                int pool, double* gH, void* stream) {
-    return bh_warp_bwd_f(img, H64, g_out, g_cov, B, C, h, w, pool, gH, 0, stream);
-}
-
-int bh_warp_bwd_f(const float* img, const double* H64, const float* g_out, const float* g_cov, int B, int C, int h, int w,
-                  int pool, double* gH, int flags, void* stream) {
+                int pool, double* gH, int flags, void* stream) {
     if (!H64 || !gH || B < 0 || (g_out && !img)) return BH_E_BADARG;
     if ((h % 16) || (w % 16) || (pool != 1 && pool != 2 && pool != 4 && pool != 8 && pool != 16 && pool != 32) || (h % pool) || (w % pool)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
@@ -439,8 +429,8 @@ size_t bh_warp_bwd_img_scratch_doubles(int B, int C, int h, int w, int flags) {
     return (flags & BH_F_DETERMINISTIC) ? (size_t)B * C * h * w * BH_ACC_WORDS : 0;
 }
 
-int bh_warp_bwd_img_f(const double* H64, const float* g_out, int B, int C, int h, int w, float* g_img, double* scratch, int flags,
-                      void* stream) {
+int bh_warp_bwd_img(const double* H64, const float* g_out, int B, int C, int h, int w, float* g_img, double* scratch, int flags,
+                    void* stream) {
     if (!H64 || !g_out || !g_img || B < 0 || C < 1 || ((flags & BH_F_DETERMINISTIC) && !scratch)) return BH_E_BADARG;
     if ((h % 16) || (w % 16)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;

@@ -5,8 +5,8 @@ config/s-coco/nguyen-orig-lr-5e-3.yaml).  LEARNING_KEYS = (patch_2, image_1, del
 (L1Loss).  Upstream builds H_hat = four_point_to_homography(corners, delta_hat, crop=False) in full-image coordinates, warps the
 whole image_1 with it (warp_image: kornia.warp_perspective, bilinear, zeros, align_corners=True) and crops every sample at its
 corners.  Here only the crop window is sampled: with Hp the 4-point homography of the patch corners [[0,0],[P,0],[P,P],[0,P]]
-and o the integer top-left corner, H_hat.(o + u) = o + Hp.u, so patch_hat = bh_photo_warp_fwd_f(image_1, Hp, o) after the
-existing 4-point solve (bh_h4pt_fwd); the backward runs the adjoint w.r.t. Hp (bh_photo_warp_bwd_f) and then bh_h4pt_bwd.
+and o the integer top-left corner, H_hat.(o + u) = o + Hp.u, so patch_hat = bh_photo_warp_fwd(image_1, Hp, o) after the
+existing 4-point solve (bh_h4pt_fwd); the backward runs the adjoint w.r.t. Hp (bh_photo_warp_bwd) and then bh_h4pt_bwd.
 image_1 is data and gets no gradient.
 
 The corners must be integer-valued axis-aligned squares of one size across the batch (what HomographyNetPrep produces,
@@ -79,7 +79,7 @@ class Model(nn.Module):
                                  "(HomographyNetPrep, transforms.py:505-521)")
             P = int(size[0].item())
             if P % 16:
-                raise ValueError("PhotometricHead: patch size %d is not a multiple of 16 (bh_photo_warp_fwd_f)" % P)
+                raise ValueError("PhotometricHead: patch size %d is not a multiple of 16 (bh_photo_warp_fwd)" % P)
             if c.is_cuda:
                 cls._checked = (weakref.ref(corners), corners._version, P)
         return P, c[:, 0, :].to(device, torch.float32).contiguous()

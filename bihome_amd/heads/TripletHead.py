@@ -8,7 +8,7 @@ trainable feature extractor on the warped patches, and reduce
 with the HIP kernels: bh_h4pt_fwd/bwd, bh_warp_fwd/bwd (pool = 1: the warped ones-mask IS the pooled coverage), the conv stack executor
 for the extractor, bh_zhang_triplet_fwd/bwd and bh_bihome_loss_fwd.  Trained masks (FIX_MASK False, round 4): each mask rides through the
 warp as a second channel next to its patch, the triplet adjoint also returns the gradients of the unwarped masks, and the warp's
-adjoint w.r.t. the image (bh_warp_bwd_img_f) takes the warped masks' gradients back to the mask predictor.
+adjoint w.r.t. the image (bh_warp_bwd_img) takes the warped masks' gradients back to the mask predictor.
 
 Reference quirk kept (results must equal the reference's): with a NUMERIC margin and 'channel-agnostic' aggregation - the shipped
 zhang-orig config - `torch.max(sum_c l1 - sum_c l3 + margin, zeros_like(l1))` (:104-105,:141-142) broadcasts [B,h,w] against [B,1,h,w]

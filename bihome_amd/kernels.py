@@ -241,7 +241,7 @@ def dlt_bwd(pf, choice, eig, g_delta, n, P, g_H=None):
     _chk(pf); _chk(choice, torch.int64); _chk(eig, torch.float64); _chk(g_delta); _chk(g_H, torch.float64)
     B, _, h, w = pf.shape
     g_pf = torch.zeros_like(pf)
-    check(lib.bh_dlt_bwd_f(_p(pf), _p(choice), _p(eig), _p(g_delta), _p(g_H), B, n, P, h, w, _p(g_pf), _fdet(), _stream()), "bh_dlt_bwd")
+    check(lib.bh_dlt_bwd(_p(pf), _p(choice), _p(eig), _p(g_delta), _p(g_H), B, n, P, h, w, _p(g_pf), _fdet(), _stream()), "bh_dlt_bwd")
     return g_pf
 
 
@@ -259,11 +259,8 @@ def dsac_scores_fwd(pf, Hd, n, method="repr_error", thr=0.0, beta=0.0):
     B, _, h, w = pf.shape
     err = torch.empty(B, n, dtype=torch.float32, device=pf.device)
     scores = torch.empty_like(err)
-    if method == "repr_error":
-        check(lib.bh_dsac_score(_p(pf), _p(Hd), B, n, h, w, _p(err), None, _stream()), "bh_dsac_score")
-    else:
-        m, thr, beta = _dsac_method(method, thr, beta)
-        check(lib.bh_dsac_score_m(_p(pf), _p(Hd), B, n, h, w, m, thr, beta, _p(err), None, _stream()), "bh_dsac_score_m")
+    m, thr, beta = _dsac_method(method, thr, beta)
+    check(lib.bh_dsac_score(_p(pf), _p(Hd), B, n, h, w, m, thr, beta, _p(err), None, _stream()), "bh_dsac_score")
     check(lib.bh_dsac_scores_fwd(_p(err), B, n, _p(scores), _stream()), "bh_dsac_scores_fwd")
     return scores, err
 
@@ -275,13 +272,9 @@ def dsac_scores_bwd(pf, Hd, scores, g_scores, n, method="repr_error", thr=0.0, b
     g_err = torch.empty_like(scores)
     g_Hd = torch.empty(B * n, 9, dtype=torch.float64, device=pf.device)
     g_pf = torch.zeros_like(pf)
-    if method == "repr_error":
-        check(lib.bh_dsac_scores_bwd_f(_p(pf), _p(Hd), _p(scores), _p(g_scores), B, n, h, w, _p(g_err), _p(g_Hd), _p(g_pf), _fdet(), _stream()),
-              "bh_dsac_scores_bwd")
-    else:
-        m, thr, beta = _dsac_method(method, thr, beta)
-        check(lib.bh_dsac_scores_bwd_m(_p(pf), _p(Hd), _p(scores), _p(g_scores), B, n, h, w, m, thr, beta, _p(g_err), _p(g_Hd), _p(g_pf),
-                                       _fdet(), _stream()), "bh_dsac_scores_bwd_m")
+    m, thr, beta = _dsac_method(method, thr, beta)
+    check(lib.bh_dsac_scores_bwd(_p(pf), _p(Hd), _p(scores), _p(g_scores), B, n, h, w, m, thr, beta, _p(g_err), _p(g_Hd), _p(g_pf),
+                                 _fdet(), _stream()), "bh_dsac_scores_bwd")
     return g_pf, g_Hd
 
 
@@ -301,7 +294,7 @@ def scale_samples_bwd(g_y, x, s, rep, want_gx):
     L = x.numel() // x.shape[0]
     g_x = torch.empty_like(g_y) if want_gx else None
     g_s = torch.empty(Bn, dtype=torch.float32, device=x.device)
-    check(lib.bh_scale_samples_bwd_f(_p(g_y), _p(x), _p(s), Bn, L, rep, _p(g_x), _p(g_s), _fdet(), _stream()), "bh_scale_samples_bwd")
+    check(lib.bh_scale_samples_bwd(_p(g_y), _p(x), _p(s), Bn, L, rep, _p(g_x), _p(g_s), _fdet(), _stream()), "bh_scale_samples_bwd")
     return g_x, g_s
 
 
@@ -311,11 +304,8 @@ def dsac_score(pf, Hd, n, method="repr_error", thr=0.0, beta=0.0):
     B, _, h, w = pf.shape
     err = torch.empty(B, n, dtype=torch.float32, device=pf.device)
     best = torch.empty(B, dtype=torch.int64, device=pf.device)
-    if method == "repr_error":
-        check(lib.bh_dsac_score(_p(pf), _p(Hd), B, n, h, w, _p(err), _p(best), _stream()), "bh_dsac_score")
-    else:
-        m, thr, beta = _dsac_method(method, thr, beta)
-        check(lib.bh_dsac_score_m(_p(pf), _p(Hd), B, n, h, w, m, thr, beta, _p(err), _p(best), _stream()), "bh_dsac_score_m")
+    m, thr, beta = _dsac_method(method, thr, beta)
+    check(lib.bh_dsac_score(_p(pf), _p(Hd), B, n, h, w, m, thr, beta, _p(err), _p(best), _stream()), "bh_dsac_score")
     return err, best
 
 
@@ -389,7 +379,7 @@ def warp_fwd(img, H64, pool=4, want_cov=True):
     out = torch.empty_like(img)
     cov = torch.empty(B, h // pool, w // pool, dtype=torch.float32, device=img.device) if want_cov else None
     with _Timed("warp_fwd_kernel", 0.0, 4.0 * (img.numel() + out.numel() + (cov.numel() if want_cov else 0))):     # 8 B/px/channel
-        check(lib.bh_warp_fwd_f(_p(img), _p(H64), B, C, h, w, pool, _p(out), _p(cov), _fdet(), _stream()), "bh_warp_fwd")
+        check(lib.bh_warp_fwd(_p(img), _p(H64), B, C, h, w, pool, _p(out), _p(cov), _fdet(), _stream()), "bh_warp_fwd")
     return out, cov
 
 
@@ -397,7 +387,7 @@ def mask_coverage_fwd(H64, h, w, pool=4):
     _chk(H64, torch.float64)
     B = H64.shape[0]
     cov = torch.empty(B, h // pool, w // pool, dtype=torch.float32, device=H64.device)
-    check(lib.bh_warp_fwd_f(None, _p(H64), B, 1, h, w, pool, None, _p(cov), _fdet(), _stream()), "bh_warp_fwd(cov)")
+    check(lib.bh_warp_fwd(None, _p(H64), B, 1, h, w, pool, None, _p(cov), _fdet(), _stream()), "bh_warp_fwd(cov)")
     return cov
 
 
@@ -407,7 +397,7 @@ def warp_bwd(img, H64, g_out, g_cov, pool=4, gH=None):
     if gH is None:
         gH = torch.zeros(B, 9, dtype=torch.float64, device=img.device)
     with _Timed("warp_bwd_kernel", 0.0, 4.0 * (img.numel() + g_out.numel() + (g_cov.numel() if g_cov is not None else 0))):
-        check(lib.bh_warp_bwd_f(_p(img), _p(H64), _p(g_out), _p(g_cov), B, C, h, w, pool, _p(gH), _fdet(), _stream()), "bh_warp_bwd")
+        check(lib.bh_warp_bwd(_p(img), _p(H64), _p(g_out), _p(g_cov), B, C, h, w, pool, _p(gH), _fdet(), _stream()), "bh_warp_bwd")
     return gH
 
 
@@ -424,7 +414,7 @@ def photo_warp_fwd(img, Hp64, origin, P):
     _photo_shapes(B, Hp64, origin)
     out = torch.empty(B, C, P, P, dtype=torch.float32, device=img.device)
     with _Timed("photo_warp_fwd_kernel", 0.0, 4.0 * 5 * out.numel()):        # four gathered taps + one write per output pixel
-        check(lib.bh_photo_warp_fwd_f(_p(img), _p(Hp64), _p(origin), B, C, Hi, Wi, int(P), _p(out), _fdet(), _stream()), "bh_photo_warp_fwd_f")
+        check(lib.bh_photo_warp_fwd(_p(img), _p(Hp64), _p(origin), B, C, Hi, Wi, int(P), _p(out), _fdet(), _stream()), "bh_photo_warp_fwd")
     return out
 
 
@@ -438,8 +428,8 @@ def photo_warp_bwd(img, Hp64, origin, g_out, P, gH=None):
     if gH is None:
         gH = torch.zeros(B, 9, dtype=torch.float64, device=img.device)
     with _Timed("photo_warp_bwd_kernel", 0.0, 4.0 * 5 * g_out.numel()):
-        check(lib.bh_photo_warp_bwd_f(_p(img), _p(Hp64), _p(origin), _p(g_out), B, C, Hi, Wi, int(P), _p(gH), _fdet(), _stream()),
-              "bh_photo_warp_bwd_f")
+        check(lib.bh_photo_warp_bwd(_p(img), _p(Hp64), _p(origin), _p(g_out), B, C, Hi, Wi, int(P), _p(gH), _fdet(), _stream()),
+              "bh_photo_warp_bwd")
     return gH
 
 
@@ -451,7 +441,7 @@ def warp_bwd_img(H64, g_out):
     flags = _fdet()
     n = lib.bh_warp_bwd_img_scratch_doubles(B, C, h, w, flags)
     scratch = torch.empty(n, dtype=torch.float64, device=g_out.device) if n else None
-    check(lib.bh_warp_bwd_img_f(_p(H64), _p(g_out), B, C, h, w, _p(g_img), _p(scratch), flags, _stream()), "bh_warp_bwd_img_f")
+    check(lib.bh_warp_bwd_img(_p(H64), _p(g_out), B, C, h, w, _p(g_img), _p(scratch), flags, _stream()), "bh_warp_bwd_img")
     return g_img
 
 
@@ -495,8 +485,8 @@ def triplet_l1_fwd(f1, f2, f1w, f2w, m1w, m2w, m1=None, m2=None):
     M2 = torch.empty_like(M1)
     numden = torch.empty(B, 4, dtype=torch.float64, device=f1.device)
     with _Timed("triplet_fwd_kernel", 0.0, 4.0 * (4 * f1.numel() + 4 * M1.numel())):      # 4 feature maps in, masks in, M1 / M2 out
-        check(lib.bh_triplet_l1_fwd_f(_p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), B, hf * wf, C,
-                                      _p(M1), _p(M2), _p(numden), _fdet(), _stream()), "bh_triplet_l1_fwd")
+        check(lib.bh_triplet_l1_fwd(_p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), B, hf * wf, C,
+                                    _p(M1), _p(M2), _p(numden), _fdet(), _stream()), "bh_triplet_l1_fwd")
     return M1, M2, numden
 
 
@@ -510,8 +500,8 @@ def oneline_loss_fwd(f1, f2, f1w, m1w, margin, m2=None, rep=1, sample_w=None):
     numden = torch.empty(B, 2, dtype=torch.float64, device=f1.device)
     per = torch.empty(B, dtype=torch.float32, device=f1.device)
     loss = torch.empty(1, dtype=torch.float32, device=f1.device)
-    check(lib.bh_oneline_loss_fwd_f(_p(f1), _p(f2), _p(f1w), _p(m1w), _p(m2), B, hf * wf, C, float(margin), rep, _p(sample_w), _p(T),
-                                    _p(numden), _p(per), _p(loss), _fdet(), _stream()), "bh_oneline_loss_fwd")
+    check(lib.bh_oneline_loss_fwd(_p(f1), _p(f2), _p(f1w), _p(m1w), _p(m2), B, hf * wf, C, float(margin), rep, _p(sample_w), _p(T),
+                                  _p(numden), _p(per), _p(loss), _fdet(), _stream()), "bh_oneline_loss_fwd")
     return loss, T, numden, per
 
 
@@ -550,9 +540,9 @@ def zhang_triplet_bwd(g_loss, f1, f2, f1w, f2w, m1w, m2w, T1, T2, numden, hinge,
     g_m2w = torch.empty_like(m2w) if f2w is not None else None
     g_m1 = torch.empty_like(m1w) if mask_grads else None
     g_m2 = torch.empty_like(m1w) if mask_grads else None
-    check(lib.bh_zhang_triplet_bwd_m(_p(g_loss), _p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), _p(T1), _p(T2), _p(numden),
-                                     B, hw, int(bool(hinge)), _p(g_f1), _p(g_f2), _p(g_f1w), _p(g_f2w), _p(g_m1w), _p(g_m2w), _p(g_m1), _p(g_m2),
-                                     _stream()), "bh_zhang_triplet_bwd_m")
+    check(lib.bh_zhang_triplet_bwd(_p(g_loss), _p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), _p(T1), _p(T2), _p(numden),
+                                   B, hw, int(bool(hinge)), _p(g_f1), _p(g_f2), _p(g_f1w), _p(g_f2w), _p(g_m1w), _p(g_m2w), _p(g_m1), _p(g_m2),
+                                   _stream()), "bh_zhang_triplet_bwd")
     if mask_grads:
         return g_f1, g_f2, g_f1w, g_f2w, g_m1w, g_m2w, g_m1, g_m2
     return g_f1, g_f2, g_f1w, g_f2w, g_m1w, g_m2w
@@ -776,8 +766,8 @@ def bn_fwd_coeffs(stats, gamma, beta, rmean, rvar, groups, rows, C, eps, momentu
     """(scale, shift) table of a training-mode BatchNorm from its forward sums (+ the running-statistics update).
     amax: zeroed magnitude record - receives the a-priori bound of the BatchNorm's output."""
     table = torch.empty((groups, C, 2), dtype=torch.float32, device=stats.device)
-    check(lib.bh_bn_fwd_coeffs_amax(_p(stats), _p(gamma), _p(beta), _p(rmean), _p(rvar), groups, rows, C, float(eps), float(momentum),
-                                    _p(table), _p(amax), _stream()), "bh_bn_fwd_coeffs")
+    check(lib.bh_bn_fwd_coeffs(_p(stats), _p(gamma), _p(beta), _p(rmean), _p(rvar), groups, rows, C, float(eps), float(momentum),
+                               _p(table), _p(amax), _stream()), "bh_bn_fwd_coeffs")
     return table
 
 
@@ -809,7 +799,7 @@ def conv_fwd(x, w, bias, d, bn_sums=None, groups=1, res=None, relu=False, wpacke
                 ws_["done"] = ws_["filled"] = True
                 return y
         with _Timed("warp_fwd_kernel", 0.0, 4.0 * (2 * x.numel() + (ws_["cov"].numel() if ws_["cov"] is not None else 0))):
-            check(lib.bh_warp_fwd_f(_p(ws_["src"]), _p(ws_["H64"]), B_, 1, h_, w_, int(ws_["pool"]), _p(x), _p(ws_["cov"]), _fdet(), _stream()),
+            check(lib.bh_warp_fwd(_p(ws_["src"]), _p(ws_["H64"]), B_, 1, h_, w_, int(ws_["pool"]), _p(x), _p(ws_["cov"]), _fdet(), _stream()),
                   "bh_warp_fwd")
         ws_["filled"] = True
     if isinstance(x, BnOnLoad):
@@ -1119,8 +1109,8 @@ def bn_fwd(x, gamma, beta, rmean, rvar, res, groups, eps, momentum, relu, traini
     flags = (1 if relu else 0) | (2 if res is not None else 0) | (8 if stats_ready else 0) | (BN_DETERMINISTIC if deterministic() else 0)
     nb = 4.0 * x.numel() * ((2 if (training and not stats_ready) else 1) + 1 + (1 if res is not None else 0))
     with _Timed("bn_fwd(%d kernels)" % (2 if (training and not stats_ready) else 1) + (" g%d rows%d C%d" % (groups, rows, C) if TIMING_DETAIL else ""), 0.0, nb):
-        check(lib.bh_bn_fwd_amax(_p(x), _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(res), _p(y), _p(stats), groups, rows, C,
-                                 float(eps), float(momentum), flags, 0 if training else 1, _p(amax), _stream()), "bh_bn_fwd")
+        check(lib.bh_bn_fwd(_p(x), _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(res), _p(y), _p(stats), groups, rows, C,
+                            float(eps), float(momentum), flags, 0 if training else 1, _p(amax), _stream()), "bh_bn_fwd")
     if amax is not None:
         y._bh_amax = amax           # zeroed magnitude record, now max |y| (measured by the apply kernel)
     return y, stats
@@ -1145,9 +1135,9 @@ def bn_bwd(gy, y, x, gamma, stats, rmean, rvar, groups, eps, relu, training, wan
     passes = 1 if sums_ready is not None else 2
     nb = 4.0 * x.numel() * (passes * (2 + (1 if (relu and not mask_from_x) else 0)) + 1 + (1 if want_gres else 0))
     with _Timed("bn_bwd(%d kernels)" % (1 if sums_ready is not None else 3) + (" g%d rows%d C%d" % (groups, rows, C) if TIMING_DETAIL else ""), 0.0, nb):
-        check(lib.bh_bn_bwd_amax(_p(gy), _p(y), _p(x), _p(gamma), _p(beta), _p(stats), _p(gx), _p(gres), _p(ggamma), _p(gbeta),
-                                 _p(scratch), groups, rows, C, float(eps), flags, 0 if training else 1, _p(rmean), _p(rvar),
-                                 _p(amax), _stream()), "bh_bn_bwd")
+        check(lib.bh_bn_bwd(_p(gy), _p(y), _p(x), _p(gamma), _p(beta), _p(stats), _p(gx), _p(gres), _p(ggamma), _p(gbeta),
+                            _p(scratch), groups, rows, C, float(eps), flags, 0 if training else 1, _p(rmean), _p(rvar),
+                            _p(amax), _stream()), "bh_bn_bwd")
     if amax is not None:
         gx._bh_amax = amax          # zeroed magnitude record, now max |gx|
     return gx, gres
@@ -1250,7 +1240,7 @@ TAIL_ROUTE_LDS_MOMENTS = 2  # include/bihome.h BH_TAIL_ROUTE_LDS_MOMENTS
 
 def tail_fwd(x, w1, b1, gamma, beta, rmean, rvar, w2, b2, groups, hw, eps, momentum, training, route=0):
     """x NHWC [N,h,w,Ci] -> out NCHW [N,Co,h,w] through conv1x1+BN+ReLU+conv1x1 (fused); returns (out, ws).
-    route: per-call bits of bh_tail_fwd_route (TAIL_ROUTE_VALU_FWD keeps the per-pixel VALU kernel)."""
+    route: per-call bits of bh_tail_fwd (TAIL_ROUTE_VALU_FWD keeps the per-pixel VALU kernel)."""
     _chk(x)
     N, h, w, Ci = x.shape
     Cm, Co = w1.shape[0], w2.shape[0]
@@ -1259,9 +1249,9 @@ def tail_fwd(x, w1, b1, gamma, beta, rmean, rvar, w2, b2, groups, hw, eps, momen
     ws = torch.empty(lib.bh_tail_ws_doubles(groups, Ci, Cm), dtype=torch.float64, device=x.device)
     fl = 2.0 * N * h * w * Cm * (Ci + Co)
     with _Timed("tail_fwd(4 kernels)", fl, 4.0 * (x.numel() * (2 if training else 1) + out.numel())):
-        check(lib.bh_tail_fwd_route(_p(x), _p(w1), _p(b1), _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(w2), _p(b2), _p(out),
-                                    _p(ws), groups, rows, hw, Ci, Cm, Co, float(eps), float(momentum), 0 if training else 1,
-                                    int(route), _stream()), "bh_tail_fwd")
+        check(lib.bh_tail_fwd(_p(x), _p(w1), _p(b1), _p(gamma), _p(beta), _p(rmean), _p(rvar), _p(w2), _p(b2), _p(out),
+                              _p(ws), groups, rows, hw, Ci, Cm, Co, float(eps), float(momentum), 0 if training else 1,
+                              int(route), _stream()), "bh_tail_fwd")
     return out, ws
 
 
@@ -1275,9 +1265,9 @@ def tail_bwd(gout, x, w1, b1, gamma, beta, w2, ws, rmean, rvar, groups, hw, eps,
     scratch = torch.empty(lib.bh_tail_scratch_floats(groups, Ci, Cm), dtype=torch.float32, device=x.device)
     fl = 2.0 * N * h * w * Cm * (3 * Ci + 2 * Co + Ci)
     with _Timed("tail_bwd(5 kernels)", fl, 4.0 * (x.numel() * 3 + gout.numel() * 3)):
-        check(lib.bh_tail_bwd_f(_p(gout), _p(x), _p(w1), _p(b1), _p(gamma), _p(beta), _p(w2), _p(ws), _p(rmean), _p(rvar),
-                                _p(gx), _p(gw1), _p(ggamma), _p(gbeta), _p(gw2), _p(gb2), _p(scratch), groups, rows, hw, Ci,
-                                Cm, Co, float(eps), 0 if training else 1, _fdet(), _stream()), "bh_tail_bwd")
+        check(lib.bh_tail_bwd(_p(gout), _p(x), _p(w1), _p(b1), _p(gamma), _p(beta), _p(w2), _p(ws), _p(rmean), _p(rvar),
+                              _p(gx), _p(gw1), _p(ggamma), _p(gbeta), _p(gw2), _p(gb2), _p(scratch), groups, rows, hw, Ci,
+                              Cm, Co, float(eps), 0 if training else 1, _fdet(), _stream()), "bh_tail_bwd")
     return gx
 
 

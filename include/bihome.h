@@ -14,6 +14,10 @@
  * over; *internal* feature maps of the conv stacks are NHWC float32 ("pixels x channels"), conv
  * weights are [Cout][kh][kw][Cin] (= a torch channels_last OIHW tensor), transposed-conv weights
  * [Cin][kh][kw][Cout] (= channels_last IOHW).  Homographies are row-major 3x3.
+ *
+ * One operation, one entry point: it has the plain name and takes ALL its arguments; the optional ones are NULL / 0.  ABI version 2
+ * (bh_version) removed the _f / _m / _amax / _route twins of version 1: each full-signature call took the plain name of the short form
+ * that forwarded to it.
  */
 #ifndef BIHOME_H
 #define BIHOME_H
@@ -41,17 +45,18 @@ int bh_device_arch(char* buf, int buflen);
  *     gradients: bh_conv_wgrad_det with a workspace of bh_conv_wgrad_det_bytes(d) - partial tiles added in split order (split-operand /
  *     stride-1 kernels) or integer-limb shadow entries (every other shape).  bh_conv_wgrad / bh_conv_bias_grad have no workspace
  *     and stay atomic;
- *   - BatchNorm (flags & BH_BN_DETERMINISTIC in bh_bn_fwd* / bh_bn_bwd*): the statistics pass writes, and every pass reads, the limb
+ *   - BatchNorm (flags & BH_BN_DETERMINISTIC in bh_bn_fwd / bh_bn_bwd and their fused forms): the statistics pass writes, and every pass reads, the limb
  *     encoding.  A sums table must be written and read in ONE mode (the forward that leaves sums for its backward, a conv epilogue and
  *     the BatchNorm that consumes its statistics); bh_bn_fwd_coeffs looks at both encodings;
- *   - bh_warp_bwd_f, bh_triplet_l1_fwd_f, bh_oneline_loss_fwd_f, bh_scale_samples_bwd_f, bh_dsac_scores_bwd_f, bh_tail_bwd_f
+ *   - bh_warp_bwd, bh_photo_warp_bwd, bh_triplet_l1_fwd, bh_oneline_loss_fwd, bh_scale_samples_bwd, bh_dsac_scores_bwd, bh_tail_bwd
  *     (flags & BH_F_DETERMINISTIC): one workgroup per sample / channel is the only writer of its sums;
- *   - bh_dlt_bwd_f: duplicates of a sample's indices are added in point order inside the wave, hypotheses in launch order;
- *   - bh_warp_fwd_f with pool = 32: the pooled coverage by a one-writer kernel (the default adds four quarter-window sums with atomics).
- * The entry points without the _f suffix are the same calls with flags = 0.  Same arithmetic otherwise: results differ from the
- * default only by the order of additions.  A HIP graph replays whatever bits its captured launches carried. */
-#define BH_F_DETERMINISTIC 1          /* flags argument of the bh_*_f entry points */
-#define BH_BN_DETERMINISTIC 32        /* flags argument of bh_bn_fwd / bh_bn_fwd_amax / bh_bn_bwd / bh_bn_bwd_amax */
+ *   - bh_dlt_bwd: duplicates of a sample's indices are added in point order inside the wave, hypotheses in launch order;
+ *   - bh_warp_fwd with pool = 32: the pooled coverage by a one-writer kernel (the default adds four quarter-window sums with atomics);
+ *   - bh_warp_bwd_img: integer-limb entries in the caller's scratch instead of float atomics.
+ * flags = 0 is the default (atomic) form of each.  Same arithmetic otherwise: results differ from the default only by the order of
+ * additions.  A HIP graph replays whatever bits its captured launches carried. */
+#define BH_F_DETERMINISTIC 1          /* flags argument of the entry points listed above */
+#define BH_BN_DETERMINISTIC 32        /* flags argument of the BatchNorm entry points (bh_bn_fwd, bh_bn_bwd, bh_bn_stats, ...) */
 /* Measured matrix-pipe peak for the roofline: sustained TFLOP/s of a bare v_mfma_f32_32x32x16_bf16 stream on the whole
  * chip (two workgroups of four waves per CU, ~5 ms), with constant operands (random_operands = 0) or random-bit operands (1: the data
  * toggling of real tensors - on MI355X the power-limited rate, 25-35 % below the first).  Synchronises the stream.  sink_dev: 4 bytes of
@@ -84,52 +89,38 @@ int bh_dlt_fwd(const float* pf, const int64_t* choice, int B, int n, int P, int 
                float* Hdlt, float* delta_hat, double* eig, void* stream);
 /* adjoint: g_delta[B*n,4,2] -> g_pf[B,2,h,w] += (scatter-add at the sampled indices; caller zeroes) */
 /* g_Hdlt[B*n,9] (double, NULL ok): gradient that reaches the normalised homography itself (from the hypothesis scores,
- * bh_dsac_scores_bwd), added to the one that arrives through delta_hat */
+ * bh_dsac_scores_bwd), added to the one that arrives through delta_hat.  flags: BH_F_DETERMINISTIC */
 int bh_dlt_bwd(const float* pf, const int64_t* choice, const double* eig, const float* g_delta, const double* g_Hdlt,
-               int B, int n, int P, int h, int w, float* g_pf, void* stream);
-int bh_dlt_bwd_f(const float* pf, const int64_t* choice, const double* eig, const float* g_delta, const double* g_Hdlt,
-                 int B, int n, int P, int h, int w, float* g_pf, int flags, void* stream);      /* flags: BH_F_DETERMINISTIC */
+               int B, int n, int P, int h, int w, float* g_pf, int flags, void* stream);
 
-/* DSACSoftmax.__score_hypotheses ('repr_error'), src/heads/ransac_utils.py:76-128, and the
- * arg-max of softmax(-err) == arg-min of err at src/heads/PerceptualHead.py:755-757:
- * err[B,n] = sum over all h*w points of |H.coord - (coord + pf)|_1 ; best[B] int64 (first minimum). */
-int bh_dsac_score(const float* pf, const float* Hdlt, int B, int n, int h, int w,
-                  float* err, int64_t* best, void* stream);
-
-/* scores[B,n] = softmax(-err) over the hypotheses (ransac_utils.py:126): the weights of the score-weighted multi-hypothesis
- * losses (PerceptualHead.py:276-280,505-511,708-710).  Adjoint of scoring + softmax: g_scores[B,n] -> g_err[B,n] (scratch,
- * overwritten), g_Hdlt[B*n,9] (double, overwritten; feed to bh_dlt_bwd) and g_pf[B,2,h,w] += (atomics; the reprojection
- * error sees every point of the field: sign(H.coord - map) per point). */
-int bh_dsac_scores_fwd(const float* err, int B, int n, float* scores, void* stream);
-int bh_dsac_scores_bwd(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h,
-                       int w, float* g_err, double* g_Hdlt, float* g_pf, void* stream);
-int bh_dsac_scores_bwd_f(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h,
-                         int w, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream);
-
-/* The scoring methods of DSACSoftmax.__score_hypotheses (ransac_utils.py:76-128) behind one pair of calls.  Per point (x, y) of the field
- * and hypothesis j: t = H_j.(x, y) (scale s = |qz| > 1e-8 ? 1/qz : 1, as in bh_dsac_score), m = (x + pf[b,0,y,x], y + pf[b,1,y,x]),
- * e = sqrt((tx - mx)^2 + (ty - my)^2), all fp32.
- *   BH_DSAC_REPR_ERROR     score = sum |t - m|_1: bh_dsac_score / bh_dsac_scores_bwd_f themselves (delegated, bitwise the same); thr and
- *                          beta are checked and otherwise unused
+/* Hypothesis scoring of DSACSoftmax.__score_hypotheses, src/heads/ransac_utils.py:76-128, all its methods behind one pair of calls, and the
+ * softmax over the hypotheses between them.  Per point (x, y) of the field (all h*w of them) and hypothesis j: t = H_j.(x, y) (scale
+ * s = |qz| > 1e-8 ? 1/qz : 1), m = (x + pf[b,0,y,x], y + pf[b,1,y,x]), e = sqrt((tx - mx)^2 + (ty - my)^2), all fp32.
+ *   BH_DSAC_REPR_ERROR     'repr_error': score[B,n] = sum over the points of |t - m|_1; thr and beta are checked and otherwise unused
  *   BH_DSAC_INLIERS        'inliers_ratio' (:98-103): score = #{points with e < thr} / (h*w); the comparison strict, the count an integer
  *                          (independent of the order of execution).  No adjoint: upstream's comparison cuts the graph
  *   BH_DSAC_SOFT_INLIERS   'soft_inliers_ratio' (:105-111): score = sum over the points of sigmoid(beta (e - thr)), accumulated in double
- * SIGN CONVENTION, upstream's and kept: the weights are softmax(-score) (:126, bh_dsac_scores_fwd, unchanged) and the evaluation pick is
- * their arg-max = the FIRST MINIMUM of score (best[B] int64, NULL ok).  The soft score thus counts soft OUTLIERS and the lower one wins.
- * The hard ratio counts INLIERS and is negated too: upstream prefers the hypothesis with the FEWEST inliers.  That is an upstream quirk;
- * it is reproduced, not repaired.
- * bh_dsac_scores_bwd_m: adjoint of scoring + softmax for the soft method (method 0: bh_dsac_scores_bwd_f).  scores[B,n] the softmax weights,
- * g_scores[B,n] -> g_err[B,n] (scratch, overwritten: the gradient w.r.t. the raw scores), g_Hdlt[B*n,9] (double, overwritten) and
- * g_pf[B,2,h,w] += (atomics).  d score / d e = beta sg (1 - sg) with sg = sigmoid(beta (e - thr)); d e / d t = (t - m) / e and exactly 0 where
- * e == 0 (torch's sub-gradient of norm); through the quotient as in bh_dsac_scores_bwd.  flags & BH_F_DETERMINISTIC: one workgroup per
- * sample adds the hypotheses in order - bit-identical from call to call (the contract of bh_dsac_scores_bwd_f).
+ * SIGN CONVENTION, upstream's and kept: the weights are softmax(-score) (:126, bh_dsac_scores_fwd) and the evaluation pick
+ * (src/heads/PerceptualHead.py:755-757) is their arg-max = the FIRST MINIMUM of score (best[B] int64, NULL ok).  The soft score thus
+ * counts soft OUTLIERS and the lower one wins.  The hard ratio counts INLIERS and is negated too: upstream prefers the hypothesis with
+ * the FEWEST inliers.  That is an upstream quirk; it is reproduced, not repaired.
+ * bh_dsac_scores_fwd: scores[B,n] = softmax(-err) over the hypotheses (ransac_utils.py:126): the weights of the score-weighted
+ * multi-hypothesis losses (PerceptualHead.py:276-280,505-511,708-710).
+ * bh_dsac_scores_bwd: adjoint of scoring + softmax for BH_DSAC_REPR_ERROR and BH_DSAC_SOFT_INLIERS.  scores[B,n] the softmax weights,
+ * g_scores[B,n] -> g_err[B,n] (scratch, overwritten: the gradient w.r.t. the raw scores), g_Hdlt[B*n,9] (double, overwritten; feed to
+ * bh_dlt_bwd) and g_pf[B,2,h,w] += (atomics; every point of the field is seen).  'repr_error': sign(t - m) per point.  Soft method:
+ * d score / d e = beta sg (1 - sg) with sg = sigmoid(beta (e - thr)); d e / d t = (t - m) / e and exactly 0 where e == 0 (torch's
+ * sub-gradient of norm).  Both go through the quotient t = q / qz.  flags & BH_F_DETERMINISTIC: one workgroup per sample adds the
+ * hypotheses in order - bit-identical from call to call.
  * BH_E_BADARG, checked before any launch: an unknown method, BH_DSAC_INLIERS passed to the adjoint, thr or beta NaN, thr < 0, n < 1,
- * h or w < 1, a NULL pointer other than best.  BH_E_UNSUPPORTED: h*w > 2^30.  B == 0: BH_OK, nothing launched. */
+ * h or w < 1, a NULL pointer other than best.  BH_E_UNSUPPORTED: h*w > 2^30 (the two inlier-count methods).  B == 0: BH_OK, nothing
+ * launched. */
 enum { BH_DSAC_REPR_ERROR = 0, BH_DSAC_INLIERS = 1, BH_DSAC_SOFT_INLIERS = 2 };
-int bh_dsac_score_m(const float* pf, const float* Hdlt, int B, int n, int h, int w, int method, float thr, float beta,
-                    float* score, int64_t* best, void* stream);
-int bh_dsac_scores_bwd_m(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h, int w,
-                         int method, float thr, float beta, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream);
+int bh_dsac_score(const float* pf, const float* Hdlt, int B, int n, int h, int w, int method, float thr, float beta,
+                  float* score, int64_t* best, void* stream);
+int bh_dsac_scores_fwd(const float* err, int B, int n, float* scores, void* stream);
+int bh_dsac_scores_bwd(const float* pf, const float* Hdlt, const float* scores, const float* g_scores, int B, int n, int h, int w,
+                       int method, float thr, float beta, float* g_err, double* g_Hdlt, float* g_pf, int flags, void* stream);
 
 /* Robust homography of a perspective field: RANSAC over K minimal samples + least-squares refit on the inliers of the winner - the
  * estimator of upstream's NoOpHead._postprocess, cv2.findHomography(src, dst, cv2.RANSAC, 10) over all h*w correspondences
@@ -199,48 +190,42 @@ int bh_homography_refine_lm(const float* pf, const uint8_t* mask, int B, int h, 
  * + AvgPool2d(k) (src/heads/PerceptualHead.py:380-382,401,447-459) fused into the same pass.
  * ------------------------------------------------------------------------------------------- */
 /* img[B,C,h,w] (NULL => only the coverage is produced), H64[B,9]; out[B,C,h,w] (may be NULL when
- * img is NULL); cov[B,h/pool,w/pool] (NULL => skipped). h,w multiples of pool; pool in {1,2,4,8,16,32}. */
+ * img is NULL); cov[B,h/pool,w/pool] (NULL => skipped). h,w multiples of pool; pool in {1,2,4,8,16,32}.
+ * flags: BH_F_DETERMINISTIC (matters for pool = 32) */
 int bh_warp_fwd(const float* img, const double* H64, int B, int C, int h, int w, int pool,
-                float* out, float* cov, void* stream);
-int bh_warp_fwd_f(const float* img, const double* H64, int B, int C, int h, int w, int pool,
-                  float* out, float* cov, int flags, void* stream);         /* flags: BH_F_DETERMINISTIC (matters for pool = 32) */
+                float* out, float* cov, int flags, void* stream);
 /* adjoint w.r.t. H only (the image is data): g_out[B,C,h,w] (NULL ok), g_cov[B,h/pool,w/pool]
- * (NULL ok) -> gH[B,9] += (double, atomics; caller zeroes) */
+ * (NULL ok) -> gH[B,9] += (double, atomics; caller zeroes).  flags: BH_F_DETERMINISTIC */
 int bh_warp_bwd(const float* img, const double* H64, const float* g_out, const float* g_cov,
-                int B, int C, int h, int w, int pool, double* gH, void* stream);
-int bh_warp_bwd_f(const float* img, const double* H64, const float* g_out, const float* g_cov,
-                  int B, int C, int h, int w, int pool, double* gH, int flags, void* stream);
+                int B, int C, int h, int w, int pool, double* gH, int flags, void* stream);
 /* Photometric head (src/heads/PhotometricHead.py:29-41, Nguyen et al.'s unsupervised baseline): H_hat = four_point_to_homography(corners,
  * delta_hat, crop=False) (:29-30, src/data/utils.py:7-33), image_warped = warp_image(image_1, H_hat) (:33-35, utils.py:54-59) and the
  * per-sample crop image_warped[b, :, c[0,1]:c[3,1], c[0,0]:c[1,0]] (:38-42) in ONE gather over the crop window only.  Written in patch
  * coordinates: Hp64[B,9] = bh_h4pt_fwd(delta_hat) for the corners [[0,0],[P,0],[P,P],[0,P]], origin[B,2] float = the integer top-left
  * corner (x, y) of each patch; then H_hat.(o + u) = o + Hp.u and out[b,c,j,i] = bilinear img[b,c](origin_b + Hp_b.(i, j, 1)), zero padding
  * outside the Hi x Wi image (kornia.warp_perspective, align_corners=True).  img[B,C,Hi,Wi], out[B,C,P,P]; P a multiple of 16. */
-int bh_photo_warp_fwd_f(const float* img, const double* Hp64, const float* origin, int B, int C, int Hi, int Wi, int P, float* out,
-                        int flags, void* stream);
+int bh_photo_warp_fwd(const float* img, const double* Hp64, const float* origin, int B, int C, int Hi, int Wi, int P, float* out,
+                      int flags, void* stream);
 /* adjoint w.r.t. Hp only (image_1 is data): g_out[B,C,P,P] -> gH[B,9] double += (the caller zeroes it; feed to bh_h4pt_bwd).
  * flags & BH_F_DETERMINISTIC: one workgroup per sample is the only writer of gH[b]; otherwise workgroup sums are added with atomics. */
-int bh_photo_warp_bwd_f(const float* img, const double* Hp64, const float* origin, const float* g_out, int B, int C, int Hi, int Wi,
-                        int P, double* gH, int flags, void* stream);
+int bh_photo_warp_bwd(const float* img, const double* Hp64, const float* origin, const float* g_out, int B, int C, int Hi, int Wi,
+                      int P, double* gH, int flags, void* stream);
 /* adjoint w.r.t. the IMAGE (the trained masks of the Zhang baseline are warped, src/heads/TripletHead.py:60,69, and their gradient must
  * reach the mask predictor): g_out[B,C,h,w] -> g_img[B,C,h,w] (overwritten) = transpose of the bilinear gather with the same taps and
  * zero padding.  flags & BH_F_DETERMINISTIC: scratch = bh_warp_bwd_img_scratch_doubles(...) doubles (integer-limb entries); else NULL. */
 size_t bh_warp_bwd_img_scratch_doubles(int B, int C, int h, int w, int flags);
-int bh_warp_bwd_img_f(const double* H64, const float* g_out, int B, int C, int h, int w, float* g_img, double* scratch, int flags,
-                      void* stream);
+int bh_warp_bwd_img(const double* H64, const float* g_out, int B, int C, int h, int w, float* g_img, double* scratch, int flags,
+                    void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * biHomE triplet L1 reduction (triplet_resnet_loss, double-line / l1 / channel-agnostic / str margin:
  * src/heads/PerceptualHead.py:559-561, 609-665).  Features are NHWC [B,hw,C].
  * ------------------------------------------------------------------------------------------- */
 /* M1[B,hw] = sum_c |f1w-f2| - sum_c |f1-f2| ; M2[B,hw] = sum_c |f2w-f1| - sum_c |f1-f2| ;
- * numden[B,4] (double) = { sum m1w*m2*M1, sum m1w*m2, sum m2w*m1*M2, sum m2w*m1 } ; m1,m2 NULL => ones. */
+ * numden[B,4] (double) = { sum m1w*m2*M1, sum m1w*m2, sum m2w*m1*M2, sum m2w*m1 } ; m1,m2 NULL => ones.  flags: BH_F_DETERMINISTIC */
 int bh_triplet_l1_fwd(const float* f1, const float* f2, const float* f1w, const float* f2w,
                       const float* m1w, const float* m2w, const float* m1, const float* m2,
-                      int B, int hw, int C, float* M1, float* M2, double* numden, void* stream);
-int bh_triplet_l1_fwd_f(const float* f1, const float* f2, const float* f1w, const float* f2w,
-                        const float* m1w, const float* m2w, const float* m1, const float* m2,
-                        int B, int hw, int C, float* M1, float* M2, double* numden, int flags, void* stream);
+                      int B, int hw, int C, float* M1, float* M2, double* numden, int flags, void* stream);
 /* loss4[4] = { loss, ln1, ln2, ln3 }: ln_k = sum_b num/max(den,1); ln3 = sum_b ||H1 H2 - I||_F^2;
  * loss = ln1 + ln2 + mu*ln3 (PerceptualHead.py:656-665) */
 int bh_bihome_loss_fwd(const double* numden, const double* H1, const double* H2, int B, float mu,
@@ -259,13 +244,11 @@ int bh_bihome_loss_bwd(const float* g_loss, const float* f1, const float* f2, co
  * T[B,hw] = pre-hinge value (kept for the adjoint), numden[B,2] double, loss[1]. */
 /* Multi-hypothesis form (RANSAC_HYPOTHESIS_NO = rep > 1, PerceptualHead.py:352-361,505-511): B counts hypotheses
  * (samples * rep); f1, f2, m2 hold one entry per SAMPLE (row b / rep), f1w / m1w / T one per hypothesis; sample_w[B]
- * (NULL = 1) = DSAC score of the hypothesis, loss = sum_b sample_w[b] * loss_b; per_sample[B] (NULL ok) = loss_b. */
+ * (NULL = 1) = DSAC score of the hypothesis, loss = sum_b sample_w[b] * loss_b; per_sample[B] (NULL ok) = loss_b.
+ * flags: BH_F_DETERMINISTIC */
 int bh_oneline_loss_fwd(const float* f1, const float* f2, const float* f1w, const float* m1w, const float* m2, int B, int hw,
                         int C, float margin, int rep, const float* sample_w, float* T, double* numden, float* per_sample,
-                        float* loss, void* stream);
-int bh_oneline_loss_fwd_f(const float* f1, const float* f2, const float* f1w, const float* m1w, const float* m2, int B, int hw,
-                          int C, float margin, int rep, const float* sample_w, float* T, double* numden, float* per_sample,
-                          float* loss, int flags, void* stream);
+                        float* loss, int flags, void* stream);
 /* adjoint: g_loss[1] -> g_f1w[B,hw,C], g_m1w[B,hw] (overwritten); d loss / d sample_w[b] = g_loss * per_sample[b] */
 int bh_oneline_loss_bwd(const float* g_loss, const float* f2, const float* f1w, const float* m1w, const float* m2,
                         const float* T, const double* numden, int B, int hw, int C, int rep, const float* sample_w,
@@ -276,19 +259,15 @@ int bh_oneline_loss_bwd(const float* g_loss, const float* f2, const float* f1w, 
  * hinge != 0: h = max(., 0) (numeric margin, :98-107); hinge == 0: h = identity and margin is ignored (string margin, :92-97).
  * T1 / T2[B,hw] = pre-hinge values (for the adjoint), numden[B,4] double (overwritten) -> bh_bihome_loss_fwd gives ln1 + ln2 + mu ln3
  * (:150-152; one line: pass identity homographies and mu = 0).  The adjoint writes the gradients of ALL FOUR feature maps (the extractor
- * is trainable here) and of the two warped masks (overwritten); the unwarped masks are constants. */
+ * is trainable here) and of the two warped masks (overwritten), and on request those of the UNWARPED masks (trained masks, FIX_MASK False:
+ * m2 weights line 1, m1 line 2): g_m1 / g_m2[B,hw] overwritten, NULL = not wanted (the masks are constants). */
 int bh_zhang_triplet_fwd(const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w, const float* m2w,
                          const float* m1, const float* m2, int B, int hw, float margin, int hinge, float* T1, float* T2, double* numden,
                          void* stream);
 int bh_zhang_triplet_bwd(const float* g_loss, const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
                          const float* m2w, const float* m1, const float* m2, const float* T1, const float* T2, const double* numden, int B,
-                         int hw, int hinge, float* g_f1, float* g_f2, float* g_f1w, float* g_f2w, float* g_m1w, float* g_m2w, void* stream);
-/* the same adjoint with the gradients of the UNWARPED masks (trained masks, FIX_MASK False: m2 weights line 1, m1 line 2):
- * g_m1 / g_m2[B,hw] overwritten, NULL = not wanted (bh_zhang_triplet_bwd is this call with both NULL). */
-int bh_zhang_triplet_bwd_m(const float* g_loss, const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
-                           const float* m2w, const float* m1, const float* m2, const float* T1, const float* T2, const double* numden, int B,
-                           int hw, int hinge, float* g_f1, float* g_f2, float* g_f1w, float* g_f2w, float* g_m1w, float* g_m2w,
-                           float* g_m1, float* g_m2, void* stream);
+                         int hw, int hinge, float* g_f1, float* g_f2, float* g_f1w, float* g_f2w, float* g_m1w, float* g_m2w,
+                         float* g_m1, float* g_m2, void* stream);
 /* Trained content masks (src/backbones/ContentAware.py:24-26,28-35,47-50,128-134) after the mask predictor's last BatchNorm y[N,P]
  * (P = h w pixels of a one-channel map): s = sigmoid(y); strength > 0: m = clamp(s / (max_p s * strength), 0, 1) (per-sample maximum),
  * else m = s; g = m * f (f, g NULL: the mask only).  smax[N] / imax[N]: the maximum of s and its first pixel (kept for the adjoint).
@@ -298,12 +277,10 @@ int bh_mask_fwd(const float* y, const float* f, int N, int P, float strength, fl
 int bh_mask_bwd(const float* y, const float* f, const float* m, const float* smax, const int* imax, const float* g_m, const float* g_g,
                 int N, int P, float strength, float* g_y, float* g_f, void* stream);
 /* y[b,:] = x[b / rep,:] * s[b] over Bn hypotheses of L floats (the score weighting of multihead_resnet_loss,
- * PerceptualHead.py:276-280) and its adjoint (g_x only for rep = 1, may be NULL; g_s[Bn] overwritten). */
+ * PerceptualHead.py:276-280) and its adjoint (g_x only for rep = 1, may be NULL; g_s[Bn] overwritten; flags: BH_F_DETERMINISTIC). */
 int bh_scale_samples_fwd(const float* x, const float* s, int Bn, long long L, int rep, float* y, void* stream);
 int bh_scale_samples_bwd(const float* g_y, const float* x, const float* s, int Bn, long long L, int rep, float* g_x, float* g_s,
-                         void* stream);
-int bh_scale_samples_bwd_f(const float* g_y, const float* x, const float* s, int Bn, long long L, int rep, float* g_x, float* g_s,
-                           int flags, void* stream);
+                         int flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Conv stacks (Rethinking._forward src/backbones/Rethinking.py:284-294 with blocks
@@ -347,7 +324,7 @@ typedef struct {
      * device memory) of the operand tensors - a_bound: the tensor the launch convolves (x for forward / weight gradient - of the
      * BatchNorm OUTPUT for the *_bnin forms -, gy for dgrad); b_bound: gy of the weight gradient.  A record holds an upper bound
      * of max |element| as the maximum over its 16 slots (one per 128-byte line; non-negative floats): written by bh_absmax, by the
-     * *_amax forms of the BatchNorm entry points (measured) or by bh_bn_fwd_coeffs_amax (|gamma| sqrt(rows) + |beta|).  A bound
+     * amax outputs of the BatchNorm entry points (measured) or by bh_bn_fwd_coeffs (|gamma| sqrt(rows) + |beta|).  A bound
      * that is too small overflows fp16 (inf / NaN in the result, never a silently wrong value); one that is too large by 2^j
      * costs j of the 18 binades of full precision. */
     const float* a_bound;
@@ -436,12 +413,10 @@ typedef struct {
     int groups;
     int relu;
 } bh_bn_in;
-int bh_bn_fwd_coeffs(const double* stats, const float* gamma, const float* beta, float* running_mean, float* running_var, int groups,
-                     int rows, int C, float eps, float momentum, float* table, void* stream);
-/* bh_bn_fwd_coeffs + the magnitude record of the BatchNorm's OUTPUT (what the *_bnin consumers convolve): the a-priori bound
+/* amax_y (NULL ok): the magnitude record of the BatchNorm's OUTPUT (what the *_bnin consumers convolve): the a-priori bound
  * max_c 2 (|gamma_c| sqrt(rows) + |beta_c|) - a normalised sample is at most sqrt(rows - 1) standard deviations from its mean. */
-int bh_bn_fwd_coeffs_amax(const double* stats, const float* gamma, const float* beta, float* running_mean, float* running_var, int groups,
-                          int rows, int C, float eps, float momentum, float* table, float* amax_y, void* stream);
+int bh_bn_fwd_coeffs(const double* stats, const float* gamma, const float* beta, float* running_mean, float* running_var, int groups,
+                     int rows, int C, float eps, float momentum, float* table, float* amax_y, void* stream);
 int bh_conv_fwd_bnin(const float* x, const float* w, const float* bias, float* y, const bh_conv_desc* d, double* sums, int groups,
                      const bh_bn_in* bni, void* stream);
 int bh_conv_wgrad_bnin(const float* x, const float* gy, float* gw, float* gbias, const bh_conv_desc* d, float* ws, long long ws_bytes,
@@ -549,33 +524,25 @@ int bh_conv_bias_grad(const float* gy, float* gbias, const bh_conv_desc* d, void
 int bh_bn_stats_doubles(int groups, int C);
 int bh_bn_scratch_doubles(int groups, int C);
 /* C: a multiple of 4 (<= 1024, C/4 dividing 256), or 1 (round 3: the one-channel BatchNorms of the Zhang feature extractor /
- * mask predictor, ContentAware.py:24-26,68-70 - csrc/bn1.hip, same contract). */
+ * mask predictor, ContentAware.py:24-26,68-70 - csrc/bn1.hip, same contract; BH_E_UNSUPPORTED with a magnitude record).
+ * amax_y (NULL ok; BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |y| (precision 4 consumers). */
 int bh_bn_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
               const float* res, float* y, double* stats, int groups, int rows, int C, float eps, float momentum,
-              int flags, int use_running, void* stream);
-/* the same, and amax_y (BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |y| (precision 4 consumers) */
-int bh_bn_fwd_amax(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
-                   const float* res, float* y, double* stats, int groups, int rows, int C, float eps, float momentum,
-                   int flags, int use_running, float* amax_y, void* stream);
+              int flags, int use_running, float* amax_y, void* stream);
 /* adjoint. gy: grad w.r.t. y; y: the forward output (for the relu mask); x: forward input.
  * -> gx (overwritten), gres (written when non-NULL: = masked gy), ggamma/gbeta += (NULL ok => frozen).
  * flags bit2 (only without residual): recompute the ReLU mask from x (y is not read, may be NULL).
  * flags bit4: `scratch` already holds the gradient sums (bh_bn_stats_doubles() layout) accumulated by
- * bh_conv_dgrad_bnreduce - one launch instead of three. */
+ * bh_conv_dgrad_bnreduce - one launch instead of three.
+ * amax_gx (NULL ok; BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |gx|. */
 int bh_bn_bwd(const float* gy, const float* y, const float* x, const float* gamma, const float* beta, const double* stats,
               float* gx, float* gres, float* ggamma, float* gbeta, double* scratch,
               int groups, int rows, int C, float eps, int flags, int use_running,
-              const float* running_mean, const float* running_var, void* stream);
-
-/* the same, and amax_gx (BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |gx| */
-int bh_bn_bwd_amax(const float* gy, const float* y, const float* x, const float* gamma, const float* beta, const double* stats,
-                   float* gx, float* gres, float* ggamma, float* gbeta, double* scratch,
-                   int groups, int rows, int C, float eps, int flags, int use_running,
-                   const float* running_mean, const float* running_var, float* amax_gx, void* stream);
+              const float* running_mean, const float* running_var, float* amax_gx, void* stream);
 
 /* BatchNorm (+ReLU) + MaxPool2d(3, 2, 1) in one pass (round 4: conv1-bn1-relu-maxpool of the backbone stem, Rethinking.py:31-36, and of the
  * perceptual extractor): x[N,Hi,Wi,C] -> y[N,Ho,Wo,C], idx (one byte per element: window position 0..8 of the first maximum, as
- * bh_maxpool3s2_fwd; NULL ok).  stats / flags / use_running / momentum / amax_y as in bh_bn_fwd_amax (flags: bit0 relu, bit3 sums ready,
+ * bh_maxpool3s2_fwd; NULL ok).  stats / flags / use_running / momentum / amax_y as in bh_bn_fwd (flags: bit0 relu, bit3 sums ready,
  * BH_BN_DETERMINISTIC).  The activation between BatchNorm and pooling is never stored: the adjoint is bh_maxpool3s2_bwd followed by bh_bn_bwd
  * with the mask recomputed from x (flags bit2). */
 int bh_bn_maxpool_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var, float* y,
@@ -584,7 +551,7 @@ int bh_bn_maxpool_fwd(const float* x, const float* gamma, const float* beta, flo
 /* Adjoint of bh_bn_maxpool_fwd in one call (round 5): gy[N,Ho,Wo,C] and idx as written by the forward, x the BatchNorm input -> gx[N,Hi,Wi,C]
  * (and ggamma / gbeta +=, NULL ok).  The full-resolution gradient between pooling and BatchNorm is never stored (bh_maxpool3s2_bwd + bh_bn_bwd
  * wrote and re-read it: 850 -> 490 MB on the extractor stem, /root/reference/src/heads/PerceptualHead.py:50-60).  scratch: bh_bn_scratch_doubles
- * doubles; flags: bit0 relu (mask recomputed from x), BH_BN_DETERMINISTIC; use_running / running_* / amax_gx as in bh_bn_bwd_amax.  The sums are
+ * doubles; flags: bit0 relu (mask recomputed from x), BH_BN_DETERMINISTIC; use_running / running_* / amax_gx as in bh_bn_bwd.  The sums are
  * chunk partials added in fixed order: bitwise reproducible in either mode. */
 int bh_bn_maxpool_bwd(const float* gy, const unsigned char* idx, const float* x, const float* gamma, const float* beta, const double* stats,
                       float* gx, float* ggamma, float* gbeta, double* scratch, int groups, int N, int Hi, int Wi, int C, float eps, int flags,
@@ -592,7 +559,7 @@ int bh_bn_maxpool_bwd(const float* gy, const unsigned char* idx, const float* x,
 /* BatchNorm (+ReLU, no residual) adjoint whose output gradient is the dgrad of a 1x1 / stride-1 convolution with KC = 16 or 32 output channels
  * (round 5): gs[groups*rows][KC] is the gradient of THAT CONVOLUTION's output, w[KC][C] its kernel-layout weight ([Co][1][1][Ci]); the
  * BatchNorm's output gradient g = gs w is rebuilt per element in both passes and never stored (the decoder units' BatchNorm + ReLU + 1x1
- * conv, /root/reference/src/backbones/utils.py:60-82).  Equivalent to bh_conv_dgrad (1x1) followed by bh_bn_bwd_amax with flags bit0 | bit2
+ * conv, /root/reference/src/backbones/utils.py:60-82).  Equivalent to bh_conv_dgrad (1x1) followed by bh_bn_bwd with flags bit0 | bit2
  * (training mode), up to the summation order of the KC products.  scratch: bh_bn_scratch_doubles; flags: bit0 relu, BH_BN_DETERMINISTIC. */
 int bh_bn_bwd_from_1x1(const float* gs, const float* w, int KC, const float* x, const float* gamma, const float* beta, const double* stats,
                        float* gx, float* ggamma, float* gbeta, double* scratch, int groups, int rows, int C, float eps, int flags,
@@ -600,7 +567,7 @@ int bh_bn_bwd_from_1x1(const float* gs, const float* w, int KC, const float* x, 
 /* Two-branch join (round 4): y = act(bn_a(xa) + bn_b(xb)), both BatchNorms in training mode with their own statistics tables (already
  * accumulated: by the producers' epilogues or bh_bn_stats-style passes) - the end of ResNet50DeconvBlock / the strided ResNet34ConvBlock
  * (src/backbones/utils.py:60-82, 85-112) without writing the normalised lower branch.  flags: bit0 relu, BH_BN_DETERMINISTIC.  Running
- * statistics of both are updated (NULL: skipped).  amax_y as in bh_bn_fwd_amax.
+ * statistics of both are updated (NULL: skipped).  amax_y as in bh_bn_fwd.
  * Adjoint: gy, y (ReLU mask), xa, xb -> gxa, gxb (overwritten), ggamma / gbeta of both += (NULL ok); scratch: bh_bn_join_scratch_doubles()
  * doubles; amax_gxa / amax_gxb (NULL ok) receive max |gxa| / max |gxb|.  One reduce pass for the three sums (sum d, sum d xhat_a,
  * sum d xhat_b with d = gy [y > 0]) and one apply pass. */
@@ -628,36 +595,28 @@ int bh_bn_join_bwd_remask(const float* gy, const float* xa, const float* xb, con
  *   Conv2d(Ci,Cm,1,bias) -> BatchNorm2d(Cm) -> ReLU -> Conv2d(Cm,Co,1,bias), NHWC x[groups*rows,Ci] -> NCHW out[N,Co,h,w]
  * (hw = h*w pixels per image, rows = pixels per group).  The Cm-channel intermediate is never materialised: its batch
  * statistics are derived from the first/second moments of x (a 1x1 conv is linear).  Ci in {8,16}, Cm multiple of
- * 64 (<= 256), Co <= 4.  ws: bh_tail_ws_doubles() doubles (kept for the adjoint); scratch: bh_tail_scratch_floats(). */
+ * 64 (<= 256), Co <= 4.  ws: bh_tail_ws_doubles() doubles (kept for the adjoint); scratch: bh_tail_scratch_floats().
+ * route, per call (no process state): 0 = the library's choice - round 4: for Ci = 16, Co <= 2, rows % 32 == 0 and
+ * hw % 32 == 0 the Ci -> Cm product runs on the matrix pipe in the exact three-bf16-piece arithmetic (tail_fwd_mfma_kernel);
+ * bit 0 (BH_TAIL_ROUTE_VALU_FWD) keeps the per-pixel VALU kernel (tests compare the two, tools time them). */
 int bh_tail_ws_doubles(int groups, int Ci, int Cm);
 int bh_tail_scratch_floats(int groups, int Ci, int Cm);
+#define BH_TAIL_ROUTE_VALU_FWD 1
+#define BH_TAIL_ROUTE_LDS_MOMENTS 2      /* bit 1: the input moments by the LDS-slab kernel instead of the matrix-pipe one (Ci = 16) */
 int bh_tail_fwd(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta,
                 float* running_mean, float* running_var, const float* w2, const float* b2, float* out, double* ws,
                 int groups, int rows, int hw, int Ci, int Cm, int Co, float eps, float momentum, int use_running,
-                void* stream);
-/* Same call with a per-call route (no process state): 0 = the library's choice - round 4: for Ci = 16, Co <= 2, rows % 32 == 0 and
- * hw % 32 == 0 the Ci -> Cm product runs on the matrix pipe in the exact three-bf16-piece arithmetic (tail_fwd_mfma_kernel);
- * bit 0 (BH_TAIL_ROUTE_VALU_FWD) keeps the per-pixel VALU kernel (tests compare the two, tools time them). */
-#define BH_TAIL_ROUTE_VALU_FWD 1
-#define BH_TAIL_ROUTE_LDS_MOMENTS 2      /* bit 1: the input moments by the LDS-slab kernel instead of the matrix-pipe one (Ci = 16) */
-int bh_tail_fwd_route(const float* x, const float* w1, const float* b1, const float* gamma, const float* beta,
-                      float* running_mean, float* running_var, const float* w2, const float* b2, float* out, double* ws,
-                      int groups, int rows, int hw, int Ci, int Cm, int Co, float eps, float momentum, int use_running,
-                      int route, void* stream);
+                int route, void* stream);
 /* adjoint: gout[N,Co,h,w] -> gx[groups*rows,Ci] (overwritten, NULL ok); gw1[Cm][Ci], ggamma, gbeta, gw2[Co][Cm], gb2 +=
  * Round 4: pixels whose output gradient is exactly zero are skipped by the reduction (they add exactly zero: on the biHomE path only
  * the DSAC-sampled points of the field carry a gradient), and gx = c0 - M x (the BatchNorm mean terms, an affine map of x made once
- * per group) + the Cm-channel term where the gradient is non-zero.  Dense gradients take the per-lane channel loop as before. */
+ * per group) + the Cm-channel term where the gradient is non-zero.  Dense gradients take the per-lane channel loop as before.
+ * flags: BH_F_DETERMINISTIC (the bias gradient gb2) */
 int bh_tail_bwd(const float* gout, const float* x, const float* w1, const float* b1, const float* gamma,
                 const float* beta, const float* w2, const double* ws, const float* running_mean,
                 const float* running_var, float* gx, float* gw1, float* ggamma, float* gbeta, float* gw2, float* gb2,
                 float* scratch, int groups, int rows, int hw, int Ci, int Cm, int Co, float eps, int use_running,
-                void* stream);
-int bh_tail_bwd_f(const float* gout, const float* x, const float* w1, const float* b1, const float* gamma,
-                  const float* beta, const float* w2, const double* ws, const float* running_mean,
-                  const float* running_var, float* gx, float* gw1, float* ggamma, float* gbeta, float* gw2, float* gb2,
-                  float* scratch, int groups, int rows, int hw, int Ci, int Cm, int Co, float eps, int use_running,
-                  int flags, void* stream);                                   /* flags: BH_F_DETERMINISTIC (the bias gradient gb2) */
+                int flags, void* stream);
 
 /* Synthetic pair generator (next-row f1): HomographyNetPrep + PhotometricDistortSimple + DictToGrayscale +
  * DictStandardize of src/data/transforms.py:296-330,344-378,441-725 for B samples in one launch.

@@ -628,10 +628,10 @@ def test_c_abi_error_codes(K):
     assert lib.bh_conv_wgrad(P(x.data_ptr()), P(y.data_ptr()), P(w.data_ptr()), None, ctypes.byref(bad), s) == -2
     st = K.bn_stats_buffer(1, 6, "cuda")
     z = torch.zeros(4, 6, device="cuda")
-    assert lib.bh_bn_fwd(P(z.data_ptr()), None, None, None, None, None, P(z.data_ptr()), P(st.data_ptr()), 1, 4, 6, 1e-5, 0.1, 0, 0, s) == -2
+    assert lib.bh_bn_fwd(P(z.data_ptr()), None, None, None, None, None, P(z.data_ptr()), P(st.data_ptr()), 1, 4, 6, 1e-5, 0.1, 0, 0, None, s) == -2
     img = torch.zeros(1, 1, 24, 24, device="cuda")
     H = torch.eye(3, dtype=torch.float64, device="cuda").reshape(1, 9)
-    assert lib.bh_warp_fwd(P(img.data_ptr()), P(H.data_ptr()), 1, 1, 24, 24, 4, P(img.data_ptr()), None, s) == -2
+    assert lib.bh_warp_fwd(P(img.data_ptr()), P(H.data_ptr()), 1, 1, 24, 24, 4, P(img.data_ptr()), None, 0, s) == -2
     with pytest.raises(BihomeLibError, match="BH_E_UNSUPPORTED"):
         K.warp_fwd(img, H)
     with pytest.raises(RuntimeError, match="no CPU"):

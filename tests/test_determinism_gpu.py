@@ -151,7 +151,7 @@ def test_limb_accumulation_of_batchnorm_sums_is_exact_and_repeatable(det):
 
 def test_two_models_of_one_process_run_in_different_modes():
     """Round-3 VERDICT item 8: the library has no process-wide mode - the bit travels with every call (bh_conv_desc.route, the BatchNorm
-    flags, the flags argument of the bh_*_f entry points) and a model keeps the mode it was built with.  A deterministic and a default
+    flags, the flags argument of the entry points that take BH_F_DETERMINISTIC) and a model keeps the mode it was built with.  A deterministic and a default
     model are built in ONE process and stepped alternately; the deterministic one must reproduce, bit for bit, the run of a deterministic
     model that had the process to itself, whatever the other one does in between."""
     from bihome_amd import kernels as K

@@ -1,4 +1,4 @@
-"""DSAC inlier-count scoring (bh_dsac_score_m / bh_dsac_scores_bwd_m, SCORING_METHOD 'inliers_ratio' / 'soft_inliers_ratio'): the
+"""DSAC inlier-count scoring (bh_dsac_score / bh_dsac_scores_bwd, SCORING_METHOD 'inliers_ratio' / 'soft_inliers_ratio'): the
 boundary, the head's kwargs, and the yardstick of tests/test_dsac_scoring_gpu.py - a float64 torch restatement of
 DSACSoftmax.__score_hypotheses (ransac_utils.py:76-128), checked here on its own against the fixtures the reference's modules wrote
 (tools/make_golden_dsac_scoring.py), together with the conditions that tool promises about them."""
@@ -64,7 +64,7 @@ def _prototype(name):
     return want
 
 
-@pytest.mark.parametrize("name,nargs", [("bh_dsac_score_m", 12), ("bh_dsac_scores_bwd_m", 16)])
+@pytest.mark.parametrize("name,nargs", [("bh_dsac_score", 12), ("bh_dsac_scores_bwd", 16)])
 def test_header_and_ctypes_signature_agree(name, nargs):
     from bihome_amd import _lib
     want = _prototype(name)
@@ -77,7 +77,7 @@ def test_header_and_ctypes_signature_agree(name, nargs):
 
 def test_bad_arguments_are_refused_before_any_launch():
     from bihome_amd import _lib
-    f, g = _lib.lib.bh_dsac_score_m, _lib.lib.bh_dsac_scores_bwd_m
+    f, g = _lib.lib.bh_dsac_score, _lib.lib.bh_dsac_scores_bwd
     p = ctypes.c_void_p(64)         # never dereferenced: the argument check comes first
     nan = float("nan")
     for method in (0, 1, 2):

@@ -1,4 +1,4 @@
-"""bh_dsac_score_m / bh_dsac_scores_bwd_m on the MI355X against the float64 restatement of tests/test_dsac_scoring_cpu.py (torch
+"""bh_dsac_score / bh_dsac_scores_bwd on the MI355X against the float64 restatement of tests/test_dsac_scoring_cpu.py (torch
 autograd for the adjoint), and the head with SCORING_METHOD 'soft_inliers_ratio' / 'inliers_ratio' against the fixtures the reference's
 own modules wrote (tools/make_golden_dsac_scoring.py).
 
@@ -127,7 +127,9 @@ def test_hard_pick_is_the_first_minimum_on_a_tie():
 
 
 @pytest.mark.parametrize("det", [0, 1])
-def test_method_zero_is_the_existing_path_bitwise(det):
+def test_method_zero_is_repeatable_bitwise(det):
+    """Method 0 ('repr_error') of the one pair of entry points, called twice: the same bits (its agreement with the reference is
+    test_head_kernels_gpu.py's and the golden tests')."""
     from bihome_amd import _lib
     from bihome_amd import kernels as K
     B, n, h, w = 3, 4, 32, 24
@@ -136,19 +138,15 @@ def test_method_zero_is_the_existing_path_bitwise(det):
     p, st = K._p, K._stream
     err = [torch.empty(B, n, device="cuda") for _ in range(2)]
     best = [torch.empty(B, dtype=torch.int64, device="cuda") for _ in range(2)]
-    assert _lib.lib.bh_dsac_score(p(pf), p(Hf), B, n, h, w, p(err[0]), p(best[0]), st()) == 0
-    assert _lib.lib.bh_dsac_score_m(p(pf), p(Hf), B, n, h, w, 0, 0.0, 0.0, p(err[1]), p(best[1]), st()) == 0
+    for i in range(2):
+        assert _lib.lib.bh_dsac_score(p(pf), p(Hf), B, n, h, w, 0, 0.0, 0.0, p(err[i]), p(best[i]), st()) == 0
     assert torch.equal(err[0], err[1]) and torch.equal(best[0], best[1])
     s = torch.empty(B, n, device="cuda")
     assert _lib.lib.bh_dsac_scores_fwd(p(err[0]), B, n, p(s), st()) == 0
     outs = []
-    for call in ("f", "m"):
+    for _ in range(2):
         ge, gH, gp = torch.empty(B, n, device="cuda"), torch.empty(B * n, 9, dtype=torch.float64, device="cuda"), torch.zeros_like(pf)
-        if call == "f":
-            rc = _lib.lib.bh_dsac_scores_bwd_f(p(pf), p(Hf), p(s), p(gs), B, n, h, w, p(ge), p(gH), p(gp), det, st())
-        else:
-            rc = _lib.lib.bh_dsac_scores_bwd_m(p(pf), p(Hf), p(s), p(gs), B, n, h, w, 0, 0.0, 0.0, p(ge), p(gH), p(gp), det, st())
-        assert rc == 0
+        assert _lib.lib.bh_dsac_scores_bwd(p(pf), p(Hf), p(s), p(gs), B, n, h, w, 0, 0.0, 0.0, p(ge), p(gH), p(gp), det, st()) == 0
         outs.append((ge, gH, gp))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     if det:                                                 # (the default path's float atomics into g_pf are order-dependent by contract)

@@ -1,5 +1,5 @@
 """The photometric baseline on the MI355X (config/s-coco/nguyen-orig-lr-5e-3.yaml): the warp-and-crop gather of PhotometricHead
-(bh_photo_warp_fwd_f) and its adjoint against a float64 restatement from the oracle, the identity map, the whole model against the
+(bh_photo_warp_fwd) and its adjoint against a float64 restatement from the oracle, the identity map, the whole model against the
 reference's own modules (tests/golden/nguyen_orig_b4_*.npz, tools/make_golden_nguyen.py), determinism and HIP-graph capture, the
 device data path (bh_synth_image) and the pds-coco sibling (NoOpHead + L1Loss)."""
 import numpy as np

@@ -101,7 +101,7 @@ def test_zhang_triplet_kernels(B, h, margin, double):
 
 
 def _check_unwarped_mask_gradients(K, f, m, margin, hinge, double, gen):
-    """Trained masks (round 4): the unwarped masks m2 (line 1) / m1 (line 2) enter bh_zhang_triplet_fwd and bh_zhang_triplet_bwd_m returns
+    """Trained masks (round 4): the unwarped masks m2 (line 1) / m1 (line 2) enter bh_zhang_triplet_fwd and bh_zhang_triplet_bwd returns
     their gradients as well - against torch float64 autograd."""
     B, h = f[0].shape[0], f[0].shape[-1]
     u = [torch.rand(B, h, h, generator=gen) for _ in range(2)]                   # m1, m2
@@ -174,7 +174,7 @@ def test_mask_gate_kernels(strength):
 
 @pytest.mark.parametrize("det", [False, True])
 def test_warp_adjoint_with_respect_to_the_image(det):
-    """bh_warp_bwd_img_f is the transpose of bh_warp_fwd's bilinear gather: <warp(img), g> == <img, warp^T(g)> for random images and
+    """bh_warp_bwd_img is the transpose of bh_warp_fwd's bilinear gather: <warp(img), g> == <img, warp^T(g)> for random images and
     gradients under homographies that push part of the patch out of the image (zero padding), and equal to torch float64 autograd of
     grid_sample-style sampling through the forward kernel's linearity (finite differences are exact for a linear map)."""
     from bihome_amd import kernels as K

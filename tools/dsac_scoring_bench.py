@@ -1,9 +1,9 @@
-"""Time the DSAC soft inlier-count score and its adjoint (bh_dsac_score_m / bh_dsac_scores_bwd_m, 'soft_inliers_ratio') on one GPU.
+"""Time the DSAC soft inlier-count score and its adjoint (bh_dsac_score / bh_dsac_scores_bwd, 'soft_inliers_ratio') on one GPU.
 
     python tools/dsac_scoring_bench.py [--reps 50]
 
 B = 64 fields of 128 x 128, n in {4, 64} hypotheses.  Two baselines on the same device and shapes: the torch formulation of
-ransac_utils.py:76-128 (fp32 eager ops + autograd), and the unchanged 'repr_error' kernels (bh_dsac_score / bh_dsac_scores_bwd_f: one
+ransac_utils.py:76-128 (fp32 eager ops + autograd), and the unchanged 'repr_error' kernels (method 0 of the same two calls: one
 workgroup per hypothesis, the field re-read n times).  Forward = raw scores + softmax; backward = the adjoint given the weights' gradient.
 Medians over --reps timed calls with HIP events after 5 warm-up calls; one JSON line per n.  The only pass / fail: the kernels beat torch."""
 import argparse

@@ -40,7 +40,7 @@ if d.precision == 4:
     def ffused(i): check(lib.bh_stem7_fwd_warp(p(src[i]), p(H64), 4, p(w), None, p(y[i]), ctypes.byref(d), p(warped), p(cov), p(sums), 2, st()), "fwd fused")
     def ffused_noimg(i): check(lib.bh_stem7_fwd_warp(p(src[i]), p(H64), 4, p(w), None, p(y[i]), ctypes.byref(d), None, p(cov), p(sums), 2, st()), "fwd fused")
     def ftwo(i):
-        check(lib.bh_warp_fwd_f(p(src[i]), p(H64), B, 1, size, size, 4, p(warped), p(cov), 0, st()), "warp_fwd")
+        check(lib.bh_warp_fwd(p(src[i]), p(H64), B, 1, size, size, 4, p(warped), p(cov), 0, st()), "warp_fwd")
         check(lib.bh_conv_fwd_bnstats(p(warped), p(w), None, p(y[i]), ctypes.byref(d), p(sums), 2, st()), "fwd plain")
     for rnd in range(3):
         print("round %d: plain stem fwd %.1f us | with the warp folded in %.1f us (without the image write %.1f) | warp_fwd + plain %.1f us"
