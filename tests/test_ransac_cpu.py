@@ -4,6 +4,7 @@ kwargs, and the yardstick the GPU tests (tests/test_ransac_gpu.py) compare again
 include/bihome.h and checked here on its own: on a field with 0.3 px noise, a 30 % block of wrong offsets and 5 % scattered outliers
 it recovers the true 4-point offsets to a fraction of a pixel where the least-squares fit of the lattice points is off by tens."""
 import ctypes
+import functools
 import os
 import re
 
@@ -27,22 +28,74 @@ def make_inputs(B=B_TEST, K=K_TEST, pair_seed=PAIR_SEED, noise_seed=NOISE_SEED, 
     d = synth.make_pairs(B, seed=pair_seed, target=True)
     clean = np.asarray(d["target"], np.float32)
     _, _, h, w = clean.shape
-    rng = np.random.default_rng(noise_seed)
+    pf = _corrupt(clean, np.random.default_rng(noise_seed))
+    choice = torch.randint(0, h * w, (B, K, 4), generator=torch.Generator().manual_seed(choice_seed)).numpy()
+    return pf.astype(np.float32), choice.astype(np.int64), np.asarray(d["delta"], np.float64), clean
+
+
+def _corrupt(clean, rng, reach=False):
+    """clean [B,2,h,w] float32 -> float64: 0.3 px noise, a contiguous 30 % block at one far-away offset, 5 % scattered outliers.
+    reach: the block's offset lies 90 px beyond the farthest true offset inside the block, not 90 px from the one at its centre
+    (for a field that varies by tens of pixels across the block)."""
+    B, _, h, w = clean.shape
     pf = clean.astype(np.float64) + rng.normal(0.0, 0.3, clean.shape)
-    bh, bw = h // 2, int(np.ceil(0.3 * h * w / (h // 2)))          # a contiguous block of 30 % of the patch
-    assert bh * bw >= 0.3 * h * w
+    bh = max(h // 2, 1)
+    bw = int(np.ceil(0.3 * h * w / bh))                             # a contiguous block of 30 % of the patch
+    assert bh * bw >= 0.3 * h * w and bw <= w
     for b in range(B):
         y0, x0 = int(rng.integers(0, h - bh + 1)), int(rng.integers(0, w - bw + 1))
         ang = rng.uniform(0, 2 * np.pi)
         centre = clean[b, :, y0 + bh // 2, x0 + bw // 2].astype(np.float64)
-        const = centre + 90.0 * np.array([np.cos(ang), np.sin(ang)])
+        far = np.sqrt(((clean[b, :, y0:y0 + bh, x0:x0 + bw] - centre[:, None, None]) ** 2).sum(0)).max() if reach else 0.0
+        const = centre + (90.0 + far) * np.array([np.cos(ang), np.sin(ang)])
         away = np.sqrt(((clean[b, :, y0:y0 + bh, x0:x0 + bw] - const[:, None, None]) ** 2).sum(0)).min()
         assert away >= 40.0, away                                   # every pixel of the block is >= 40 px from its true offset
         pf[b, :, y0:y0 + bh, x0:x0 + bw] = const[:, None, None]
         idx = rng.choice(h * w, size=int(round(0.05 * h * w)), replace=False)      # a further 5 %: scattered, uniform in +-64 px
         pf[b].reshape(2, -1)[:, idx] = rng.uniform(-64.0, 64.0, (2, idx.size))
+    return pf
+
+
+def _four_point(src, dst):
+    """The homography through four correspondences, H22 = 1 (float64)."""
+    S = np.zeros((8, 8))
+    for i in range(4):
+        (x, y), (u, v) = src[i], dst[i]
+        S[2 * i] = [x, y, 1, 0, 0, 0, -x * u, -y * u]
+        S[2 * i + 1] = [0, 0, 0, x, y, 1, -x * v, -y * v]
+    return np.append(np.linalg.solve(S, np.asarray(dst, np.float64).reshape(8)), 1.0).reshape(3, 3)
+
+
+def make_field_inputs(B, K, h, w, seed, choice_seed):
+    """make_inputs at any field size: per sample a random 4-point homography (corner offsets uniform in +-0.25 min(h, w)) evaluated in
+    float64, then make_inputs' noise, block and scattered outliers; the draws from a seeded torch.randint.
+    -> pf [B,2,h,w] float32, choice [B,K,4] int64, delta [B,4,2] (truth), clean [B,2,h,w] float32 (the exact field)."""
+    rng = np.random.default_rng(seed)
+    c = np.array([[0, 0], [w, 0], [w, h], [0, h]], np.float64)
+    delta = rng.uniform(-0.25 * min(h, w), 0.25 * min(h, w), (B, 4, 2))
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    clean = np.empty((B, 2, h, w))
+    for b in range(B):
+        q = np.stack([xs, ys, np.ones_like(xs)], -1) @ _four_point(c, c + delta[b]).T
+        assert (q[..., 2] > 0.1).all()
+        clean[b] = np.stack([q[..., 0] / q[..., 2] - xs, q[..., 1] / q[..., 2] - ys])
+    clean = clean.astype(np.float32)
+    pf = _corrupt(clean, rng, reach=True)
     choice = torch.randint(0, h * w, (B, K, 4), generator=torch.Generator().manual_seed(choice_seed)).numpy()
-    return pf.astype(np.float32), choice.astype(np.int64), np.asarray(d["delta"], np.float64), clean
+    return pf.astype(np.float32), choice.astype(np.int64), delta, clean
+
+
+# (B, K, h, w, thr): the smallest shapes at which bh_ransac_homography's kernels take their other paths
+FIELD_CASES = [
+    (2, 1100, 37, 83, 10.0),     # N = 3071: two count tiles, the second partial; K = 1024 + 76; B*K = 2200 = 34 * 64 + 24; odd w
+    (1, 2100, 16, 16, 5.0),      # three passes of the 1024-entry table (1024, 1024, 52); N = 256: one strip of one tile
+    (3, 70, 5, 7, 3.0),          # N = 35: less than one wave; K = 64 + 6; many invalid draws
+    (2, 200, 9, 300, 10.0),      # wide and short, w no power of two; N = 2700: one full tile and a partial one
+    (2, 130, 3, 700, 10.0),      # w > 512, h = 3; N = 2100
+]
+FIELD_SEEDS = [(101, 201), (102, 202), (103, 203), (104, 204), (125, 225)]      # (field, draws) per case
+TIE_CASES = (0, 2)
+WILD_H, WILD_W, WILD_THR = 24, 20, 0.05
 
 
 # ------------------------------------------------------------------------------------------------
@@ -123,6 +176,27 @@ def squared_error(pf, H):
     return e, (qz > 0) & np.isfinite(qz)
 
 
+def fp32_margins(pf, hyp):
+    """What fp32 can do to the inlier test, for inputs the relative 1e-4 of counts()' border does not cover (a threshold far below the
+    offsets, a horizon inside the field).  The kernel evaluates q = H (x, y, 1) with two fused multiply-adds per coordinate (error
+    <= 2 eps S, S the sum of the absolute terms), a = qx - u qz and b = qy - v qz with one each, and tests a^2 + b^2 <= (thr qz)^2.
+    -> d [B,K,N]: the float64 reprojection distance in px; slack [B,K,N]: a bound in px on what the fp32 evaluation moves d, or the
+    threshold, by; horizon [B,K,N]: |qz| over the bound 2 eps Sz on its own fp32 error (the sign of qz is safe where this is large); front [B,K,N]: qz > 0
+    (a pixel behind is an outlier whatever its d)."""
+    x, y, u, v = _coords(pf)
+    H = hyp.astype(np.float32).astype(np.float64)[..., None]
+    eps = FLT_EPSILON
+    with np.errstate(all="ignore"):
+        qz = H[..., 6, :] * x + H[..., 7, :] * y + H[..., 8, :]
+        sx = np.abs(H[..., 0, :] * x) + np.abs(H[..., 1, :] * y) + np.abs(H[..., 2, :])
+        sy = np.abs(H[..., 3, :] * x) + np.abs(H[..., 4, :] * y) + np.abs(H[..., 5, :])
+        sz = np.abs(H[..., 6, :] * x) + np.abs(H[..., 7, :] * y) + np.abs(H[..., 8, :])
+        au, av = np.abs(u)[:, None], np.abs(v)[:, None]
+        d = np.sqrt(squared_error(pf, hyp)[0])
+        slack = (2 * eps * (sx + sy + (au + av) * sz) + 2 * eps * sz * d) / np.abs(qz) + eps * (au + av) + 4 * eps * d
+        return d, slack, np.abs(qz) / (2 * eps * sz), qz > 0
+
+
 def counts(pf, hyp, valid, thr=THR):
     """-> count [B,K] (-1 invalid), border [B,K]: pixels whose squared error lies within a relative 1e-4 of thr^2."""
     e, ok = squared_error(pf, hyp)
@@ -157,29 +231,30 @@ def _hartley(p):
     return np.array([[s, 0, -s * m[0]], [0, s, -s * m[1]], [0, 0, 1.0]])
 
 
-def dlt(src, dst, h, w):
-    """Hartley-normalised DLT (smallest eigenvector of A^T A), /(H22 + 1e-8); -> (H [3,3], delta_hat [4,2])."""
+def dlt(src, dst, h, w, svd=False):
+    """Hartley-normalised DLT (smallest eigenvector of A^T A; svd: the last right singular vector of A instead, a second float64
+    formulation to measure this one's own sensitivity with), /(H22 + 1e-8); -> (H [3,3], delta_hat [4,2])."""
     T1, T2 = _hartley(src), _hartley(dst)
     a = np.concatenate([src, np.ones((len(src), 1))], 1) @ T1.T
     q = np.concatenate([dst, np.ones((len(dst), 1))], 1) @ T2.T
     z = np.zeros_like(a)
     A = np.concatenate([np.concatenate([a, z, -q[:, :1] * a], 1), np.concatenate([z, a, -q[:, 1:2] * a], 1)], 0)
-    _, vec = np.linalg.eigh(A.T @ A)
-    H = np.linalg.inv(T2) @ vec[:, 0].reshape(3, 3) @ T1
+    vec = np.linalg.svd(A)[2][-1] if svd else np.linalg.eigh(A.T @ A)[1][:, 0]
+    H = np.linalg.inv(T2) @ vec.reshape(3, 3) @ T1
     H = H / (H[2, 2] + 1e-8)
     c = np.array([[0, 0], [w, 0], [w, h], [0, h]], np.float64)
     p = np.concatenate([c, np.ones((4, 1))], 1) @ H.T
     return H, p[:, :2] / p[:, 2:] - c
 
 
-def refit(pf, mask):
+def refit(pf, mask, svd=False):
     """Least squares over the pixels of mask -> H [B,3,3], delta_hat [B,4,2]."""
     B, _, h, w = pf.shape
     x, y, u, v = _coords(pf)
     Hs, ds = [], []
     for b in range(B):
         m = mask[b].reshape(-1).astype(bool)
-        H, dh = dlt(np.stack([x[m], y[m]], 1), np.stack([u[b][m], v[b][m]], 1), h, w)
+        H, dh = dlt(np.stack([x[m], y[m]], 1), np.stack([u[b][m], v[b][m]], 1), h, w, svd)
         Hs.append(H); ds.append(dh)
     return np.stack(Hs), np.stack(ds)
 
@@ -216,6 +291,48 @@ def candidates(count, border, best):
         c = np.nonzero(count[b] + border[b] >= count[b, best[b]] - border[b, best[b]])[0]
         out.append((set(c.tolist()), bool((border[b, c] == 0).all())))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def field_case(i):
+    """FIELD_CASES[i]: its inputs and the restatement's results on them.  Computed once per process; nobody writes into it."""
+    B, K, h, w, thr = FIELD_CASES[i]
+    pf, choice, delta, clean = make_field_inputs(B, K, h, w, *FIELD_SEEDS[i])
+    r = ransac_reference(pf, choice, thr)
+    r.update(pf=pf, choice=choice, delta=delta, clean=clean, thr=thr)
+    return r
+
+
+@functools.lru_cache(maxsize=None)
+def tie_case(i):
+    """The exact field of FIELD_CASES[i], where every valid hypothesis counts h*w: the first three draws of every sample are made
+    invalid (a repeated index), and a copy of the first valid draw is appended as hypothesis K - so the winner is pinned by the
+    lowest-k rule alone, at a k >= 3, against an identical hypothesis in another lane of the selection kernel."""
+    B, K, h, w, thr = FIELD_CASES[i]
+    _, choice, delta, clean = make_field_inputs(B, K, h, w, *FIELD_SEEDS[i])
+    choice = choice.copy()
+    choice[:, :3] = [1, 1, 2, h * w - 1]
+    _, valid = hypotheses(clean, choice)
+    first = np.argmax(valid, 1)
+    choice = np.concatenate([choice, choice[np.arange(B), first][:, None]], 1)
+    r = ransac_reference(clean, choice, thr)
+    r.update(pf=clean, choice=choice, delta=delta, thr=thr, first=first)
+    return r
+
+
+WILD_B, WILD_K, WILD_SEED, WILD_CHOICE_SEED = 4, 6, 32, 33
+
+
+@functools.lru_cache(maxsize=None)
+def wild_case():
+    """A field without structure (uniform +-64 px) under a 0.05 px threshold: a valid hypothesis explains its own four points, if
+    it keeps them in front (qz > 0), and nothing else - counts of 0 to 4, the boundary of the fallback rule n_inl = count >= 4 ?"""
+    pf = np.random.default_rng(WILD_SEED).uniform(-64.0, 64.0, (WILD_B, 2, WILD_H, WILD_W)).astype(np.float32)
+    choice = torch.randint(0, WILD_H * WILD_W, (WILD_B, WILD_K, 4), generator=torch.Generator().manual_seed(WILD_CHOICE_SEED)).numpy()
+    choice = choice.astype(np.int64)
+    r = ransac_reference(pf, choice, WILD_THR)
+    r.update(pf=pf, choice=choice, thr=WILD_THR)
+    return r
 
 
 @pytest.fixture(scope="module")
@@ -324,3 +441,91 @@ def test_restatement_invalid_and_fallback_cases():
     deg = np.tile(np.array([3, 3, 7, 9], np.int64), (2, 4, 1))
     r = ransac_reference(pf, deg)
     assert (r["n_inl"] == 0).all() and (r["mask"] == 1).all() and np.isfinite(r["H"]).all()
+
+
+# ------------------------------------------------------------------------------------------------
+# the other shapes (FIELD_CASES), the tie and the fallback boundary: conditions of tests/test_ransac_gpu.py, on the restatement alone
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("i", range(len(FIELD_CASES)))
+def test_conditions_at_the_other_shapes(i):
+    """Per case: few border pixels (the cap of the 128 x 128 test), EVERY sample's candidate set exact - so the GPU's winner is pinned
+    for every sample -, both valid and invalid hypotheses, and on the exact field every valid hypothesis counts h*w with no border
+    pixel.  Also printed: what the refit's float64 formulation itself is good for (eigh of A^T A against the SVD of A on the same
+    masks) - at most 2.3e-10 px in delta_hat and a relative 2e-8 in H (the sign of H22 + 1e-8) when the test was written, far inside
+    the bands the GPU comparison uses (2e-5 px scaled by max(h, w) / 128; rtol 1e-5), which therefore stand as they are."""
+    B, K, h, w, thr = FIELD_CASES[i]
+    r = field_case(i)
+    n = h * w
+    assert r["pf"].shape == (B, 2, h, w) and r["pf"].dtype == np.float32 and r["choice"].shape == (B, K, 4)
+    cand = candidates(r["count"], r["border"], r["best"])
+    share = r["valid"].mean()
+    print("case %d %s: border pixels %d (cap %.0f), valid %.0f %%, best %s n_inl %s, candidates %s exact %s" %
+          (i, FIELD_CASES[i], r["border"].sum(), 1e-3 * B * K * n, 100 * share, r["best"], r["n_inl"], [len(c) for c, _ in cand],
+           [e for _, e in cand]))
+    assert r["border"].sum() <= 1e-3 * B * K * n
+    assert all(exact for _, exact in cand)
+    assert r["valid"].any() and (~r["valid"]).any() and (r["count"][~r["valid"]] == -1).all()
+    assert (r["n_inl"] >= 4).all() and (r["mask"].reshape(B, -1).sum(1) == r["n_inl"]).all()
+    hyp, valid = hypotheses(r["clean"], r["choice"])
+    count, border = counts(r["clean"], hyp, valid, thr)
+    assert (count[valid] == n).all() and (count[~valid] == -1).all() and border.sum() == 0
+    Hs, ds = refit(r["pf"], r["mask"], svd=True)
+    print("case %d: refit, eigh of A^T A against SVD of A: max |delta_hat| difference %.3e px, max relative |H| difference %.3e; "
+          "max |delta_hat| %.1f px, MACE %s" % (i, np.abs(ds - r["delta_hat"]).max(), (np.abs(Hs - r["H"]) / np.abs(r["H"])).max(),
+                                                np.abs(r["delta_hat"]).max(), mace(r["delta_hat"], r["delta"])))
+    assert np.abs(ds - r["delta_hat"]).max() <= 2e-6 * max(1.0, max(h, w) / 128.0)        # a tenth of the band: it needs no widening
+
+
+def test_some_first_valid_hypothesis_is_not_the_first():
+    first = [np.argmax(field_case(i)["valid"], 1) for i in range(len(FIELD_CASES))]
+    print("first valid hypothesis per case and sample:", first)
+    assert any((f > 0).any() for f in first)
+
+
+@pytest.mark.parametrize("i", TIE_CASES)
+def test_conditions_of_the_tie(i):
+    B, K, h, w, thr = FIELD_CASES[i]
+    r = tie_case(i)
+    first = r["first"]
+    print("tie on case %d: first valid hypothesis %s, its copy at k = %d (lane %d)" % (i, first, K, K % 64))
+    assert r["choice"].shape == (B, K + 1, 4) and not r["valid"][:, :3].any()
+    assert (first >= 3).all() and r["valid"][np.arange(B), first].all() and not any(r["valid"][b, :first[b]].any() for b in range(B))
+    assert K >= 64 and (first % 64 != K % 64).all()                          # the copy sits in another lane of the selection
+    assert np.array_equal(r["choice"][:, K], r["choice"][np.arange(B), first])
+    assert np.array_equal(r["hyp"][:, K], r["hyp"][np.arange(B), first])
+    assert (r["count"][r["valid"]] == h * w).all() and r["border"].sum() == 0 and (~r["valid"]).sum() > 3 * B
+    assert np.array_equal(r["best"], first) and (r["n_inl"] == h * w).all()
+
+
+def test_conditions_of_the_fallback_boundary():
+    """The field without structure: a pixel is either within 0.1 thr (a draw's own points, off only by the fp32 rounding of the nine
+    coefficients) or beyond 2 thr.  Offsets of +-64 px against a threshold of 0.05 px, and hypotheses with a horizon inside the field,
+    are beyond what the relative 1e-4 of `border` was made for, so the distance of every decision from the threshold, and of every qz
+    from 0, is held here to 10x a bound on the error of the kernel's fp32 evaluation (fp32_margins): fp32 must count what the
+    restatement counts.  Some sample's best count is exactly 4, and some sample has valid hypotheses but none with 4 inliers."""
+    r = wild_case()
+    v = r["valid"]
+    d, slack, horizon, front = fp32_margins(r["pf"], r["hyp"])
+    d, slack, horizon, front = d[v], slack[v], horizon[v], front[v]
+    near = d <= 2 * WILD_THR
+    top = r["count"].max(1)
+    room = (np.abs(d - WILD_THR) / slack)[front]
+    print("wild field: counts of the valid hypotheses %s; best %s with counts %s; largest error below the threshold %.2e px, smallest "
+          "above %.3f px; smallest |d - thr| / (fp32 error bound) %.1f, smallest |qz| / (its fp32 error bound) %.1f" %
+          (np.bincount(r["count"][v], minlength=5), r["best"], top, d[near].max(), d[~near & np.isfinite(d)].min(),
+           room.min(), horizon.min()))
+    assert r["border"].sum() == 0 and r["count"][v].max() == 4 and r["count"][v].min() < 4
+    assert d[near].max() <= 0.1 * WILD_THR
+    assert horizon.min() >= 10.0 and room.min() >= 10.0
+    a, b = np.nonzero(top == 4)[0], np.nonzero((top >= 0) & (top < 4))[0]
+    assert len(a) and len(b)
+    assert (r["n_inl"][a] == 4).all() and (r["n_inl"][b] == 0).all() and (r["mask"][b] == 1).all()
+    assert (r["best"][b] > 0).any() and (r["best"][a] > 0).any()
+    for s in a:                                                              # the four inliers are the draw's own points
+        assert np.array_equal(np.nonzero(r["mask"][s].reshape(-1))[0], np.sort(r["choice"][s, r["best"][s]]))
+    assert np.isfinite(r["H"]).all() and np.isfinite(r["delta_hat"]).all()
+    Hs, ds = refit(r["pf"], r["mask"], svd=True)
+    rel = np.abs(ds - r["delta_hat"]).reshape(WILD_B, -1).max(1) / (np.abs(r["delta_hat"]).reshape(WILD_B, -1).max(1) + max(WILD_H, WILD_W))
+    print("wild field: refit, eigh against SVD: |delta_hat| difference relative to the corner coordinate %s; max |delta_hat| %s" %
+          (rel, np.abs(r["delta_hat"]).reshape(WILD_B, -1).max(1)))
+    assert (rel <= 2e-5 / 128 / 10).all()

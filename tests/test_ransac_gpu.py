@@ -3,7 +3,10 @@ noise, a 30 % block of wrong offsets, 5 % scattered outliers; B = 6, K = 128, se
 
 Integer results are compared as integers.  fp32 and float64 can only decide a pixel differently where its float64 squared error lies
 within a relative 1e-4 of thr^2 ("border" pixels; the fp32 test's own rounding is ~1e-6 of thr^2), so counts may differ by at most the
-number of border pixels of that hypothesis, and where no candidate winner has a border pixel the winner is pinned exactly."""
+number of border pixels of that hypothesis, and where no candidate winner has a border pixel the winner is pinned exactly.
+
+The same comparison runs at the shapes of R.FIELD_CASES - fields of 35 to 3071 pixels that are no multiple of any tile, K up to 2100 -
+and on two constructed inputs: a tie that only the lowest-k rule decides, and a best count of exactly 4 / below 4."""
 import os
 import sys
 
@@ -107,7 +110,126 @@ def test_exact_field_agrees_with_the_lattice_path(K, case):
     assert np.array_equal(count == -1, ~valid)
     assert (count[valid] == h * w).all()
     assert (n_inl.cpu().numpy() == h * w).all()
+    assert np.array_equal(best.cpu().numpy(), np.argmax(valid, 1))      # every valid hypothesis ties: the first one wins
     assert np.abs(dh.cpu().numpy() - case["delta"]).max() / np.abs(case["delta"]).max() < 1e-3
+
+
+# ------------------------------------------------------------------------------------------------
+# the other shapes: R.FIELD_CASES (what each reaches is said there; their conditions are asserted in tests/test_ransac_cpu.py)
+# ------------------------------------------------------------------------------------------------
+NAMES = ("delta_hat", "H", "best", "n_inl", "count", "mask")
+
+
+def call(K, pf, choice, thr):
+    """-> (the call's device tensors in NAMES' order, the same as numpy arrays by name)"""
+    out = K.ransac_homography(dev(pf), dev(choice, torch.int64), thr, want_mask=True)
+    torch.cuda.synchronize()
+    return out, {n: t.cpu().numpy() for n, t in zip(NAMES, out)}
+
+
+def dh_atol(h, w, reach=0.0):
+    """2e-5 px is fp32 output rounding at the 128-pixel corner coordinates of the first tests: it grows with the coordinate."""
+    return 2e-5 * max(1.0, (max(h, w) + reach) / 128.0)
+
+
+@pytest.fixture(scope="module", params=range(len(R.FIELD_CASES)), ids=["%dx%dx%dx%d" % c[:4] for c in R.FIELD_CASES])
+def field(K, request):
+    ref = R.field_case(request.param)
+    out, gpu = call(K, ref["pf"], ref["choice"], ref["thr"])
+    return dict(ref=ref, out=out, gpu=gpu)
+
+
+def test_counts_at_other_shapes(field):
+    ref, gpu = field["ref"], field["gpu"]
+    diff = np.abs(gpu["count"].astype(np.int64) - ref["count"])
+    print("border pixels %d; hypotheses whose count differs: %d, largest difference %d; invalid %d of %d"
+          % (ref["border"].sum(), (diff > 0).sum(), diff.max(), (~ref["valid"]).sum(), ref["valid"].size))
+    assert gpu["count"].dtype == np.int32 and gpu["count"].shape == ref["count"].shape
+    assert np.array_equal(gpu["count"] == -1, ~ref["valid"])
+    assert (diff <= ref["border"]).all(), np.argwhere(diff > ref["border"])
+
+
+def test_best_at_other_shapes(field):
+    """Every sample's candidate set is exact (tests/test_ransac_cpu.py): the winner is pinned for every sample."""
+    ref, gpu = field["ref"], field["gpu"]
+    B = len(ref["best"])
+    print("best gpu %s ref %s, n_inl gpu %s ref %s" % (gpu["best"], ref["best"], gpu["n_inl"], ref["n_inl"]))
+    assert gpu["best"].dtype == np.int64 and gpu["n_inl"].dtype == np.int32
+    assert np.array_equal(gpu["best"], ref["best"])
+    assert np.array_equal(gpu["n_inl"], gpu["count"][np.arange(B), gpu["best"]])
+
+
+def test_mask_at_other_shapes(field):
+    ref, gpu = field["ref"], field["gpu"]
+    B = len(ref["best"])
+    assert gpu["mask"].dtype == np.uint8 and gpu["mask"].shape == ref["mask"].shape
+    assert set(np.unique(gpu["mask"]).tolist()) <= {0, 1}
+    assert np.array_equal(gpu["mask"].reshape(B, -1).astype(np.int64).sum(1), gpu["n_inl"])
+    rmask, rborder = R.inlier_mask(ref["pf"], ref["hyp"], gpu["best"], gpu["n_inl"], ref["thr"])
+    differ = gpu["mask"] != rmask
+    print("mask pixels that differ from the restatement: %d (border pixels of the winners: %d)" % (differ.sum(), rborder.sum()))
+    assert not (differ & ~rborder).any()
+
+
+def test_refit_at_other_shapes(field):
+    """test_refit_on_the_gpus_own_mask's bands, delta_hat's scaled with the corner coordinate (dh_atol).  What the float64 yardstick
+    itself is good for at these sizes is measured in tests/test_ransac_cpu.py (test_conditions_at_the_other_shapes): 2.3e-10 px."""
+    ref, gpu = field["ref"], field["gpu"]
+    h, w = ref["pf"].shape[2:]
+    H, dh = R.refit(ref["pf"], gpu["mask"])
+    print("refit: max |H - ref| %.3e, max |delta_hat - ref| %.3e (allowed %.3e); MACE against the true offsets %s"
+          % (np.abs(gpu["H"] - H).max(), np.abs(gpu["delta_hat"] - dh).max(), dh_atol(h, w), R.mace(gpu["delta_hat"].astype(np.float64), ref["delta"])))
+    np.testing.assert_allclose(gpu["H"], H, rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(gpu["delta_hat"], dh, atol=dh_atol(h, w))
+
+
+def test_two_calls_agree_bit_for_bit_at_other_shapes(K, field):
+    again, _ = call(K, field["ref"]["pf"], field["ref"]["choice"], field["ref"]["thr"])
+    for name, a, b in zip(NAMES, field["out"], again):
+        assert torch.equal(a, b), name
+
+
+@pytest.mark.parametrize("i", R.TIE_CASES)
+def test_lowest_k_wins_a_tie_across_lanes(K, i):
+    """Exact field, the first three draws invalid, the first valid draw repeated as the last hypothesis (R.tie_case): every valid
+    hypothesis counts h*w, and the selection has to return the first of them."""
+    ref = R.tie_case(i)
+    h, w = ref["pf"].shape[2:]
+    _, gpu = call(K, ref["pf"], ref["choice"], ref["thr"])
+    print("first valid hypothesis %s, best %s" % (ref["first"], gpu["best"]))
+    assert np.array_equal(gpu["count"] == -1, ~ref["valid"])
+    assert (gpu["count"][ref["valid"]] == h * w).all()
+    assert np.array_equal(gpu["best"], ref["first"]) and (ref["first"] >= 3).all()
+    assert (gpu["n_inl"] == h * w).all() and (gpu["mask"] == 1).all()
+
+
+def test_fallback_boundary(K):
+    """R.wild_case: a best count of exactly 4 is refitted on its four points; a best count below 4, with valid hypotheses there, falls
+    back to every point.  delta_hat's band is dh_atol at the corner's own coordinate (these homographies send corners thousands of
+    pixels away; tests/test_ransac_cpu.py holds the yardstick's own sensitivity to a tenth of that band)."""
+    ref = R.wild_case()
+    pf, choice = ref["pf"], ref["choice"]
+    B, _, h, w = pf.shape
+    _, gpu = call(K, pf, choice, ref["thr"])
+    top = ref["count"].max(1)
+    a, b = np.nonzero(top == 4)[0], np.nonzero((top >= 0) & (top < 4))[0]
+    print("counts gpu %s; best %s, n_inl %s" % (gpu["count"].tolist(), gpu["best"], gpu["n_inl"]))
+    assert len(a) and len(b)
+    assert np.array_equal(gpu["count"], ref["count"])                   # no border pixel: exact
+    assert np.array_equal(gpu["best"], ref["best"])
+    assert (gpu["n_inl"][a] == 4).all() and (gpu["n_inl"][b] == 0).all()
+    for s in a:
+        assert np.array_equal(np.nonzero(gpu["mask"][s].reshape(-1))[0], np.sort(choice[s, gpu["best"][s]]))
+    assert (gpu["mask"][b] == 1).all()
+    want = np.ones((B, h, w), np.uint8)
+    want[a] = gpu["mask"][a]
+    H, dh = R.refit(pf, want)
+    assert np.isfinite(gpu["H"]).all() and np.isfinite(gpu["delta_hat"]).all()
+    np.testing.assert_allclose(gpu["H"], H, rtol=1e-5, atol=1e-6)
+    for s in range(B):
+        err, tol = np.abs(gpu["delta_hat"][s] - dh[s]).max(), dh_atol(h, w, np.abs(dh[s]).max())
+        print("sample %d (%s): max |delta_hat| %.1f, max |delta_hat - ref| %.3e (allowed %.3e)" % (s, "4 inliers" if s in a else "all points", np.abs(dh[s]).max(), err, tol))
+        assert err <= tol
 
 
 def test_fallback_when_every_hypothesis_is_invalid(K):

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_ransac_cpu import _coords, mace, make_inputs, ransac_reference  # noqa: E402
+from test_ransac_cpu import FIELD_CASES, _coords, field_case, mace, make_inputs, ransac_reference  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NOISE2_SEED, NOISE2_SIGMA = 3, 2.0
@@ -26,6 +26,28 @@ def make_noisy_inputs():
     pf, choice, delta, clean = make_inputs()
     rng = np.random.default_rng(NOISE2_SEED)
     return (pf.astype(np.float64) + rng.normal(0.0, NOISE2_SIGMA, pf.shape)).astype(np.float32), choice, delta, clean
+
+
+SHAPES = [(64, 256), (160, 136), (3, 700), (5, 7), (37, 83)]
+
+
+def make_shape_inputs(h, w, B=2):
+    """A field of any size for the polish alone: one mild homography + N(0, 1 px), a random mask of 80 %, and a start that is off by
+    a few tenths of a pixel.  -> pf [B,2,h,w] f32, mask [B,h,w] u8, start [B,3,3] f32"""
+    g = np.random.default_rng(17)
+    Ht = np.array([[1.02, 0.03, 4.0], [-0.02, 0.98, -3.0], [1e-4, -5e-5, 1.0]])
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    q = np.stack([xs, ys, np.ones_like(xs)], -1) @ Ht.T
+    field = np.stack([q[..., 0] / q[..., 2] - xs, q[..., 1] / q[..., 2] - ys])
+    pf = (field[None] + g.normal(0.0, 1.0, (B, 2, h, w))).astype(np.float32)
+    mask = (g.uniform(size=(B, h, w)) < 0.8).astype(np.uint8)
+    start = np.tile((Ht + np.array([[2e-3, -1e-3, 0.3], [1e-3, 2e-3, -0.2], [2e-6, 1e-6, 0.0]]))[None], (B, 1, 1)).astype(np.float32)
+    return pf, mask, start
+
+
+def dh_atol(h, w):
+    """The GPU comparison's band for delta_hat: 2e-5 px is fp32 output rounding at 128-pixel corner coordinates."""
+    return 2e-5 * max(1.0, max(h, w) / 128.0)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -187,6 +209,31 @@ def test_conditions_the_gpu_comparison_rests_on(sets, name, least_move):
     assert np.abs(a["delta_hat"] - z["delta_hat"]).max() <= 1e-9
     assert (moved >= least_move).all(), moved
     assert np.isfinite(a["H"]).all() and (a["H"][:, 2, 2] == 1.0).all()
+
+
+@pytest.mark.parametrize("h,w", SHAPES)
+def test_conditions_at_the_other_field_shapes(h, w):
+    """The restatement alone, on what tests/test_ransac_lm_gpu.py::test_other_field_shapes runs: the polish moves the corners by at
+    least 100x the band of that comparison (dh_atol), the cost never rises and every sample accepts a step."""
+    pf, mask, start = make_shape_inputs(h, w)
+    a, z = lm_reference(pf, start, mask, LM_ITERS), lm_reference(pf, start, mask, 0)
+    moved = np.abs(a["delta_hat"] - z["delta_hat"]).reshape(len(pf), -1).max(1)
+    print("%d x %d: corners moved by %s (100x the band: %.3e), accepted %s, cost %s -> %s" %
+          (h, w, moved, 100 * dh_atol(h, w), a["info"][:, 2], a["info"][:, 0], a["info"][:, 1]))
+    assert (moved >= 100 * dh_atol(h, w)).all()
+    assert (np.diff(a["costs"], axis=1) <= 0).all() and (a["info"][:, 2] >= 1).all()
+    assert np.isfinite(a["H"]).all() and np.isfinite(a["delta_hat"]).all()
+
+
+def test_conditions_of_the_chained_run():
+    """RANSAC then the polish on FIELD_CASES[0] (37 x 83, K = 1100), on the restatement's own mask and refit."""
+    _, _, h, w, _ = FIELD_CASES[0]
+    r = field_case(0)
+    a = lm_reference(r["pf"], r["H"], r["mask"], LM_ITERS)
+    moved = np.abs(a["delta_hat"] - r["delta_hat"]).reshape(len(a["H"]), -1).max(1)
+    print("37 x 83 after RANSAC: corners moved by", moved, "accepted", a["info"][:, 2])
+    assert (moved >= 100 * dh_atol(h, w)).all() and (a["info"][:, 2] >= 1).all()
+    assert (np.diff(a["costs"], axis=1) <= 0).all()
 
 
 def test_polish_helps_on_the_noisy_field_and_leaves_an_exact_one(sets):
