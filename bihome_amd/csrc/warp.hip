@@ -1,47 +1,12 @@
 // Fused homography warp: out(x,y) = bilinear img(H.(x,y,1)) with zero padding, plus the pooled
-// in-bounds coverage of the same map (= AvgPool(warp(ones))), and the adjoint w.r.t. H.
+// in-bounds coverage of the same map (= AvgPool(warp(ones))), and the adjoints w.r.t. H and w.r.t. the image.
 // HBM-bound: 8 B per pixel per channel (one gathered read, one coalesced write).
-// Tile = 16x16 output pixels per 256-thread block; a wavefront owns a 16x4 strip, i.e. exactly one
+// Every kernel here takes its per-pixel tap - coordinates, validity, weights, offsets - from make_tap4 (warp_tap.h) and gathers through
+// the tap's offsets, so the kernels of every pooling size, forward and adjoint, see bitwise the same taps.
+// Generic kernels: tile = 16x16 output pixels per 256-thread block; a wavefront owns a 16x4 strip, i.e. exactly one
 // row of pooling windows for pool=4, so the pooled coverage is a pure in-wave shuffle reduction.
 #include "common.h"
 #include "warp_tap.h"
-
-struct Tap {
-    float x0f, y0f, fx, fy;
-    bool vx0, vx1, vy0, vy1;
-};
-
-__device__ __forceinline__ void project(const double* __restrict__ Hm, int x, int y, float& u, float& v, float& iz,
-                                        bool& guard) {
-    // same arithmetic order as transform_points on the pixel grid, in float like grid_sample's input
-    float fx = (float)x, fy = (float)y;
-    float h0 = (float)Hm[0], h1 = (float)Hm[1], h2 = (float)Hm[2], h3 = (float)Hm[3], h4 = (float)Hm[4],
-          h5 = (float)Hm[5], h6 = (float)Hm[6], h7 = (float)Hm[7], h8 = (float)Hm[8];
-    // (the coordinate arithmetic of warp_tap.h make_tap4, spelled the same way: the kernels of every pooling size agree bitwise on where a
-    //  pixel lands - and so on which side of an integer coordinate, where the bilinear derivative jumps)
-    float qx = __builtin_fmaf(h0, fx, __builtin_fmaf(h1, fy, h2)), qy = __builtin_fmaf(h3, fx, __builtin_fmaf(h4, fy, h5)),
-          qz = __builtin_fmaf(h6, fx, __builtin_fmaf(h7, fy, h8));
-    guard = !(fabsf(qz) > 1e-8f);
-    float r = __builtin_amdgcn_rcpf(qz);
-    r = __builtin_fmaf(__builtin_fmaf(-qz, r, 1.0f), r, r);
-    iz = guard ? 1.0f : r;
-    u = qx * iz;
-    v = qy * iz;
-}
-
-__device__ __forceinline__ Tap make_tap(float u, float v, int w, int h) {
-    Tap t;
-    t.x0f = floorf(u);
-    t.y0f = floorf(v);
-    t.fx = u - t.x0f;
-    t.fy = v - t.y0f;
-    // comparisons in float so that wild coordinates (inf/nan/huge) are simply out of bounds
-    t.vx0 = (t.x0f >= 0.0f) && (t.x0f <= (float)(w - 1));
-    t.vx1 = (t.x0f >= -1.0f) && (t.x0f <= (float)(w - 2));
-    t.vy0 = (t.y0f >= 0.0f) && (t.y0f <= (float)(h - 1));
-    t.vy1 = (t.y0f >= -1.0f) && (t.y0f <= (float)(h - 2));
-    return t;
-}
 
 // sum over a pool x pool window held by lanes of one wave laid out 16 wide x 4 tall (lane = ty*16+tx)
 __device__ __forceinline__ float window_sum_16x4(float v, int pool) {
@@ -59,26 +24,18 @@ __global__ void __launch_bounds__(256) warp_fwd_kernel(const float* __restrict__
     const int b = blockIdx.z;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int x = blockIdx.x * 16 + tx, y = blockIdx.y * 16 + ty;
-    float u, v, iz;
-    bool guard;
-    project(H64 + (size_t)b * 9, x, y, u, v, iz, guard);
-    Tap t = make_tap(u, v, w, h);
-    const int x0 = (int)fminf(fmaxf(t.x0f, -2.0f), (float)w), y0 = (int)fminf(fmaxf(t.y0f, -2.0f), (float)h);
-    const float w00 = (1 - t.fx) * (1 - t.fy), w01 = t.fx * (1 - t.fy), w10 = (1 - t.fx) * t.fy, w11 = t.fx * t.fy;
-    const bool v00 = t.vx0 && t.vy0, v01 = t.vx1 && t.vy0, v10 = t.vx0 && t.vy1, v11 = t.vx1 && t.vy1;
+    const unsigned plane = (unsigned)h * (unsigned)w;
+    const Tap4 t = make_tap4(load_h(H64 + (size_t)b * 9), x, y, w, h);
+    float w00, w01, w10, w11, cv;      // cv: the warped all-ones mask at this pixel
+    tap_weights(t, w00, w01, w10, w11, cv);
     if (img) {
         for (int c = 0; c < C; ++c) {
-            const float* p = img + ((size_t)b * C + c) * h * w;
-            float acc = 0.0f;
-            if (v00) acc += p[y0 * w + x0] * w00;
-            if (v01) acc += p[y0 * w + x0 + 1] * w01;
-            if (v10) acc += p[(y0 + 1) * w + x0] * w10;
-            if (v11) acc += p[(y0 + 1) * w + x0 + 1] * w11;
-            out[((size_t)b * C + c) * h * w + (size_t)y * w + x] = acc;
+            const __amdgpu_buffer_rsrc_t rs = plane_rsrc(img + ((size_t)b * C + c) * plane, plane * 4u);
+            out[((size_t)b * C + c) * plane + (unsigned)y * (unsigned)w + x] =
+                tap_blend(ldtap(rs, t.o00), ldtap(rs, t.o01), ldtap(rs, t.o10), ldtap(rs, t.o11), w00, w01, w10, w11);
         }
     }
     if (cov) {
-        float cv = (v00 ? w00 : 0.0f) + (v01 ? w01 : 0.0f) + (v10 ? w10 : 0.0f) + (v11 ? w11 : 0.0f);
         const int pw = w / pool;
         if (pool <= 4) {
             float s = window_sum_16x4(cv, pool);
@@ -115,16 +72,12 @@ __global__ void __launch_bounds__(256) warp_cov32_kernel(const double* __restric
     __shared__ float part[4];
     const int b = blockIdx.z;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const Hf H = load_h(H64 + (size_t)b * 9);
     float tot = 0.0f;
     for (int q = 0; q < 4; ++q) {
         const int x = blockIdx.x * 32 + (q & 1) * 16 + tx, y = blockIdx.y * 32 + (q >> 1) * 16 + ty;
-        float u, v, iz;
-        bool guard;
-        project(H64 + (size_t)b * 9, x, y, u, v, iz, guard);
-        const Tap t = make_tap(u, v, w, h);
-        const float w00 = (1 - t.fx) * (1 - t.fy), w01 = t.fx * (1 - t.fy), w10 = (1 - t.fx) * t.fy, w11 = t.fx * t.fy;
-        const bool v00 = t.vx0 && t.vy0, v01 = t.vx1 && t.vy0, v10 = t.vx0 && t.vy1, v11 = t.vx1 && t.vy1;
-        const float cv = (v00 ? w00 : 0.0f) + (v01 ? w01 : 0.0f) + (v10 ? w10 : 0.0f) + (v11 ? w11 : 0.0f);
+        float w00, w01, w10, w11, cv;
+        tap_weights(make_tap4(H, x, y, w, h), w00, w01, w10, w11, cv);
         const float s = window_sum_16x4(cv, 16);           // the 16 x 4 strip of this wave
         __syncthreads();
         if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
@@ -141,43 +94,40 @@ __global__ void __launch_bounds__(256) warp_bwd_kernel(const float* __restrict__
     __shared__ double part[4][9];
     const int b = blockIdx.z;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const Hf H = load_h(H64 + (size_t)b * 9);
+    const unsigned plane = (unsigned)h * (unsigned)w;
     double acc9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // (deterministic mode: grid (1, 1, B) - one workgroup walks every tile of its sample and is the only writer of gH[b])
     for (int by = blockIdx.y; by < h / 16; by += gridDim.y)
     for (int bx = blockIdx.x; bx < w / 16; bx += gridDim.x) {
     const int x = bx * 16 + tx, y = by * 16 + ty;
-    float u, v, iz;
-    bool guard;
-    project(H64 + (size_t)b * 9, x, y, u, v, iz, guard);
-    Tap t = make_tap(u, v, w, h);
-    const int x0 = (int)fminf(fmaxf(t.x0f, -2.0f), (float)w), y0 = (int)fminf(fmaxf(t.y0f, -2.0f), (float)h);
-    const bool v00 = t.vx0 && t.vy0, v01 = t.vx1 && t.vy0, v10 = t.vx0 && t.vy1, v11 = t.vx1 && t.vy1;
-    // d(bilinear)/du = sum_taps val * d(weight)/du, out-of-bounds taps contribute nothing (grid_sampler_2d_backward)
+    const Tap4 t = make_tap4(H, x, y, w, h);
     float gu = 0.0f, gv = 0.0f;
+    if (g_cov) {
+        // coverage part: d/du of sum(valid taps' weights) = (vx1 - vx0) * (wy0 + wy1), same for v
+        const float gc = g_cov[(size_t)b * (h / pool) * (w / pool) + (size_t)(y / pool) * (w / pool) + x / pool] / (float)(pool * pool);
+        const float sy = t.wy0 + t.wy1, sx = t.wx0 + t.wx1;
+        gu = gc * ((t.vx1 ? sy : 0.0f) - (t.vx0 ? sy : 0.0f));
+        gv = gc * ((t.vy1 ? sx : 0.0f) - (t.vy0 ? sx : 0.0f));
+    }
     if (img && g_out) {
         for (int c = 0; c < C; ++c) {
-            const float* p = img + ((size_t)b * C + c) * h * w;
-            float go = g_out[((size_t)b * C + c) * h * w + (size_t)y * w + x];
-            float p00 = v00 ? p[y0 * w + x0] : 0.0f, p01 = v01 ? p[y0 * w + x0 + 1] : 0.0f;
-            float p10 = v10 ? p[(y0 + 1) * w + x0] : 0.0f, p11 = v11 ? p[(y0 + 1) * w + x0 + 1] : 0.0f;
-            gu += go * ((p01 - p00) * (1 - t.fy) + (p11 - p10) * t.fy);
-            gv += go * ((p10 - p00) * (1 - t.fx) + (p11 - p01) * t.fx);
+            const __amdgpu_buffer_rsrc_t rs = plane_rsrc(img + ((size_t)b * C + c) * plane, plane * 4u);
+            const float go = g_out[((size_t)b * C + c) * plane + (unsigned)y * (unsigned)w + x];
+            // taps outside the image load 0: they contribute nothing (grid_sampler_2d_backward)
+            const float p00 = ldtap(rs, t.o00), p01 = ldtap(rs, t.o01), p10 = ldtap(rs, t.o10), p11 = ldtap(rs, t.o11);
+            // d(bilinear)/du = sum_taps val * d(weight)/du; the per-axis weights are 0 on rows / columns outside
+            gu += go * ((p01 - p00) * t.wy0 + (p11 - p10) * t.wy1);
+            gv += go * ((p10 - p00) * t.wx0 + (p11 - p01) * t.wx1);
         }
-    }
-    if (g_cov) {
-        float gc = g_cov[(size_t)b * (h / pool) * (w / pool) + (size_t)(y / pool) * (w / pool) + x / pool] /
-                   (float)(pool * pool);
-        float o00 = v00 ? 1.0f : 0.0f, o01 = v01 ? 1.0f : 0.0f, o10 = v10 ? 1.0f : 0.0f, o11 = v11 ? 1.0f : 0.0f;
-        gu += gc * ((o01 - o00) * (1 - t.fy) + (o11 - o10) * t.fy);
-        gv += gc * ((o10 - o00) * (1 - t.fx) + (o11 - o01) * t.fx);
     }
     // u = qx*iz, v = qy*iz, iz = 1/qz (or 1 under the guard)
     double s[9];
     {
-    const double fx = (double)x, fy = (double)y, dgu = (double)gu, dgv = (double)gv, diz = (double)iz;
+    const double fx = (double)x, fy = (double)y, dgu = (double)gu, dgv = (double)gv, diz = (double)t.iz;
     s[0] = dgu * diz * fx; s[1] = dgu * diz * fy; s[2] = dgu * diz;
     s[3] = dgv * diz * fx; s[4] = dgv * diz * fy; s[5] = dgv * diz;
-    double gz = guard ? 0.0 : -(dgu * (double)u + dgv * (double)v) * diz;
+    double gz = t.guard ? 0.0 : -(dgu * (double)t.u + dgv * (double)t.v) * diz;
     s[6] = gz * fx; s[7] = gz * fy; s[8] = gz;
     }
 #pragma unroll
@@ -203,8 +153,8 @@ __global__ void __launch_bounds__(256) warp_bwd_kernel(const float* __restrict__
 //   * four consecutive pixels of a row per thread and RPT rows per thread: the output is one 16-byte store per lane,
 //     a thread's four pixels are one pooling-window row (the pooled coverage needs two shuffles over the wave's four
 //     rows), and the adjoint's nine double sums are reduced across the wave once per 4*RPT pixels;
-//   * taps clamped into the image with the validity folded into per-axis weights (w00 = wx0 * wy0, products with an
-//     exact 0 or 1 - same values as masking), unsigned 32-bit indexing, 1/qz as v_rcp_f32 + one Newton step;
+//   * the tap's validity is folded into per-axis weights (w00 = wx0 * wy0, products with an exact 0 or 1 - same values as
+//     masking) and into out-of-range buffer offsets, unsigned 32-bit indexing, 1/qz as v_rcp_f32 + one Newton step;
 //   * adjoint: per row sum(a) and sum(a * x) are accumulated and multiplied by y once per row.
 // grid (w/64, h/(16*RPT), B), block 256 = 16 (x quads) x 16 (rows); a wave = 16 quads x 4 rows; row r of a thread is
 // y = (blockIdx.y * RPT + r) * 16 + ty.
@@ -327,8 +277,8 @@ __global__ void __launch_bounds__(256) warp_bwd4_kernel(const float* __restrict_
 // ---------------------------------------------------------------------------------------------
 // adjoint w.r.t. the IMAGE (round 4: the trained masks of the Zhang baseline are warped - src/heads/TripletHead.py:60,69 - and their
 // gradient has to reach the mask predictor): g_img[b,c,tap] += g_out[b,c,y,x] * bilinear weight, the transpose of warp_fwd_kernel's
-// gather with the same taps, weights and validity.  A scatter with float atomics into the caller-zeroed g_img; a deterministic call adds
-// into integer-limb entries (common.h) and a second kernel rounds them to float.  grid (w/16, h/16, B)
+// gather: the same make_tap4, its weights, and the elements its offsets name.  A scatter with float atomics into the caller-zeroed g_img;
+// a deterministic call adds into integer-limb entries (common.h) and a second kernel rounds them to float.  grid (w/16, h/16, B)
 // ---------------------------------------------------------------------------------------------
 template <bool DET>
 __global__ void __launch_bounds__(256) warp_bwd_img_kernel(const double* __restrict__ H64, const float* __restrict__ g_out, int C, int h, int w,
@@ -336,25 +286,23 @@ __global__ void __launch_bounds__(256) warp_bwd_img_kernel(const double* __restr
     const int b = blockIdx.z;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     const int x = blockIdx.x * 16 + tx, y = blockIdx.y * 16 + ty;
-    float u, v, iz;
-    bool guard;
-    project(H64 + (size_t)b * 9, x, y, u, v, iz, guard);
-    Tap t = make_tap(u, v, w, h);
-    const int x0 = (int)fminf(fmaxf(t.x0f, -2.0f), (float)w), y0 = (int)fminf(fmaxf(t.y0f, -2.0f), (float)h);
-    const float w00 = (1 - t.fx) * (1 - t.fy), w01 = t.fx * (1 - t.fy), w10 = (1 - t.fx) * t.fy, w11 = t.fx * t.fy;
-    const bool v00 = t.vx0 && t.vy0, v01 = t.vx1 && t.vy0, v10 = t.vx0 && t.vy1, v11 = t.vx1 && t.vy1;
+    const Tap4 t = make_tap4(load_h(H64 + (size_t)b * 9), x, y, w, h);
+    float w00, w01, w10, w11, ws_;
+    tap_weights(t, w00, w01, w10, w11, ws_);
     for (int c = 0; c < C; ++c) {
         const size_t base = ((size_t)b * C + c) * h * w;
         const float g = g_out[base + (size_t)y * w + x];
         if (g == 0.0f) continue;
-        auto add = [&](size_t idx, float val) {
-            if constexpr (DET) bh_det_add(entries + idx * BH_ACC_WORDS, (double)val);
-            else atomicAdd(g_img + idx, val);
+        // (the element a tap's byte offset names; a tap outside the image has no element)
+        auto add = [&](unsigned off, float val) {
+            if (off == TAP_OUTSIDE) return;
+            if constexpr (DET) bh_det_add(entries + (base + off / 4) * BH_ACC_WORDS, (double)val);
+            else atomicAdd(g_img + base + off / 4, val);
         };
-        if (v00) add(base + (size_t)y0 * w + x0, g * w00);
-        if (v01) add(base + (size_t)y0 * w + x0 + 1, g * w01);
-        if (v10) add(base + (size_t)(y0 + 1) * w + x0, g * w10);
-        if (v11) add(base + (size_t)(y0 + 1) * w + x0 + 1, g * w11);
+        add(t.o00, g * w00);
+        add(t.o01, g * w01);
+        add(t.o10, g * w10);
+        add(t.o11, g * w11);
     }
 }
 
@@ -372,12 +320,19 @@ void bh_warp_tune(int which, int n) {
 }
 #endif
 
+// what the warp kernels take: whole 16 x 16 tiles, whole pooling windows of a size the coverage reductions know, and a plane whose byte
+// offsets fit the tap's 32 bits
+static bool warp_shape_ok(int h, int w, int pool) {
+    return !(h % 16) && !(w % 16) && (pool == 1 || pool == 2 || pool == 4 || pool == 8 || pool == 16 || pool == 32) && !(h % pool) && !(w % pool) &&
+           (long long)h * w < (1ll << 30);
+}
+
 extern "C" {
 
 int bh_warp_fwd(const float* img, const double* H64, int B, int C, int h, int w, int pool, float* out, float* cov,
                 int flags, void* stream) {
     if (!H64 || B < 0 || (img && !out) || (!img && !cov)) return BH_E_BADARG;
-    if ((h % 16) || (w % 16) || (pool != 1 && pool != 2 && pool != 4 && pool != 8 && pool != 16 && pool != 32) || (h % pool) || (w % pool)) return BH_E_UNSUPPORTED;
+    if (!warp_shape_ok(h, w, pool)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
     if (pool == 4 && (w % 64) == 0) {
         const int rpt = (g_warp_rpt_fwd == 2 && h % 32 == 0) ? 2 : 1;
@@ -406,7 +361,7 @@ int bh_warp_fwd(const float* img, const double* H64, int B, int C, int h, int w,
 int bh_warp_bwd(const float* img, const double* H64, const float* g_out, const float* g_cov, int B, int C, int h, int w,
                 int pool, double* gH, int flags, void* stream) {
     if (!H64 || !gH || B < 0 || (g_out && !img)) return BH_E_BADARG;
-    if ((h % 16) || (w % 16) || (pool != 1 && pool != 2 && pool != 4 && pool != 8 && pool != 16 && pool != 32) || (h % pool) || (w % pool)) return BH_E_UNSUPPORTED;
+    if (!warp_shape_ok(h, w, pool)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
     if (pool == 4 && (w % 64) == 0) {
         int rpt = g_warp_rpt_bwd;
@@ -432,7 +387,7 @@ size_t bh_warp_bwd_img_scratch_doubles(int B, int C, int h, int w, int flags) {
 int bh_warp_bwd_img(const double* H64, const float* g_out, int B, int C, int h, int w, float* g_img, double* scratch, int flags,
                     void* stream) {
     if (!H64 || !g_out || !g_img || B < 0 || C < 1 || ((flags & BH_F_DETERMINISTIC) && !scratch)) return BH_E_BADARG;
-    if ((h % 16) || (w % 16)) return BH_E_UNSUPPORTED;
+    if (!warp_shape_ok(h, w, 1)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
     hipStream_t s = bh_stream(stream);
     const size_t n = (size_t)B * C * h * w;

@@ -634,6 +634,8 @@ def test_c_abi_error_codes(K):
     assert lib.bh_warp_fwd(P(img.data_ptr()), P(H.data_ptr()), 1, 1, 24, 24, 4, P(img.data_ptr()), None, 0, s) == -2
     with pytest.raises(BihomeLibError, match="BH_E_UNSUPPORTED"):
         K.warp_fwd(img, H)
+    # a plane of 2^30 pixels: its byte offsets no longer fit the tap's 32 bits (B = 0: nothing would be launched either way)
+    assert lib.bh_warp_fwd(P(img.data_ptr()), P(H.data_ptr()), 0, 1, 32768, 32768, 4, P(img.data_ptr()), None, 0, s) == -2
     with pytest.raises(RuntimeError, match="no CPU"):
         K.conv_fwd(x.cpu(), w, None, d)
 
