@@ -69,6 +69,10 @@ SIGNATURES = {
     "bh_bihome_loss_bwd": [P] * 14 + [c_int, c_int, c_int, c_float] + [P] * 6 + [P],
     "bh_oneline_loss_fwd": [P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, P, P, P, P, P, c_int, P],
     "bh_oneline_loss_bwd": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P],
+    "bh_oneline_cos_loss_fwd": [P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, P, P, P, P, P, c_int, P],
+    "bh_oneline_cos_loss_bwd": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P],
+    "bh_triplet_hinge_fwd": [P] * 8 + [c_int, c_int, c_int, c_float, P, P, P, c_int, P],
+    "bh_triplet_hinge_bwd": [P] * 14 + [c_int, c_int, c_int, c_float, c_float] + [P] * 6 + [P],
     "bh_zhang_triplet_fwd": [P] * 8 + [c_int, c_int, c_float, c_int, P, P, P, P],
     "bh_zhang_triplet_bwd": [P] * 12 + [c_int, c_int, c_int] + [P] * 8 + [P],
     "bh_warp_bwd_img": [P, P, c_int, c_int, c_int, c_int, P, P, c_int, P],

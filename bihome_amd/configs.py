@@ -154,6 +154,23 @@ def _ihome(base):
     return cfg
 
 
+def _ihome_cos(base):
+    """iHomE on cosine distances (PerceptualHead.py:485-499): `_ihome` with TRIPLET_DISTANCE 'cosine'.  No yaml for it ships upstream
+    (the distance is one of the paper's ablation axes); the kwargs follow the biHomE configs."""
+    cfg = _ihome(base)
+    cfg["MODEL"]["HEAD"]["TRIPLET_DISTANCE"] = "cosine"
+    return cfg
+
+
+def _bihome_aware(base):
+    """biHomE with the hinge inside the channel sum (PerceptualHead.py:624-625,644-645): TRIPLET_AGGREGATION 'channel-aware' and a
+    numeric TRIPLET_MARGIN.  No yaml for it ships upstream (the aggregation and the margin are ablation axes of the paper); everything
+    else as in the biHomE configs."""
+    cfg = copy.deepcopy(base)
+    cfg["MODEL"]["HEAD"].update(TRIPLET_AGGREGATION="channel-aware", TRIPLET_MARGIN=1.0)
+    return cfg
+
+
 def _multihead(base):
     """multihead_resnet_loss variant (PerceptualHead.py:230-235,245-315): TRIPLET_LOSS '' - the head returns the extractor
     features of patch_2 and of the warped patch_1 and the driver applies a torch loss to them (train.py:318-322).  No
@@ -170,7 +187,8 @@ def get(name):
     only in HomographyNetPrep's photometric max_delta, 0 vs 32, and the log dir).  'zeng-bihome-rgb256' is the
     build-side extension BASELINE.json configs[4] names (256x256 RGB patches, 6-channel stem; no upstream
     counterpart - SURVEY.md 0).  'nguyen-orig' = config/s-coco/nguyen-orig-lr-5e-3.yaml (PhotometricHead); 'nguyen-orig-pds' =
-    config/pds-coco/nguyen-orig-lr-5e-3.yaml, which upstream made a different experiment (NoOpHead + L1Loss), not a data variant."""
+    config/pds-coco/nguyen-orig-lr-5e-3.yaml, which upstream made a different experiment (NoOpHead + L1Loss), not a data variant.
+    '*-ihome', '*-multihead', '*-ihome-cos' and '*-bihome-aware' are loss-branch variants without a yaml upstream (see their builders)."""
     if name == "zeng-bihome-rgb256":
         cfg = copy.deepcopy(ZENG_BIHOME)
         cfg["MODEL"]["BACKBONE"].update(IMAGE_SIZE=256, PATCH_CHANNELS=3)
@@ -183,6 +201,10 @@ def get(name):
         return copy.deepcopy(NGUYEN_ORIG if name == "nguyen-orig" else NGUYEN_ORIG_PDS)
     if name in ("zeng-ihome", "detone-ihome"):
         return _ihome(ZENG_BIHOME if name == "zeng-ihome" else DETONE_BIHOME)
+    if name in ("zeng-ihome-cos", "detone-ihome-cos"):
+        return _ihome_cos(ZENG_BIHOME if name == "zeng-ihome-cos" else DETONE_BIHOME)
+    if name in ("zeng-bihome-aware", "detone-bihome-aware"):
+        return _bihome_aware(ZENG_BIHOME if name == "zeng-bihome-aware" else DETONE_BIHOME)
     base = name[:-4] if name.endswith("-pds") else name
     cfg = copy.deepcopy({"zeng-bihome": ZENG_BIHOME, "detone-bihome": DETONE_BIHOME, "zeng-orig": ZENG_ORIG,
                          "detone-orig": DETONE_ORIG, "zhang-orig": ZHANG_ORIG, "zhang-bihome": ZHANG_BIHOME}[base])

@@ -248,6 +248,231 @@ __global__ void __launch_bounds__(256) oneline_bwd_kernel(const float* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// one-line variant with TRIPLET_DISTANCE 'cosine' (PerceptualHead.py:485-499, hinge :505, scores :508-511):
+//   c(x, y) = x.y / (max(|x|, eps) max(|y|, eps)), eps = 1e-8 (torch.cosine_similarity: each norm clamped on its own)
+//   t = c(f1, f2) - c(f1w, f2) + margin;  loss_b = sum_p w max(t, 0) / max(sum_p w, 1),  w = m1w * m2
+// Same layout, outputs and batch sum (oneline_loss_kernel) as the L1 pair.  Five sums per pixel: two dots, three squared norms.
+// ---------------------------------------------------------------------------------------------
+#define COS_EPS 1e-8f
+__device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+__global__ void __launch_bounds__(256) oneline_cos_fwd_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
+                                                              const float* __restrict__ f1w, const float* __restrict__ m1w,
+                                                              const float* __restrict__ m2, int hw, int C, float margin, int rep,
+                                                              float* __restrict__ T, double* __restrict__ numden) {
+    __shared__ double part[4][2];
+    const int b = blockIdx.y, bs = b / rep;
+    const int LP = min(64, C / 4), PPW = 64 / LP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane / LP, cl = lane % LP;
+    const int wave_global = blockIdx.x * 4 + wave, nwaves = gridDim.x * 4;
+    double a_n = 0, a_d = 0;
+    for (int p0 = wave_global * PPW; p0 < hw; p0 += nwaves * PPW) {
+        const int p = p0 + sub;
+        float d13 = 0, d1w = 0, n1 = 0, n2 = 0, nw = 0;
+        if (p < hw) {
+            const size_t base = ((size_t)b * hw + p) * C, bases = ((size_t)bs * hw + p) * C;
+            for (int c = cl * 4; c < C; c += LP * 4) {
+                const float4 a1 = ld4(f1 + bases + c), a2 = ld4(f2 + bases + c), a1w = ld4(f1w + base + c);
+                d13 += dot4(a1, a2); d1w += dot4(a1w, a2);
+                n1 += dot4(a1, a1); n2 += dot4(a2, a2); nw += dot4(a1w, a1w);
+            }
+        }
+        for (int off = 1; off < LP; off <<= 1) {
+            d13 += __shfl_xor(d13, off, 64); d1w += __shfl_xor(d1w, off, 64);
+            n1 += __shfl_xor(n1, off, 64); n2 += __shfl_xor(n2, off, 64); nw += __shfl_xor(nw, off, 64);
+        }
+        if (p < hw && cl == 0) {
+            const size_t q = (size_t)b * hw + p;
+            const float r2 = fmaxf(sqrtf(n2), COS_EPS);
+            const float c13 = d13 / (fmaxf(sqrtf(n1), COS_EPS) * r2), c1w = d1w / (fmaxf(sqrtf(nw), COS_EPS) * r2);
+            const float t = c13 - c1w + margin;                   // (1 - c1w) - (1 - c13) + margin
+            T[q] = t;
+            const float w = m1w[q] * (m2 ? m2[(size_t)bs * hw + p] : 1.0f);
+            a_n += (double)(w * fmaxf(t, 0.0f)); a_d += (double)w;
+        }
+    }
+    a_n = wave_sum(a_n); a_d = wave_sum(a_d);
+    if (lane == 0) { part[wave][0] = a_n; part[wave][1] = a_d; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        atomicAdd(numden + (size_t)b * 2 + threadIdx.x, part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+}
+
+// adjoint: d t / d f1w = -(f2 iw i2 - c1w iw f1w / |f1w|), iw = 1 / max(|f1w|, eps), i2 = 1 / max(|f2|, eps).  torch clamps the VALUE of
+// the norm only (in place, outside autograd): its gradient f1w / |f1w| flows below eps too, and is 0 at the zero vector, which thus gets
+// f2 i2 / eps.  The three sums it needs (f1w.f2, |f1w|^2, |f2|^2) are
+// RECOMPUTED from the two maps this pass reads anyway - the forward stores nothing beyond T; the second channel loop re-reads what the
+// same wave has just loaded (cache hits, no further HBM traffic).
+__global__ void __launch_bounds__(256) oneline_cos_bwd_kernel(const float* __restrict__ g_loss, const float* __restrict__ f2,
+                                                              const float* __restrict__ f1w, const float* __restrict__ m1w,
+                                                              const float* __restrict__ m2, const float* __restrict__ T,
+                                                              const double* __restrict__ numden, int hw, int C, int rep,
+                                                              const float* __restrict__ sample_w,
+                                                              float* __restrict__ g_f1w, float* __restrict__ g_m1w) {
+    const int b = blockIdx.y, bs = b / rep;
+    const float g = g_loss[0] * (sample_w ? sample_w[b] : 1.0f);
+    const float N = (float)numden[b * 2], D = (float)numden[b * 2 + 1];
+    const float den = fmaxf(D, 1.0f);
+    const float dd = (D > 1.0f) ? -N / (den * den) : 0.0f;
+    const int LP = min(64, C / 4), PPW = 64 / LP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane / LP, cl = lane % LP;
+    const int wave_global = blockIdx.x * 4 + wave, nwaves = gridDim.x * 4;
+    for (int p0 = wave_global * PPW; p0 < hw; p0 += nwaves * PPW) {
+        const int p = p0 + sub;
+        const bool in = p < hw;                                   // (every lane takes part in the shuffles)
+        const size_t q = (size_t)b * hw + (in ? p : 0);
+        const size_t base = q * C, bases = ((size_t)bs * hw + (in ? p : 0)) * C;
+        float d1w = 0, n2 = 0, nw = 0;
+        if (in)
+            for (int c = cl * 4; c < C; c += LP * 4) {
+                const float4 a2 = ld4(f2 + bases + c), a1w = ld4(f1w + base + c);
+                d1w += dot4(a1w, a2); n2 += dot4(a2, a2); nw += dot4(a1w, a1w);
+            }
+        for (int off = 1; off < LP; off <<= 1) {
+            d1w += __shfl_xor(d1w, off, 64); n2 += __shfl_xor(n2, off, 64); nw += __shfl_xor(nw, off, 64);
+        }
+        if (!in) continue;
+        const float rw = sqrtf(nw);
+        const float iw = 1.0f / fmaxf(rw, COS_EPS), i2 = 1.0f / fmaxf(sqrtf(n2), COS_EPS);
+        const float mm2 = m2 ? m2[(size_t)bs * hw + p] : 1.0f, t = T[q];
+        const float k = (t > 0.0f) ? g * m1w[q] * mm2 / den : 0.0f;         // hinge: no gradient where it is inactive
+        const float ka = -k * iw * i2;                                       // times f2
+        const float kb = (rw > 0.0f) ? k * (d1w * iw * i2) * iw / rw : 0.0f;          // times f1w
+        for (int c = cl * 4; c < C; c += LP * 4) {
+            const float4 a2 = ld4(f2 + bases + c), a1w = ld4(f1w + base + c);
+            *reinterpret_cast<float4*>(g_f1w + base + c) =
+                make_float4(ka * a2.x + kb * a1w.x, ka * a2.y + kb * a1w.y, ka * a2.z + kb * a1w.z, ka * a2.w + kb * a1w.w);
+        }
+        if (cl == 0) g_m1w[q] = g * mm2 * (fmaxf(t, 0.0f) / den + dd);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// biHomE with a numeric margin and 'channel-aware' aggregation (PerceptualHead.py:624-625, 644-645): the hinge sits INSIDE the channel sum,
+//   M1[p] = sum_c max(|f1w_c - f2_c| - |f1_c - f2_c| + margin, 0),   M2[p] = sum_c max(|f2w_c - f1_c| - |f1_c - f2_c| + margin, 0)
+// numden and everything after it as in triplet_fwd_kernel / bihome_loss_kernel.  Kernels of their own: the default pair above keeps its
+// inner loops without a branch.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float hinge1(float w, float o, float s, float margin) { return fmaxf(fabsf(w - o) - fabsf(s - o) + margin, 0.0f); }
+__device__ __forceinline__ float hinge_4(float4 w, float4 o, float4 s, float m) {
+    return hinge1(w.x, o.x, s.x, m) + hinge1(w.y, o.y, s.y, m) + hinge1(w.z, o.z, s.z, m) + hinge1(w.w, o.w, s.w, m);
+}
+// k sgn(w - o) where the channel's hinge term is active (the forward's expression, so both passes see the same indicator)
+__device__ __forceinline__ float hinge_g(float w, float o, float s, float margin, float k) {
+    return (fabsf(w - o) - fabsf(s - o) + margin > 0.0f) ? k * sgn(w - o) : 0.0f;
+}
+
+// grid (TRIP_FWD_BLOCKS_PER_SAMPLE, B), block 256
+__global__ void __launch_bounds__(256) triplet_hinge_fwd_kernel(const float* __restrict__ f1, const float* __restrict__ f2,
+                                                                const float* __restrict__ f1w, const float* __restrict__ f2w,
+                                                                const float* __restrict__ m1w, const float* __restrict__ m2w,
+                                                                const float* __restrict__ m1, const float* __restrict__ m2,
+                                                                int hw, int C, float margin, float* __restrict__ M1,
+                                                                float* __restrict__ M2, double* __restrict__ numden) {
+    __shared__ double part[4][4];
+    const int b = blockIdx.y;
+    const int LP = min(64, C / 4), PPW = 64 / LP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane / LP, cl = lane % LP;
+    const int wave_global = blockIdx.x * 4 + wave, nwaves = gridDim.x * 4;
+    double a_n1 = 0, a_d1 = 0, a_n2 = 0, a_d2 = 0;
+    for (int p0 = wave_global * PPW; p0 < hw; p0 += nwaves * PPW) {
+        const int p = p0 + sub;
+        float s1 = 0, s2 = 0;
+        if (p < hw) {
+            const size_t base = ((size_t)b * hw + p) * C;
+            for (int c = cl * 4; c < C; c += LP * 4) {
+                const float4 a1 = ld4(f1 + base + c), a2 = ld4(f2 + base + c), a1w = ld4(f1w + base + c), a2w = ld4(f2w + base + c);
+                s1 += hinge_4(a1w, a2, a1, margin);
+                s2 += hinge_4(a2w, a1, a2, margin);
+            }
+        }
+        for (int off = 1; off < LP; off <<= 1) { s1 += __shfl_xor(s1, off, 64); s2 += __shfl_xor(s2, off, 64); }
+        if (p < hw && cl == 0) {
+            const size_t q = (size_t)b * hw + p;
+            M1[q] = s1; M2[q] = s2;
+            const float wa = m1w[q] * (m2 ? m2[q] : 1.0f), wb = m2w[q] * (m1 ? m1[q] : 1.0f);
+            a_n1 += (double)(wa * s1); a_d1 += (double)wa;
+            a_n2 += (double)(wb * s2); a_d2 += (double)wb;
+        }
+    }
+    a_n1 = wave_sum(a_n1); a_d1 = wave_sum(a_d1); a_n2 = wave_sum(a_n2); a_d2 = wave_sum(a_d2);
+    if (lane == 0) { part[wave][0] = a_n1; part[wave][1] = a_d1; part[wave][2] = a_n2; part[wave][3] = a_d2; }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        atomicAdd(numden + (size_t)b * 4 + threadIdx.x,
+                  part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+}
+
+// grid (TRIP_BWD_BLOCKS_PER_SAMPLE, B, 2), block 256: triplet_bwd_kernel's direction split and batch rotation; each direction reads
+// THREE maps (fw, fo and fs, the third operand of its hinge) and recomputes the per-channel indicator instead of loading a stored mask.
+__global__ void __launch_bounds__(256) triplet_hinge_bwd_kernel(const float* __restrict__ g_loss, const float* __restrict__ f1,
+                                                                const float* __restrict__ f2, const float* __restrict__ f1w,
+                                                                const float* __restrict__ f2w, const float* __restrict__ m1w,
+                                                                const float* __restrict__ m2w, const float* __restrict__ m1,
+                                                                const float* __restrict__ m2, const float* __restrict__ M1,
+                                                                const float* __restrict__ M2, const double* __restrict__ numden,
+                                                                const double* __restrict__ H1, const double* __restrict__ H2,
+                                                                int hw, int C, float margin, float mu, float* __restrict__ g_f1w,
+                                                                float* __restrict__ g_f2w, float* __restrict__ g_m1w,
+                                                                float* __restrict__ g_m2w, double* __restrict__ gH1,
+                                                                double* __restrict__ gH2) {
+    const int dir = blockIdx.z;
+    const int b = dir ? (int)((blockIdx.y + gridDim.y / 3u + 1u) % gridDim.y) : (int)blockIdx.y;
+    const float g = g_loss[0];
+    const double* nd = numden + (size_t)b * 4;
+    if (blockIdx.x == 0 && dir == 0 && threadIdx.x < 9) {
+        // ln3 = ||H1 H2 - I||^2 : gP = 2 mu g P ; gH1 = gP H2^T ; gH2 = H1^T gP
+        const double* A = H1 + (size_t)b * 9;
+        const double* Bm = H2 + (size_t)b * 9;
+        double P[9];
+        mat3_mul(A, Bm, P);
+        P[0] -= 1.0; P[4] -= 1.0; P[8] -= 1.0;
+        const double k = 2.0 * (double)mu * (double)g;
+        const int r = threadIdx.x / 3, c = threadIdx.x % 3;
+        double a = 0, d = 0;
+        for (int t = 0; t < 3; ++t) {
+            a += P[r * 3 + t] * Bm[c * 3 + t];
+            d += A[t * 3 + r] * P[t * 3 + c];
+        }
+        gH1[(size_t)b * 9 + threadIdx.x] = k * a;
+        gH2[(size_t)b * 9 + threadIdx.x] = k * d;
+    }
+    const float Nn = (float)nd[dir * 2], Dd = (float)nd[dir * 2 + 1];
+    const float den = fmaxf(Dd, 1.0f);
+    const float dd = (Dd > 1.0f) ? -Nn / (den * den) : 0.0f;
+    const float* __restrict__ fw = dir ? f2w : f1w;
+    const float* __restrict__ fo = dir ? f1 : f2;
+    const float* __restrict__ fs = dir ? f2 : f1;
+    const float* __restrict__ mw = dir ? m2w : m1w;
+    const float* __restrict__ mo = dir ? m1 : m2;
+    const float* __restrict__ Mx = dir ? M2 : M1;
+    float* __restrict__ g_fw = dir ? g_f2w : g_f1w;
+    float* __restrict__ g_mw = dir ? g_m2w : g_m1w;
+    const int LP = min(64, C / 4), PPW = 64 / LP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int sub = lane / LP, cl = lane % LP;
+    const int wave_global = blockIdx.x * 4 + wave, nwaves = gridDim.x * 4;
+    for (int p0 = wave_global * PPW; p0 < hw; p0 += nwaves * PPW) {
+        const int p = p0 + sub;
+        if (p >= hw) continue;
+        const size_t q = (size_t)b * hw + p;
+        const float mm = mo ? mo[q] : 1.0f;
+        const float k = g * mw[q] * mm / den;
+        const size_t base = q * C;
+        for (int c = cl * 4; c < C; c += LP * 4) {
+            const float4 aw = ld4(fw + base + c), ao = ld4(fo + base + c), as = ld4(fs + base + c);
+            *reinterpret_cast<float4*>(g_fw + base + c) =
+                make_float4(hinge_g(aw.x, ao.x, as.x, margin, k), hinge_g(aw.y, ao.y, as.y, margin, k),
+                            hinge_g(aw.z, ao.z, as.z, margin, k), hinge_g(aw.w, ao.w, as.w, margin, k));
+        }
+        if (cl == 0) g_mw[q] = g * mm * (Mx[q] / den + dd);
+    }
+}
+
 __global__ void __launch_bounds__(256) scale_samples_fwd_kernel(const float* __restrict__ x, const float* __restrict__ sc, long long L,
                                                                 int rep, float* __restrict__ y) {
     const int b = blockIdx.y;
@@ -427,6 +652,71 @@ int bh_oneline_loss_bwd(const float* g_loss, const float* f2, const float* f1w, 
     if (B == 0) return BH_OK;
     hipLaunchKernelGGL(oneline_bwd_kernel, dim3(TRIP_BLOCKS_PER_SAMPLE, B), dim3(256), 0, bh_stream(stream), g_loss, f2, f1w,
                        m1w, m2, T, numden, hw, C, rep, sample_w, g_f1w, g_m1w);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+int bh_oneline_cos_loss_fwd(const float* f1, const float* f2, const float* f1w, const float* m1w, const float* m2, int B, int hw,
+                            int C, float margin, int rep, const float* sample_w, float* T, double* numden, float* per_sample,
+                            float* loss, int flags, void* stream) {
+    if (!f1 || !f2 || !f1w || !m1w || !T || !numden || !loss || B < 0 || hw < 1 || rep < 1 || B % rep) return BH_E_BADARG;
+    if (C % 4 || C < 4 || (C / 4 < 64 && (64 % (C / 4)))) return BH_E_UNSUPPORTED;
+    if (B > 65535) return BH_E_UNSUPPORTED;
+    hipStream_t s = bh_stream(stream);
+    if (B > 0) {
+        hipError_t e = hipMemsetAsync(numden, 0, sizeof(double) * 2 * (size_t)B, s);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(oneline_cos_fwd_kernel, dim3((flags & BH_F_DETERMINISTIC) ? 1 : TRIP_BLOCKS_PER_SAMPLE, B), dim3(256), 0, s, f1, f2, f1w, m1w, m2,
+                           hw, C, margin, rep, T, numden);
+        BH_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(oneline_loss_kernel, dim3(1), dim3(256), 0, s, numden, B, sample_w, per_sample, loss);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+int bh_oneline_cos_loss_bwd(const float* g_loss, const float* f2, const float* f1w, const float* m1w, const float* m2,
+                            const float* T, const double* numden, int B, int hw, int C, int rep, const float* sample_w,
+                            float* g_f1w, float* g_m1w, void* stream) {
+    if (!g_loss || !f2 || !f1w || !m1w || !T || !numden || !g_f1w || !g_m1w || B < 0 || hw < 1 || rep < 1 || B % rep) return BH_E_BADARG;
+    if (C % 4 || C < 4 || (C / 4 < 64 && (64 % (C / 4)))) return BH_E_UNSUPPORTED;
+    if (B == 0) return BH_OK;
+    if (B > 65535) return BH_E_UNSUPPORTED;
+    hipLaunchKernelGGL(oneline_cos_bwd_kernel, dim3(TRIP_BLOCKS_PER_SAMPLE, B), dim3(256), 0, bh_stream(stream), g_loss, f2, f1w,
+                       m1w, m2, T, numden, hw, C, rep, sample_w, g_f1w, g_m1w);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+int bh_triplet_hinge_fwd(const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
+                         const float* m2w, const float* m1, const float* m2, int B, int hw, int C, float margin, float* M1,
+                         float* M2, double* numden, int flags, void* stream) {
+    if (!f1 || !f2 || !f1w || !f2w || !m1w || !m2w || !M1 || !M2 || !numden || B < 0 || hw < 1) return BH_E_BADARG;
+    if (C % 4 || C < 4 || (C / 4 < 64 && (64 % (C / 4)))) return BH_E_UNSUPPORTED;
+    if (B == 0) return BH_OK;
+    if (B > 65535) return BH_E_UNSUPPORTED;
+    hipError_t e = hipMemsetAsync(numden, 0, sizeof(double) * 4 * (size_t)B, bh_stream(stream));
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(triplet_hinge_fwd_kernel, dim3((flags & BH_F_DETERMINISTIC) ? 1 : TRIP_FWD_BLOCKS_PER_SAMPLE, B), dim3(256), 0, bh_stream(stream),
+                       f1, f2, f1w, f2w, m1w, m2w, m1, m2, hw, C, margin, M1, M2, numden);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+int bh_triplet_hinge_bwd(const float* g_loss, const float* f1, const float* f2, const float* f1w, const float* f2w,
+                         const float* m1w, const float* m2w, const float* m1, const float* m2, const float* M1,
+                         const float* M2, const double* numden, const double* H1, const double* H2, int B, int hw, int C,
+                         float margin, float mu, float* g_f1w, float* g_f2w, float* g_m1w, float* g_m2w, double* gH1,
+                         double* gH2, void* stream) {
+    if (!g_loss || !f1 || !f2 || !f1w || !f2w || !m1w || !m2w || !M1 || !M2 || !numden || !H1 || !H2 || !g_f1w ||
+        !g_f2w || !g_m1w || !g_m2w || !gH1 || !gH2 || B < 0 || hw < 1)
+        return BH_E_BADARG;
+    if (C % 4 || C < 4 || (C / 4 < 64 && (64 % (C / 4)))) return BH_E_UNSUPPORTED;
+    if (B == 0) return BH_OK;
+    if (B > 65535) return BH_E_UNSUPPORTED;
+    hipLaunchKernelGGL(triplet_hinge_bwd_kernel, dim3(TRIP_BWD_BLOCKS_PER_SAMPLE, B, 2), dim3(256), 0, bh_stream(stream), g_loss,
+                       f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden, H1, H2, hw, C, margin, mu, g_f1w, g_f2w, g_m1w,
+                       g_m2w, gH1, gH2);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

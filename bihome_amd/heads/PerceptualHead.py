@@ -2,10 +2,11 @@
 
 Contract: `Model(backbone, **cfg['MODEL']['HEAD'])`; `forward(data) -> (loss, delta_gt,
 delta_hat[B,4,2])`; `predict_homography(data) -> (delta_hat[B,4,2], None)`; state-dict keys
-`auxiliary_resnet.resnet.{conv1,bn1,layer1.*}` and `backbone.*` as upstream.  Only the branch the shipped
-biHomE configs select is built (TRIPLET_LOSS 'double-line', TRIPLET_DISTANCE 'l1', TRIPLET_AGGREGATION
-'channel-agnostic', str TRIPLET_MARGIN, SAMPLING_STRATEGY 'downsample-mask', AUXILIARY_RESNET 'resnet34'
-layer 1); anything else raises.  Reference: src/heads/PerceptualHead.py:15-767, src/heads/ransac_utils.py:26-161,
+`auxiliary_resnet.resnet.{conv1,bn1,layer1.*}` and `backbone.*` as upstream.  Built loss branches (Model._check_loss_branch):
+double-line 'l1' with a str TRIPLET_MARGIN (the shipped biHomE configs; either TRIPLET_AGGREGATION) or with a numeric margin
+and 'channel-aware'; one-line 'l1' / 'cosine' with a numeric margin; the multihead feature loss (TRIPLET_LOSS '').
+SAMPLING_STRATEGY 'downsample-mask', AUXILIARY_RESNET 'resnet34' layers 1-4; anything else raises with the reason.
+Reference: src/heads/PerceptualHead.py:15-767, src/heads/ransac_utils.py:26-161,
 src/data/utils.py:7-59.
 
 Data flow of one training forward (both directions stacked along the batch axis, "2B"):
@@ -267,7 +268,10 @@ class _BiHomELoss(torch.autograd.Function):
         warped, cov, wl, featw = _extractor_of_warp(aux, patches, H64, pool, groups=2)      # :371-382,:392-401,:447-459
         f1, f2, f1w, f2w = feat[:B], feat[B:], featw.detach()[:B], featw.detach()[B:]
         m1w, m2w = cov[:B], cov[B:]
-        M1, M2, numden = K.triplet_l1_fwd(f1, f2, f1w, f2w, m1w, m2w)      # :559-561,:609-653
+        if head.hinge_per_channel:                               # numeric margin, 'channel-aware' :624-625,:644-645
+            M1, M2, numden = K.triplet_hinge_fwd(f1, f2, f1w, f2w, m1w, m2w, head.triplet_margin)
+        else:
+            M1, M2, numden = K.triplet_l1_fwd(f1, f2, f1w, f2w, m1w, m2w)      # :559-561,:609-653
         loss4 = K.bihome_loss_fwd(numden, H64[:B], H64[B:], head.triplet_mu)   # :656-665
         ctx.head, ctx.B, ctx.pool = head, B, pool
         ctx.saved = (delta, patches, H64, feat, featw, wl, cov, M1, M2, numden)
@@ -283,8 +287,12 @@ class _BiHomELoss(torch.autograd.Function):
         h = patches.shape[-1]
         g = g_loss.reshape(1).to(torch.float32).contiguous()
         fw = featw.detach()
-        gfeatw, gcov, gH = K.bihome_loss_bwd(g, feat[:B], feat[B:], fw[:B], fw[B:], cov[:B], cov[B:], None, None, M1, M2, numden,
-                                             H64[:B], H64[B:], head.triplet_mu, joined=True)      # (both directions in one tensor each)
+        if head.hinge_per_channel:
+            gfeatw, gcov, gH = K.triplet_hinge_bwd(g, feat[:B], feat[B:], fw[:B], fw[B:], cov[:B], cov[B:], None, None, M1, M2, numden,
+                                                   H64[:B], H64[B:], head.triplet_margin, head.triplet_mu, joined=True)
+        else:
+            gfeatw, gcov, gH = K.bihome_loss_bwd(g, feat[:B], feat[B:], fw[:B], fw[B:], cov[:B], cov[B:], None, None, M1, M2, numden,
+                                                 H64[:B], H64[B:], head.triplet_mu, joined=True)      # (both directions in one tensor each)
         _extractor_dgrad_into_warp(head.auxiliary_resnet, featw, wl, gfeatw, patches, H64, gcov, ctx.pool, gH)
         gdelta = K.h4pt_bwd(delta, H64, gH, h)
         return gdelta, None, None
@@ -293,7 +301,7 @@ class _BiHomELoss(torch.autograd.Function):
 @K.scoped_function
 class _IHomELoss(torch.autograd.Function):
     """triplet_resnet_loss, one-line branch (iHomE; PerceptualHead.py:320-538): only patch_1 is warped, hinge with a
-    numeric margin.  patches[2B,1,h,w] = cat(patch_1, patch_2); delta[B,4,2] = delta_hat_12."""
+    numeric margin on L1 or cosine distances (head.triplet_distance).  patches[2B,1,h,w] = cat(patch_1, patch_2); delta[B,4,2] = delta_hat_12."""
 
     @staticmethod
     def forward(ctx, delta, patches, head, scores=None, n=1):
@@ -315,9 +323,10 @@ class _IHomELoss(torch.autograd.Function):
         p1 = patches[:B].contiguous() if n == 1 else patches[:B].repeat_interleave(n, 0)   # :352 one copy per hypothesis
         warped, cov, wl, featw = _extractor_of_warp(aux, p1, H64, pool, groups=1)           # :371-382 + downsample (:447-451)
         sw = scores.contiguous() if scores is not None else None
-        loss, T, numden, per = K.oneline_loss_fwd(feat[:B], feat[B:], featw.detach(), cov, head.triplet_margin, rep=n,
-                                                  sample_w=sw)    # :474-533
-        ctx.head, ctx.pool, ctx.n = head, pool, n
+        cosine = head.triplet_distance == 'cosine'               # :485-499 instead of :468-482
+        loss, T, numden, per = (K.oneline_cos_loss_fwd if cosine else K.oneline_loss_fwd)(
+            feat[:B], feat[B:], featw.detach(), cov, head.triplet_margin, rep=n, sample_w=sw)    # :474-533
+        ctx.head, ctx.pool, ctx.n, ctx.cosine = head, pool, n, cosine
         ctx.saved = (delta, p1, H64, feat[B:], featw, wl, cov, T, numden, sw, per)
         head.last = {"loss4": loss, "H_4pt": H32, "warped": warped, "coverage": cov, "f1": feat[:B], "f2": feat[B:],
                      "f1w": featw.detach()}
@@ -329,7 +338,8 @@ class _IHomELoss(torch.autograd.Function):
         ctx.saved = None
         h = p1.shape[-1]
         g = g_loss.reshape(1).to(torch.float32).contiguous()
-        gfw, gcov = K.oneline_loss_bwd(g, f2, featw.detach(), cov, T, numden, rep=ctx.n, sample_w=sw)
+        gfw, gcov = (K.oneline_cos_loss_bwd if ctx.cosine else K.oneline_loss_bwd)(g, f2, featw.detach(), cov, T, numden, rep=ctx.n,
+                                                                                   sample_w=sw)
         gH = torch.zeros_like(H64)
         _extractor_dgrad_into_warp(ctx.head.auxiliary_resnet, featw, wl, gfw, p1, H64, gcov, ctx.pool, gH)
         gdelta = K.h4pt_bwd(delta, H64, gH, h)
@@ -401,21 +411,12 @@ class Model(nn.Module):
                 self.scoring_distance_threshold = float(kwargs['SCORING_DISTANCE_THRESHOLD'])
         self.triplet_version = kwargs['TRIPLET_LOSS']
         self.multihead = self.triplet_version == ''           # PerceptualHead.py:108,:230-235 -> multihead_resnet_loss
-        common = ('dual' not in self.triplet_version and kwargs.get('TRIPLET_DISTANCE') == 'l1'
-                  and not len(kwargs.get('MASK_KEYS', [])) and 'upsample' not in str(kwargs.get('SAMPLING_STRATEGY', ''))
-                  and not kwargs.get('MASK_CRD', False))
         self.one_line = 'one-line' in self.triplet_version
-        if self.multihead:                 # features out, a torch loss is applied by the driver (train.py:318-322)
-            ok = True
-        elif self.one_line:                # iHomE: PerceptualHead.py:465-538, hinge with a numeric margin
-            ok = common and isinstance(kwargs.get('TRIPLET_MARGIN'), (int, float))
-        else:                              # biHomE: PerceptualHead.py:540-665
-            ok = (common and 'double-line' in self.triplet_version and isinstance(kwargs.get('TRIPLET_MARGIN'), str)
-                  and kwargs.get('TRIPLET_AGGREGATION') == 'channel-agnostic')
-        if not ok:
-            raise NotImplementedError("built: biHomE (double-line / l1 / channel-agnostic / str margin), iHomE (one-line / l1 / "
-                                      "numeric margin) and the multihead feature loss (TRIPLET_LOSS ''), no MASK_KEYS / MASK_CRD, downsample-mask - see SURVEY.md 2 for what is out of "
-                                      "scope")
+        self.triplet_distance = kwargs.get('TRIPLET_DISTANCE')
+        self.triplet_aggregation = kwargs.get('TRIPLET_AGGREGATION')
+        self.hinge_per_channel = False     # double-line: numeric margin + 'channel-aware' (the hinge inside the channel sum)
+        if not self.multihead:             # (multihead: features out, a torch loss is applied by the driver, train.py:318-322)
+            self._check_loss_branch(kwargs)
         self.triplet_mu = kwargs.get('TRIPLET_MU', 0.0)
         self.triplet_margin = kwargs.get('TRIPLET_MARGIN')
         self.auxiliary_resnet = AuxiliaryResnet(**kwargs)
@@ -428,6 +429,47 @@ class Model(nn.Module):
         self.prefetch_features = os.environ.get("BIHOME_OVERLAP", "1") != "0"      # default on, see net.Runner
         if isinstance(backbone, nn.Module):
             backbone.register_forward_pre_hook(self._prefetch_hook)
+
+    def _check_loss_branch(self, kwargs):
+        """The branches of upstream's triplet_resnet_loss (PerceptualHead.py:320-714), one case each - the table of INTEGRATION.md
+        "PerceptualHead loss branches".  Built: one-line 'l1' / 'cosine' with a numeric margin; double-line 'l1' with a string margin
+        (either aggregation: sum(l1 - l3) == sum(l1) - sum(l3)) or with a numeric margin and 'channel-aware'."""
+        margin, dist, agg = kwargs.get('TRIPLET_MARGIN'), self.triplet_distance, self.triplet_aggregation
+        numeric = isinstance(margin, (int, float)) and not isinstance(margin, bool)
+        if 'dual' in self.triplet_version:
+            raise NotImplementedError("TRIPLET_LOSS 'dual' needs the backbone's own trainable feature extractor "
+                                      "(PerceptualHead.py:407-441); out of scope, SURVEY.md 2")
+        if len(kwargs.get('MASK_KEYS', [])) or kwargs.get('MASK_CRD', False):
+            raise NotImplementedError("MASK_KEYS / MASK_CRD (content masks, PerceptualHead.py:334-337,531-535) are not built")
+        if 'upsample' in str(kwargs.get('SAMPLING_STRATEGY', '')):
+            raise NotImplementedError("SAMPLING_STRATEGY 'upsample-*' (PerceptualHead.py:353-375) is not built; built: 'downsample-mask'")
+        if self.one_line:                  # iHomE: PerceptualHead.py:465-538, hinge with a numeric margin
+            if dist == 'l2':
+                raise NotImplementedError("one-line 'l2': upstream has no such branch (PerceptualHead.py:468-502 knows 'l1' and 'cosine')")
+            if dist not in ('l1', 'cosine'):
+                raise ValueError("unknown TRIPLET_DISTANCE %r (upstream: assert False, PerceptualHead.py:501-502)" % (dist,))
+            if not numeric:
+                raise NotImplementedError("one-line needs a numeric TRIPLET_MARGIN (upstream multiplies it into a tensor, "
+                                          "PerceptualHead.py:505)")
+            return
+        if 'double-line' not in self.triplet_version:
+            raise NotImplementedError("TRIPLET_LOSS %r: built are 'one-line', 'double-line' and '' (multihead)" % (self.triplet_version,))
+        if dist in ('l2', 'cosine'):       # biHomE: PerceptualHead.py:540-665
+            raise NotImplementedError("double-line %r: upstream's distances are already [B,h,w] there, so its sum(dim=1) runs over image "
+                                      "rows and the mask product only broadcasts for accidental shapes, PerceptualHead.py:580-603,"
+                                      "615-653" % (dist,))
+        if dist != 'l1':
+            raise NotImplementedError("double-line TRIPLET_DISTANCE %r: upstream asserts False, PerceptualHead.py:605-606" % (dist,))
+        if agg not in ('channel-aware', 'channel-agnostic'):
+            raise NotImplementedError("TRIPLET_AGGREGATION %r: upstream asserts False, PerceptualHead.py:621-622" % (agg,))
+        if isinstance(margin, str):        # :617-620 - both aggregations are the same value: the existing L1 kernels
+            return
+        if not numeric:
+            raise NotImplementedError("TRIPLET_MARGIN must be a string (no hinge) or a number, got %r" % (margin,))
+        if agg == 'channel-agnostic':
+            raise NotImplementedError("double-line numeric margin 'channel-agnostic': upstream's second line asserts shape [64,64] and "
+                                      "both lines broadcast [B,h,w] against [B,C,h,w], PerceptualHead.py:627-628,646-649")
+        self.hinge_per_channel = True      # :624-625,:644-645
 
     def _stack_patches(self, data):
         e1, e2 = self.patch_keys

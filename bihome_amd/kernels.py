@@ -476,23 +476,31 @@ def mask_bwd(y, f, m, smax, imax, g_m, g_g, strength, want_gf=True):
 # ------------------------------------------------------------------------------------------------
 # triplet
 # ------------------------------------------------------------------------------------------------
-def triplet_l1_fwd(f1, f2, f1w, f2w, m1w, m2w, m1=None, m2=None):
-    """features NHWC [B,hf,wf,C]; masks [B,hf,wf]."""
+def _triplet_fwd(entry, kernel, margin, f1, f2, f1w, f2w, m1w, m2w, m1, m2):
     for t in (f1, f2, f1w, f2w, m1w, m2w, m1, m2):
         _chk(t)
     B, hf, wf, C = f1.shape
     M1 = torch.empty(B, hf, wf, dtype=torch.float32, device=f1.device)
     M2 = torch.empty_like(M1)
     numden = torch.empty(B, 4, dtype=torch.float64, device=f1.device)
-    with _Timed("triplet_fwd_kernel", 0.0, 4.0 * (4 * f1.numel() + 4 * M1.numel())):      # 4 feature maps in, masks in, M1 / M2 out
-        check(lib.bh_triplet_l1_fwd(_p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), B, hf * wf, C,
-                                    _p(M1), _p(M2), _p(numden), _fdet(), _stream()), "bh_triplet_l1_fwd")
+    with _Timed(kernel, 0.0, 4.0 * (4 * f1.numel() + 4 * M1.numel())):      # 4 feature maps in, masks in, M1 / M2 out
+        check(getattr(lib, entry)(_p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), B, hf * wf, C, *margin,
+                                  _p(M1), _p(M2), _p(numden), _fdet(), _stream()), entry)
     return M1, M2, numden
 
 
-def oneline_loss_fwd(f1, f2, f1w, m1w, margin, m2=None, rep=1, sample_w=None):
-    """iHomE one-line hinge loss (PerceptualHead.py:465-538): returns (loss[1], T[B,hf,wf], numden[B,2], per_sample[B]).
-    rep > 1: B = samples * rep hypotheses; f1 / f2 / m2 hold one entry per sample; sample_w[B] = DSAC scores."""
+def triplet_l1_fwd(f1, f2, f1w, f2w, m1w, m2w, m1=None, m2=None):
+    """features NHWC [B,hf,wf,C]; masks [B,hf,wf]."""
+    return _triplet_fwd("bh_triplet_l1_fwd", "triplet_fwd_kernel", (), f1, f2, f1w, f2w, m1w, m2w, m1, m2)
+
+
+def triplet_hinge_fwd(f1, f2, f1w, f2w, m1w, m2w, margin, m1=None, m2=None):
+    """biHomE with the hinge inside the channel sum ('channel-aware', numeric margin: PerceptualHead.py:624-625,644-645); shapes and
+    returns as triplet_l1_fwd."""
+    return _triplet_fwd("bh_triplet_hinge_fwd", "triplet_hinge_fwd_kernel", (float(margin),), f1, f2, f1w, f2w, m1w, m2w, m1, m2)
+
+
+def _oneline_fwd(entry, f1, f2, f1w, m1w, margin, m2, rep, sample_w):
     for t in (f1, f2, f1w, m1w, m2, sample_w):
         _chk(t)
     B, hf, wf, C = f1w.shape
@@ -500,19 +508,39 @@ def oneline_loss_fwd(f1, f2, f1w, m1w, margin, m2=None, rep=1, sample_w=None):
     numden = torch.empty(B, 2, dtype=torch.float64, device=f1.device)
     per = torch.empty(B, dtype=torch.float32, device=f1.device)
     loss = torch.empty(1, dtype=torch.float32, device=f1.device)
-    check(lib.bh_oneline_loss_fwd(_p(f1), _p(f2), _p(f1w), _p(m1w), _p(m2), B, hf * wf, C, float(margin), rep, _p(sample_w), _p(T),
-                                  _p(numden), _p(per), _p(loss), _fdet(), _stream()), "bh_oneline_loss_fwd")
+    check(getattr(lib, entry)(_p(f1), _p(f2), _p(f1w), _p(m1w), _p(m2), B, hf * wf, C, float(margin), rep, _p(sample_w), _p(T),
+                              _p(numden), _p(per), _p(loss), _fdet(), _stream()), entry)
     return loss, T, numden, per
 
 
-def oneline_loss_bwd(g_loss, f2, f1w, m1w, T, numden, m2=None, rep=1, sample_w=None):
+def _oneline_bwd(entry, g_loss, f2, f1w, m1w, T, numden, m2, rep, sample_w):
     _chk(g_loss); _chk(sample_w)
     B, hf, wf, C = f1w.shape
     g_f1w = torch.empty_like(f1w)
     g_m1w = torch.empty(B, hf, wf, dtype=torch.float32, device=f1w.device)
-    check(lib.bh_oneline_loss_bwd(_p(g_loss), _p(f2), _p(f1w), _p(m1w), _p(m2), _p(T), _p(numden), B, hf * wf, C, rep, _p(sample_w),
-                                  _p(g_f1w), _p(g_m1w), _stream()), "bh_oneline_loss_bwd")
+    check(getattr(lib, entry)(_p(g_loss), _p(f2), _p(f1w), _p(m1w), _p(m2), _p(T), _p(numden), B, hf * wf, C, rep, _p(sample_w),
+                              _p(g_f1w), _p(g_m1w), _stream()), entry)
     return g_f1w, g_m1w
+
+
+def oneline_loss_fwd(f1, f2, f1w, m1w, margin, m2=None, rep=1, sample_w=None):
+    """iHomE one-line hinge loss (PerceptualHead.py:465-538): returns (loss[1], T[B,hf,wf], numden[B,2], per_sample[B]).
+    rep > 1: B = samples * rep hypotheses; f1 / f2 / m2 hold one entry per sample; sample_w[B] = DSAC scores."""
+    return _oneline_fwd("bh_oneline_loss_fwd", f1, f2, f1w, m1w, margin, m2, rep, sample_w)
+
+
+def oneline_loss_bwd(g_loss, f2, f1w, m1w, T, numden, m2=None, rep=1, sample_w=None):
+    return _oneline_bwd("bh_oneline_loss_bwd", g_loss, f2, f1w, m1w, T, numden, m2, rep, sample_w)
+
+
+def oneline_cos_loss_fwd(f1, f2, f1w, m1w, margin, m2=None, rep=1, sample_w=None):
+    """The one-line hinge loss on cosine distances (TRIPLET_DISTANCE 'cosine', PerceptualHead.py:485-499): arguments and returns as
+    oneline_loss_fwd, T = c(f1, f2) - c(f1w, f2) + margin."""
+    return _oneline_fwd("bh_oneline_cos_loss_fwd", f1, f2, f1w, m1w, margin, m2, rep, sample_w)
+
+
+def oneline_cos_loss_bwd(g_loss, f2, f1w, m1w, T, numden, m2=None, rep=1, sample_w=None):
+    return _oneline_bwd("bh_oneline_cos_loss_bwd", g_loss, f2, f1w, m1w, T, numden, m2, rep, sample_w)
 
 
 def zhang_triplet_fwd(f1, f2, f1w, f2w, m1w, m2w, margin, hinge, m1=None, m2=None):
@@ -556,22 +584,33 @@ def bihome_loss_fwd(numden, H1, H2, mu):
     return loss4
 
 
-def bihome_loss_bwd(g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden, H1, H2, mu, joined=False):
-    """joined: the two directions' outputs are the halves of ONE [2B, ...] tensor each and (g_fw, g_mw, gH) are returned whole (the
-    caller's extractor / warp adjoints take both directions in one call: no torch.cat of 33 MB)."""
+def _bihome_bwd(entry, kernel, maps, margin, g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden, H1, H2, mu, joined):
     _chk(g_loss)
     B, hf, wf, C = f1.shape
     g_fw = torch.empty((2 * B,) + tuple(f1w.shape[1:]), dtype=torch.float32, device=f1.device)
     g_mw = torch.empty((2 * B,) + tuple(m1w.shape[1:]), dtype=torch.float32, device=f1.device)
     gH = torch.empty(2 * B, 9, dtype=torch.float64, device=f1.device)
     g_f1w, g_f2w, g_m1w, g_m2w, gH1, gH2 = g_fw[:B], g_fw[B:], g_mw[:B], g_mw[B:], gH[:B], gH[B:]
-    with _Timed("triplet_bwd_kernel", 0.0, 4.0 * (6 * f1.numel() + 6 * M1.numel())):      # 4 feature maps in, 2 gradients out
-        check(lib.bh_bihome_loss_bwd(_p(g_loss), _p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), _p(M1),
-                                     _p(M2), _p(numden), _p(H1), _p(H2), B, hf * wf, C, float(mu), _p(g_f1w), _p(g_f2w),
-                                     _p(g_m1w), _p(g_m2w), _p(gH1), _p(gH2), _stream()), "bh_bihome_loss_bwd")
+    with _Timed(kernel, 0.0, 4.0 * (maps * f1.numel() + 6 * M1.numel())):      # feature maps read + the 2 gradients written
+        check(getattr(lib, entry)(_p(g_loss), _p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), _p(M1),
+                                  _p(M2), _p(numden), _p(H1), _p(H2), B, hf * wf, C, *margin, float(mu), _p(g_f1w), _p(g_f2w),
+                                  _p(g_m1w), _p(g_m2w), _p(gH1), _p(gH2), _stream()), entry)
     if joined:
         return g_fw, g_mw, gH
     return g_f1w, g_f2w, g_m1w, g_m2w, gH1, gH2
+
+
+def bihome_loss_bwd(g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden, H1, H2, mu, joined=False):
+    """joined: the two directions' outputs are the halves of ONE [2B, ...] tensor each and (g_fw, g_mw, gH) are returned whole (the
+    caller's extractor / warp adjoints take both directions in one call: no torch.cat of 33 MB)."""
+    return _bihome_bwd("bh_bihome_loss_bwd", "triplet_bwd_kernel", 6, (), g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden,
+                       H1, H2, mu, joined)
+
+
+def triplet_hinge_bwd(g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden, H1, H2, margin, mu, joined=False):
+    """The adjoint of triplet_hinge_fwd + bihome_loss_fwd; arguments (plus the margin) and returns as bihome_loss_bwd."""
+    return _bihome_bwd("bh_triplet_hinge_bwd", "triplet_hinge_bwd_kernel", 8, (float(margin),), g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2,
+                       M1, M2, numden, H1, H2, mu, joined)
 
 
 # ------------------------------------------------------------------------------------------------

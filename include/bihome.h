@@ -48,7 +48,8 @@ int bh_device_arch(char* buf, int buflen);
  *   - BatchNorm (flags & BH_BN_DETERMINISTIC in bh_bn_fwd / bh_bn_bwd and their fused forms): the statistics pass writes, and every pass reads, the limb
  *     encoding.  A sums table must be written and read in ONE mode (the forward that leaves sums for its backward, a conv epilogue and
  *     the BatchNorm that consumes its statistics); bh_bn_fwd_coeffs looks at both encodings;
- *   - bh_warp_bwd, bh_photo_warp_bwd, bh_triplet_l1_fwd, bh_oneline_loss_fwd, bh_scale_samples_bwd, bh_dsac_scores_bwd, bh_tail_bwd
+ *   - bh_warp_bwd, bh_photo_warp_bwd, bh_triplet_l1_fwd, bh_triplet_hinge_fwd, bh_oneline_loss_fwd, bh_oneline_cos_loss_fwd,
+ *     bh_scale_samples_bwd, bh_dsac_scores_bwd, bh_tail_bwd
  *     (flags & BH_F_DETERMINISTIC): one workgroup per sample / channel is the only writer of its sums;
  *   - bh_dlt_bwd: duplicates of a sample's indices are added in point order inside the wave, hypotheses in launch order;
  *   - bh_warp_fwd with pool = 32: the pooled coverage by a one-writer kernel (the default adds four quarter-window sums with atomics);
@@ -253,6 +254,34 @@ int bh_oneline_loss_fwd(const float* f1, const float* f2, const float* f1w, cons
 int bh_oneline_loss_bwd(const float* g_loss, const float* f2, const float* f1w, const float* m1w, const float* m2,
                         const float* T, const double* numden, int B, int hw, int C, int rep, const float* sample_w,
                         float* g_f1w, float* g_m1w, void* stream);
+/* One-line variant with TRIPLET_DISTANCE 'cosine' (src/heads/PerceptualHead.py:485-499, the hinge :505, the scores :508-511):
+ *   c(x, y) = sum_c x_c y_c / (max(|x|_2, eps) max(|y|_2, eps)), eps = 1e-8 (torch.cosine_similarity: each norm is clamped on its own;
+ *   a zero vector gives c = 0 and receives the gradient y_hat / eps)
+ *   t = c(f1, f2) - c(f1w, f2) + margin  ( = (1 - c1w) - (1 - c13) + margin );  loss as bh_oneline_loss_fwd with this t.
+ * Arguments, outputs (T = t before the hinge), the multi-hypothesis form, flags and the batch sum are those of bh_oneline_loss_fwd / _bwd.
+ * fp32 per pixel (sqrtf and division), double across pixels.  The adjoint recomputes f1w.f2, |f1w|^2 and |f2|^2 from the two maps it
+ * reads anyway; as in torch only the VALUE of a norm is clamped - its gradient f1w / |f1w| is taken wherever |f1w| > 0.
+ * BH_E_UNSUPPORTED: B > 65535. */
+int bh_oneline_cos_loss_fwd(const float* f1, const float* f2, const float* f1w, const float* m1w, const float* m2, int B, int hw,
+                            int C, float margin, int rep, const float* sample_w, float* T, double* numden, float* per_sample,
+                            float* loss, int flags, void* stream);
+int bh_oneline_cos_loss_bwd(const float* g_loss, const float* f2, const float* f1w, const float* m1w, const float* m2,
+                            const float* T, const double* numden, int B, int hw, int C, int rep, const float* sample_w,
+                            float* g_f1w, float* g_m1w, void* stream);
+/* biHomE with a numeric margin and TRIPLET_AGGREGATION 'channel-aware' (double-line / l1: src/heads/PerceptualHead.py:624-625, 644-645) -
+ * the hinge inside the channel sum, the same margin in both directions:
+ *   M1[B,hw] = sum_c max(|f1w_c - f2_c| - |f1_c - f2_c| + margin, 0) ; M2[B,hw] = sum_c max(|f2w_c - f1_c| - |f1_c - f2_c| + margin, 0)
+ * numden[B,4] as bh_triplet_l1_fwd (flags: BH_F_DETERMINISTIC); bh_bihome_loss_fwd turns it into the loss.  The adjoint is
+ * bh_bihome_loss_bwd's with g_f1w_c = k [t1_c > 0] sgn(f1w_c - f2_c): the per-channel indicator is recomputed (each direction reads
+ * three maps), nothing of size [B,hw,C] is stored.  BH_E_UNSUPPORTED: B > 65535. */
+int bh_triplet_hinge_fwd(const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
+                         const float* m2w, const float* m1, const float* m2, int B, int hw, int C, float margin, float* M1,
+                         float* M2, double* numden, int flags, void* stream);
+int bh_triplet_hinge_bwd(const float* g_loss, const float* f1, const float* f2, const float* f1w, const float* f2w,
+                         const float* m1w, const float* m2w, const float* m1, const float* m2, const float* M1,
+                         const float* M2, const double* numden, const double* H1, const double* H2, int B, int hw, int C,
+                         float margin, float mu, float* g_f1w, float* g_f2w, float* g_m1w, float* g_m2w, double* gH1,
+                         double* gH2, void* stream);
 /* Zhang et al. content-aware triplet loss (TripletHead.forward, src/heads/TripletHead.py:75-152) on ONE-channel full-resolution feature
  * maps f*[B,hw] (the ContentAware feature extractor, src/backbones/ContentAware.py:57-81) and masks m*[B,hw] (m1 / m2 NULL = ones: FIX_MASK):
  *   num1 = sum_p m1w m2 h(|f1w - f2| - |f1 - f2| + margin), den1 = sum_p m1w m2; num2 / den2 with (f2w, f1, m2w m1); f2w NULL: one line.
