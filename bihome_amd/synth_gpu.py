@@ -2,7 +2,10 @@
 
 Same sample distribution as the host generator `bihome_amd.synth.make_pairs` (which mirrors
 `HomographyNetPrep`, src/data/transforms.py:441-725), but the crops/warps run in one HIP kernel
-(`bh_synth_pairs`) over base images that stay resident in HBM, so a training loop never waits for CPU workers."""
+(`bh_synth_batch`) over base images that stay resident in HBM, so a training loop never waits for CPU workers.
+Grayscale or RGB patches, the 'all_points' perspective-field target of the supervised configurations, and - with
+`photometric_draws='device'` - the photometric records drawn on the device as well (`photometric_records`): nothing of a
+step's batch is then made on, or copied from, the host."""
 import ctypes
 
 import numpy as np
@@ -13,19 +16,67 @@ from . import synth
 from ._lib import check, lib
 
 
+def photometric_records(u, max_delta):
+    """[..., 11] uniforms in [0, 1) -> [..., 6] PhotometricDistortSimple records in the layout and with the distribution of
+    `synth.draw_photometric` (transforms.py:296-330): a pure tensor function (no loop over records, any device).  Columns of `u`:
+    0 brightness on, 1 its value; 2 contrast before (on) or after the HSV part; 3 contrast on, 4 its value; 5 saturation on, 6 its
+    value; 7 hue on, 8 its value; 9 permutation on, 10 its index.  A coin is `u >= 0.5` (randint(2) = floor(2u)), a value
+    lo + (hi - lo) u, the index floor(6u).  Arithmetic in double (lo + (hi - lo) u near zero has no relative accuracy in float32),
+    result float32."""
+    u = u.double()
+    on = u >= 0.5
+    md = float(max_delta)
+    lower, upper = 1.0 - md / 32 * 0.5, 1.0 + md / 32 * 0.5
+    one, zero = torch.ones_like(u[..., 0]), torch.zeros_like(u[..., 0])
+    br = torch.where(on[..., 0], -md + 2 * md * u[..., 1], zero)
+    first = on[..., 2]
+    con = torch.where(on[..., 3], lower + (upper - lower) * u[..., 4], one)
+    c1, c2 = torch.where(first, con, one), torch.where(first, one, con)
+    sat = torch.where(on[..., 5], lower + (upper - lower) * u[..., 6], one)
+    hue = torch.where(on[..., 7], -md / 2 + md * u[..., 8], zero)
+    perm = torch.where(on[..., 9], torch.floor(6 * u[..., 10]).clamp(max=5), zero) if md > 0 else zero
+    return torch.stack([br, c1, sat, hue, c2, perm], -1).to(torch.float32)
+
+
+def batch_spec(cfg):
+    """GpuPairGenerator keyword arguments for a `configs.get(name)` dictionary (needs no GPU).  The patch geometry, the distortion
+    and the target come from DATA; the head decides what else its batch carries: PhotometricHead warps the whole image_1 (and
+    its corners), NoOpHead's '4_points' predict_homography reads the corners."""
+    data, head = cfg["DATA"], cfg["MODEL"]["HEAD"]["NAME"]
+    return {"patch": data["PATCH_SIZE"], "rho": data["RHO"], "photometric_max_delta": data.get("PHOTOMETRIC_MAX_DELTA", 0),
+            "channels": data.get("PATCH_CHANNELS", 1), "target_gen": data.get("TARGET_GEN"),
+            "image": head == "PhotometricHead", "corners": head in ("PhotometricHead", "NoOpHead")}
+
+
 class GpuPairGenerator:
 
-    def __init__(self, n_images=16, patch=128, rho=32, seed=42, photometric_max_delta=0, device="cuda"):
+    def __init__(self, n_images=16, patch=128, rho=32, seed=42, photometric_max_delta=0, device="cuda", channels=1,
+                 target_gen=None, corners=False, photometric_draws="host", image=False):
+        if channels not in (1, 3):
+            raise ValueError("channels must be 1 (grayscale) or 3 (RGB)")
+        if target_gen not in (None, "4_points", "all_points"):
+            raise ValueError("target_gen must be None, '4_points' or 'all_points'")
+        if photometric_draws not in ("host", "device"):
+            raise ValueError("photometric_draws must be 'host' or 'device'")
+        if image and channels != 1:
+            raise ValueError("image=True produces the grayscale image_1 of the photometric head: channels must be 1")
         rng = np.random.Generator(np.random.PCG64(seed))
         self.h = max(240, patch + 2 * rho + 48)
         self.w = max(320, patch + 2 * rho + 128)
         imgs = np.stack([synth.texture_image(rng, self.h, self.w).transpose(2, 0, 1) for _ in range(n_images)])
         self.images = torch.tensor(imgs, dtype=torch.float32, device=device).contiguous()      # [NI,3,H,W] 0..255
         self.patch, self.rho, self.pmd = patch, rho, photometric_max_delta
+        self.channels, self.target_gen, self.corners, self.image = channels, target_gen, corners, image
+        self.photometric_draws = photometric_draws
         self.gen = torch.Generator(device=device)
         self.gen.manual_seed(seed)
         self._rs = np.random.RandomState(seed)            # photometric decisions (host draws, reference order)
         self.device = device
+
+    @classmethod
+    def from_config(cls, cfg, seed=42, n_images=16, device="cuda", photometric_draws="device"):
+        """The generator whose `next(B)` is the complete batch of the model `cfg` (a `configs.get(name)` dictionary) builds."""
+        return cls(n_images=n_images, seed=seed, device=device, photometric_draws=photometric_draws, **batch_spec(cfg))
 
     def draw(self, B):
         """Random sample parameters exactly as transforms.py:505-506,538 draw them (uniform integer position with a
@@ -37,7 +88,11 @@ class GpuPairGenerator:
         origin = torch.stack([px - half, py - half], 1).to(torch.float32).contiguous()
         delta = torch.randint(-self.rho, self.rho, (B, 4, 2), generator=g, device=dev).to(torch.float32).contiguous()
         photo = None
-        if self.pmd > 0:
+        if self.pmd > 0 and self.photometric_draws == "device":
+            # the same decisions from one device draw: no Python loop over the batch, no host-to-device copy
+            u = torch.rand((B, 2, 11), generator=g, device=dev)
+            photo = photometric_records(u, self.pmd).reshape(B, 12).contiguous()
+        elif self.pmd > 0:
             # PhotometricDistortSimple's decisions (transforms.py:296-330) for both images of every pair: the same record
             # layout and draw order as the host generator (synth.draw_photometric), drawn on the host - 12 floats per pair
             recs = np.stack([np.concatenate([synth.draw_photometric(self._rs, self.pmd), synth.draw_photometric(self._rs, self.pmd)])
@@ -45,28 +100,38 @@ class GpuPairGenerator:
             photo = torch.tensor(recs, dtype=torch.float32, device=dev).contiguous()
         return idx, origin, delta, photo
 
-    def make(self, idx, origin, delta, photo=None, image=False):
+    def make(self, idx, origin, delta, photo=None, image=None):
         """image=True: also image_1 [B,1,h,w] (the whole standardised grayscale image 1 under its photometric record, bh_synth_image:
-        its crop at the corners is patch_1 bitwise) and corners [B,4,2] - the batch of the photometric head (nguyen-orig)."""
-        B, P = delta.shape[0], self.patch
+        its crop at the corners is patch_1 bitwise) and corners [B,4,2] - the batch of the photometric head (nguyen-orig).  Default:
+        what the generator was constructed with."""
+        image = self.image if image is None else image
+        if image and self.channels != 1:
+            raise ValueError("image=True produces the grayscale image_1 of the photometric head: channels must be 1")
+        B, P, C = delta.shape[0], self.patch, self.channels
         H64, _ = K.h4pt_fwd(delta, P)
-        p1 = torch.empty(B, 1, P, P, dtype=torch.float32, device=self.device)
+        p1 = torch.empty(B, C, P, P, dtype=torch.float32, device=self.device)
         p2 = torch.empty_like(p1)
+        field = torch.empty(B, 2, P, P, dtype=torch.float32, device=self.device) if self.target_gen == "all_points" else None
         pv = ctypes.c_void_p
-        check(lib.bh_synth_pairs(pv(self.images.data_ptr()), pv(idx.data_ptr()), pv(origin.data_ptr()), pv(H64.data_ptr()),
+        check(lib.bh_synth_batch(pv(self.images.data_ptr()), pv(idx.data_ptr()), pv(origin.data_ptr()), pv(H64.data_ptr()),
                                  pv(photo.data_ptr()) if photo is not None else None, B, self.images.shape[0], self.h,
-                                 self.w, P, 0.443, 0.129, pv(p1.data_ptr()), pv(p2.data_ptr()),
-                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_synth_pairs")
+                                 self.w, P, C, 0.443, 0.129, pv(p1.data_ptr()), pv(p2.data_ptr()),
+                                 pv(field.data_ptr()) if field is not None else None,
+                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_synth_batch")
         out = {"patch_1": p1, "patch_2": p2, "delta": delta}
+        if self.target_gen is not None:
+            out["target"] = delta if self.target_gen == "4_points" else field            # transforms.py:628-633 / :635-685
+        if image or self.corners:
+            # corners in HomographyNetPrep's order (top-left, top-right, bottom-right, bottom-left; transforms.py:510-513)
+            sq = torch.tensor([[0, 0], [P, 0], [P, P], [0, P]], dtype=torch.float32, device=self.device)
+            out["corners"] = (origin[:, None, :] + sq).contiguous()
         if image:
             im = torch.empty(B, 1, self.h, self.w, dtype=torch.float32, device=self.device)
             check(lib.bh_synth_image(pv(self.images.data_ptr()), pv(idx.data_ptr()), pv(photo.data_ptr()) if photo is not None else None,
                                      B, self.images.shape[0], self.h, self.w, 0.443, 0.129, pv(im.data_ptr()),
                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_synth_image")
-            # corners in HomographyNetPrep's order (top-left, top-right, bottom-right, bottom-left; transforms.py:510-513)
-            sq = torch.tensor([[0, 0], [P, 0], [P, P], [0, P]], dtype=torch.float32, device=self.device)
-            out["image_1"], out["corners"] = im, (origin[:, None, :] + sq).contiguous()
+            out["image_1"] = im
         return out
 
-    def next(self, B, image=False):
+    def next(self, B, image=None):
         return self.make(*self.draw(B), image=image)

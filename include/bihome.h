@@ -655,10 +655,20 @@ int bh_tail_bwd(const float* gout, const float* x, const float* w1, const float*
  * applied after the HSV part, channel-permutation index 0..5 into ((0,1,2),(0,2,1),(1,0,2),(1,2,0),(2,0,1),(2,1,0))}
  * (transforms.py:141-245; OpenCV float HSV), or NULL for no distortion.  The distortion is applied to the image before
  * it is warped, as upstream.  patch1 = crop, patch2(x) = image(origin + Hpatch.x) bilinear; both standardised
- * ((gray/255 - mean)/std), [B,1,P,P]. */
+ * ((gray/255 - mean)/std), [B,1,P,P].  This is bh_synth_batch with C = 1 and no target: the same kernel, the same bits. */
 int bh_synth_pairs(const float* images, const int* img_idx, const float* origin, const double* Hpatch, const float* photo,
                    int B, int n_images, int Hs, int Ws, int P, float mean, float std, float* patch1, float* patch2,
                    void* stream);
+
+/* The generator in its general form (same inputs and argument rules as bh_synth_pairs).  C = 1: grayscale patches [B,1,P,P].  C = 3
+ * (BASELINE.json configs[4]): patch1 / patch2 are [B,3,P,P], channel c = the permuted, distorted channel c itself, standardised
+ * ((v/255 - mean)/std) - no grayscale step; sampling as for C = 1 (bilinear, each tap zero outside the base image, the photometric
+ * record applied to the image before the warp).  target: NULL, or [B,2,P,P] = HomographyNetPrep's 'all_points' perspective field
+ * (transforms.py:635-685): channel 0 / 1 = x / y of Hpatch.(x,y,1) dehomogenised minus (x,y), evaluated in double from the Hpatch
+ * the warp uses and stored as float.  BH_E_BADARG: a NULL required pointer, std == 0, C not 1 or 3; BH_E_UNSUPPORTED: P % 16 != 0. */
+int bh_synth_batch(const float* images, const int* img_idx, const float* origin, const double* Hpatch, const float* photo,
+                   int B, int n_images, int Hs, int Ws, int P, int C, float mean, float std, float* patch1, float* patch2,
+                   float* target, void* stream);
 
 /* image_1 for the photometric head (config/s-coco/nguyen-orig-lr-5e-3.yaml: HomographyNetPrep's image_1 after DictToGrayscale and
  * DictStandardize, transforms.py:344-378): image1[B,1,Hs,Ws] = the whole base image images[img_idx[b]] under image 1's photometric record

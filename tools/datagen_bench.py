@@ -1,0 +1,126 @@
+"""Time a batch from the two pair generators: the host generator (synth.make_pairs, one numpy loop over the samples) and the device
+generator (synth_gpu.GpuPairGenerator.next: the draws, the 8x8 solves and bh_synth_batch), microseconds per batch, one JSON line per
+case:
+
+    gray               zeng-bihome's batch: 1-channel 128 x 128 patches, B = 64
+    gray+all_points    zeng-orig's batch: the same plus the perspective-field target
+    rgb256             zeng-bihome-rgb256's batch: 3-channel 256 x 256 patches, rho 64, B = 32
+    pds host draws     zeng-bihome-pds' batch with the photometric records drawn in Python and copied to the device every step
+    pds device draws   the same with photometric_draws='device'
+    kernel A/B         --other-lib PATH: bh_synth_pairs of another build of the library (e.g. the parent commit's, built in a git
+                       worktree with `make -C bihome_amd/csrc`) against this build's, on the same inputs, launches only, the two
+                       alternating round by round in this one process, and whether the two outputs are the same bits
+
+    python tools/datagen_bench.py [--other-lib ../parent/bihome_amd/libbihome_hip.so]
+
+Device cases: `--warmup` batches, then `--rounds` rounds of `--reps` batches, each round between two device events with one synchronise
+at its end (so a round's time is the device's, host gaps included: what a training loop that waits for the batch sees); median, min and
+max over the rounds are reported - the spread is max - min.  The host generator is timed with the host clock over --host-reps calls
+(each call also makes its four base images, as the function does for every batch)."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from bihome_amd import _lib, kernels as K, synth  # noqa: E402
+from bihome_amd.synth_gpu import GpuPairGenerator  # noqa: E402
+
+
+def stats(us):
+    s = sorted(us)
+    return {"median_us": round(s[len(s) // 2], 2), "min_us": round(s[0], 2), "max_us": round(s[-1], 2), "spread_us": round(s[-1] - s[0], 2)}
+
+
+def device_rounds(fns, reps, rounds, warmup):
+    """fns: {name: callable}.  Per round every callable gets its own timed window of `reps` calls, in turn (interleaved)."""
+    for fn in fns.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    us = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            us[k].append(a.elapsed_time(b) * 1e3 / reps)
+    return {k: stats(v) for k, v in us.items()}
+
+
+def host_time(reps, **kw):
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        synth.make_pairs(**kw)
+        t.append((time.perf_counter() - t0) * 1e6)
+    return stats(t)
+
+
+def kernel_ab(other_path, B, reps, rounds, warmup):
+    """bh_synth_pairs of two builds on one set of inputs (gray, no records, no target), launches only."""
+    other = ctypes.CDLL(other_path)
+    other.bh_synth_pairs.argtypes = _lib.SIGNATURES["bh_synth_pairs"]
+    other.bh_synth_pairs.restype = ctypes.c_int
+    gen = GpuPairGenerator(seed=7)
+    idx, origin, delta, _ = gen.draw(B)
+    H64, _ = K.h4pt_fwd(delta, gen.patch)
+    pv = ctypes.c_void_p
+    stream = pv(torch.cuda.current_stream().cuda_stream)
+    outs, fns = {}, {}
+    for name, fn in (("other", other.bh_synth_pairs), ("this", _lib.lib.bh_synth_pairs)):
+        p1 = torch.empty(B, 1, gen.patch, gen.patch, device="cuda")
+        p2 = torch.empty_like(p1)
+        args = (pv(gen.images.data_ptr()), pv(idx.data_ptr()), pv(origin.data_ptr()), pv(H64.data_ptr()), None, B, gen.images.shape[0],
+                gen.h, gen.w, gen.patch, 0.443, 0.129, pv(p1.data_ptr()), pv(p2.data_ptr()), stream)
+        outs[name] = (p1, p2)
+        fns[name] = (lambda fn=fn, args=args: _lib.check(fn(*args), "bh_synth_pairs"))
+    res = device_rounds(fns, reps, rounds, warmup)
+    res["same_bits"] = bool(torch.equal(outs["other"][0], outs["this"][0]) and torch.equal(outs["other"][1], outs["this"][1]))
+    res["this_minus_other_median_us"] = round(res["this"]["median_us"] - res["other"]["median_us"], 2)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--host-reps", type=int, default=2)
+    ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--other-lib", default=None, help="another build of libbihome_hip.so for the kernel A/B case")
+    ap.add_argument("--kernel-reps", type=int, default=2000)
+    args = ap.parse_args()
+    dev = torch.cuda.get_device_name(0)
+    cases = [
+        ("gray", 64, dict(), dict()),
+        ("gray+all_points", 64, dict(target_gen="all_points"), dict(target=True)),
+        ("rgb256", 32, dict(patch=256, rho=64, channels=3), dict(patch=256, rho=64, channels=3)),
+        ("pds host draws", 64, dict(photometric_max_delta=32, photometric_draws="host"), dict(photometric_max_delta=32)),
+        ("pds device draws", 64, dict(photometric_max_delta=32, photometric_draws="device"), None),
+    ]
+    for name, B, gkw, hkw in cases:
+        gen = GpuPairGenerator(**gkw)
+        res = {"tool": "datagen_bench", "case": name, "batch": B, "device": dev, "reps": args.reps, "rounds": args.rounds,
+               "device_generator": device_rounds({"next": lambda: gen.next(B)}, args.reps, args.rounds, args.warmup)["next"]}
+        if hkw is not None and not args.no_host:
+            res["host_generator"] = dict(host_time(args.host_reps, batch=B, **hkw), reps=args.host_reps)
+        print(json.dumps(res), flush=True)
+    res = {"tool": "datagen_bench", "case": "kernel A/B (gray, no target)", "batch": 64, "device": dev, "reps": args.kernel_reps,
+           "rounds": args.rounds}
+    if args.other_lib:
+        res.update(kernel_ab(args.other_lib, 64, args.kernel_reps, args.rounds, args.warmup))
+    else:
+        res["not_measured"] = "no --other-lib given"
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
