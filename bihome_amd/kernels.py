@@ -497,7 +497,7 @@ def triplet_l1_fwd(f1, f2, f1w, f2w, m1w, m2w, m1=None, m2=None):
 def triplet_hinge_fwd(f1, f2, f1w, f2w, m1w, m2w, margin, m1=None, m2=None):
     """biHomE with the hinge inside the channel sum ('channel-aware', numeric margin: PerceptualHead.py:624-625,644-645); shapes and
     returns as triplet_l1_fwd."""
-    return _triplet_fwd("bh_triplet_hinge_fwd", "triplet_hinge_fwd_kernel", (float(margin),), f1, f2, f1w, f2w, m1w, m2w, m1, m2)
+    return _triplet_fwd("bh_triplet_hinge_fwd", "triplet_fwd_kernel<L1ChannelHinge, 2>", (float(margin),), f1, f2, f1w, f2w, m1w, m2w, m1, m2)
 
 
 def _oneline_fwd(entry, f1, f2, f1w, m1w, margin, m2, rep, sample_w):
@@ -609,7 +609,7 @@ def bihome_loss_bwd(g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden, 
 
 def triplet_hinge_bwd(g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden, H1, H2, margin, mu, joined=False):
     """The adjoint of triplet_hinge_fwd + bihome_loss_fwd; arguments (plus the margin) and returns as bihome_loss_bwd."""
-    return _bihome_bwd("bh_triplet_hinge_bwd", "triplet_hinge_bwd_kernel", 8, (float(margin),), g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2,
+    return _bihome_bwd("bh_triplet_hinge_bwd", "triplet_bwd_kernel<L1ChannelHinge, 2>", 8, (float(margin),), g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2,
                        M1, M2, numden, H1, H2, mu, joined)
 
 

@@ -221,6 +221,9 @@ int bh_warp_bwd_img(const double* H64, const float* g_out, int B, int C, int h, 
 /* ---------------------------------------------------------------------------------------------
  * biHomE triplet L1 reduction (triplet_resnet_loss, double-line / l1 / channel-agnostic / str margin:
  * src/heads/PerceptualHead.py:559-561, 609-665).  Features are NHWC [B,hw,C].
+ * Every entry point of the loss family on [B,hw,C] features (bh_triplet_l1_fwd, bh_bihome_loss_bwd, bh_oneline_loss_*, bh_oneline_cos_loss_*,
+ * bh_triplet_hinge_*): BH_E_BADARG for a NULL operand, B < 0, hw < 1, rep < 1 or B % rep; BH_E_UNSUPPORTED unless C is a multiple of 4
+ * with C / 4 a divisor of 64 or at least 64, and for B > 65535; B == 0 is BH_OK.
  * ------------------------------------------------------------------------------------------- */
 /* M1[B,hw] = sum_c |f1w-f2| - sum_c |f1-f2| ; M2[B,hw] = sum_c |f2w-f1| - sum_c |f1-f2| ;
  * numden[B,4] (double) = { sum m1w*m2*M1, sum m1w*m2, sum m2w*m1*M2, sum m2w*m1 } ; m1,m2 NULL => ones.  flags: BH_F_DETERMINISTIC */
@@ -260,8 +263,7 @@ int bh_oneline_loss_bwd(const float* g_loss, const float* f2, const float* f1w, 
  *   t = c(f1, f2) - c(f1w, f2) + margin  ( = (1 - c1w) - (1 - c13) + margin );  loss as bh_oneline_loss_fwd with this t.
  * Arguments, outputs (T = t before the hinge), the multi-hypothesis form, flags and the batch sum are those of bh_oneline_loss_fwd / _bwd.
  * fp32 per pixel (sqrtf and division), double across pixels.  The adjoint recomputes f1w.f2, |f1w|^2 and |f2|^2 from the two maps it
- * reads anyway; as in torch only the VALUE of a norm is clamped - its gradient f1w / |f1w| is taken wherever |f1w| > 0.
- * BH_E_UNSUPPORTED: B > 65535. */
+ * reads anyway; as in torch only the VALUE of a norm is clamped - its gradient f1w / |f1w| is taken wherever |f1w| > 0. */
 int bh_oneline_cos_loss_fwd(const float* f1, const float* f2, const float* f1w, const float* m1w, const float* m2, int B, int hw,
                             int C, float margin, int rep, const float* sample_w, float* T, double* numden, float* per_sample,
                             float* loss, int flags, void* stream);
@@ -273,7 +275,7 @@ int bh_oneline_cos_loss_bwd(const float* g_loss, const float* f2, const float* f
  *   M1[B,hw] = sum_c max(|f1w_c - f2_c| - |f1_c - f2_c| + margin, 0) ; M2[B,hw] = sum_c max(|f2w_c - f1_c| - |f1_c - f2_c| + margin, 0)
  * numden[B,4] as bh_triplet_l1_fwd (flags: BH_F_DETERMINISTIC); bh_bihome_loss_fwd turns it into the loss.  The adjoint is
  * bh_bihome_loss_bwd's with g_f1w_c = k [t1_c > 0] sgn(f1w_c - f2_c): the per-channel indicator is recomputed (each direction reads
- * three maps), nothing of size [B,hw,C] is stored.  BH_E_UNSUPPORTED: B > 65535. */
+ * three maps), nothing of size [B,hw,C] is stored. */
 int bh_triplet_hinge_fwd(const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
                          const float* m2w, const float* m1, const float* m2, int B, int hw, int C, float margin, float* M1,
                          float* M2, double* numden, int flags, void* stream);

@@ -194,18 +194,22 @@ def test_warp_identity_and_consistency(K):
     assert err.item() < 0.02, err.item()        # same convention => sub-interpolation-noise residual
 
 
-@pytest.mark.parametrize("B,hf,C", [(5, 32, 64), (2, 8, 16), (3, 4, 256), (2, 16, 128)])
-def test_triplet_fwd_bwd(K, B, hf, C):
+# hw = 25 with C = 64 / 16: LP = 16 / 4 lanes per pixel, 4 / 16 pixels per wave pass, the last pass partly filled; C = 512: two float4 per lane
+@pytest.mark.parametrize("masks", [False, True])
+@pytest.mark.parametrize("B,hf,C", [(5, 32, 64), (2, 8, 16), (3, 4, 256), (2, 16, 128), (2, 5, 64), (2, 5, 16), (2, 4, 512)])
+def test_triplet_fwd_bwd(K, B, hf, C, masks):
     rng = np.random.Generator(np.random.PCG64(B + C))
     f = [rng.standard_normal((B, hf, hf, C)).astype(np.float32) for _ in range(4)]
     m1w = rng.uniform(0, 1, (B, hf, hf)).astype(np.float32)
     m2w = rng.uniform(0, 1, (B, hf, hf)).astype(np.float32)
     m1w[0] *= 1e-4                                   # force the max(den, 1) clamp branch on one sample
+    m1, m2 = (rng.uniform(0, 1, (B, hf, hf)).astype(np.float32) for _ in range(2)) if masks else (None, None)      # content masks
+    dm1, dm2 = (dev(m) if masks else None for m in (m1, m2))
     dl = rand_delta(B, 5, 8)
     H1, _ = K.h4pt_fwd(dev(dl), 128)
     H2, _ = K.h4pt_fwd(dev(-dl[::-1].copy()), 128)
     mu = 0.01
-    M1, M2, nd = K.triplet_l1_fwd(*[dev(a) for a in f], dev(m1w), dev(m2w))
+    M1, M2, nd = K.triplet_l1_fwd(*[dev(a) for a in f], dev(m1w), dev(m2w), dm1, dm2)
     loss4 = K.bihome_loss_fwd(nd, H1, H2, mu)
     T = lambda a: torch.tensor(a, dtype=torch.float64)
     f1, f2, f1w, f2w = [T(a).requires_grad_(True) for a in f]
@@ -213,16 +217,17 @@ def test_triplet_fwd_bwd(K, B, hf, C):
     h1 = H1.cpu().reshape(B, 3, 3).clone().requires_grad_(True)
     h2 = H2.cpu().reshape(B, 3, 3).clone().requires_grad_(True)
     l1, l2, l3 = (f1w - f2).abs().sum(-1), (f2w - f1).abs().sum(-1), (f1 - f2).abs().sum(-1)
-    d1, d2 = a1.sum((-1, -2)), a2.sum((-1, -2))
-    ln1 = ((a1 * (l1 - l3)).sum((-1, -2)) / torch.max(d1, torch.ones_like(d1))).sum()
-    ln2 = ((a2 * (l2 - l3)).sum((-1, -2)) / torch.max(d2, torch.ones_like(d2))).sum()
+    w1, w2 = (a1 * T(m2), a2 * T(m1)) if masks else (a1, a2)          # line 1 is weighted by m1w * m2, line 2 by m2w * m1
+    d1, d2 = w1.sum((-1, -2)), w2.sum((-1, -2))
+    ln1 = ((w1 * (l1 - l3)).sum((-1, -2)) / torch.max(d1, torch.ones_like(d1))).sum()
+    ln2 = ((w2 * (l2 - l3)).sum((-1, -2)) / torch.max(d2, torch.ones_like(d2))).sum()
     ln3 = ((h1 @ h2 - torch.eye(3, dtype=torch.float64)) ** 2).sum()
     loss = ln1 + ln2 + mu * ln3
     np.testing.assert_allclose(loss4.cpu().numpy(), [loss.item(), ln1.item(), ln2.item(), ln3.item()], rtol=2e-5)
     np.testing.assert_allclose(M1.cpu().numpy(), (l1 - l3).detach().numpy(), rtol=1e-4, atol=1e-4)
     (loss * 0.7).backward()
     g = torch.tensor([0.7], device="cuda")
-    gf1w, gf2w, gm1w, gm2w, gH1, gH2 = K.bihome_loss_bwd(g, *[dev(a) for a in f], dev(m1w), dev(m2w), None, None, M1, M2,
+    gf1w, gf2w, gm1w, gm2w, gH1, gH2 = K.bihome_loss_bwd(g, *[dev(a) for a in f], dev(m1w), dev(m2w), dm1, dm2, M1, M2,
                                                          nd, H1, H2, mu)
     np.testing.assert_allclose(gf1w.cpu().numpy(), f1w.grad.numpy(), rtol=1e-5, atol=1e-9)
     np.testing.assert_allclose(gf2w.cpu().numpy(), f2w.grad.numpy(), rtol=1e-5, atol=1e-9)
@@ -329,9 +334,14 @@ def test_gpu_pair_generator_matches_reference_fixture(K, golden):
     print("bh_synth_pairs vs reference fixture: max abs difference %.2e (standardised units)" % worst)
 
 
-@pytest.mark.parametrize("B,hf,C,margin", [(3, 32, 64, 1.0), (2, 8, 128, 0.0), (1, 16, 64, 25.0)])
+ACTIVE_MARGINS = (36.0, 9.0, 290.0)        # chosen per shape so that the hinge is active at 20 - 80 % of the pixels (asserted below)
+
+
+@pytest.mark.parametrize("B,hf,C,margin", [(3, 32, 64, 1.0), (2, 8, 128, 0.0), (1, 16, 64, 25.0),
+                                           (2, 5, 64, 36.0), (2, 5, 16, 9.0), (2, 4, 512, 290.0)])
 def test_oneline_hinge_loss_fwd_bwd(B, hf, C, margin):
-    """bh_oneline_loss_fwd/bwd (iHomE, PerceptualHead.py:474-538) against torch float64 autograd of the same formula."""
+    """bh_oneline_loss_fwd/bwd (iHomE, PerceptualHead.py:474-538) against torch float64 autograd of the same formula.  The first three
+    parameter sets leave the hinge (almost) everywhere inactive; the last three have both states and partly filled wave passes."""
     import torch.nn.functional as F
     from bihome_amd import kernels as K
     g = torch.Generator().manual_seed(B * 7 + hf)
@@ -346,6 +356,8 @@ def test_oneline_hinge_loss_fwd_bwd(B, hf, C, margin):
     den = m.sum((-1, -2))
     ref = ((m * torch.clamp(t, min=0)).sum((-1, -2)) / torch.max(den, torch.ones_like(den))).sum()
     ref.backward()
+    if margin in ACTIVE_MARGINS:
+        assert 0.2 < (t > 0).double().mean().item() < 0.8
     loss, T, numden, per = K.oneline_loss_fwd(f1.cuda(), f2.cuda(), f1w.cuda(), m1w.cuda(), margin)
     assert abs(loss.item() - ref.item()) <= 2e-5 * abs(ref.item()) + 1e-6
     gf, gm = K.oneline_loss_bwd(torch.ones(1, device="cuda"), f2.cuda(), f1w.cuda(), m1w.cuda(), T, numden)
@@ -406,18 +418,21 @@ def test_scale_samples_and_scored_hinge_vs_torch64():
     f1, f2 = torch.randn(B, hf, hf, C, generator=g), torch.randn(B, hf, hf, C, generator=g)
     f1w = f2.repeat_interleave(n, 0) + 0.7 * torch.randn(B * n, hf, hf, C, generator=g)
     m1w = torch.rand(B * n, hf, hf, generator=g)
-    a, b, c, m, sc = (t.double().requires_grad_(rq) for t, rq in ((f1, False), (f2, False), (f1w, True), (m1w, True), (s, True)))
-    t = (c - b.repeat_interleave(n, 0)).abs().sum(-1) - (a - b).abs().sum(-1).repeat_interleave(n, 0) + 1.0
-    den = m.sum((-1, -2))
-    per = (m * torch.clamp(t, min=0)).sum((-1, -2)) / torch.max(den, torch.ones_like(den))
-    ref = (per * sc).sum()
-    ref.backward()
-    loss, T, numden, perk = K.oneline_loss_fwd(f1.cuda(), f2.cuda(), f1w.cuda(), m1w.cuda(), 1.0, rep=n, sample_w=s.cuda())
-    assert abs(loss.item() - ref.item()) <= 2e-5 * abs(ref.item())
-    assert (perk.cpu().double() - per.detach()).abs().max() <= 2e-5 * per.detach().abs().max()
-    gf, gm = K.oneline_loss_bwd(torch.ones(1, device="cuda"), f2.cuda(), f1w.cuda(), m1w.cuda(), T, numden, rep=n, sample_w=s.cuda())
-    assert (gf.cpu().double() - c.grad).abs().max() <= 2e-5 * c.grad.abs().max() + 1e-8
-    assert (gm.cpu().double() - m.grad).abs().max() <= 2e-4 * m.grad.abs().max() + 1e-7
+    for margin in (1.0, 36.0):                # 36: the hinge is active at about half of the pixels (1: almost nowhere)
+        a, b, c, m, sc = (t.double().requires_grad_(rq) for t, rq in ((f1, False), (f2, False), (f1w, True), (m1w, True), (s, True)))
+        t = (c - b.repeat_interleave(n, 0)).abs().sum(-1) - (a - b).abs().sum(-1).repeat_interleave(n, 0) + margin
+        if margin > 1.0:
+            assert 0.2 < (t > 0).double().mean().item() < 0.8
+        den = m.sum((-1, -2))
+        per = (m * torch.clamp(t, min=0)).sum((-1, -2)) / torch.max(den, torch.ones_like(den))
+        ref = (per * sc).sum()
+        ref.backward()
+        loss, T, numden, perk = K.oneline_loss_fwd(f1.cuda(), f2.cuda(), f1w.cuda(), m1w.cuda(), margin, rep=n, sample_w=s.cuda())
+        assert abs(loss.item() - ref.item()) <= 2e-5 * abs(ref.item())
+        assert (perk.cpu().double() - per.detach()).abs().max() <= 2e-5 * per.detach().abs().max()
+        gf, gm = K.oneline_loss_bwd(torch.ones(1, device="cuda"), f2.cuda(), f1w.cuda(), m1w.cuda(), T, numden, rep=n, sample_w=s.cuda())
+        assert (gf.cpu().double() - c.grad).abs().max() <= 2e-5 * c.grad.abs().max() + 1e-8
+        assert (gm.cpu().double() - m.grad).abs().max() <= 2e-4 * m.grad.abs().max() + 1e-7
 
 
 @pytest.mark.parametrize("prec", [0, 4])

@@ -13,8 +13,9 @@ from test_loss_variants_cpu import aware_loss, aware_terms, cosine_loss
 
 pytestmark = pytest.mark.gpu
 
-# (B, hf, C): the L1 test's three shapes; hw = 25 (not a multiple of the pixels per wave pass) with LP = 64; two float4 per lane
-SHAPES = [(3, 32, 64), (2, 8, 128), (1, 16, 64), (2, 5, 256), (2, 4, 512)]
+# (B, hf, C): the L1 test's three shapes; hw = 25 with LP = 64 lanes per pixel (one pixel per wave pass); two float4 per lane; hw = 25
+# with LP = 16 (four pixels per pass, the last pass a quarter full) and with LP = 4 (sixteen per pass, the second pass 9 of 16)
+SHAPES = [(3, 32, 64), (2, 8, 128), (1, 16, 64), (2, 5, 256), (2, 4, 512), (2, 5, 64), (2, 5, 16)]
 COS_MARGIN, AWARE_MARGIN = 0.8, 0.5          # c1w ~ 0.82, c13 ~ 0 / |f1w - f2| ~ 0.56, |f1 - f2| ~ 1.13 on these inputs: both hinge states
 FLIP = 1e-5                                  # |t| below this share of its scale: the float32 indicator may differ from the float64 one
 
@@ -144,6 +145,45 @@ def test_deterministic_bit_gives_identical_results():
             runs.append(out)
     for x, y in zip(*runs):
         assert torch.equal(x, y)
+
+
+@pytest.mark.parametrize("metric", ["l1", "hinge"])
+def test_double_line_pair_is_symmetric_in_its_lines(metric):
+    """Swapping the two images - (f2, f1, f2w, f1w, m2w, m1w, m2, m1) - swaps M1 / M2, the halves of numden and the two directions'
+    gradients bit for bit: the adjoint's direction select (the hinge's third operand included) and its batch rotation (B = 3: by 2).
+    ln3 = ||H1 H2 - I||^2 is not symmetric: gH stays out."""
+    from bihome_amd import kernels as K
+    B, hf, C = 3, 5, 64
+    f1, f2, f1w, f2w, m1w, m2w, m1, m2, dl = (_cu(x) for x in aware_inputs(B, hf, C, True))
+    H, _ = K.h4pt_fwd(dl, 128)
+    g = torch.tensor([0.7], device="cuda")
+    if metric == "l1":
+        fwd = K.triplet_l1_fwd
+        bwd = lambda *a: K.bihome_loss_bwd(g, *a, H, H, 0.01)
+    else:
+        fwd = lambda *a: K.triplet_hinge_fwd(*a[:6], AWARE_MARGIN, *a[6:])
+        bwd = lambda *a: K.triplet_hinge_bwd(g, *a, H, H, AWARE_MARGIN, 0.01)
+    ab, ba = (f1, f2, f1w, f2w, m1w, m2w, m1, m2), (f2, f1, f2w, f1w, m2w, m1w, m2, m1)
+    with K.det_scope(True):
+        M1, M2, nd = fwd(*ab)
+        N1, N2, ns = fwd(*ba)
+        gf1w, gf2w, gm1w, gm2w = bwd(*ab, M1, M2, nd)[:4]
+        hf1w, hf2w, hm1w, hm2w = bwd(*ba, N1, N2, ns)[:4]
+    assert M1.abs().max() > 0 and gf1w.abs().max() > 0 and gm1w.abs().max() > 0
+    assert torch.equal(N1, M2) and torch.equal(N2, M1)
+    assert torch.equal(ns[:, :2], nd[:, 2:]) and torch.equal(ns[:, 2:], nd[:, :2])
+    assert torch.equal(hf1w, gf2w) and torch.equal(hf2w, gf1w)
+    assert torch.equal(hm1w, gm2w) and torch.equal(hm2w, gm1w)
+
+
+def test_one_line_value_is_the_double_line_first_line():
+    """T of the one-line L1 loss at margin 0 is M1 of the double-line one on the same three maps: sum |f1w - f2| - sum |f1 - f2|, summed
+    in the same order by the same code."""
+    from bihome_amd import kernels as K
+    f1, f2, f1w, f2w, m1w, m2w = (_cu(x) for x in aware_inputs(2, 5, 64, False)[:6])
+    T = K.oneline_loss_fwd(f1, f2, f1w, m1w, 0.0)[1]
+    M1 = K.triplet_l1_fwd(f1, f2, f1w, f2w, m1w, m2w)[0]
+    assert T.abs().max() > 0 and torch.equal(T, M1)
 
 
 def _head_only(aggregation):
