@@ -75,6 +75,11 @@ SIGNATURES = {
     "bh_triplet_hinge_bwd": [P] * 14 + [c_int, c_int, c_int, c_float, c_float] + [P] * 6 + [P],
     "bh_zhang_triplet_fwd": [P] * 8 + [c_int, c_int, c_float, c_int, P, P, P, P],
     "bh_zhang_triplet_bwd": [P] * 12 + [c_int, c_int, c_int] + [P] * 8 + [P],
+    "bh_l2norm_fwd": [P, c_int, c_int, P, P, P],
+    "bh_l2norm_bwd": [P, P, P, c_int, c_int, P, P],
+    "bh_relu_bwd": [P, P, c_int64, P, P],
+    "bh_oneline_anchor_bwd": [P] * 8 + [c_int, c_int, c_int, c_int, P, c_int, P, P, P],
+    "bh_bihome_anchor_bwd": [P] * 10 + [c_int, c_int, c_int, c_float, c_int, P, P, P],
     "bh_warp_bwd_img": [P, P, c_int, c_int, c_int, c_int, P, P, c_int, P],
     "bh_photo_warp_fwd": [P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],
     "bh_photo_warp_bwd": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, P],

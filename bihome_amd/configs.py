@@ -182,13 +182,23 @@ def _multihead(base):
     return cfg
 
 
+def _proj(cfg):
+    """A config with the trainable projection head on the perceptual features (WITH_PROJECTION_HEAD, PerceptualHead.py:41-48,69-74):
+    64 -> 128 -> 64 on the layer-1 features.  No yaml for it ships upstream (the kwarg is read with a None default)."""
+    cfg["MODEL"]["HEAD"]["WITH_PROJECTION_HEAD"] = [[64, 128], [128, 64]]
+    return cfg
+
+
 def get(name):
     """'zeng-bihome' / 'detone-bihome' = config/s-coco/*; the '-pds' variants = config/pds-coco/* (the two trees differ
     only in HomographyNetPrep's photometric max_delta, 0 vs 32, and the log dir).  'zeng-bihome-rgb256' is the
     build-side extension BASELINE.json configs[4] names (256x256 RGB patches, 6-channel stem; no upstream
     counterpart - SURVEY.md 0).  'nguyen-orig' = config/s-coco/nguyen-orig-lr-5e-3.yaml (PhotometricHead); 'nguyen-orig-pds' =
     config/pds-coco/nguyen-orig-lr-5e-3.yaml, which upstream made a different experiment (NoOpHead + L1Loss), not a data variant.
-    '*-ihome', '*-multihead', '*-ihome-cos' and '*-bihome-aware' are loss-branch variants without a yaml upstream (see their builders)."""
+    '*-ihome', '*-multihead', '*-ihome-cos' and '*-bihome-aware' are loss-branch variants without a yaml upstream (see their builders);
+    'zeng-ihome-proj', 'zeng-ihome-cos-proj' and 'detone-bihome-proj' add the trainable projection head to theirs (`_proj`)."""
+    if name in ("zeng-ihome-proj", "zeng-ihome-cos-proj", "detone-bihome-proj"):
+        return _proj(get(name[:-5]))
     if name == "zeng-bihome-rgb256":
         cfg = copy.deepcopy(ZENG_BIHOME)
         cfg["MODEL"]["BACKBONE"].update(IMAGE_SIZE=256, PATCH_CHANNELS=3)

@@ -5,7 +5,10 @@ delta_hat[B,4,2])`; `predict_homography(data) -> (delta_hat[B,4,2], None)`; stat
 `auxiliary_resnet.resnet.{conv1,bn1,layer1.*}` and `backbone.*` as upstream.  Built loss branches (Model._check_loss_branch):
 double-line 'l1' with a str TRIPLET_MARGIN (the shipped biHomE configs; either TRIPLET_AGGREGATION) or with a numeric margin
 and 'channel-aware'; one-line 'l1' / 'cosine' with a numeric margin; the multihead feature loss (TRIPLET_LOSS '').
-SAMPLING_STRATEGY 'downsample-mask', AUXILIARY_RESNET 'resnet34' layers 1-4; anything else raises with the reason.
+SAMPLING_STRATEGY 'downsample-mask', AUXILIARY_RESNET 'resnet34' layers 1-4; WITH_PROJECTION_HEAD (a trainable per-pixel MLP on the
+frozen features, :41-48,69-74) on the one-line and double-line branches; anything else raises with the reason.
+WITH_PROJECTION_HEAD, one-line: the projected maps are divided by their L2 norm over channels WITHOUT an epsilon, as upstream (:470-479,
+:487-496) - a pixel whose projected vector is exactly zero gives NaN in the loss, as it does upstream.
 Reference: src/heads/PerceptualHead.py:15-767, src/heads/ransac_utils.py:26-161,
 src/data/utils.py:7-59.
 
@@ -61,6 +64,65 @@ class _ResNetStem(nn.Module):
         self.out_channels = cin
 
 
+def _loss_width_ok(c):
+    """The channel counts the loss kernels take (csrc/triplet.hip, csrc/proj.hip)."""
+    return c >= 4 and c % 4 == 0 and (c // 4 >= 64 or 64 % (c // 4) == 0)
+
+
+class _ProjectionHead(nn.ModuleList):
+    """PerceptualHead.py:41-48,69-74: Linear layers with a ReLU between them, applied per pixel to the NHWC feature map.  The container
+    is upstream's nn.ModuleList (state-dict keys `projection_head.{0,2,..}.{weight,bias}`); the layers run as 1x1 convs of a TRAINABLE
+    net.Runner of their own (a ReLU in the epilogue of the Linear in front of it), separate from the frozen extractor's: gradients live
+    in its FlatGrads buffer, step.build_optimizer finds it through net.trainable_runners.  It runs several times per step (unwarped and
+    warped maps): its gradients are final only after the last of those backward walks."""
+
+    def __init__(self, widths, precision):
+        super().__init__()
+        for idx, (cin, cout) in enumerate(widths):
+            self.append(nn.Linear(cin, cout))
+            if idx != len(widths) - 1:
+                self.append(nn.ReLU())
+        # 1x1 convs run the generic fp32 MFMA kernel in every fp32-accurate mode; 'bf16' keeps its bf16 operands
+        self.precision = 'bf16' if K.PRECISION[str(precision).lower()] == 1 else 'f32-mfma'
+        self._runner = None
+
+    def _build(self):
+        prog = net.Program()
+        prog.sequential(0, self)
+        return net.Runner(self, prog, trainable=True, precision=self.precision)
+
+    def forward(self, x):
+        """x NHWC [N,h,w,Cin] -> [N,h,w,Cout], one autograd node (net.NetFunction)."""
+        if self._runner is None:
+            self._runner = self._build()
+        return self._runner(x.contiguous(), 1)
+
+
+def _projection_widths(spec, in_channels):
+    """Validate WITH_PROJECTION_HEAD (a list of [in, out] pairs, PerceptualHead.py:44-48) against what the kernels take."""
+    try:
+        widths = [(int(a), int(b)) for a, b in spec]
+    except (TypeError, ValueError):
+        widths = []
+    if not widths:
+        raise NotImplementedError("WITH_PROJECTION_HEAD must be a non-empty list of [in, out] pairs (PerceptualHead.py:44-48), got %r"
+                                  % (spec,))
+    if widths[0][0] != in_channels:
+        raise ValueError("WITH_PROJECTION_HEAD: the first layer takes %d channels, the extractor's output layer has %d (64 * 2^(layer - 1))"
+                         % (widths[0][0], in_channels))
+    for (_, a), (b, _) in zip(widths[:-1], widths[1:]):
+        if a != b:
+            raise ValueError("WITH_PROJECTION_HEAD: consecutive layers do not chain (%d outputs into %d inputs)" % (a, b))
+    for _, hidden in widths[:-1]:
+        if hidden < 4 or hidden % 4:
+            raise NotImplementedError("WITH_PROJECTION_HEAD: hidden width %d - the conv route of the Linear layers and the ReLU adjoint "
+                                      "work on float4 groups: hidden widths are multiples of 4" % hidden)
+    if not _loss_width_ok(widths[-1][1]):
+        raise NotImplementedError("WITH_PROJECTION_HEAD: last width %d - the loss kernels take a multiple of 4 whose quarter divides 64 "
+                                  "or is at least 64 (4, 8, 16, 32, 64, 128, 256, 260, ...)" % widths[-1][1])
+    return widths
+
+
 class AuxiliaryResnet(nn.Module):
     """PerceptualHead.py:15-76 for AUXILIARY_RESNET='resnet34', AUXILIARY_RESNET_OUTPUT_LAYER 1..4 (:24-33,:62-67).
     Output is NHWC [N, h/s, w/s, C] with (s, C) = (4, 64), (8, 128), (16, 256), (32, 512) - the layout the triplet
@@ -72,8 +134,6 @@ class AuxiliaryResnet(nn.Module):
         self.output_layer = int(kwargs.get('AUXILIARY_RESNET_OUTPUT_LAYER', 1))
         if kwargs.get('AUXILIARY_RESNET', 'resnet34') != 'resnet34' or not 1 <= self.output_layer <= 4:
             raise NotImplementedError("only AUXILIARY_RESNET='resnet34' with OUTPUT_LAYER 1..4 is built")
-        if kwargs.get('WITH_PROJECTION_HEAD') is not None:
-            raise NotImplementedError("WITH_PROJECTION_HEAD is not used by any shipped config")
         self.resnet = _ResNetStem(self.output_layer)
         self.stride = 4 << (self.output_layer - 1)      # feature-map stride = the mask downsample factor (:450)
         self.freeze = kwargs.get('AUXILIARY_RESNET_FREEZE', True)
@@ -82,6 +142,12 @@ class AuxiliaryResnet(nn.Module):
         for p in self.resnet.parameters():          # PerceptualHead.py:36-39
             p.requires_grad = False
         self.precision = kwargs.get('PRECISION', os.environ.get('BIHOME_PRECISION', 'f32'))
+        # PerceptualHead.py:41-48: trainable whatever the extractor's freeze (only self.resnet is frozen, :36-39)
+        self.with_projection_head = kwargs.get('WITH_PROJECTION_HEAD')
+        if self.with_projection_head is not None:
+            self.projection_head = _ProjectionHead(_projection_widths(self.with_projection_head, self.resnet.out_channels), self.precision)
+        else:
+            self.projection_head = nn.ModuleList()
         net.to_kernel_layout_(self)
         self._runners = {}
         self._fold = {}             # one BatchNorm-folding cache for every program over these modules
@@ -106,8 +172,13 @@ class AuxiliaryResnet(nn.Module):
             self._runners[in_ch] = net.Runner(self, prog, trainable=False, precision=self.precision, fold_cache=self._fold)
         return self._runners[in_ch]
 
+    def project(self, feat):
+        """The projection head on NHWC features (PerceptualHead.py:69-74); differentiable w.r.t. `feat` and the head's parameters."""
+        return self.projection_head(feat)
+
     def forward(self, x, groups=1):
-        """x [N,1|3,h,w] NCHW -> NHWC features; BatchNorms follow self.training (batch statistics in
+        """x [N,1|3,h,w] NCHW -> NHWC features of the frozen extractor (the projection head is applied by the loss nodes: `project`);
+        BatchNorms follow self.training (batch statistics in
         training although the weights are frozen - SURVEY.md 7), one statistic set per group."""
         net.to_kernel_layout_(self)
         N, C, h, w = x.shape
@@ -266,7 +337,16 @@ class _BiHomELoss(torch.autograd.Function):
         H64, H32 = K.h4pt_fwd(delta, h)                          # _warp -> four_point_to_homography :237-243
         pool = aux.stride                                        # :450 downsample_factor = mask size // feature size
         warped, cov, wl, featw = _extractor_of_warp(aux, patches, H64, pool, groups=2)      # :371-382,:392-401,:447-459
-        f1, f2, f1w, f2w = feat[:B], feat[B:], featw.detach()[:B], featw.detach()[B:]
+        proj = None
+        if aux.with_projection_head is not None:                 # :69-74; the double-line maps are NOT normalised (:545-557 commented out)
+            with torch.enable_grad():
+                fwl = featw.detach().requires_grad_(True)
+                pa, pw = aux.project(feat), aux.project(fwl)
+            proj = (pa, pw, fwl)
+            pre, feat, fw = (feat, featw.detach()), pa.detach(), pw.detach()
+        else:
+            fw = featw.detach()
+        f1, f2, f1w, f2w = feat[:B], feat[B:], fw[:B], fw[B:]
         m1w, m2w = cov[:B], cov[B:]
         if head.hinge_per_channel:                               # numeric margin, 'channel-aware' :624-625,:644-645
             M1, M2, numden = K.triplet_hinge_fwd(f1, f2, f1w, f2w, m1w, m2w, head.triplet_margin)
@@ -274,25 +354,36 @@ class _BiHomELoss(torch.autograd.Function):
             M1, M2, numden = K.triplet_l1_fwd(f1, f2, f1w, f2w, m1w, m2w)      # :559-561,:609-653
         loss4 = K.bihome_loss_fwd(numden, H64[:B], H64[B:], head.triplet_mu)   # :656-665
         ctx.head, ctx.B, ctx.pool = head, B, pool
-        ctx.saved = (delta, patches, H64, feat, featw, wl, cov, M1, M2, numden)
+        ctx.saved = (delta, patches, H64, feat, featw, wl, cov, M1, M2, numden, fw, proj)
         head.last = {"loss4": loss4, "H_4pt": H32, "warped": warped, "coverage": cov, "numden": numden,
                      "f1": f1, "f2": f2, "f1w": f1w}
+        if proj is not None:
+            head.last.update(features=pre[0], features_warped=pre[1])      # the extractor's maps, in front of the projection
         return loss4[0]
 
     @staticmethod
     def backward(ctx, g_loss):
-        delta, patches, H64, feat, featw, wl, cov, M1, M2, numden = ctx.saved
+        delta, patches, H64, feat, featw, wl, cov, M1, M2, numden, fw, proj = ctx.saved
         ctx.saved = None
         B, head = ctx.B, ctx.head
         h = patches.shape[-1]
         g = g_loss.reshape(1).to(torch.float32).contiguous()
-        fw = featw.detach()
         if head.hinge_per_channel:
             gfeatw, gcov, gH = K.triplet_hinge_bwd(g, feat[:B], feat[B:], fw[:B], fw[B:], cov[:B], cov[B:], None, None, M1, M2, numden,
                                                    H64[:B], H64[B:], head.triplet_margin, head.triplet_mu, joined=True)
         else:
             gfeatw, gcov, gH = K.bihome_loss_bwd(g, feat[:B], feat[B:], fw[:B], fw[B:], cov[:B], cov[B:], None, None, M1, M2, numden,
                                                  H64[:B], H64[B:], head.triplet_mu, joined=True)      # (both directions in one tensor each)
+        if proj is not None:
+            # the unwarped maps carry gradient into the projection's weights; then its two backward walks (weight gradients accumulate,
+            # the input gradient of the warped maps only - the extractor is frozen)
+            pa, pw, fwl = proj
+            ga = torch.empty_like(feat)
+            K.bihome_anchor_bwd(g, feat[:B], feat[B:], fw[:B], fw[B:], cov[:B], cov[B:], numden,
+                                margin=head.triplet_margin if head.hinge_per_channel else None, out=ga)
+            if pa.requires_grad:                                 # (not when every projection parameter was frozen by the caller)
+                torch.autograd.backward([pa], [ga])
+            (gfeatw,) = torch.autograd.grad(pw, fwl, gfeatw)
         _extractor_dgrad_into_warp(head.auxiliary_resnet, featw, wl, gfeatw, patches, H64, gcov, ctx.pool, gH)
         gdelta = K.h4pt_bwd(delta, H64, gH, h)
         return gdelta, None, None
@@ -324,22 +415,44 @@ class _IHomELoss(torch.autograd.Function):
         warped, cov, wl, featw = _extractor_of_warp(aux, p1, H64, pool, groups=1)           # :371-382 + downsample (:447-451)
         sw = scores.contiguous() if scores is not None else None
         cosine = head.triplet_distance == 'cosine'               # :485-499 instead of :468-482
+        proj = None
+        if aux.with_projection_head is not None:
+            # :69-74, then x / |x|_2 over channels of all three maps (:470-479, :487-496); f1 and f2 in one call (per-pixel layers)
+            with torch.enable_grad():
+                fwl = featw.detach().requires_grad_(True)
+                pa, pw = aux.project(feat), aux.project(fwl)
+            pre = (feat, featw.detach())
+            (feat, ia), (fw, iw) = K.l2norm_fwd(pa.detach()), K.l2norm_fwd(pw.detach())
+            proj = (pa, pw, fwl, feat, ia, iw)
+        else:
+            fw = featw.detach()
         loss, T, numden, per = (K.oneline_cos_loss_fwd if cosine else K.oneline_loss_fwd)(
-            feat[:B], feat[B:], featw.detach(), cov, head.triplet_margin, rep=n, sample_w=sw)    # :474-533
+            feat[:B], feat[B:], fw, cov, head.triplet_margin, rep=n, sample_w=sw)    # :474-533
         ctx.head, ctx.pool, ctx.n, ctx.cosine = head, pool, n, cosine
-        ctx.saved = (delta, p1, H64, feat[B:], featw, wl, cov, T, numden, sw, per)
+        ctx.saved = (delta, p1, H64, feat[B:], featw, wl, cov, T, numden, sw, per, fw, proj)
         head.last = {"loss4": loss, "H_4pt": H32, "warped": warped, "coverage": cov, "f1": feat[:B], "f2": feat[B:],
-                     "f1w": featw.detach()}
+                     "f1w": fw}
+        if proj is not None:
+            head.last.update(features=pre[0], features_warped=pre[1])      # the extractor's maps, in front of the projection
         return loss[0]
 
     @staticmethod
     def backward(ctx, g_loss):
-        delta, p1, H64, f2, featw, wl, cov, T, numden, sw, per = ctx.saved
+        delta, p1, H64, f2, featw, wl, cov, T, numden, sw, per, fw, proj = ctx.saved
         ctx.saved = None
         h = p1.shape[-1]
         g = g_loss.reshape(1).to(torch.float32).contiguous()
-        gfw, gcov = (K.oneline_cos_loss_bwd if ctx.cosine else K.oneline_loss_bwd)(g, f2, featw.detach(), cov, T, numden, rep=ctx.n,
-                                                                                   sample_w=sw)
+        gfw, gcov = (K.oneline_cos_loss_bwd if ctx.cosine else K.oneline_loss_bwd)(g, f2, fw, cov, T, numden, rep=ctx.n, sample_w=sw)
+        if proj is not None:
+            # anchor adjoint -> normalisation adjoints -> the projection's two backward walks (weight gradients accumulate; the input
+            # gradient of the warped maps only - the extractor is frozen)
+            pa, pw, fwl, ya, ia, iw = proj
+            B = ya.shape[0] // 2
+            ga = torch.empty_like(ya)
+            K.oneline_anchor_bwd(g, ya[:B], ya[B:], fw, cov, T, numden, rep=ctx.n, sample_w=sw, cosine=ctx.cosine, out=ga)
+            if pa.requires_grad:                                 # (not when every projection parameter was frozen by the caller)
+                torch.autograd.backward([pa], [K.l2norm_bwd(ga, ya, ia)])
+            (gfw,) = torch.autograd.grad(pw, fwl, K.l2norm_bwd(gfw, fw, iw))
         gH = torch.zeros_like(H64)
         _extractor_dgrad_into_warp(ctx.head.auxiliary_resnet, featw, wl, gfw, p1, H64, gcov, ctx.pool, gH)
         gdelta = K.h4pt_bwd(delta, H64, gH, h)
@@ -419,6 +532,10 @@ class Model(nn.Module):
             self._check_loss_branch(kwargs)
         self.triplet_mu = kwargs.get('TRIPLET_MU', 0.0)
         self.triplet_margin = kwargs.get('TRIPLET_MARGIN')
+        if self.multihead and kwargs.get('WITH_PROJECTION_HEAD') is not None:
+            raise NotImplementedError("WITH_PROJECTION_HEAD with the multihead feature loss (TRIPLET_LOSS '') is not built: the projected "
+                                      "features of patch_2 are repeated per hypothesis (PerceptualHead.py:276-280) and the trainable "
+                                      "projection would need the gradient w.r.t. a repeated feature map; built: 'one-line', 'double-line'")
         self.auxiliary_resnet = AuxiliaryResnet(**kwargs)
         self.last = {}
         # The features of the two unwarped patches depend on the batch only, not on the backbone: their extractor pass is

@@ -614,6 +614,74 @@ def triplet_hinge_bwd(g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2, M1, M2, numden
 
 
 # ------------------------------------------------------------------------------------------------
+# trainable projection head (csrc/proj.hip)
+# ------------------------------------------------------------------------------------------------
+def l2norm_fwd(x):
+    """x [..., C] -> (y = x / |x|_2 over the last axis, inv[...] = 1 / |x|_2): PerceptualHead.py:470-479 (no epsilon, as upstream)."""
+    _chk(x)
+    C = x.shape[-1]
+    y, inv = torch.empty_like(x), torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    with _Timed("l2norm_fwd_kernel", 0.0, 8.0 * x.numel()):
+        check(lib.bh_l2norm_fwd(_p(x), x.numel() // C, C, _p(y), _p(inv), _stream()), "bh_l2norm_fwd")
+    return y, inv
+
+
+def l2norm_bwd(g, y, inv):
+    """gx = inv (g - y (y . g)): the adjoint of l2norm_fwd from its outputs."""
+    _chk(g); _chk(y); _chk(inv)
+    C = y.shape[-1]
+    gx = torch.empty_like(y)
+    with _Timed("l2norm_bwd_kernel", 0.0, 12.0 * y.numel()):
+        check(lib.bh_l2norm_bwd(_p(g), _p(y), _p(inv), y.numel() // C, C, _p(gx), _stream()), "bh_l2norm_bwd")
+    return gx
+
+
+def relu_bwd(gy, y):
+    """gx = gy [y > 0] (y: the ReLU's output)."""
+    _chk(gy); _chk(y)
+    gx = torch.empty_like(gy)
+    with _Timed("relu_bwd_kernel", 0.0, 12.0 * y.numel()):
+        check(lib.bh_relu_bwd(_p(gy), _p(y), y.numel(), _p(gx), _stream()), "bh_relu_bwd")
+    return gx
+
+
+def oneline_anchor_bwd(g_loss, f1, f2, f1w, m1w, T, numden, m2=None, rep=1, sample_w=None, cosine=False, out=None):
+    """(g_f1, g_f2) [samples,hf,wf,C]: the gradient of oneline_loss_fwd / oneline_cos_loss_fwd w.r.t. the unwarped maps, the `rep`
+    hypotheses of a sample added in order (include/bihome.h bh_oneline_anchor_bwd).  out: a [2 samples,hf,wf,C] tensor whose halves take
+    the two gradients."""
+    for t in (g_loss, f1, f2, f1w, m1w, T, m2, sample_w):
+        _chk(t)
+    _chk(numden, torch.float64)
+    B, hf, wf, C = f1w.shape
+    if out is None:
+        out = torch.empty((2 * f1.shape[0],) + tuple(f1.shape[1:]), dtype=torch.float32, device=f1.device)
+    _chk(out)
+    g_f1, g_f2 = out[:f1.shape[0]], out[f1.shape[0]:]
+    with _Timed("oneline_anchor_bwd_kernel", 0.0, 4.0 * (4 * f1.numel() + f1w.numel())):
+        check(lib.bh_oneline_anchor_bwd(_p(g_loss), _p(f1), _p(f2), _p(f1w), _p(m1w), _p(m2), _p(T), _p(numden), B, hf * wf, C, rep,
+                                        _p(sample_w), int(bool(cosine)), _p(g_f1), _p(g_f2), _stream()), "bh_oneline_anchor_bwd")
+    return g_f1, g_f2
+
+
+def bihome_anchor_bwd(g_loss, f1, f2, f1w, f2w, m1w, m2w, numden, m1=None, m2=None, margin=None, out=None):
+    """(g_f1, g_f2) [B,hf,wf,C]: the gradient of triplet_l1_fwd (margin None) / triplet_hinge_fwd (numeric margin) + bihome_loss_fwd
+    w.r.t. the unwarped maps (include/bihome.h bh_bihome_anchor_bwd).  out: a [2B,hf,wf,C] tensor whose halves take the two gradients."""
+    for t in (g_loss, f1, f2, f1w, f2w, m1w, m2w, m1, m2):
+        _chk(t)
+    _chk(numden, torch.float64)
+    B, hf, wf, C = f1.shape
+    if out is None:
+        out = torch.empty((2 * B, hf, wf, C), dtype=torch.float32, device=f1.device)
+    _chk(out)
+    g_f1, g_f2 = out[:B], out[B:]
+    with _Timed("bihome_anchor_bwd_kernel", 0.0, 4.0 * 6 * f1.numel()):
+        check(lib.bh_bihome_anchor_bwd(_p(g_loss), _p(f1), _p(f2), _p(f1w), _p(f2w), _p(m1w), _p(m2w), _p(m1), _p(m2), _p(numden), B, hf * wf,
+                                       C, float(margin or 0.0), int(margin is not None), _p(g_f1), _p(g_f2), _stream()),
+              "bh_bihome_anchor_bwd")
+    return g_f1, g_f2
+
+
+# ------------------------------------------------------------------------------------------------
 # conv stacks
 # ------------------------------------------------------------------------------------------------
 # conv arithmetic (bh_conv_desc.precision).  'f32' (default) asks for fp32 ACCURACY and lets the library pick the evaluation.

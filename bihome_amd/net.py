@@ -162,9 +162,11 @@ class Program:
         self.nslots += 1
         return self.nslots - 1
 
-    def conv(self, src, mod, in_nchw=False, out_nchw=False, weight_fn=None):
+    def conv(self, src, mod, in_nchw=False, out_nchw=False, weight_fn=None, relu=False):
+        """relu: the activation in the conv's own epilogue (bh_conv_fwd_act) - a conv / Linear followed directly by nn.ReLU, no BatchNorm
+        in between (the projection head's layers); its adjoint masks the output gradient first (kernels.relu_bwd)."""
         dst = self._new()
-        self.ops.append(Op("conv", src, dst, mod, extra={"in_nchw": in_nchw, "out_nchw": out_nchw, "weight_fn": weight_fn}))
+        self.ops.append(Op("conv", src, dst, mod, relu=relu, extra={"in_nchw": in_nchw, "out_nchw": out_nchw, "weight_fn": weight_fn}))
         return dst
 
     def bn(self, src, mod, relu=False, res=None):
@@ -196,7 +198,10 @@ class Program:
         while i < len(mods):
             m = mods[i]
             if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d, nn.Linear)):
-                src = self.conv(src, m)
+                relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                src = self.conv(src, m, relu=relu)
+                if relu:
+                    i += 1
             elif isinstance(m, nn.BatchNorm2d):
                 relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
                 src = self.bn(src, m, relu=relu)
@@ -377,7 +382,9 @@ def _fw_conv(s, i, op, src):
         pk = packer.entries[id(op.mod.weight)]
     wsrc = s.input_source if op.src == 0 else None
     fused_stats = s.plan.fused_stats
-    if i in fused_stats and d.N % groups == 0:
+    if op.relu:
+        out = K.conv_fwd(src, wk, op.mod.bias, d, relu=True, wpacked=pk[1] if pk else None, warp_src=wsrc)
+    elif i in fused_stats and d.N % groups == 0:
         b = fused_stats[i]
         out = K.conv_fwd(src, wk, op.mod.bias, d, bn_sums=_bn_stats_slice(s, b, d.Co), groups=groups,
                          wpacked=pk[1] if pk else None, warp_src=wsrc)
@@ -595,6 +602,8 @@ def _enqueue_wgrad(s, i, op, g, x, d):
 def _bw_conv(s, i, op, g, x, need_src_grad):
     ctx, plan, grads = s.ctx, s.plan, s.grads
     d, wk = ctx.descs[i], ctx.weights[i]
+    if op.relu:                                   # the activation ran in this conv's epilogue: its adjoint in front of everything else
+        g = K.relu_bwd(g, s.slots[op.dst])
     if s.want_wgrad and op.mod.weight.requires_grad and op.extra["weight_fn"] is None:
         _enqueue_wgrad(s, i, op, g, x, d)
     if not need_src_grad:
@@ -821,7 +830,8 @@ _RUNNERS = weakref.WeakSet()
 
 def trainable_runners(model):
     """Every conv-stack executor of `model` that owns a flat gradient buffer (built now if the module has not run yet): the backbone's,
-    and for the ContentAware backbone the feature extractor's and a trained mask predictor's."""
+    for the ContentAware backbone the feature extractor's and a trained mask predictor's, and a PerceptualHead's projection head
+    (heads.PerceptualHead._ProjectionHead)."""
     out = []
     for m in model.modules():
         if not (hasattr(m, "_build") and hasattr(m, "__dict__") and "_runner" in m.__dict__):

@@ -69,7 +69,7 @@ def plan_fused_stats(prog, ix, training):
         for i, op in enumerate(ops):
             j = ix.producer.get(op.src)
             if (op.kind == "bn" and j is not None and ops[j].kind == "conv" and ix.users.get(op.src, 0) == 1
-                    and not ops[j].extra["out_nchw"] and ops[j].mod.weight.dim() == 4):
+                    and not ops[j].extra["out_nchw"] and ops[j].mod.weight.dim() == 4 and not ops[j].relu):
                 fused_stats[j] = i
     return fused_stats
 
@@ -150,7 +150,7 @@ def plan_folded(prog, ix, fold):
         for i, op in enumerate(ops):
             j = ix.producer.get(op.src)
             if (op.kind == "bn" and j is not None and ops[j].kind == "conv" and ix.users.get(op.src, 0) == 1
-                    and not ops[j].extra["out_nchw"]):
+                    and not ops[j].extra["out_nchw"] and not ops[j].relu):
                 folded[i] = j
     return folded
 
@@ -246,7 +246,7 @@ def plan_fuse_bias(prog, ix, ctx, want_wgrad, fuse_bn):
         for j, op in enumerate(ops):
             p = ix.producer.get(op.src)
             if (op.kind == "conv" and j not in fuse_bn and p is not None and ops[p].kind == "conv" and ix.users.get(op.src, 0) == 1
-                    and j in descs and p in descs and descs[j].bh_reduce_ok):
+                    and j in descs and p in descs and descs[j].bh_reduce_ok and not ops[p].relu):
                 pm = ops[p].mod
                 if pm.bias is not None and pm.bias.requires_grad and pm.weight.requires_grad and ops[p].extra["weight_fn"] is None:
                     fuse_bias[j] = p

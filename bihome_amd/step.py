@@ -265,7 +265,8 @@ class _Reducers:
 def attach_reducer(model, bucket_bytes=8 << 20):
     """Data-parallel training: give every trainable runner of the backbone a FlatGradReducer (RCCL all-reduce SUM of its flat
     gradient buffer, launched bucket by bucket from inside the backward pass).  Rethinking / ResNet34 own one buffer; the ContentAware
-    backbone (round 4: round-3 VERDICT missing #3) two - the resnet's and the feature extractor's."""
+    backbone (round 4: round-3 VERDICT missing #3) two - the resnet's and the feature extractor's.  A PerceptualHead with a projection
+    head (WITH_PROJECTION_HEAD) owns one more: it runs several times per step, so its exchange is deferred to allreduce()."""
     from .ddp import FlatGradReducer
     backbone = model[0]
     runners = []
@@ -280,6 +281,12 @@ def attach_reducer(model, bucket_bytes=8 << 20):
                 net.to_kernel_layout_(sub)
                 sub._runner = sub._build()
             runners.append(sub._runner)
+    aux = getattr(model[1], "auxiliary_resnet", None) if len(model) > 1 else None
+    ph = getattr(aux, "projection_head", None)
+    if ph is not None and hasattr(ph, "_build"):
+        if ph._runner is None:
+            ph._runner = ph._build()
+        runners.append(ph._runner)
     dev = next(backbone.parameters()).device
     reds = []
     for k, r in enumerate(runners):

@@ -314,6 +314,41 @@ int bh_scale_samples_bwd(const float* g_y, const float* x, const float* s, int B
                          int flags, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Trainable projection head on the perceptual features (AuxiliaryResnet WITH_PROJECTION_HEAD, src/heads/PerceptualHead.py:41-48,
+ * 69-74; csrc/proj.hip).  Its Linear layers run as 1x1 convs (bh_conv_fwd_act / bh_conv_dgrad / bh_conv_wgrad); below is the rest.
+ * C of every map: the loss kernels' set (a multiple of 4 with C / 4 a divisor of 64 or at least 64, else BH_E_UNSUPPORTED).  No atomics:
+ * every output element has one writer and a fixed summation order (bitwise repeatable in every mode).
+ * --------------------------------------------------------------------------------------------- */
+/* The L2 normalisation over channels of the one-line loss (src/heads/PerceptualHead.py:470-479, 487-496: x / torch.norm(x, p=2, dim=1)):
+ *   y[M,C] = x / |x|_2 per pixel, inv[M] = 1 / |x|_2.  No epsilon, as upstream: a zero vector gives NaN in y and in the gradients.
+ * adjoint: gx = inv (g - y (y . g)). */
+int bh_l2norm_fwd(const float* x, int M, int C, float* y, float* inv, void* stream);
+int bh_l2norm_bwd(const float* g, const float* y, const float* inv, int M, int C, float* gx, void* stream);
+/* The adjoint of the nn.ReLU between two projection layers (src/heads/PerceptualHead.py:46-47): gx[n] = gy [y > 0], y the ReLU's
+ * OUTPUT; n a multiple of 4. */
+int bh_relu_bwd(const float* gy, const float* y, long long n, float* gx, void* stream);
+/* The gradient of the one-line loss (bh_oneline_loss_fwd, cosine = 0: src/heads/PerceptualHead.py:481-482; bh_oneline_cos_loss_fwd,
+ * cosine = 1: :498-499; hinge, scores and masks :505-538) w.r.t. the UNWARPED maps - what bh_oneline_loss_bwd / _cos_loss_bwd leave out
+ * because a frozen extractor has no use for it.  Arguments as the forward's (B hypotheses = samples * rep, T and numden its outputs);
+ *   k_q = [T_q > 0] g_loss sample_w_q m1w_q m2 / max(den_q, 1)      (the existing adjoint's k), q = b rep + h
+ *   l1:      g_f1[b] = - sum_h k_q sgn(f1 - f2)           g_f2[b] = sum_h k_q (sgn(f1 - f2) - sgn(f1w_q - f2))
+ *   cosine:  g_f1[b] = sum_h k_q dc(f1, f2)/df1           g_f2[b] = sum_h k_q (dc(f1, f2)/df2 - dc(f1w_q, f2)/df2)
+ * g_f1, g_f2 [B / rep, hw, C] (overwritten): per SAMPLE, the hypotheses added in the order h = 0 .. rep - 1 by one thread.  The cosine
+ * form keeps bh_oneline_cos_loss_bwd's convention: the value of a norm is clamped at 1e-8, its gradient is not and is 0 at the zero
+ * vector. */
+int bh_oneline_anchor_bwd(const float* g_loss, const float* f1, const float* f2, const float* f1w, const float* m1w, const float* m2,
+                          const float* T, const double* numden, int B, int hw, int C, int rep, const float* sample_w, int cosine,
+                          float* g_f1, float* g_f2, void* stream);
+/* The same for the double-line loss (bh_triplet_l1_fwd, hinge = 0: src/heads/PerceptualHead.py:559-561, 617-620; bh_triplet_hinge_fwd,
+ * hinge = 1: :624-625, 644-645; masks and sums :631-657): ka = g_loss m1w m2 / max(den1, 1), kb = g_loss m2w m1 / max(den2, 1),
+ *   g_f1 = - ka I1 sgn(f1 - f2) - kb I2 (sgn(f2w - f1) + sgn(f1 - f2))      g_f2 = ka I1 (sgn(f1 - f2) - sgn(f1w - f2)) + kb I2 sgn(f1 - f2)
+ * with I1 = I2 = 1, or per channel the forward's indicators [|f1w - f2| - |f1 - f2| + margin > 0], [|f2w - f1| - |f1 - f2| + margin > 0].
+ * numden[B,4] the forward's; m1 / m2 may be NULL (= 1); g_f1, g_f2 [B,hw,C] overwritten.  Elementwise. */
+int bh_bihome_anchor_bwd(const float* g_loss, const float* f1, const float* f2, const float* f1w, const float* f2w, const float* m1w,
+                         const float* m2w, const float* m1, const float* m2, const double* numden, int B, int hw, int C, float margin,
+                         int hinge, float* g_f1, float* g_f2, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Conv stacks (Rethinking._forward src/backbones/Rethinking.py:284-294 with blocks
  * src/backbones/utils.py:60-131; ResNet34 src/backbones/ResNet34.py:15-28; AuxiliaryResnet.forward
  * src/heads/PerceptualHead.py:50-76).  Replace ATen conv2d / conv_transpose2d / batch_norm / relu /
