@@ -592,6 +592,11 @@ class Model(nn.Module):
         e1, e2 = self.patch_keys
         p1, p2 = data[e1], data[e2]
         B = p1.shape[0]
+        P = self.patch_size
+        for e, t in ((e1, p1), (e2, p2)):
+            if t.dim() != 4 or tuple(t.shape[-2:]) != (P, P):
+                raise ValueError("PerceptualHead: '%s' must be [B,C,%d,%d] (PATCH_SIZE x PATCH_SIZE square patches), got %s"
+                                 % (e, P, P, tuple(t.shape)))
         return torch.cat([p1.reshape(B, -1, self.patch_size, self.patch_size),
                           p2.reshape(B, -1, self.patch_size, self.patch_size)], 0)
 

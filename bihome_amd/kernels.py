@@ -206,21 +206,30 @@ def _chk(t, dtype=torch.float32):
 # ------------------------------------------------------------------------------------------------
 # geometry
 # ------------------------------------------------------------------------------------------------
+def _extents(size):
+    """size: one number for a square patch, or a (W, H) pair -> (W, H) floats."""
+    W, H = size if isinstance(size, (tuple, list)) else (size, size)
+    return float(W), float(H)
+
+
 def h4pt_fwd(delta, size):
-    """delta [B,4,2] f32 -> (H64 [B,9] f64, H32 [B,3,3] f32)."""
+    """delta [B,4,2] f32 -> (H64 [B,9] f64, H32 [B,3,3] f32); size: the patch extent, or (W, H) for the corners
+    [[0,0],[W,0],[W,H],[0,H]]."""
     _chk(delta)
+    W, H = _extents(size)
     B = delta.shape[0]
     H64 = torch.empty(B, 9, dtype=torch.float64, device=delta.device)
     H32 = torch.empty(B, 3, 3, dtype=torch.float32, device=delta.device)
-    check(lib.bh_h4pt_fwd(_p(delta), B, float(size), float(size), _p(H64), _p(H32), _stream()), "bh_h4pt_fwd")
+    check(lib.bh_h4pt_fwd(_p(delta), B, W, H, _p(H64), _p(H32), _stream()), "bh_h4pt_fwd")
     return H64, H32
 
 
 def h4pt_bwd(delta, H64, gH, size):
     _chk(delta); _chk(H64, torch.float64); _chk(gH, torch.float64)
+    W, H = _extents(size)
     B = delta.shape[0]
     gd = torch.empty(B, 4, 2, dtype=torch.float32, device=delta.device)
-    check(lib.bh_h4pt_bwd(_p(delta), _p(H64), _p(gH), B, float(size), float(size), _p(gd), _stream()), "bh_h4pt_bwd")
+    check(lib.bh_h4pt_bwd(_p(delta), _p(H64), _p(gH), B, W, H, _p(gd), _stream()), "bh_h4pt_bwd")
     return gd
 
 

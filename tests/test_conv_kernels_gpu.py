@@ -20,10 +20,14 @@ def rnd(shape, seed):
     return np.random.Generator(np.random.PCG64(seed)).standard_normal(shape).astype(np.float32)
 
 
+ERRORS = []          # every close() leaves its (normalised error, tolerance) here: a caller can print the largest of a case under `pytest -s`
+
+
 def close(a, ref, tol=3e-5):
     a, ref = np.asarray(a, np.float64), np.asarray(ref, np.float64)
     scale = np.abs(ref).max() + 1e-30
     err = np.abs(a - ref).max() / scale
+    ERRORS.append((err, tol))
     assert err < tol, "max normalised error %.3e (tol %.1e)" % (err, tol)
 
 
@@ -35,13 +39,23 @@ CONV_CASES = [
     (1, 20, 24, 40, 3, 1, 1), (1, 1, 512, 8, 1, 1, 0),
 ]
 
+# (N, Hi, Wi, Ci, Co, k, stride, pad) with Hi != Wi; tests/test_rectangular_gpu.py runs each as Hi x Wi and as Wi x Hi.  Widths 16 / 32 / 64 with a
+# power-of-two Hi * Wi take the shift decodes of the kernels' pixel -> (image, row, column) maps, the others the divisions
+RECT_CONV_CASES = [
+    (2, 16, 32, 64, 64, 3, 1, 1), (1, 20, 28, 24, 40, 3, 1, 1), (2, 16, 32, 64, 128, 3, 2, 1), (2, 12, 20, 64, 128, 3, 2, 1),
+    (2, 16, 24, 64, 128, 1, 2, 0), (1, 32, 64, 32, 16, 1, 1, 0), (1, 24, 40, 16, 128, 1, 1, 0),
+]
 
-@pytest.mark.parametrize("N,Hi,Ci,Co,k,s,p", CONV_CASES)
-def test_conv2d_fwd_dgrad_wgrad(K, N, Hi, Ci, Co, k, s, p):
-    x = rnd((N, Ci, Hi, Hi), 1)
+
+def check_conv2d_fwd_dgrad_wgrad(K, N, Hi, Wi, Ci, Co, k, s, p, route=0, variants=None):
+    """Forward, dgrad, accumulating dgrad, weight and bias gradient of one layer on an Hi x Wi map against torch float64;
+    `variants` {which: prefix}: the kernels the launches must run (bh_conv_variant)."""
+    x = rnd((N, Ci, Hi, Wi), 1)
     w = (rnd((Co, Ci, k, k), 2) / np.sqrt(Ci * k * k)).astype(np.float32)
     b = rnd((Co,), 3)
-    d = K.conv_desc(N, Hi, Hi, Ci, Co, k, s, p)
+    d = K.conv_desc(N, Hi, Wi, Ci, Co, k, s, p, route=route)
+    for which, prefix in (variants or {}).items():
+        assert K.conv_variant(d, which).startswith(prefix), (which, K.conv_variant(d, which))
     xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
     wt = torch.tensor(w, dtype=torch.float64, requires_grad=True)
     bt = torch.tensor(b, dtype=torch.float64, requires_grad=True)
@@ -66,12 +80,18 @@ def test_conv2d_fwd_dgrad_wgrad(K, N, Hi, Ci, Co, k, s, p):
     close(gb.cpu(), bt.grad)
 
 
-@pytest.mark.parametrize("N,Hi,Ci,Co", [(2, 8, 256, 256), (2, 8, 256, 128), (1, 16, 128, 64), (1, 32, 64, 32), (1, 64, 32, 16)])
-def test_conv_transpose_2x2(K, N, Hi, Ci, Co):
-    x = rnd((N, Ci, Hi, Hi), 5)
+@pytest.mark.parametrize("N,Hi,Ci,Co,k,s,p", CONV_CASES)
+def test_conv2d_fwd_dgrad_wgrad(K, N, Hi, Ci, Co, k, s, p):
+    check_conv2d_fwd_dgrad_wgrad(K, N, Hi, Hi, Ci, Co, k, s, p)
+
+
+def check_conv_transpose_2x2(K, N, Hi, Wi, Ci, Co, variants=None):
+    x = rnd((N, Ci, Hi, Wi), 5)
     w = (rnd((Ci, Co, 2, 2), 6) / np.sqrt(Ci)).astype(np.float32)
     b = rnd((Co,), 7)
-    d = K.conv_desc(N, Hi, Hi, Ci, Co, 2, 2, 0, transposed=True)
+    d = K.conv_desc(N, Hi, Wi, Ci, Co, 2, 2, 0, transposed=True)
+    for which, prefix in (variants or {}).items():
+        assert K.conv_variant(d, which).startswith(prefix), (which, K.conv_variant(d, which))
     xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
     wt = torch.tensor(w, dtype=torch.float64, requires_grad=True)
     bt = torch.tensor(b, dtype=torch.float64, requires_grad=True)
@@ -91,14 +111,20 @@ def test_conv_transpose_2x2(K, N, Hi, Ci, Co):
     close(gb.cpu(), bt.grad)
 
 
-@pytest.mark.parametrize("N,Hi,Ci,Co", [(3, 32, 2, 64), (2, 48, 3, 64), (8, 128, 2, 64), (5, 160, 2, 64)])
-def test_first_conv_nchw_input(K, N, Hi, Ci, Co):
+@pytest.mark.parametrize("N,Hi,Ci,Co", [(2, 8, 256, 256), (2, 8, 256, 128), (1, 16, 128, 64), (1, 32, 64, 32), (1, 64, 32, 16)])
+def test_conv_transpose_2x2(K, N, Hi, Ci, Co):
+    check_conv_transpose_2x2(K, N, Hi, Hi, Ci, Co)
+
+
+def check_first_conv_nchw_input(K, N, Hi, Wi, Ci, Co, variants=None):
     """7x7/2 on the NCHW network input (Rethinking.py:31, ResNet34.py:17): scalar gather path; two planes and >= 512 8x8 tiles
     (the last two cases): stem7_fwd_kernel<2> and the dedicated weight-gradient kernel (round 4: bh_stem7_wgrad - accumulates into gw,
     bitwise repeatable)."""
-    x = rnd((N, Ci, Hi, Hi), 9)
+    x = rnd((N, Ci, Hi, Wi), 9)
     w = rnd((Co, Ci, 7, 7), 10) / 10
-    d = K.conv_desc(N, Hi, Hi, Ci, Co, 7, 2, 3, in_nchw=True)
+    d = K.conv_desc(N, Hi, Wi, Ci, Co, 7, 2, 3, in_nchw=True)
+    for which, prefix in (variants or {}).items():
+        assert K.conv_variant(d, which).startswith(prefix), (which, K.conv_variant(d, which))
     xt = torch.tensor(x, dtype=torch.float64)
     wt = torch.tensor(w, dtype=torch.float64, requires_grad=True)
     ref = F.conv2d(xt, wt, None, stride=2, padding=3)
@@ -110,7 +136,7 @@ def test_first_conv_nchw_input(K, N, Hi, Ci, Co):
     gw = torch.zeros_like(wg)
     K.conv_wgrad(torch.tensor(x).cuda(), torch.tensor(gy).permute(0, 2, 3, 1).contiguous().cuda(), gw, None, d)
     close(gw.cpu().permute(0, 3, 1, 2), wt.grad)
-    if N * (Hi // 16) ** 2 >= 512 and Ci == 2:
+    if N * (Hi // 16) * (Wi // 16) >= 512 and Ci == 2:
         from bihome_amd._lib import lib
         import ctypes
         assert lib.bh_stem7_wgrad_ws_bytes(ctypes.byref(d)) > 0
@@ -122,26 +148,37 @@ def test_first_conv_nchw_input(K, N, Hi, Ci, Co):
         assert torch.equal(gw3, gw)                                                                                         # no atomics
 
 
-@pytest.mark.parametrize("N,Hi,det", [(2, 32, False), (8, 64, False), (3, 128, False), (8, 64, True)])
-def test_gray_stem_conv_and_its_dgrad(K, N, Hi, det):
+@pytest.mark.parametrize("N,Hi,Ci,Co", [(3, 32, 2, 64), (2, 48, 3, 64), (8, 128, 2, 64), (5, 160, 2, 64)])
+def test_first_conv_nchw_input(K, N, Hi, Ci, Co):
+    check_first_conv_nchw_input(K, N, Hi, Hi, Ci, Co)
+
+
+def check_gray_stem_conv_and_its_dgrad(K, N, Hi, Wi, det, variants=None):
     """Extractor conv1 on a 1-channel image (PerceptualHead.py:52-55) and the dgrad the warp needs.  Small: the direct gather kernel;
     large: one kernel (tile GEMM + overlap-add in LDS + atomics into the image, round 4: bh_stem7_dgrad_c1); large in a deterministic
     call: the two-pass form (1x1 GEMM into a tap table + col2im)."""
     if det:
         with K.det_scope(True):
-            return test_gray_stem_conv_and_its_dgrad(K, N, Hi, False)
-    x = rnd((N, 1, Hi, Hi), 12)
+            return check_gray_stem_conv_and_its_dgrad(K, N, Hi, Wi, False, variants)
+    x = rnd((N, 1, Hi, Wi), 12)
     w = rnd((64, 1, 7, 7), 13) / 7
-    d = K.conv_desc(N, Hi, Hi, 1, 64, 7, 2, 3)
+    d = K.conv_desc(N, Hi, Wi, 1, 64, 7, 2, 3)
+    for which, prefix in (variants or {}).items():
+        assert K.conv_variant(d, which).startswith(prefix), (which, K.conv_variant(d, which))
     xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
     ref = F.conv2d(xt, torch.tensor(w, dtype=torch.float64), None, stride=2, padding=3)
     wg = torch.tensor(w).permute(0, 2, 3, 1).contiguous().cuda()
-    y = K.conv_fwd(torch.tensor(x).reshape(N, Hi, Hi, 1).cuda(), wg, None, d)
+    y = K.conv_fwd(torch.tensor(x).reshape(N, Hi, Wi, 1).cuda(), wg, None, d)
     close(y.cpu().permute(0, 3, 1, 2), ref.detach())
     gy = rnd(tuple(ref.shape), 14)
     ref.backward(torch.tensor(gy, dtype=torch.float64))
     gx = K.conv_dgrad(torch.tensor(gy).permute(0, 2, 3, 1).contiguous().cuda(), wg, d)
-    close(gx.cpu().reshape(N, 1, Hi, Hi), xt.grad)
+    close(gx.cpu().reshape(N, 1, Hi, Wi), xt.grad)
+
+
+@pytest.mark.parametrize("N,Hi,det", [(2, 32, False), (8, 64, False), (3, 128, False), (8, 64, True)])
+def test_gray_stem_conv_and_its_dgrad(K, N, Hi, det):
+    check_gray_stem_conv_and_its_dgrad(K, N, Hi, Hi, det)
 
 
 @pytest.mark.parametrize("N,Hi,scale", [(8, 64, 1.0), (4, 128, 1e-4), (3, 128, 30.0)])
@@ -170,14 +207,15 @@ def test_gray_stem_dgrad_in_fp16_pieces(K, N, Hi, scale):
     assert err[4] <= 1.5 * err[0] + 1e-8 and err[(4, "dim")] <= 1.5 * err[(0, "dim")] + 1e-7, err
 
 
-def test_last_conv_nchw_output(K):
+def check_last_conv_nchw_output(K, N, Hi, Wi, Ci=128, Co=2, variants=None):
     """1x1 128->2 with bias writing the NCHW perspective field (Rethinking.py:147) and adjoints fed by an
     NCHW gradient."""
-    N, Hi, Ci, Co = 2, 16, 128, 2
-    x = rnd((N, Ci, Hi, Hi), 15)
+    x = rnd((N, Ci, Hi, Wi), 15)
     w = rnd((Co, Ci, 1, 1), 16) / 11
     b = rnd((Co,), 17)
-    d = K.conv_desc(N, Hi, Hi, Ci, Co, 1, 1, 0, out_nchw=True)
+    d = K.conv_desc(N, Hi, Wi, Ci, Co, 1, 1, 0, out_nchw=True)
+    for which, prefix in (variants or {}).items():
+        assert K.conv_variant(d, which).startswith(prefix), (which, K.conv_variant(d, which))
     xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
     wt = torch.tensor(w, dtype=torch.float64, requires_grad=True)
     bt = torch.tensor(b, dtype=torch.float64, requires_grad=True)
@@ -185,7 +223,7 @@ def test_last_conv_nchw_output(K):
     xg = torch.tensor(x).permute(0, 2, 3, 1).contiguous().cuda()
     wg = torch.tensor(w).permute(0, 2, 3, 1).contiguous().cuda()
     y = K.conv_fwd(xg, wg, torch.tensor(b).cuda(), d)
-    assert tuple(y.shape) == (N, Co, Hi, Hi)
+    assert tuple(y.shape) == (N, Co, Hi, Wi)
     close(y.cpu(), ref.detach())
     gy = rnd(tuple(ref.shape), 18)
     ref.backward(torch.tensor(gy, dtype=torch.float64))
@@ -196,6 +234,10 @@ def test_last_conv_nchw_output(K):
     K.conv_wgrad(xg, gyg, gw, gb, d)
     close(gw.cpu().permute(0, 3, 1, 2), wt.grad)
     close(gb.cpu(), bt.grad)
+
+
+def test_last_conv_nchw_output(K):
+    check_last_conv_nchw_output(K, 2, 16, 16)
 
 
 @pytest.mark.parametrize("groups,N,H,C,relu,res,training", [
@@ -241,9 +283,8 @@ def test_batchnorm_fwd_bwd(K, groups, N, H, C, relu, res, training):
         close(gres.cpu().permute(0, 3, 1, 2), rt.grad, 1e-6)
 
 
-@pytest.mark.parametrize("N,H,C", [(2, 64, 64), (1, 17, 8), (3, 8, 256)])
-def test_maxpool_gap_add(K, N, H, C):
-    x = rnd((N, C, H, H), 30)
+def check_maxpool_gap_add(K, N, H, W, C):
+    x = rnd((N, C, H, W), 30)
     x[0, :, 2:5, 2:5] = 1.5                      # ties inside windows: first-maximum rule
     xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
     ref = F.max_pool2d(xt, 3, 2, 1)
@@ -257,11 +298,16 @@ def test_maxpool_gap_add(K, N, H, C):
     g = K.gap_fwd(xg)
     close(g.cpu().reshape(N, C), x.mean((2, 3)), 1e-6)
     gg = K.gap_bwd(g, tuple(xg.shape))
-    close(gg.cpu(), np.broadcast_to(g.cpu().numpy() / (H * H), (N, H, H, C)), 1e-6)
+    close(gg.cpu(), np.broadcast_to(g.cpu().numpy() / (H * W), (N, H, W, C)), 1e-6)
     a, b = torch.tensor(rnd((1001,), 32)).cuda(), torch.tensor(rnd((1001,), 33)).cuda()
     s = a + b
     K.add_(a, b)
     assert torch.equal(a, s)
+
+
+@pytest.mark.parametrize("N,H,C", [(2, 64, 64), (1, 17, 8), (3, 8, 256)])
+def test_maxpool_gap_add(K, N, H, C):
+    check_maxpool_gap_add(K, N, H, H, C)
 
 
 def relerr64(a, b):
@@ -414,22 +460,16 @@ def test_bf16_operand_mode(K, N, Hi, Ci, Co, k, s, p):
     close(gw.cpu().permute(0, 3, 1, 2), wt.grad, 1e-2)
 
 
-@pytest.mark.parametrize("N,H,Ci,Co,k,groups", [
-    (8, 16, 32, 64, 3, 2),      # halo-tiled 3x3 kernel, BN = 64: statistics in the conv epilogue
-    (6, 8, 64, 32, 3, 2),       # BN = 32 variant; 8x8 images: the two sub-tiles of a workgroup can sit in different groups
-    (2, 8, 32, 64, 3, 2),       # one image per group: every workgroup straddles the group boundary
-    (4, 8, 16, 32, 1, 2),       # 1x1 conv: generic kernel, statistics in its epilogue (128 pixels per group)
-    (2, 4, 16, 32, 1, 2),       # 16 pixels per group: generic kernel + statistics launch
-    (4, 16, 32, 128, 1, 2),     # 128-wide N tile
-])
-def test_conv_fwd_with_batchnorm_sums(K, N, H, Ci, Co, k, groups):
+def check_conv_fwd_with_batchnorm_sums(K, N, H, W, Ci, Co, k, groups, variant=None):
     """bh_conv_fwd_bnstats: per-group, per-channel (sum y, sum y^2) of the conv output, as BatchNorm consumes them."""
     from bihome_amd._lib import ROUTE_HALO_SMALL
     if True:
-        x = torch.tensor(rnd((N, H, H, Ci), 70)).cuda()
+        x = torch.tensor(rnd((N, H, W, Ci), 70)).cuda()
         w = torch.tensor(rnd((Co, k, k, Ci), 71) * 0.1).cuda()
         b = torch.tensor(rnd((Co,), 72)).cuda()
-        d = K.conv_desc(N, H, H, Ci, Co, k, 1, k // 2, route=ROUTE_HALO_SMALL)   # let the halo kernel take these small grids
+        d = K.conv_desc(N, H, W, Ci, Co, k, 1, k // 2, route=ROUTE_HALO_SMALL)   # let the halo kernel take these small grids
+        if variant:
+            assert K.conv_variant(d, "fwd", bn_groups=groups).startswith(variant), K.conv_variant(d, "fwd", bn_groups=groups)
         sums = K.bn_stats_buffer(groups, Co, "cuda")
         y = K.conv_fwd(x, w, b, d, bn_sums=sums, groups=groups)
         y0 = K.conv_fwd(x, w, b, d)
@@ -445,25 +485,35 @@ def test_conv_fwd_with_batchnorm_sums(K, N, H, Ci, Co, k, groups):
         close(o1.cpu(), o2.cpu(), 1e-5)
 
 
-@pytest.mark.parametrize("N,H,C,Co,groups,relu,res,acc", [
-    (8, 16, 64, 64, 2, True, False, False),     # inner BatchNorm of a residual unit: mask recomputed from z
-    (8, 16, 64, 32, 2, True, True, True),       # block-output BatchNorm: residual added, gradient joined (accumulate)
-    (4, 8, 32, 64, 2, False, False, False),     # no ReLU, 32-channel variant of the dgrad kernel
+@pytest.mark.parametrize("N,H,Ci,Co,k,groups", [
+    (8, 16, 32, 64, 3, 2),      # halo-tiled 3x3 kernel, BN = 64: statistics in the conv epilogue
+    (6, 8, 64, 32, 3, 2),       # BN = 32 variant; 8x8 images: the two sub-tiles of a workgroup can sit in different groups
+    (2, 8, 32, 64, 3, 2),       # one image per group: every workgroup straddles the group boundary
+    (4, 8, 16, 32, 1, 2),       # 1x1 conv: generic kernel, statistics in its epilogue (128 pixels per group)
+    (2, 4, 16, 32, 1, 2),       # 16 pixels per group: generic kernel + statistics launch
+    (4, 16, 32, 128, 1, 2),     # 128-wide N tile
 ])
-def test_dgrad_epilogue_accumulates_batchnorm_backward_sums(K, N, H, C, Co, groups, relu, res, acc):
+def test_conv_fwd_with_batchnorm_sums(K, N, H, Ci, Co, k, groups):
+    check_conv_fwd_with_batchnorm_sums(K, N, H, H, Ci, Co, k, groups)
+
+
+def check_dgrad_epilogue_accumulates_batchnorm_backward_sums(K, N, H, W, C, Co, groups, relu, res, acc, variant=None):
     """bh_conv_dgrad_bnreduce + bh_bn_bwd(flags bit4) against the three-launch BatchNorm adjoint on the same gradient."""
     from bihome_amd._lib import ROUTE_HALO_SMALL
     if True:
-        z = torch.tensor(rnd((N, H, H, C), 80) * 1.5 + 0.3).cuda()
-        r = torch.tensor(rnd((N, H, H, C), 81)).cuda() if res else None
+        z = torch.tensor(rnd((N, H, W, C), 80) * 1.5 + 0.3).cuda()
+        r = torch.tensor(rnd((N, H, W, C), 81)).cuda() if res else None
         gm, bt = torch.tensor(1 + 0.3 * rnd((C,), 82)).cuda(), torch.tensor(0.2 * rnd((C,), 83)).cuda()
         rm, rv = torch.zeros(C, device="cuda"), torch.ones(C, device="cuda")
         y, st = K.bn_fwd(z, gm, bt, rm, rv, r, groups, 1e-5, 0.1, relu, True)
         # the conv that consumes y: 3x3, C -> Co
-        d = K.conv_desc(N, H, H, C, Co, 3, 1, 1, route=ROUTE_HALO_SMALL)
+        d = K.conv_desc(N, H, W, C, Co, 3, 1, 1, route=ROUTE_HALO_SMALL)
+        if variant:
+            which = "dgrad_bnr_y" if (relu and res) else "dgrad_bnr_z"
+            assert K.conv_variant(d, which, accumulate=acc).startswith(variant), K.conv_variant(d, which, accumulate=acc)
         w = torch.tensor(rnd((Co, 3, 3, C), 84) * 0.1).cuda()
-        gy = torch.tensor(rnd((N, H, H, Co), 85)).cuda()
-        part = torch.tensor(rnd((N, H, H, C), 86)).cuda() if acc else None      # gradient already joined from another branch
+        gy = torch.tensor(rnd((N, H, W, Co), 85)).cuda()
+        part = torch.tensor(rnd((N, H, W, C), 86)).cuda() if acc else None      # gradient already joined from another branch
         # reference path: plain dgrad, then the three-launch adjoint
         g_ref = K.conv_dgrad(gy, w, d, out=part.clone()) if acc else K.conv_dgrad(gy, w, d)
         gg0, gb0 = torch.zeros(C, device="cuda"), torch.zeros(C, device="cuda")
@@ -481,6 +531,15 @@ def test_dgrad_epilogue_accumulates_batchnorm_backward_sums(K, N, H, C, Co, grou
         close(gb1.cpu(), gb0.cpu(), 2e-5)
         if res:
             assert torch.equal(gr1, gr0)
+
+
+@pytest.mark.parametrize("N,H,C,Co,groups,relu,res,acc", [
+    (8, 16, 64, 64, 2, True, False, False),     # inner BatchNorm of a residual unit: mask recomputed from z
+    (8, 16, 64, 32, 2, True, True, True),       # block-output BatchNorm: residual added, gradient joined (accumulate)
+    (4, 8, 32, 64, 2, False, False, False),     # no ReLU, 32-channel variant of the dgrad kernel
+])
+def test_dgrad_epilogue_accumulates_batchnorm_backward_sums(K, N, H, C, Co, groups, relu, res, acc):
+    check_dgrad_epilogue_accumulates_batchnorm_backward_sums(K, N, H, H, C, Co, groups, relu, res, acc)
 
 
 @pytest.mark.parametrize("N,H,Ci,Co,k", [(2, 8, 64, 64, 3), (1, 32, 64, 128, 3), (3, 16, 128, 64, 3), (2, 4, 64, 64, 3),
@@ -528,39 +587,42 @@ def test_conv3x3_two_tile_positions_per_workgroup(K):
     assert float((res[0][2] - res[1][2]).abs().max() / res[1][2].abs().max()) < 1e-6
 
 
-@pytest.mark.parametrize("N,H,Ci,relu", [(4, 128, 1, False), (4, 128, 2, False), (2, 256, 3, False), (1, 256, 6, True)])
-def test_stem7_forward_kernel(K, N, H, Ci, relu):
+def check_stem7_forward_kernel(K, N, H, W, Ci, relu):
     """csrc/stem7.hip (7x7 / stride 2 / pad 3 stems, NCHW planes -> NHWC) against torch float64 and the generic kernel."""
     from bihome_amd._lib import ROUTE_NO_STEM7
     g = torch.Generator().manual_seed(5)
-    x = torch.randn(N, Ci, H, H, generator=g, dtype=torch.float64)
+    x = torch.randn(N, Ci, H, W, generator=g, dtype=torch.float64)
     w = torch.randn(64, Ci, 7, 7, generator=g, dtype=torch.float64) * 0.1
     b = torch.randn(64, generator=g, dtype=torch.float64)
     ref = F.conv2d(x, w, b, 2, 3)
     if relu:
         ref = F.relu(ref)
-    d = K.conv_desc(N, H, H, Ci, 64, 7, 2, 3, in_nchw=Ci != 1)
+    d = K.conv_desc(N, H, W, Ci, 64, 7, 2, 3, in_nchw=Ci != 1)
     assert K.conv_variant(d, "fwd") == "stem7_fwd_kernel<%d>" % Ci
     xk = x.float().cuda().contiguous()
     if Ci == 1:
-        xk = xk.view(N, H, H, 1)
+        xk = xk.view(N, H, W, 1)
     wk = w.float().cuda().permute(0, 2, 3, 1).contiguous()
     y = K.conv_fwd(xk, wk, b.float().cuda(), d, relu=relu)
     close(y.permute(0, 3, 1, 2).cpu(), ref, 2e-5)
-    d0 = K.conv_desc(N, H, H, Ci, 64, 7, 2, 3, in_nchw=Ci != 1, route=ROUTE_NO_STEM7)
+    d0 = K.conv_desc(N, H, W, Ci, 64, 7, 2, 3, in_nchw=Ci != 1, route=ROUTE_NO_STEM7)
     assert K.conv_variant(d0, "fwd").startswith("conv_gemm_kernel")
     y0 = K.conv_fwd(xk, wk, b.float().cuda(), d0, relu=relu)
     close(y.cpu(), y0.cpu(), 2e-5)
 
 
-@pytest.mark.parametrize("N,H,Ci,relu,scale", [(4, 128, 1, False, 1.0), (4, 128, 2, True, 1.0), (16, 64, 1, False, 300.0), (8, 128, 2, False, 1e-3)])
-def test_stem7_forward_in_fp16_pieces(K, N, H, Ci, relu, scale):
+@pytest.mark.parametrize("N,H,Ci,relu", [(4, 128, 1, False), (4, 128, 2, False), (2, 256, 3, False), (1, 256, 6, True)])
+def test_stem7_forward_kernel(K, N, H, Ci, relu):
+    check_stem7_forward_kernel(K, N, H, H, Ci, relu)
+
+
+def check_stem7_forward_in_fp16_pieces(K, N, H, W, Ci, relu, scale):
     """Round 6 (stem7_fwd_f16_kernel, csrc/stem7.hip; bh_conv_desc.precision = 4): the one- and two-plane stems in the fp16-piece
     arithmetic of the 3x3 layers - against torch float64, next to the fp32-input MFMA kernel on the same data (error <= 1.5x its error),
     with inputs of very different magnitudes (the patch's scale is taken per tile, the filter bank's per launch: no magnitude record), dark
     tiles in a bright image, and the BatchNorm sums of the epilogue."""
     g = torch.Generator().manual_seed(7 + Ci)
-    x = torch.randn(N, Ci, H, H, generator=g, dtype=torch.float64) * scale
+    x = torch.randn(N, Ci, H, W, generator=g, dtype=torch.float64) * scale
     x[0, :, : H // 2] *= 1e-4                                 # a dark half image: its tiles get their own scale
     x[-1, :, 16:32, 16:32] = 0.0                              # an all-zero tile
     w = torch.randn(64, Ci, 7, 7, generator=g, dtype=torch.float64) * 0.1
@@ -570,11 +632,11 @@ def test_stem7_forward_in_fp16_pieces(K, N, H, Ci, relu, scale):
         ref = F.relu(ref)
     xk = x.float().cuda().contiguous()
     if Ci == 1:
-        xk = xk.view(N, H, H, 1)
+        xk = xk.view(N, H, W, 1)
     wk = w.float().cuda().permute(0, 2, 3, 1).contiguous()
     err = {}
     for prec in (0, 4):
-        d = K.conv_desc(N, H, H, Ci, 64, 7, 2, 3, in_nchw=Ci != 1, precision=prec)
+        d = K.conv_desc(N, H, W, Ci, 64, 7, 2, 3, in_nchw=Ci != 1, precision=prec)
         assert K.conv_variant(d, "fwd") == ("stem7_fwd_f16_kernel<%d>" if prec == 4 else "stem7_fwd_kernel<%d>") % Ci
         y = K.conv_fwd(xk, wk, b.float().cuda(), d, relu=relu)
         yd = y.permute(0, 3, 1, 2).cpu().double()
@@ -582,18 +644,23 @@ def test_stem7_forward_in_fp16_pieces(K, N, H, Ci, relu, scale):
         # per dark region as well: the dark half image must keep its relative accuracy
         dark = ((yd[0, :, : H // 4 - 2] - ref[0, :, : H // 4 - 2]).norm() / ref[0, :, : H // 4 - 2].norm()).item()
         err[(prec, "dark")] = dark
-    print("\nstem forward N%d H%d Ci%d scale %g: rel-L2 vs f64  fp32-input MFMA %.2e  fp16 pieces %.2e;  dark half image %.2e / %.2e"
-          % (N, H, Ci, scale, err[0], err[4], err[(0, "dark")], err[(4, "dark")]))
+    print("\nstem forward N%d %dx%d Ci%d scale %g: rel-L2 vs f64  fp32-input MFMA %.2e  fp16 pieces %.2e;  dark half image %.2e / %.2e"
+          % (N, H, W, Ci, scale, err[0], err[4], err[(0, "dark")], err[(4, "dark")]))
     assert err[4] <= 1.5 * err[0] + 1e-8 and err[(4, "dark")] <= 1.5 * err[(0, "dark")] + 1e-7, err
     # BatchNorm statistics of the output from the epilogue (what the model asks for), in two groups
     if not relu:
-        d = K.conv_desc(N, H, H, Ci, 64, 7, 2, 3, in_nchw=Ci != 1, precision=4)
+        d = K.conv_desc(N, H, W, Ci, 64, 7, 2, 3, in_nchw=Ci != 1, precision=4)
         sums = K.bn_stats_buffer(2, 64, "cuda")
         y2 = K.conv_fwd(xk, wk, None, d, bn_sums=sums, groups=2)
         yd = y2.double().reshape(2, -1, 64)
         tab = sums.reshape(K.BN_SUM_SLOTS, 2, 64, 2, K.BN_SUM_STRIDE)[..., 0].sum(0).cpu()
         refs = torch.stack([yd.sum(1), (yd * yd).sum(1)], -1).cpu()
         assert ((tab - refs).abs() <= 1e-6 * refs.abs().max()).all()
+
+
+@pytest.mark.parametrize("N,H,Ci,relu,scale", [(4, 128, 1, False, 1.0), (4, 128, 2, True, 1.0), (16, 64, 1, False, 300.0), (8, 128, 2, False, 1e-3)])
+def test_stem7_forward_in_fp16_pieces(K, N, H, Ci, relu, scale):
+    check_stem7_forward_in_fp16_pieces(K, N, H, H, Ci, relu, scale)
 
 
 @pytest.mark.parametrize("N,H,Ci,Co,groups", [(4, 8, 32, 32, 2), (8, 8, 64, 32, 2)])
@@ -693,16 +760,7 @@ def test_conv3x3_packed_weights_match_lds_slab_path(K, N, H, Ci, Co, prec):
     assert torch.equal(y2, K.conv_fwd(x, wk, None, d))
 
 
-@pytest.mark.parametrize("N,H,Ci,Co,wide", [
-    (128, 32, 64, 64, False),    # the bench shape: two tile positions per workgroup, two chunks
-    (8, 16, 128, 128, False),    # four chunks, two n tiles
-    (8, 8, 256, 256, False),     # one sub-tile per workgroup, eight chunks
-    (4, 64, 32, 32, False),      # 32-channel tile, single chunk (one halo stage)
-    (3, 24, 96, 160, False),     # odd sub-tile count, three chunks, 64- and 32-wide n tiles
-    (5, 16, 32, 64, False),      # single chunk, odd image count
-    (8, 16, 64, 64, True),       # operands spread over 24 binades
-])
-def test_conv3x3_f32x3_is_fp32_accurate(K, N, H, Ci, Co, wide):
+def check_conv3x3_f32x3_is_fp32_accurate(K, N, H, W, Ci, Co, wide):
     """precision 2 / w_layout 2 of the packed 3x3 kernel: every fp32 operand is cut exactly into three bf16 pieces and six
     partial products per product run on the bf16 MFMA with fp32 accumulate.  Claim under test: this is fp32 arithmetic - the
     error against torch float64 is no larger than that of the fp32-input MFMA kernel on the same data (measured 0.85x), for
@@ -710,8 +768,8 @@ def test_conv3x3_f32x3_is_fp32_accurate(K, N, H, Ci, Co, wide):
     = weight, bit for bit)."""
     from bihome_amd._lib import ROUTE_HALO_SMALL
     g = torch.Generator().manual_seed(N * 7 + H)
-    x = torch.randn(N, H, H, Ci, generator=g)
-    gy = torch.randn(N, H, H, Co, generator=g)
+    x = torch.randn(N, H, W, Ci, generator=g)
+    gy = torch.randn(N, H, W, Co, generator=g)
     if wide:
         x = x * torch.exp2(torch.randint(-12, 12, x.shape, generator=g).float())
         gy = gy * torch.exp2(torch.randint(-12, 12, gy.shape, generator=g).float())
@@ -724,11 +782,12 @@ def test_conv3x3_f32x3_is_fp32_accurate(K, N, H, Ci, Co, wide):
     refd = F.conv_transpose2d(gy.double().cpu().permute(0, 3, 1, 2), wd, None, 1, 1).permute(0, 2, 3, 1)
     err = {}
     for prec in (0, 2):
-        d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=prec, route=ROUTE_HALO_SMALL)
+        d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=prec, route=ROUTE_HALO_SMALL)
         pk = K.WeightPacker(split=prec == 2)
         pf, pd = pk.get(w)
         pk.refresh()
         dp = K._with_layout(d, 2 if prec == 2 else 1)
+        assert K.conv_variant(dp, "fwd").startswith("conv3x3_halo_kernel<false,") and K.conv_variant(dp, "dgrad").startswith("conv3x3_halo_kernel<true,")
         assert K.conv_variant(dp, "fwd").endswith(",true,true,false,3,false,false>" if prec == 2 else ",true,false,false,3,false,false>")
         assert K.conv_variant(dp, "dgrad").endswith(",true,true,false,3,false,false>" if prec == 2 else ",true,false,false,3,false,false>")
         y = K.conv_fwd(x, wk, b, d, wpacked=pf)
@@ -752,8 +811,64 @@ def test_conv3x3_f32x3_is_fp32_accurate(K, N, H, Ci, Co, wide):
             t = total.view(Ci // 32, 9, NW, 2, 2, 32, 8)                                     # [c][tap][nt][s2][kh2][l31][e]
             back.view(NW, 32, 9, Ci // 32, 2, 2, 8).copy_(t.permute(2, 5, 1, 0, 3, 4, 6))    # n = nt*32 + l31, k = c*32 + (2*s2 + kh2)*8 + e
             assert torch.equal(back.float(), wk.reshape(Co, 9, Ci)) and torch.equal(back, wk.reshape(Co, 9, Ci).double())
+    print("MEASURED f32x3 3x3 N%d %dx%d %d->%d: rel-L2 vs f64  fp32-input MFMA fwd %.2e dgrad %.2e | f32x3 fwd %.2e dgrad %.2e" % (N, H, W, Ci, Co, *err[0], *err[2]))
     assert err[2][0] <= 1.1 * err[0][0] + 1e-9 and err[2][1] <= 1.1 * err[0][1] + 1e-9, err
     assert err[2][0] < 2e-6 and err[2][1] < 2e-6
+
+
+@pytest.mark.parametrize("N,H,Ci,Co,wide", [
+    (128, 32, 64, 64, False),    # the bench shape: two tile positions per workgroup, two chunks
+    (8, 16, 128, 128, False),    # four chunks, two n tiles
+    (8, 8, 256, 256, False),     # one sub-tile per workgroup, eight chunks
+    (4, 64, 32, 32, False),      # 32-channel tile, single chunk (one halo stage)
+    (3, 24, 96, 160, False),     # odd sub-tile count, three chunks, 64- and 32-wide n tiles
+    (5, 16, 32, 64, False),      # single chunk, odd image count
+    (8, 16, 64, 64, True),       # operands spread over 24 binades
+])
+def test_conv3x3_f32x3_is_fp32_accurate(K, N, H, Ci, Co, wide):
+    check_conv3x3_f32x3_is_fp32_accurate(K, N, H, H, Ci, Co, wide)
+
+
+def check_wgrad_f32x3_kernel(K, N, H, W, Ci, Co):
+    """csrc/wgrad_x3.hip (precision 2: halo-tiled, all nine taps per workgroup, three exact bf16 pieces per operand, transposing
+    LDS reads): against torch float64 with an error no larger than the fp32-input MFMA kernel's on the same data; accumulates
+    onto gw; with a workspace the split-K reduction runs in fixed order - bitwise repeatable - and agrees with the atomics
+    form to fp32 rounding."""
+    g = torch.Generator().manual_seed(N + H + Ci)
+    x = torch.randn(N, H, W, Ci, generator=g).cuda()
+    gy = torch.randn(N, H, W, Co, generator=g).cuda()
+    w = torch.zeros(Co, Ci, 3, 3, dtype=torch.float64, requires_grad=True)
+    y = F.conv2d(x.double().cpu().permute(0, 3, 1, 2), w, None, 1, 1)
+    ref = torch.autograd.grad(y, w, gy.double().cpu().permute(0, 3, 1, 2))[0].permute(0, 2, 3, 1)       # [Co][3][3][Ci]
+    err = {}
+    for prec in (0, 2):
+        d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=prec)
+        assert K.conv_variant(d, "wgrad").startswith("wgrad_x3_kernel") == (prec == 2)
+        gw = torch.zeros(Co, 3, 3, Ci, device="cuda")
+        K.conv_wgrad(x, gy, gw, None, d)
+        err[prec] = ((gw.cpu().double() - ref).norm() / ref.norm()).item()
+        g1 = torch.ones(Co, 3, 3, Ci, device="cuda")                     # gw += : the result lands on what gw holds
+        K.conv_wgrad(x, gy, g1, None, d)
+        close((g1 - 1.0).cpu(), gw.cpu(), 2e-5)
+    # (both errors are fp32 ACCUMULATION rounding over N*H*W terms - the products are exact in either form.  The f32x3 kernel adds
+    #  up to 512 pixels per accumulator before the split-K reduction, the fp32-MFMA one 64, hence up to ~1.2x at the bench shape;
+    #  without a workspace the 32-channel form adds 4 x 256 partial blocks with atomics one after the other - a longer chain of
+    #  fp32 roundings, 6e-7 on 4x64x64 - while the workspace form the models use sums them in four groups, checked below)
+    print("MEASURED f32x3 wgrad N%d %dx%d %d->%d: rel-L2 vs f64  fp32-input MFMA %.2e  f32x3 %.2e" % (N, H, W, Ci, Co, err[0], err[2]))
+    assert err[2] <= (1.5 if min(Ci, Co) % 64 == 0 else 3.0) * err[0] + 1e-8 and err[2] < 2e-6, err
+    d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=2)
+    need = K.wgrad_det_bytes(d)
+    assert 0 < need <= 40 << 20
+    ws = torch.empty(need // 4, dtype=torch.float32, device="cuda")
+    runs = []
+    for _ in range(3):
+        gw = torch.zeros(Co, 3, 3, Ci, device="cuda")
+        gb = torch.zeros(Co, device="cuda")
+        K.conv_wgrad(x, gy, gw, gb, d, det_ws=ws)
+        runs.append(gw)
+    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
+    assert ((runs[0].cpu().double() - ref).norm() / ref.norm()).item() <= 1.5 * err[0] + 1e-8
+    close(gb.cpu(), gy.double().sum((0, 1, 2)).cpu(), 1e-5)
 
 
 @pytest.mark.parametrize("N,H,Ci,Co", [
@@ -768,44 +883,7 @@ def test_conv3x3_f32x3_is_fp32_accurate(K, N, H, Ci, Co, wide):
     (2, 16, 64, 32),        # 64 -> 32: 32-channel blocks on both sides
 ])
 def test_wgrad_f32x3_kernel(K, N, H, Ci, Co):
-    """csrc/wgrad_x3.hip (precision 2: halo-tiled, all nine taps per workgroup, three exact bf16 pieces per operand, transposing
-    LDS reads): against torch float64 with an error no larger than the fp32-input MFMA kernel's on the same data; accumulates
-    onto gw; with a workspace the split-K reduction runs in fixed order - bitwise repeatable - and agrees with the atomics
-    form to fp32 rounding."""
-    g = torch.Generator().manual_seed(N + H + Ci)
-    x = torch.randn(N, H, H, Ci, generator=g).cuda()
-    gy = torch.randn(N, H, H, Co, generator=g).cuda()
-    w = torch.zeros(Co, Ci, 3, 3, dtype=torch.float64, requires_grad=True)
-    y = F.conv2d(x.double().cpu().permute(0, 3, 1, 2), w, None, 1, 1)
-    ref = torch.autograd.grad(y, w, gy.double().cpu().permute(0, 3, 1, 2))[0].permute(0, 2, 3, 1)       # [Co][3][3][Ci]
-    err = {}
-    for prec in (0, 2):
-        d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=prec)
-        assert K.conv_variant(d, "wgrad").startswith("wgrad_x3_kernel") == (prec == 2)
-        gw = torch.zeros(Co, 3, 3, Ci, device="cuda")
-        K.conv_wgrad(x, gy, gw, None, d)
-        err[prec] = ((gw.cpu().double() - ref).norm() / ref.norm()).item()
-        g1 = torch.ones(Co, 3, 3, Ci, device="cuda")                     # gw += : the result lands on what gw holds
-        K.conv_wgrad(x, gy, g1, None, d)
-        close((g1 - 1.0).cpu(), gw.cpu(), 2e-5)
-    # (both errors are fp32 ACCUMULATION rounding over N*H*W terms - the products are exact in either form.  The f32x3 kernel adds
-    #  up to 512 pixels per accumulator before the split-K reduction, the fp32-MFMA one 64, hence up to ~1.2x at the bench shape;
-    #  without a workspace the 32-channel form adds 4 x 256 partial blocks with atomics one after the other - a longer chain of
-    #  fp32 roundings, 6e-7 on 4x64x64 - while the workspace form the models use sums them in four groups, checked below)
-    assert err[2] <= (1.5 if min(Ci, Co) % 64 == 0 else 3.0) * err[0] + 1e-8 and err[2] < 2e-6, err
-    d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=2)
-    need = K.wgrad_det_bytes(d)
-    assert 0 < need <= 40 << 20
-    ws = torch.empty(need // 4, dtype=torch.float32, device="cuda")
-    runs = []
-    for _ in range(3):
-        gw = torch.zeros(Co, 3, 3, Ci, device="cuda")
-        gb = torch.zeros(Co, device="cuda")
-        K.conv_wgrad(x, gy, gw, gb, d, det_ws=ws)
-        runs.append(gw)
-    assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
-    assert ((runs[0].cpu().double() - ref).norm() / ref.norm()).item() <= 1.5 * err[0] + 1e-8
-    close(gb.cpu(), gy.double().sum((0, 1, 2)).cpu(), 1e-5)
+    check_wgrad_f32x3_kernel(K, N, H, H, Ci, Co)
 
 
 def test_conv3x3_f32x3_error_bound_under_cancellation(K):
@@ -838,14 +916,7 @@ def test_conv3x3_f32x3_error_bound_under_cancellation(K):
     assert ulps[2] <= max(1.25 * ulps[0], 4.0) and ulps[2] < 16.0, ulps      # (K = 576 terms: a few ulps of the accumulated magnitude)
 
 
-@pytest.mark.parametrize("N,H,Ci,Co,relu", [
-    (128, 32, 64, 64, True),     # bench shape, two statistics groups
-    (8, 16, 128, 64, True),      # four chunks
-    (8, 8, 256, 256, False),     # one sub-tile per workgroup, 4 KB table, no ReLU
-    (4, 64, 32, 32, True),       # 32-channel tile, single chunk
-    (6, 24, 64, 96, True),       # image borders inside every tile row, three images per group
-])
-def test_batchnorm_on_load_matches_materialised_batchnorm(K, N, H, Ci, Co, relu):
+def check_batchnorm_on_load_matches_materialised_batchnorm(K, N, H, W, Ci, Co, relu, variant=None):
     """bh_bn_fwd_coeffs + bh_conv_fwd_bnin / bh_conv_wgrad_bnin: the consumer conv applies the BatchNorm(+ReLU) in front of it
     while staging its operand, so that BatchNorm's output is never stored.  Against the unfused sequence (bh_bn_fwd writes the
     activation, the same f32x3 kernels read it): forward, forward + BatchNorm sums of the conv's own output, weight gradient
@@ -853,22 +924,24 @@ def test_batchnorm_on_load_matches_materialised_batchnorm(K, N, H, Ci, Co, relu)
     zero padding ring intact (the transform of 0 is `shift`, not 0: a wrong border shows at 1e-1)."""
     groups = 2
     g = torch.Generator().manual_seed(N + H + Ci)
-    z = (torch.randn(N, H, H, Ci, generator=g) * 1.5 + 0.3).cuda()
+    z = (torch.randn(N, H, W, Ci, generator=g) * 1.5 + 0.3).cuda()
     gamma = (torch.rand(Ci, generator=g) + 0.5).cuda()
     beta = (torch.randn(Ci, generator=g) * 0.2).cuda()
     w = (torch.randn(Co, Ci, 3, 3, generator=g) * 0.05).cuda().contiguous(memory_format=torch.channels_last)
     wk = w.permute(0, 2, 3, 1)
     b = torch.randn(Co, generator=g).cuda()
-    gy = torch.randn(N, H, H, Co, generator=g).cuda()
+    gy = torch.randn(N, H, W, Co, generator=g).cuda()
     rm0, rv0 = torch.randn(Ci, generator=g).cuda(), (torch.rand(Ci, generator=g) + 0.5).cuda()
     rm1, rv1 = rm0.clone(), rv0.clone()
     a, st = K.bn_fwd(z, gamma, beta, rm0, rv0, None, groups, 1e-5, 0.1, relu, True)
-    table = K.bn_fwd_coeffs(st, gamma, beta, rm1, rv1, groups, N * H * H // groups, Ci, 1e-5, 0.1)
+    table = K.bn_fwd_coeffs(st, gamma, beta, rm1, rv1, groups, N * H * W // groups, Ci, 1e-5, 0.1)
     assert torch.equal(rm0, rm1) and torch.equal(rv0, rv1)
-    d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=2, route=0)
+    d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=2, route=0)
     if not K.packs_3x3(d):
         from bihome_amd._lib import ROUTE_HALO_SMALL
-        d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=2, route=ROUTE_HALO_SMALL)
+        d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=2, route=ROUTE_HALO_SMALL)
+    if variant:
+        assert K.conv_variant(K._with_layout(d, 2), "fwd").startswith(variant), K.conv_variant(K._with_layout(d, 2), "fwd")
     pk = K.WeightPacker(split=True)
     pf, _ = pk.get(w)
     pk.refresh()
@@ -892,6 +965,17 @@ def test_batchnorm_on_load_matches_materialised_batchnorm(K, N, H, Ci, Co, relu)
     close(gb1.cpu(), gb0.cpu(), 1e-5)
 
 
+@pytest.mark.parametrize("N,H,Ci,Co,relu", [
+    (128, 32, 64, 64, True),     # bench shape, two statistics groups
+    (8, 16, 128, 64, True),      # four chunks
+    (8, 8, 256, 256, False),     # one sub-tile per workgroup, 4 KB table, no ReLU
+    (4, 64, 32, 32, True),       # 32-channel tile, single chunk
+    (6, 24, 64, 96, True),       # image borders inside every tile row, three images per group
+])
+def test_batchnorm_on_load_matches_materialised_batchnorm(K, N, H, Ci, Co, relu):
+    check_batchnorm_on_load_matches_materialised_batchnorm(K, N, H, H, Ci, Co, relu)
+
+
 def test_conv3x3_f32x3_layout_and_precision_must_agree(K):
     """w_layout 2 (split weights) <-> precision 2: a mismatch is a caller error, not a silently wrong operand format; precision 2
     without packed weights computes as precision 0 (bit-identical to the fp32-input MFMA kernel)."""
@@ -913,15 +997,16 @@ def test_conv3x3_f32x3_layout_and_precision_must_agree(K):
         assert rc == -1, (prec, lay, rc)            # BH_E_BADARG
 
 
-@pytest.mark.parametrize("N,H,Ci,Co", [(128, 32, 64, 64), (16, 16, 128, 128), (8, 8, 256, 256)])
-def test_wgrad_deterministic_mode_is_bitwise_repeatable(K, N, H, Ci, Co):
+def check_wgrad_deterministic_mode_is_bitwise_repeatable(K, N, H, W, Ci, Co, variant=None):
     """bh_conv_wgrad_det: split-K partial tiles + a fixed-order second pass instead of fp32 atomics.  Two runs give
     bit-identical weight gradients (the default atomics path does not), the values match torch float64, and the result
     accumulates onto what gw already holds."""
     g = torch.Generator().manual_seed(N + H)
-    x = torch.randn(N, H, H, Ci, generator=g).cuda()
-    gy = torch.randn(N, H, H, Co, generator=g).cuda()
-    d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1)
+    x = torch.randn(N, H, W, Ci, generator=g).cuda()
+    gy = torch.randn(N, H, W, Co, generator=g).cuda()
+    d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1)
+    if variant:
+        assert K.conv_variant(d, "wgrad_det").startswith(variant), K.conv_variant(d, "wgrad_det")
     need = K.wgrad_det_bytes(d)
     assert 0 < need <= 40 << 20
     ws = torch.empty(need // 4, dtype=torch.float32, device="cuda")
@@ -931,7 +1016,7 @@ def test_wgrad_deterministic_mode_is_bitwise_repeatable(K, N, H, Ci, Co):
         K.conv_wgrad(x, gy, gw, None, d, det_ws=ws)
         runs.append(gw.clone())
     assert torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
-    if N * H * H <= 8192:
+    if N * H * W <= 8192:
         ref = torch.nn.grad.conv2d_weight(x.double().cpu().permute(0, 3, 1, 2), (Co, Ci, 3, 3), gy.double().cpu().permute(0, 3, 1, 2),
                                           stride=1, padding=1).permute(0, 2, 3, 1)
         close(runs[0].cpu(), ref, 2e-5)
@@ -942,6 +1027,11 @@ def test_wgrad_deterministic_mode_is_bitwise_repeatable(K, N, H, Ci, Co):
     K.conv_wgrad(x, gy, gw2, None, d, det_ws=ws)             # accumulates
     close(gw2.cpu(), 2 * runs[0].cpu(), 1e-6)
     assert K.wgrad_det_bytes(K.conv_desc(8, 64, 64, 32, 32, 3, 1, 1)) == 0      # small-channel layers: no deterministic form
+
+
+@pytest.mark.parametrize("N,H,Ci,Co", [(128, 32, 64, 64), (16, 16, 128, 128), (8, 8, 256, 256)])
+def test_wgrad_deterministic_mode_is_bitwise_repeatable(K, N, H, Ci, Co):
+    check_wgrad_deterministic_mode_is_bitwise_repeatable(K, N, H, H, Ci, Co)
 
 
 @pytest.mark.parametrize("relu", [True, False])
@@ -976,16 +1066,15 @@ def test_batchnorm_on_load_propagates_nan(K, relu):
     assert bool(nanc[13]) and int(nanc.sum()) == 1
 
 
-@pytest.mark.parametrize("N,H,Ci,Co", [(128, 32, 64, 64), (8, 16, 128, 128), (8, 8, 256, 256), (4, 64, 32, 32), (3, 24, 96, 160)])
-def test_conv3x3_f32x2_two_piece_mode(K, N, H, Ci, Co):
+def check_conv3x3_f32x2_two_piece_mode(K, N, H, W, Ci, Co):
     """precision 3 / w_layout 3 ("f32x2"): two bf16 pieces per operand, both rounded to nearest, three MFMA products.  Stated
     accuracy: relative L2 error against torch float64 below 8e-6 for forward, dgrad and weight gradient (operand representation
     2^-18 = 3.8e-6 worst case, zero mean), i.e. >= 100x below the bf16-operand mode (2.4e-3) and ~10x above fp32; the two
     pieces of a packed weight reproduce it to 2^-17 relative."""
     from bihome_amd._lib import ROUTE_HALO_SMALL
     g = torch.Generator().manual_seed(N * 5 + H)
-    x = torch.randn(N, H, H, Ci, generator=g).cuda()
-    gy = torch.randn(N, H, H, Co, generator=g).cuda()
+    x = torch.randn(N, H, W, Ci, generator=g).cuda()
+    gy = torch.randn(N, H, W, Co, generator=g).cuda()
     w = (torch.randn(Co, Ci, 3, 3, generator=g) * 0.05).cuda().contiguous(memory_format=torch.channels_last)
     wk = w.permute(0, 2, 3, 1)
     b = torch.randn(Co, generator=g).cuda()
@@ -993,10 +1082,10 @@ def test_conv3x3_f32x2_two_piece_mode(K, N, H, Ci, Co):
     ref = F.conv2d(xd, wd, b.double().cpu(), 1, 1).permute(0, 2, 3, 1)
     refd = F.conv_transpose2d(gy.double().cpu().permute(0, 3, 1, 2), wd, None, 1, 1).permute(0, 2, 3, 1)
     refw = torch.einsum("nyxo,nyxtc->otc", gy.double().cpu(),
-                        F.unfold(xd, 3, padding=1).view(N, Ci, 9, H, H).permute(0, 3, 4, 2, 1)).reshape(Co, 3, 3, Ci)
+                        F.unfold(xd, 3, padding=1).view(N, Ci, 9, H, W).permute(0, 3, 4, 2, 1)).reshape(Co, 3, 3, Ci)
     errs = {}
     for prec in (3, 2, 1):
-        d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=prec, route=ROUTE_HALO_SMALL)
+        d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=prec, route=ROUTE_HALO_SMALL)
         if prec == 1:
             y, gx = K.conv_fwd(x, wk, b, d), K.conv_dgrad(gy, wk, d)
         else:
@@ -1004,6 +1093,7 @@ def test_conv3x3_f32x2_two_piece_mode(K, N, H, Ci, Co):
             pf, pd = pk.get(w)
             pk.refresh()
             dp = K._with_layout(d, K.packed_layout(prec))
+            assert K.conv_variant(dp, "fwd").startswith("conv3x3_halo_kernel<false,") and K.conv_variant(dp, "dgrad").startswith("conv3x3_halo_kernel<true,")
             assert K.conv_variant(dp, "fwd").endswith(",true,true,false,%d,false,false>" % K.SPLIT_PIECES[prec])
             y = K.conv_fwd(x, wk, b, d, wpacked=pf)
             s = K.bn_stats_buffer(1, Co, "cuda")
@@ -1034,6 +1124,11 @@ def test_conv3x3_f32x2_two_piece_mode(K, N, H, Ci, Co):
     assert max(errs[3]) < 8e-6, errs
     # (forward and dgrad; the bf16-operand weight gradient of some shapes runs the fp32 kernel)
     assert all(e3 < e1 / 100 for e3, e1 in zip(errs[3][:2], errs[1][:2])), errs
+
+
+@pytest.mark.parametrize("N,H,Ci,Co", [(128, 32, 64, 64), (8, 16, 128, 128), (8, 8, 256, 256), (4, 64, 32, 32), (3, 24, 96, 160)])
+def test_conv3x3_f32x2_two_piece_mode(K, N, H, Ci, Co):
+    check_conv3x3_f32x2_two_piece_mode(K, N, H, H, Ci, Co)
 
 
 @pytest.mark.parametrize("N,Ci,Co,prec,groups", [(128, 512, 512, 2, 2), (128, 512, 512, 3, 2), (16, 64, 128, 2, 1), (8, 192, 64, 2, 2)])
@@ -1200,13 +1295,12 @@ def test_batchnorm_on_load_1x1_matches_materialised_batchnorm(K, N, H, Ci, Co, r
             close(g1.cpu(), g0.cpu(), 3e-6)
 
 
-@pytest.mark.parametrize("groups,N,H,C,training", [(2, 4, 16, 64, True), (1, 3, 10, 32, True), (2, 2, 64, 64, False)])
-def test_batchnorm_relu_maxpool_in_one_pass(K, groups, N, H, C, training):
+def check_batchnorm_relu_maxpool_in_one_pass(K, groups, N, H, W, C, training):
     """bh_bn_maxpool_fwd (round 4: conv1-bn1-relu-maxpool of the stems) against bh_bn_fwd followed by bh_maxpool3s2_fwd: pooled values, arg-max
     positions, running statistics; and the adjoint through the saved positions + the BatchNorm backward with the mask recomputed from x
     equals the unfused adjoint."""
-    g = torch.Generator().manual_seed(H + C)
-    x = (torch.randn(N, H, H, C, generator=g) * 1.2 + 0.1).cuda()
+    g = torch.Generator().manual_seed(H + C + (0 if H == W else 1000 * W))
+    x = (torch.randn(N, H, W, C, generator=g) * 1.2 + 0.1).cuda()
     gamma, beta = (torch.rand(C, generator=g) + 0.5).cuda(), (torch.randn(C, generator=g) * 0.3).cuda()
     rm0, rv0 = (torch.randn(C, generator=g) * 0.1).cuda(), (torch.rand(C, generator=g) + 0.5).cuda()
     rm1, rv1 = rm0.clone(), rv0.clone()
@@ -1231,3 +1325,8 @@ def test_batchnorm_relu_maxpool_in_one_pass(K, groups, N, H, C, training):
     gx1 = K.bn_maxpool_bwd(K.PooledGrad(gp, fused.idx), x, gamma, beta, st1, rm1, rv1, groups, 1e-5, True, training, gg1, gb1, amax=rec1)
     assert torch.equal(gx1, gx0) and torch.equal(gg1, gg0) and torch.equal(gb1, gb0)
     assert float(rec1.max()) == float(rec0.max()) == float(gx0.abs().max())
+
+
+@pytest.mark.parametrize("groups,N,H,C,training", [(2, 4, 16, 64, True), (1, 3, 10, 32, True), (2, 2, 64, 64, False)])
+def test_batchnorm_relu_maxpool_in_one_pass(K, groups, N, H, C, training):
+    check_batchnorm_relu_maxpool_in_one_pass(K, groups, N, H, H, C, training)

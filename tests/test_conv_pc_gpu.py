@@ -12,8 +12,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(8, 16, 64, 64), (4, 8, 256, 256), (16, 16, 128, 128), (3, 24, 64, 128), (2, 8, 96, 64), (4, 24, 64, 64), (6, 40, 64, 64), (40, 32, 64, 64),
-          (128, 32, 64, 64), (24, 16, 32, 64)]
+# (N, H, W, Ci, Co); the last four: rectangular maps in both orientations - 16 x 32 with the shift decode of the tile index, 24 x 40 with the divisions
+SHAPES = [(8, 16, 16, 64, 64), (4, 8, 8, 256, 256), (16, 16, 16, 128, 128), (3, 24, 24, 64, 128), (2, 8, 8, 96, 64), (4, 24, 24, 64, 64), (6, 40, 40, 64, 64),
+          (40, 32, 32, 64, 64), (128, 32, 32, 64, 64), (24, 16, 16, 32, 64),
+          (4, 16, 32, 64, 64), (4, 32, 16, 64, 64), (2, 24, 40, 64, 128), (2, 40, 24, 64, 128)]
 
 
 @pytest.fixture(scope="module")
@@ -24,10 +26,15 @@ def K():
     return kernels
 
 
-def _descs(K, N, H, Ci, Co):
+def _ids(shapes):
+    """Square maps keep the ids they had as (N, H, Ci, Co)."""
+    return ["%d-%d-%d-%d" % (N, H, Ci, Co) if H == W else "%d-%dx%d-%d-%d" % (N, H, W, Ci, Co) for (N, H, W, Ci, Co) in shapes]
+
+
+def _descs(K, N, H, W, Ci, Co):
     from bihome_amd._lib import ROUTE_C3_PC, ROUTE_C3_TILE_WG, ROUTE_HALO_SMALL
-    new = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=4, route=ROUTE_HALO_SMALL | ROUTE_C3_PC)
-    old = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=4, route=ROUTE_HALO_SMALL | ROUTE_C3_TILE_WG)
+    new = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=4, route=ROUTE_HALO_SMALL | ROUTE_C3_PC)
+    old = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=4, route=ROUTE_HALO_SMALL | ROUTE_C3_TILE_WG)
     # (the persistent kernel takes the 64-channel output tile: forward Co % 64 == 0, dgrad Ci % 64 == 0; the other direction of such a
     #  layer runs the halo kernel's 32-channel tile either way)
     if Co % 64 == 0:
@@ -38,10 +45,10 @@ def _descs(K, N, H, Ci, Co):
     return new, old
 
 
-def _operands(K, N, H, Ci, Co, seed=0):
-    g = torch.Generator().manual_seed(seed + N * 7 + H + Ci)
-    x = torch.randn(N, H, H, Ci, generator=g).cuda()
-    gy = torch.randn(N, H, H, Co, generator=g).cuda()
+def _operands(K, N, H, W, Ci, Co, seed=0):
+    g = torch.Generator().manual_seed(seed + N * 7 + H + Ci + (0 if H == W else 1000 * W))
+    x = torch.randn(N, H, W, Ci, generator=g).cuda()
+    gy = torch.randn(N, H, W, Co, generator=g).cuda()
     w = (torch.randn(Co, Ci, 3, 3, generator=g) * 0.05).cuda().contiguous(memory_format=torch.channels_last)
     b = torch.randn(Co, generator=g).cuda()
     pk = K.packer_for_precision(4)
@@ -56,10 +63,10 @@ def _sums_close(a, b, tol=2e-6):
     assert (a - b).abs().max().item() <= tol * scale, ((a - b).abs().max().item(), scale)
 
 
-@pytest.mark.parametrize("N,H,Ci,Co", SHAPES)
-def test_forward_bit_identical(K, N, H, Ci, Co):
-    new, old = _descs(K, N, H, Ci, Co)
-    x, gy, wk, b, pf, pd, g = _operands(K, N, H, Ci, Co)
+@pytest.mark.parametrize("N,H,W,Ci,Co", SHAPES, ids=_ids(SHAPES))
+def test_forward_bit_identical(K, N, H, W, Ci, Co):
+    new, old = _descs(K, N, H, W, Ci, Co)
+    x, gy, wk, b, pf, pd, g = _operands(K, N, H, W, Ci, Co)
     for bias in (None, b):
         y1, y0 = K.conv_fwd(x, wk, bias, new, wpacked=pf), K.conv_fwd(x, wk, bias, old, wpacked=pf)
         assert torch.equal(y1, y0)
@@ -76,7 +83,7 @@ def test_forward_bit_identical(K, N, H, Ci, Co):
         exact = K.conv_variant(K._with_layout(new, 4), "fwd", bn_groups=groups).startswith("conv3x3_pc_kernel")
         _sums_close(tab[..., 0], yd.sum(1), 1e-11 if exact else 1e-6)
         _sums_close(tab[..., 1], (yd * yd).sum(1), 1e-11 if exact else 1e-6)
-    res = torch.randn(N, H, H, Co, generator=g).cuda()
+    res = torch.randn(N, H, W, Co, generator=g).cuda()
     y1 = K.conv_fwd(x, wk, b, new, res=res, relu=True, wpacked=pf)
     y0 = K.conv_fwd(x, wk, b, old, res=res, relu=True, wpacked=pf)
     assert torch.equal(y1, y0)
@@ -90,11 +97,11 @@ def test_epilogue_store_hazard_stress(K):
     """Round 5: a 128-bit buffer store whose data registers were overwritten by the next VALU instruction corrupted single channels in a few
     of 2048 sub-tiles, and only under some timings (csrc/conv3x3_pc.hip: the `s_nop 3` behind the store).  The forms that hit it - epilogue
     operands on the multi-tile shape - repeated, with a second stream keeping the memory system busy."""
-    N, H, Ci, Co = 128, 32, 64, 64
-    new, old = _descs(K, N, H, Ci, Co)
-    x, gy, wk, b, pf, pd, g = _operands(K, N, H, Ci, Co, seed=5)
-    res = torch.randn(N, H, H, Co, generator=g).cuda()
-    base = torch.randn(N, H, H, Ci, generator=g).cuda()
+    N, H, W, Ci, Co = 128, 32, 32, 64, 64
+    new, old = _descs(K, N, H, W, Ci, Co)
+    x, gy, wk, b, pf, pd, g = _operands(K, N, H, W, Ci, Co, seed=5)
+    res = torch.randn(N, H, W, Co, generator=g).cuda()
+    base = torch.randn(N, H, W, Ci, generator=g).cuda()
     y0 = K.conv_fwd(x, wk, b, old, res=res, relu=True, wpacked=pf)
     o0 = base.clone()
     K.conv_dgrad(gy, wk, old, out=o0, wpacked=pd)
@@ -113,14 +120,14 @@ def test_epilogue_store_hazard_stress(K):
 
 
 # (shapes the BatchNorm kernels take: two groups, C / 4 dividing 256; (4, 16, 32, 64) is a ONE-chunk forward: three barrier phases per tile)
-BN_SHAPES = [s for s in SHAPES if s[0] % 2 == 0 and 256 % (s[2] // 4) == 0] + [(4, 16, 32, 64), (24, 16, 32, 64)]
+BN_SHAPES = [s for s in SHAPES if s[0] % 2 == 0 and 256 % (s[3] // 4) == 0] + [(4, 16, 16, 32, 64), (24, 16, 16, 32, 64)]
 
 
-@pytest.mark.parametrize("N,H,Ci,Co", BN_SHAPES)
+@pytest.mark.parametrize("N,H,W,Ci,Co", BN_SHAPES, ids=_ids(BN_SHAPES))
 @pytest.mark.parametrize("relu", [True, False])
-def test_forward_batchnorm_on_load_bit_identical(K, N, H, Ci, Co, relu):
-    new, old = _descs(K, N, H, Ci, Co)
-    x, gy, wk, b, pf, pd, g = _operands(K, N, H, Ci, Co, seed=1)
+def test_forward_batchnorm_on_load_bit_identical(K, N, H, W, Ci, Co, relu):
+    new, old = _descs(K, N, H, W, Ci, Co)
+    x, gy, wk, b, pf, pd, g = _operands(K, N, H, W, Ci, Co, seed=1)
     groups = 2
     z = x * 1.5 + 0.3
     gamma = (torch.rand(Ci, generator=g) + 0.5).cuda()
@@ -129,7 +136,7 @@ def test_forward_batchnorm_on_load_bit_identical(K, N, H, Ci, Co, relu):
     st = K.bn_stats_buffer(groups, Ci, "cuda")
     K.bn_stats(z, st, groups, Ci)
     rec = K.amax_record("cuda")
-    table = K.bn_fwd_coeffs(st, gamma, beta, rm, rv, groups, N * H * H // groups, Ci, 1e-5, 0.1, amax=rec)
+    table = K.bn_fwd_coeffs(st, gamma, beta, rm, rv, groups, N * H * W // groups, Ci, 1e-5, 0.1, amax=rec)
     lazy = K.BnOnLoad(z, table, groups, relu, amax=rec)
     for sums in (False, True):
         s1 = K.bn_stats_buffer(groups, Co, "cuda") if sums else None
@@ -141,13 +148,13 @@ def test_forward_batchnorm_on_load_bit_identical(K, N, H, Ci, Co, relu):
             _sums_close(s1, s0)
 
 
-@pytest.mark.parametrize("N,H,Ci,Co", SHAPES)
-def test_dgrad_bit_identical(K, N, H, Ci, Co):
-    new, old = _descs(K, N, H, Ci, Co)
-    x, gy, wk, b, pf, pd, g = _operands(K, N, H, Ci, Co, seed=2)
+@pytest.mark.parametrize("N,H,W,Ci,Co", SHAPES, ids=_ids(SHAPES))
+def test_dgrad_bit_identical(K, N, H, W, Ci, Co):
+    new, old = _descs(K, N, H, W, Ci, Co)
+    x, gy, wk, b, pf, pd, g = _operands(K, N, H, W, Ci, Co, seed=2)
     g1, g0 = K.conv_dgrad(gy, wk, new, wpacked=pd), K.conv_dgrad(gy, wk, old, wpacked=pd)
     assert torch.equal(g1, g0)
-    base = torch.randn(N, H, H, Ci, generator=g).cuda()
+    base = torch.randn(N, H, W, Ci, generator=g).cuda()
     o1, o0 = base.clone(), base.clone()
     K.conv_dgrad(gy, wk, new, out=o1, wpacked=pd); K.conv_dgrad(gy, wk, old, out=o0, wpacked=pd)
     assert torch.equal(o1, o0)
@@ -159,19 +166,22 @@ def test_dgrad_bit_identical(K, N, H, Ci, Co):
     assert ((g1.cpu().double() - ref).norm() / ref.norm()).item() < 1e-6
 
 
-@pytest.mark.parametrize("N,H,Ci,Co", [s for s in SHAPES if s[0] % 2 == 0 and 256 % (s[2] // 4) == 0])
+REDUCE_SHAPES = [s for s in SHAPES if s[0] % 2 == 0 and 256 % (s[3] // 4) == 0]
+
+
+@pytest.mark.parametrize("N,H,W,Ci,Co", REDUCE_SHAPES, ids=_ids(REDUCE_SHAPES))
 @pytest.mark.parametrize("relu,with_y,acc", [(True, False, False), (True, True, True), (False, False, True), (True, False, True)])
-def test_dgrad_batchnorm_reduce_bit_identical(K, N, H, Ci, Co, relu, with_y, acc):
-    new, old = _descs(K, N, H, Ci, Co)
-    x, gy, wk, b, pf, pd, g = _operands(K, N, H, Ci, Co, seed=3)
+def test_dgrad_batchnorm_reduce_bit_identical(K, N, H, W, Ci, Co, relu, with_y, acc):
+    new, old = _descs(K, N, H, W, Ci, Co)
+    x, gy, wk, b, pf, pd, g = _operands(K, N, H, W, Ci, Co, seed=3)
     groups = 2
-    z = (torch.randn(N, H, H, Ci, generator=g) * 1.5 + 0.3).cuda()
+    z = (torch.randn(N, H, W, Ci, generator=g) * 1.5 + 0.3).cuda()
     gamma = (torch.rand(Ci, generator=g) + 0.5).cuda()
     beta = (torch.randn(Ci, generator=g) * 0.2).cuda()
     st = K.bn_stats_buffer(groups, Ci, "cuda")
     K.bn_stats(z, st, groups, Ci)
-    yb = torch.randn(N, H, H, Ci, generator=g).cuda() if with_y else None
-    base = torch.randn(N, H, H, Ci, generator=g).cuda()
+    yb = torch.randn(N, H, W, Ci, generator=g).cuda() if with_y else None
+    base = torch.randn(N, H, W, Ci, generator=g).cuda()
     outs = []
     for d in (new, old):
         sums = K.bn_stats_buffer(groups, Ci, "cuda")
@@ -187,11 +197,11 @@ def test_deterministic_call_is_repeatable(K):
     """In a deterministic scope (BH_ROUTE_DETERMINISTIC) the statistics leave through integer limbs: bitwise repeatable, whatever the order
     in which the workgroups arrive."""
     from bihome_amd._lib import ROUTE_HALO_SMALL
-    N, H, Ci, Co = 16, 16, 128, 128
-    x, gy, wk, b, pf, pd, g = _operands(K, N, H, Ci, Co, seed=4)
+    N, H, W, Ci, Co = 16, 16, 16, 128, 128
+    x, gy, wk, b, pf, pd, g = _operands(K, N, H, W, Ci, Co, seed=4)
     runs = []
     with K.det_scope(True):
-        d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=4, route=ROUTE_HALO_SMALL)
+        d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=4, route=ROUTE_HALO_SMALL)
         assert K.conv_variant(K._with_layout(d, 4), "fwd", bn_groups=2).startswith("conv3x3_pc_kernel")
         for _ in range(4):
             s = K.bn_stats_buffer(2, Co, "cuda")
@@ -202,7 +212,7 @@ def test_deterministic_call_is_repeatable(K):
         ds = (runs[0][1].view(torch.int64) != r[1].view(torch.int64)).reshape(-1, 16)       # (bit patterns: a negative limb read as a double is a NaN)
         assert not ds.any(), (int(ds.sum()), ds.any(0).tolist())
     # and the limbs hold the same totals as the default mode's doubles
-    d0 = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=4, route=ROUTE_HALO_SMALL)
+    d0 = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=4, route=ROUTE_HALO_SMALL)
     s0 = K.bn_stats_buffer(2, Co, "cuda")
     K.conv_fwd(x, wk, b, d0, bn_sums=s0, groups=2, wpacked=pf)
     e = runs[0][1].reshape(-1, 16)
@@ -227,19 +237,19 @@ if __name__ == "__main__":
     sys.path.insert(0, ".")
     from bihome_amd import kernels as K
     from bihome_amd._lib import ROUTE_C3_PC, ROUTE_C3_TILE_WG
-    shapes = [(128, 32, 64, 64), (128, 16, 128, 128), (128, 8, 256, 256), (128, 64, 64, 64), (128, 32, 128, 128), (128, 16, 256, 256)]
+    shapes = [(128, 32, 32, 64, 64), (128, 16, 16, 128, 128), (128, 8, 8, 256, 256), (128, 64, 64, 64, 64), (128, 32, 32, 128, 128), (128, 16, 16, 256, 256)]
     if len(sys.argv) > 1:
         shapes = [tuple(int(v) for v in a.split(",")) for a in sys.argv[1:]]
-    for (N, H, Ci, Co) in shapes:
-        x, gy, wk, b, pf, pd, g = _operands(K, N, H, Ci, Co)
-        z = (torch.randn(N, H, H, Ci, generator=g) * 1.5 + 0.3).cuda()
+    for (N, H, W, Ci, Co) in shapes:
+        x, gy, wk, b, pf, pd, g = _operands(K, N, H, W, Ci, Co)
+        z = (torch.randn(N, H, W, Ci, generator=g) * 1.5 + 0.3).cuda()
         gamma, beta = (torch.rand(Ci, generator=g) + 0.5).cuda(), (torch.randn(Ci, generator=g) * 0.2).cuda()
         st = K.bn_stats_buffer(2, Ci, "cuda"); K.bn_stats(z, st, 2, Ci)
-        base = torch.randn(N, H, H, Ci, generator=g).cuda()
+        base = torch.randn(N, H, W, Ci, generator=g).cuda()
         res = {}
         for rnd in range(3):                   # alternate the two kernels (the first variant measured in a process runs slower whatever it is)
             for tag, route in (("pc", ROUTE_C3_PC), ("halo", ROUTE_C3_TILE_WG)):
-                d = K.conv_desc(N, H, H, Ci, Co, 3, 1, 1, precision=4, route=route)
+                d = K.conv_desc(N, H, W, Ci, Co, 3, 1, 1, precision=4, route=route)
                 s = K.bn_stats_buffer(2, Co, "cuda"); s2 = K.bn_stats_buffer(2, Ci, "cuda")
                 bnr = dict(z=z, y=None, stats=st, gamma=gamma, beta=beta, eps=1e-5, relu=True, sums=s2, groups=2)
                 for name, fn in (("fwd", lambda: K.conv_fwd(x, wk, None, d, wpacked=pf)),
@@ -247,8 +257,8 @@ if __name__ == "__main__":
                                  ("dgrad", lambda: K.conv_dgrad(gy, wk, d, wpacked=pd)),
                                  ("dgrad+bnr+acc", lambda: K.conv_dgrad(gy, wk, d, out=base, wpacked=pd, bn_reduce=bnr))):
                     res.setdefault((name, tag), []).append(_bench(fn))
-        fl = 2.0 * N * H * H * Ci * Co * 9
+        fl = 2.0 * N * H * W * Ci * Co * 9
         for name in ("fwd", "fwd+stats", "dgrad", "dgrad+bnr+acc"):
             p, h = min(res[(name, "pc")]), min(res[(name, "halo")])
-            print("%-22s %-14s pc %6.1f us (%5.0f TF alg)  halo %6.1f us   %s" % ((N, H, Ci, Co), name, p, fl / p / 1e6, h,
+            print("%-22s %-14s pc %6.1f us (%5.0f TF alg)  halo %6.1f us   %s" % ((N, H, W, Ci, Co), name, p, fl / p / 1e6, h,
                   " ".join("%.1f/%.1f" % (a, c) for a, c in zip(res[(name, "pc")], res[(name, "halo")]))), flush=True)

@@ -31,12 +31,14 @@ def rand_delta(B, seed, amp=32):
     return g.uniform(-amp, amp, (B, 4, 2)).astype(np.float32)
 
 
-def test_h4pt_fwd_bwd(K):
+def check_h4pt_fwd_bwd(K, size):
+    """size: the patch extent, or (W, H)."""
+    W, H = size if isinstance(size, tuple) else (size, size)
     B = 37
     d = rand_delta(B, 1)
-    H64, H32 = K.h4pt_fwd(dev(d), 128)
+    H64, H32 = K.h4pt_fwd(dev(d), size)
     dt = torch.tensor(d, dtype=torch.float64, requires_grad=True)
-    corners = torch.tensor([[0, 0], [128, 0], [128, 128], [0, 128]], dtype=torch.float64).repeat(B, 1, 1)
+    corners = torch.tensor([[0, 0], [W, 0], [W, H], [0, H]], dtype=torch.float64).repeat(B, 1, 1)
     Href = O.four_point_to_homography(corners, dt)
     np.testing.assert_allclose(H64.cpu().numpy().reshape(B, 3, 3), Href.detach().numpy(), rtol=1e-10, atol=1e-12)
     np.testing.assert_allclose(H32.cpu().numpy(), Href.detach().numpy(), rtol=2e-6, atol=1e-7)
@@ -46,19 +48,23 @@ def test_h4pt_fwd_bwd(K):
     g = np.random.Generator(np.random.PCG64(2)).standard_normal((B, 9))
     g[:, 8] = 0
     (Href.reshape(B, 9) * torch.tensor(g)).sum().backward()
-    gd = K.h4pt_bwd(dev(d), H64, dev(g, torch.float64), 128)
+    gd = K.h4pt_bwd(dev(d), H64, dev(g, torch.float64), size)
+    print("MEASURED h4pt %s: max |H64 - f64| %.3e, max |gdelta - f64| %.3e of %.3e" % (size, np.abs(H64.cpu().numpy().reshape(B, 3, 3) - Href.detach().numpy()).max(),
+          np.abs(gd.cpu().numpy() - dt.grad.numpy()).max(), np.abs(dt.grad.numpy()).max()))
     np.testing.assert_allclose(gd.cpu().numpy(), dt.grad.numpy(), rtol=2e-5, atol=1e-7 * np.abs(dt.grad.numpy()).max())
 
 
-@pytest.mark.parametrize("n,P", [(1, 128), (4, 16), (2, 200)])
-def test_dlt_fwd_bwd(K, n, P):
-    B = 6
-    d = synth.make_head_inputs(B, seed=3, noise=0.7)
-    pf = d["pf_hat_12"]
-    choice = O.sample_choice(128 * 128, B * n * P, torch.Generator().manual_seed(5)).reshape(B, n * P)
+def test_h4pt_fwd_bwd(K):
+    check_h4pt_fwd_bwd(K, 128)
+
+
+def check_dlt_fwd_bwd(K, n, P, pf):
+    """pf [B,2,h,w]: the perspective field the hypotheses are fitted to (the corners of delta_hat are those of the field's own extents)."""
+    B, _, h, w = pf.shape
+    choice = O.sample_choice(h * w, B * n * P, torch.Generator().manual_seed(5)).reshape(B, n * P)
     Hd, dh, eig = K.dlt_fwd(dev(pf), choice.cuda(), n, P)
     # float64 oracle
-    head = O.BiHomEHead(torch.nn.Identity(), PATCH_SIZE=128, PATCH_KEYS=["patch_1", "patch_2"], DELTA_HAT_KEYS=[],
+    head = O.BiHomEHead(torch.nn.Identity(), PATCH_SIZE=max(h, w), PATCH_KEYS=["patch_1", "patch_2"], DELTA_HAT_KEYS=[],
                         PF_KEYS=["a", "b"], RANSAC_HYPOTHESIS_NO=n, POINTS_PER_HYPOTHESIS=P, TRIPLET_LOSS="double-line",
                         TRIPLET_DISTANCE="l1", TRIPLET_AGGREGATION="channel-agnostic", TRIPLET_MARGIN="inf",
                         MASK_KEYS=[], TRIPLET_MU=0.01).double()
@@ -75,7 +81,15 @@ def test_dlt_fwd_bwd(K, n, P):
     (dref.reshape(B * n, 4, 2) * torch.tensor(gd, dtype=torch.float64)).sum().backward()
     gpf = K.dlt_bwd(dev(pf), choice.cuda(), eig, dev(gd), n, P)
     ref = pft.grad.numpy()
+    print("MEASURED dlt n%d P%d %dx%d: max |Hdlt - f64| %.3e, |delta_hat - f64| %.3e, |g_pf - f64| %.3e of %.3e"
+          % (n, P, h, w, np.abs(Hd.cpu().numpy().reshape(B, n, 3, 3) - Href.detach().numpy()).max(),
+             np.abs(dh.cpu().numpy().reshape(B, n, 4, 2) - dref.detach().numpy()).max(), np.abs(gpf.cpu().numpy() - ref).max(), np.abs(ref).max()))
     np.testing.assert_allclose(gpf.cpu().numpy(), ref, rtol=1e-4, atol=1e-5 * np.abs(ref).max())
+
+
+@pytest.mark.parametrize("n,P", [(1, 128), (4, 16), (2, 200)])
+def test_dlt_fwd_bwd(K, n, P):
+    check_dlt_fwd_bwd(K, n, P, synth.make_head_inputs(6, seed=3, noise=0.7)["pf_hat_12"])
 
 
 def test_dsac_argmin_bit_exact(K, golden):
@@ -93,24 +107,45 @@ def test_dsac_argmin_bit_exact(K, golden):
 
 # ~twice the largest error measured on the five cases (round 6, `pytest -s`, profiles/r06b_gpu_tests_measured.txt: 8e-6 ... 3.8e-5 of max |dL/dH|
 # by build; rounds 1-5 allowed 2e-3): float32 coordinates and per-pixel products, double sums, against the float64 autograd of the oracle.
-# (Not tighter: the bilinear derivative jumps where a coordinate crosses an integer, and one pixel that float32 puts on the other side of
-# such a kink than float64 moves an entry by ~1e-5 of the maximum on these sizes.)
 WARP_ADJOINT_BOUND = 1e-4
 
 
-def check_warp_fwd_bwd(K, B, C, size, pool):
-    """Forward, coverage and adjoint of one shape against the oracle; returns (cov, gH, the arguments of warp_bwd) for further checks."""
+def coordinate_ties(H, h, w):
+    """Pixels at which the warp has no derivative at float32 resolution.  The bilinear sampler's derivative jumps where a source coordinate
+    crosses an integer, and the kernels place their taps from float32 coordinates (csrc/warp_tap.h: two fused multiply-adds per component of
+    H.(x, y, 1), a reciprocal good to an ulp, one product) - within 8 * 2^-24 * max(h, w) of the float64 value (the largest difference seen
+    is 3 * 2^-24 * 128, on 64 x 128).  A pixel that float64 puts closer than that to an integer can fall on either side in float32: both
+    one-sided derivatives are right there, and ONE such pixel moves dL/dH by percents (an entry is a sum of h w terms of either sign).  Met
+    on 64 x 128 with the seeded homography of check_warp_fwd_bwd: (x, y) = (126, 32) maps to u = 120.0000027 in float64 and to 119.9999924
+    in the kernel's float32 arithmetic - the adjoint was 4.0e-2 of max |dL/dH| from float64, and so is the oracle's own float32 run (its one
+    floor flip is that pixel) - while 128 x 64 and every other shape were within 3e-5.  A fraction ~4 * tie of the pixels.
+    H [B,3,3] float64 -> (tie [B,h,w] bool, cov_tie [B,h,w] bool: the ties at a kink of the warped all-ones mask, u in {-1, 0, w-1, w} or
+    v in {-1, 0, h-1, h})."""
+    tie = 8 * 2.0 ** -24 * max(h, w)
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float64), torch.arange(w, dtype=torch.float64), indexing="ij")
+    q = torch.einsum("bij,hwj->bhwi", H.detach(), torch.stack([xs, ys, torch.ones_like(xs)], -1))
+    u, v = q[..., 0] / q[..., 2], q[..., 1] / q[..., 2]
+    tu, tv = (u - u.round()).abs() < tie, (v - v.round()).abs() < tie
+    edge = lambda t, n: sum((t.round() == k) for k in (-1, 0, n - 1, n)) > 0
+    return tu | tv, (tu & edge(u, w)) | (tv & edge(v, h))
+
+
+def check_warp_fwd_bwd(K, B, C, h, w, pool, delta=None):
+    """Forward, coverage and adjoint of one shape (images of h rows and w columns) against the oracle; returns (cov, gH, the arguments of
+    warp_bwd) for further checks.  delta [B,4,2]: the corner offsets of the homographies (default: random, up to a quarter of the smaller extent)."""
+    size = h if h == w else 1000 * h + w             # (seeds)
     rng = np.random.Generator(np.random.PCG64(B * 100 + size))
-    img = rng.standard_normal((B, C, size, size)).astype(np.float32)
+    img = rng.standard_normal((B, C, h, w)).astype(np.float32)
     # smooth the image a little so that bilinear gradients are O(1)
     img = F.avg_pool2d(torch.tensor(img), 3, 1, 1).numpy()
-    delta = rand_delta(B, size, amp=size / 4.0)
-    H64, _ = K.h4pt_fwd(dev(delta), size)
+    if delta is None:
+        delta = rand_delta(B, size, amp=min(h, w) / 4.0)
+    H64, _ = K.h4pt_fwd(dev(delta), (w, h))
     out, cov = K.warp_fwd(dev(img), H64, pool)
     Ht = H64.cpu().reshape(B, 3, 3).clone().requires_grad_(True)
     imt = torch.tensor(img, dtype=torch.float64)
     ref = O.warp_image(imt, Ht)
-    refcov = F.avg_pool2d(O.warp_image(torch.ones(B, 1, size, size, dtype=torch.float64), Ht), pool).squeeze(1)
+    refcov = F.avg_pool2d(O.warp_image(torch.ones(B, 1, h, w, dtype=torch.float64), Ht), pool).squeeze(1)
     # north_star: "fp32 warp ... within 1e-4 relative".  The kernel evaluates the map in float32 (like grid_sample's float32 grid):
     # coordinate rounding ~ size * 2^-24 * few -> value error ~ 1e-5 * local gradient.  Bound: 1e-4 of the reference's range, or - where the
     # reference's OWN float32 chain (torch.inverse twice, normalise, grid_sample) is further than that from float64 - 1.5 x that spread.
@@ -119,22 +154,29 @@ def check_warp_fwd_bwd(K, B, C, size, pool):
     scale = np.abs(r64).max()
     err, spread = np.abs(o - r64).max(), np.abs(ref32 - r64).max()
     cerr = np.abs(cov.cpu().double().numpy() - refcov.detach().numpy()).max()
-    print("MEASURED warp B%d C%d %d pool%d: max|hip - f64| %.3e = %.2e of range; f32 oracle's own %.3e; coverage %.3e"
-          % (B, C, size, pool, err, err / scale, spread, cerr))
+    print("MEASURED warp B%d C%d %dx%d pool%d: max|hip - f64| %.3e = %.2e of range; f32 oracle's own %.3e; coverage %.3e"
+          % (B, C, h, w, pool, err, err / scale, spread, cerr))
     assert err <= max(1e-4 * scale, 1.5 * spread), (err, scale, spread)
     assert np.abs(o - ref32).max() <= 1e-4 * scale + 1.5 * spread
     assert cerr <= 2e-5
     go = rng.standard_normal(out.shape).astype(np.float32)
     gc = rng.standard_normal(cov.shape).astype(np.float32)
+    # no output gradient where the derivative is not defined at float32 resolution (coordinate_ties; as the ReLU inputs within rounding of
+    # zero in the BatchNorm tests): those pixels of the image, and the pooling windows with such a pixel on a kink of the coverage
+    tie, cov_tie = coordinate_ties(Ht, h, w)
+    go[np.broadcast_to(tie[:, None].numpy(), go.shape)] = 0
+    gc[F.max_pool2d(cov_tie[:, None].float(), pool).squeeze(1).numpy() > 0] = 0
+    print("MEASURED warp B%d C%d %dx%d pool%d: %d of %d pixels within float32 rounding of an integer source coordinate (%d on a coverage kink)"
+          % (B, C, h, w, pool, int(tie.sum()), tie.numel(), int(cov_tie.sum())))
     ((ref * torch.tensor(go, dtype=torch.float64)).sum() + (refcov * torch.tensor(gc, dtype=torch.float64)).sum()).backward()
     bwd_args = (dev(img), H64, dev(go), dev(gc), pool)
     gH = K.warp_bwd(*bwd_args)
     r = Ht.grad.numpy().reshape(B, 9)
     gerr = np.abs(gH.cpu().double().numpy() - r).max() / np.abs(r).max()
-    print("MEASURED warp adjoint B%d C%d %d pool%d: max error %.3e of max|dL/dH|" % (B, C, size, pool, gerr))
+    print("MEASURED warp adjoint B%d C%d %dx%d pool%d: max error %.3e of max|dL/dH|" % (B, C, h, w, pool, gerr))
     assert gerr <= WARP_ADJOINT_BOUND, gerr
     # coverage-only entry
-    cov2 = K.mask_coverage_fwd(H64, size, size, pool)
+    cov2 = K.mask_coverage_fwd(H64, h, w, pool)
     if pool > 16 and not K.deterministic():
         # a default pool-32 call adds a window's four quarter sums with float atomics, in arrival order: three roundings of a sum <= 1 per
         # launch, 2^-25 each at the most - two launches differ by 3 * 2^-24 at the most (a deterministic call has one writer: equal)
@@ -148,14 +190,25 @@ def check_warp_fwd_bwd(K, B, C, size, pool):
 @pytest.mark.parametrize("B,C,size,pool", [(5, 1, 128, 4), (2, 3, 64, 4), (3, 1, 32, 8), (2, 2, 48, 1), (1, 1, 256, 16),
                                            (2, 1, 64, 32), (2, 2, 32, 2), (3, 1, 48, 4)])
 def test_warp_fwd_bwd(K, B, C, size, pool):
-    check_warp_fwd_bwd(K, B, C, size, pool)
+    check_warp_fwd_bwd(K, B, C, size, size, pool)
+
+
+# rectangular images, each as h x w and as w x h.  48 x 64 / pool 4: the pool-4 kernels (w % 64 == 0) with one row per thread; 64 x 48: the generic
+# kernels; 64 x 128: the pool-4 kernels with several rows per thread; 64 x 96 / pool 32: 2 x 3 pooling windows of four quarter tiles
+RECT_WARP_CASES = [(2, 2, 48, 64, 4), (2, 1, 64, 128, 4), (2, 1, 32, 64, 8), (1, 1, 64, 128, 16), (2, 1, 64, 96, 32), (2, 2, 32, 48, 1), (2, 2, 32, 48, 2)]
+RECT_WARP_CASES = RECT_WARP_CASES + [(B, C, w, h, pool) for (B, C, h, w, pool) in RECT_WARP_CASES]
+
+
+@pytest.mark.parametrize("B,C,h,w,pool", RECT_WARP_CASES)
+def test_warp_fwd_bwd_rectangular(K, B, C, h, w, pool):
+    check_warp_fwd_bwd(K, B, C, h, w, pool)
 
 
 def test_warp_fwd_bwd_pool32_deterministic(K):
     """The pool-32 case in deterministic mode: the one-writer coverage kernel and the single-writer adjoint grid meet the same bounds,
     and two calls give the same bits."""
     with K.det_scope(True):
-        cov, gH, bwd_args = check_warp_fwd_bwd(K, 2, 1, 64, 32)
+        cov, gH, bwd_args = check_warp_fwd_bwd(K, 2, 1, 64, 64, 32)
         cov_again = K.warp_fwd(bwd_args[0], bwd_args[1], 32)[1]
         gH_again = K.warp_bwd(*bwd_args)
     assert torch.equal(cov_again, cov)
@@ -435,37 +488,35 @@ def test_scale_samples_and_scored_hinge_vs_torch64():
         assert (gm.cpu().double() - m.grad).abs().max() <= 2e-4 * m.grad.abs().max() + 1e-7
 
 
-@pytest.mark.parametrize("prec", [0, 4])
-@pytest.mark.parametrize("B,size,pool,with_cov", [(6, 128, 4, True), (3, 64, 4, True), (5, 128, 8, True), (4, 32, 4, False), (2, 256, 16, True),
-                                                 (16, 128, 4, True), (40, 128, 4, True), (130, 64, 4, True)])     # (the last three: several tiles per workgroup)
-def test_stem_dgrad_with_the_warp_adjoint_folded_in(K, B, size, pool, with_cov, prec):
+def check_stem_dgrad_with_the_warp_adjoint_folded_in(K, B, h, w, pool, with_cov, prec):
     """Round 6 (bh_stem7_dgrad_c1_warp, include/bihome.h): the extractor stem's dgrad that applies the warp's adjoint to the gradient it has
     just made, against the two calls it replaces - bh_stem7_dgrad_c1, then bh_warp_bwd on its output: the gradient image (when asked for)
     bit for bit, dL/dH to float rounding of the per-pixel products (same taps bitwise: warp_tap.h)."""
     import ctypes
     from bihome_amd._lib import lib, check
+    size = h if h == w else 1000 * h + w            # (seeds)
     rng = np.random.Generator(np.random.PCG64(B * 7 + size))
-    src = F.avg_pool2d(torch.tensor(rng.standard_normal((B, 1, size, size)).astype(np.float32)), 3, 1, 1).cuda().contiguous()
-    gy = torch.tensor(rng.standard_normal((B, size // 2, size // 2, 64)).astype(np.float32)).cuda()
-    w = torch.tensor((rng.standard_normal((64, 7, 7, 1)) * 0.05).astype(np.float32)).cuda()
-    gcov = torch.tensor(rng.standard_normal((B, size // pool, size // pool)).astype(np.float32)).cuda() if with_cov else None
-    H64, _ = K.h4pt_fwd(dev(rand_delta(B, size + 1, amp=size / 4.0)), size)
-    d = K.conv_desc(B, size, size, 1, 64, 7, 2, 3, precision=prec)     # (4: the window GEMM in fp16 pieces - both entry points, the same tiles)
+    src = F.avg_pool2d(torch.tensor(rng.standard_normal((B, 1, h, w)).astype(np.float32)), 3, 1, 1).cuda().contiguous()
+    gy = torch.tensor(rng.standard_normal((B, h // 2, w // 2, 64)).astype(np.float32)).cuda()
+    wt = torch.tensor((rng.standard_normal((64, 7, 7, 1)) * 0.05).astype(np.float32)).cuda()
+    gcov = torch.tensor(rng.standard_normal((B, h // pool, w // pool)).astype(np.float32)).cuda() if with_cov else None
+    H64, _ = K.h4pt_fwd(dev(rand_delta(B, size + 1, amp=min(h, w) / 4.0)), (w, h))
+    d = K.conv_desc(B, h, w, 1, 64, 7, 2, 3, precision=prec)     # (4: the window GEMM in fp16 pieces - both entry points, the same tiles)
     p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    gx0 = torch.empty(B, size, size, 1, device="cuda")
-    check(lib.bh_stem7_dgrad_c1(p(gy), p(w), p(gx0), ctypes.byref(d), stream), "bh_stem7_dgrad_c1")
+    gx0 = torch.empty(B, h, w, 1, device="cuda")
+    check(lib.bh_stem7_dgrad_c1(p(gy), p(wt), p(gx0), ctypes.byref(d), stream), "bh_stem7_dgrad_c1")
     base = torch.tensor(rng.standard_normal((B, 9))).cuda()          # gH accumulates: something is there already (ln3's gradient in the step)
-    gH0 = K.warp_bwd(src, H64, gx0.view(B, 1, size, size), gcov, pool, gH=base.clone())
+    gH0 = K.warp_bwd(src, H64, gx0.view(B, 1, h, w), gcov, pool, gH=base.clone())
     for want_gx in (True, False):
-        gx1 = torch.full((B, size, size, 1), float("nan"), device="cuda") if want_gx else None
+        gx1 = torch.full((B, h, w, 1), float("nan"), device="cuda") if want_gx else None
         gH1 = base.clone()
-        check(lib.bh_stem7_dgrad_c1_warp(p(gy), p(w), p(gx1), ctypes.byref(d), p(src), p(H64), p(gcov), pool, p(gH1), stream), "bh_stem7_dgrad_c1_warp")
+        check(lib.bh_stem7_dgrad_c1_warp(p(gy), p(wt), p(gx1), ctypes.byref(d), p(src), p(H64), p(gcov), pool, p(gH1), stream), "bh_stem7_dgrad_c1_warp")
         if want_gx:
             assert torch.equal(gx1, gx0)
         scale = (gH0 - base).abs().max().item()
         err = (gH1 - gH0).abs().max().item()
-        print("MEASURED fused stem dgrad + warp adjoint B%d %d pool%d: max |gH - two calls| %.3e of %.3e" % (B, size, pool, err, scale))
+        print("MEASURED fused stem dgrad + warp adjoint B%d %dx%d pool%d: max |gH - two calls| %.3e of %.3e" % (B, h, w, pool, err, scale))
         # (same taps bit for bit - warp_tap.h spells the coordinates as fused multiply-adds in one order; what differs is the compiler's
         #  contraction of the per-pixel float products and the order of the double sums: ~1e-7 of the sum of |terms|, and the entries are
         #  the near-cancelling sums of 16 k random-sign terms)
@@ -473,38 +524,43 @@ def test_stem_dgrad_with_the_warp_adjoint_folded_in(K, B, size, pool, with_cov, 
     # (the two calls are held against the float64 oracle by test_warp_fwd_bwd; a direct comparison on THESE inputs would measure how many
     #  pixels float32 coordinates put on the other side of an integer - the bilinear derivative jumps there - not the kernel)
     # geometries the kernel does not take are refused, not guessed
-    d2 = K.conv_desc(B, size, size, 1, 64, 7, 2, 3, precision=prec)
-    assert lib.bh_stem7_dgrad_c1_warp(p(gy), p(w), None, ctypes.byref(d2), p(src), p(H64), p(gcov), 3, p(gH1), stream) == -2
+    d2 = K.conv_desc(B, h, w, 1, 64, 7, 2, 3, precision=prec)
+    assert lib.bh_stem7_dgrad_c1_warp(p(gy), p(wt), None, ctypes.byref(d2), p(src), p(H64), p(gcov), 3, p(gH1), stream) == -2
 
 
-@pytest.mark.parametrize("det", [False, True])
-@pytest.mark.parametrize("B,size,groups,with_cov,with_img", [(4, 128, 2, True, True), (16, 64, 1, True, True), (40, 128, 2, True, False),
-                                                             (130, 64, 2, False, True), (6, 256, 1, True, True)])
-def test_stem_forward_with_the_warp_folded_in(K, B, size, groups, with_cov, with_img, det):
+@pytest.mark.parametrize("prec", [0, 4])
+@pytest.mark.parametrize("B,size,pool,with_cov", [(6, 128, 4, True), (3, 64, 4, True), (5, 128, 8, True), (4, 32, 4, False), (2, 256, 16, True),
+                                                 (16, 128, 4, True), (40, 128, 4, True), (130, 64, 4, True)])     # (the last three: several tiles per workgroup)
+def test_stem_dgrad_with_the_warp_adjoint_folded_in(K, B, size, pool, with_cov, prec):
+    check_stem_dgrad_with_the_warp_adjoint_folded_in(K, B, size, size, pool, with_cov, prec)
+
+
+def check_stem_forward_with_the_warp_folded_in(K, B, h, w, groups, with_cov, with_img, det):
     """Round 6 (bh_stem7_fwd_warp, include/bihome.h): the extractor's one-plane stem that makes the warped pixels while it fetches its
     patches, against the two calls it replaces - bh_warp_fwd, then bh_conv_fwd_bnstats on its output.  Same taps, same blend, the same
     pixels into the same arithmetic: the warped image, the pooled coverage and the stem's output bit for bit; the BatchNorm sums to the
     order of the f64 atomics (bitwise in deterministic calls)."""
     import ctypes
     from bihome_amd._lib import lib, check
+    size = h if h == w else 1000 * h + w            # (seeds)
     rng = np.random.Generator(np.random.PCG64(B * 11 + size))
-    src = F.avg_pool2d(torch.tensor(rng.standard_normal((B, 1, size, size)).astype(np.float32)), 3, 1, 1).cuda().contiguous()
-    w = torch.tensor((rng.standard_normal((64, 7, 7, 1)) * 0.05).astype(np.float32)).cuda()
-    H64, _ = K.h4pt_fwd(dev(rand_delta(B, size + 1, amp=size / 4.0)), size)
-    H64[B // 2] = torch.tensor([1., 0, 3 * size, 0, 1, 0, 0, 0, 1], dtype=torch.float64)      # one image warped entirely out of its source
+    src = F.avg_pool2d(torch.tensor(rng.standard_normal((B, 1, h, w)).astype(np.float32)), 3, 1, 1).cuda().contiguous()
+    wt = torch.tensor((rng.standard_normal((64, 7, 7, 1)) * 0.05).astype(np.float32)).cuda()
+    H64, _ = K.h4pt_fwd(dev(rand_delta(B, size + 1, amp=min(h, w) / 4.0)), (w, h))
+    H64[B // 2] = torch.tensor([1., 0, 3 * w, 0, 1, 0, 0, 0, 1], dtype=torch.float64)      # one image warped entirely out of its source
     p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     with K.det_scope(det):
-        d = K.conv_desc(B, size, size, 1, 64, 7, 2, 3, precision=4)
+        d = K.conv_desc(B, h, w, 1, 64, 7, 2, 3, precision=4)
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         warped0, cov0 = K.warp_fwd(src, H64, 4)
         s0 = K.bn_stats_buffer(groups, 64, "cuda")
-        y0 = K.conv_fwd(warped0.view(B, size, size, 1), w, None, d, bn_sums=s0, groups=groups)
+        y0 = K.conv_fwd(warped0.view(B, h, w, 1), wt, None, d, bn_sums=s0, groups=groups)
         assert K.conv_variant(d, "fwd", bn_groups=groups) == "stem7_fwd_f16_kernel<1>"
         s1 = K.bn_stats_buffer(groups, 64, "cuda")
         y1 = torch.full_like(y0, float("nan"))
         warped1 = torch.full_like(warped0, float("nan")) if with_img else None
         cov1 = torch.full_like(cov0, float("nan")) if with_cov else None
-        check(lib.bh_stem7_fwd_warp(p(src), p(H64), 4, p(w), None, p(y1), ctypes.byref(d), p(warped1), p(cov1), p(s1), groups, stream),
+        check(lib.bh_stem7_fwd_warp(p(src), p(H64), 4, p(wt), None, p(y1), ctypes.byref(d), p(warped1), p(cov1), p(s1), groups, stream),
               "bh_stem7_fwd_warp")
         if with_img:
             assert torch.equal(warped1, warped0)
@@ -517,25 +573,32 @@ def test_stem_forward_with_the_warp_folded_in(K, B, size, groups, with_cov, with
         else:
             assert (s1 - s0).abs().max().item() <= 1e-9 * s0.abs().max().item()
         # through kernels.conv_fwd (what the Runner calls): the input buffer is filled on the way
-        x2 = torch.full((B, size, size, 1), float("nan"), device="cuda")
+        x2 = torch.full((B, h, w, 1), float("nan"), device="cuda")
         cov2 = torch.full_like(cov0, float("nan"))
         source = dict(src=src, H64=H64, pool=4, cov=cov2, done=False, filled=False)
-        y2 = K.conv_fwd(x2, w, None, d, bn_sums=K.bn_stats_buffer(groups, 64, "cuda"), groups=groups, warp_src=source)
+        y2 = K.conv_fwd(x2, wt, None, d, bn_sums=K.bn_stats_buffer(groups, 64, "cuda"), groups=groups, warp_src=source)
         assert source["done"] and source["filled"]
         assert torch.equal(y2, y0) and torch.equal(x2.view_as(warped0), warped0) and torch.equal(cov2, cov0)
         # ... and where the fused kernel does not apply (fp32-input MFMA stem; pool 8) the two calls are made inside
         for prec, pool in ((0, 4), (4, 8)):
-            dd = K.conv_desc(B, size, size, 1, 64, 7, 2, 3, precision=prec)
-            x3 = torch.full((B, size, size, 1), float("nan"), device="cuda")
-            cov3 = torch.full((B, size // pool, size // pool), float("nan"), device="cuda")
+            dd = K.conv_desc(B, h, w, 1, 64, 7, 2, 3, precision=prec)
+            x3 = torch.full((B, h, w, 1), float("nan"), device="cuda")
+            cov3 = torch.full((B, h // pool, w // pool), float("nan"), device="cuda")
             source = dict(src=src, H64=H64, pool=pool, cov=cov3, done=False, filled=False)
-            y3 = K.conv_fwd(x3, w, None, dd, bn_sums=K.bn_stats_buffer(groups, 64, "cuda"), groups=groups, warp_src=source)
+            y3 = K.conv_fwd(x3, wt, None, dd, bn_sums=K.bn_stats_buffer(groups, 64, "cuda"), groups=groups, warp_src=source)
             assert source["filled"] and not source["done"]
             wref, cref = K.warp_fwd(src, H64, pool)
             assert torch.equal(x3.view_as(wref), wref) and torch.equal(cov3, cref)
-            yref = K.conv_fwd(wref.view(B, size, size, 1), w, None, dd, bn_sums=K.bn_stats_buffer(groups, 64, "cuda"), groups=groups)
+            yref = K.conv_fwd(wref.view(B, h, w, 1), wt, None, dd, bn_sums=K.bn_stats_buffer(groups, 64, "cuda"), groups=groups)
             assert torch.equal(y3, yref)
-        assert lib.bh_stem7_fwd_warp(p(src), p(H64), 8, p(w), None, p(y1), ctypes.byref(d), None, None, None, 1, stream) == -2
+        assert lib.bh_stem7_fwd_warp(p(src), p(H64), 8, p(wt), None, p(y1), ctypes.byref(d), None, None, None, 1, stream) == -2
+
+
+@pytest.mark.parametrize("det", [False, True])
+@pytest.mark.parametrize("B,size,groups,with_cov,with_img", [(4, 128, 2, True, True), (16, 64, 1, True, True), (40, 128, 2, True, False),
+                                                             (130, 64, 2, False, True), (6, 256, 1, True, True)])
+def test_stem_forward_with_the_warp_folded_in(K, B, size, groups, with_cov, with_img, det):
+    check_stem_forward_with_the_warp_folded_in(K, B, size, size, groups, with_cov, with_img, det)
 
 
 def test_extractor_of_warp_keeps_the_image_only_on_request(K):

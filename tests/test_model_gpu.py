@@ -46,15 +46,12 @@ def test_no_cpu_fallback(zeng):
         model[0]({k: torch.tensor(d[k]) for k in ("patch_1", "patch_2")})
 
 
-def test_backbone_forward_backward_vs_oracle(zeng):
-    """Backbone alone, B=2: outputs against the float64 oracle; parameter gradients against the float64
-    oracle with a tolerance tied to the oracle's own float32-vs-float64 spread (at this tiny batch a few
-    ReLU sign flips move some gradients by several percent even between two CPU precisions)."""
-    cfg, model = zeng
-    B = 2
-    d = synth.make_pairs(B, seed=3)
+def backbone_reference(cfg, d):
+    """The oracle backbone on the patch pairs d["patch_1"], d["patch_2"] [B,1,h,w] in float32 and float64, with the output gradients g12, g21:
+    {dtype: (outputs, parameter gradients, module)}, g12, g21, and the float32 run's whole-gradient relative L2 distance from the float64 run."""
+    B, _, h, w = d["patch_1"].shape
     rng = np.random.Generator(np.random.PCG64(0))
-    g12, g21 = rng.standard_normal((B, 2, 128, 128)), rng.standard_normal((B, 2, 128, 128))
+    g12, g21 = rng.standard_normal((B, 2, h, w)), rng.standard_normal((B, 2, h, w))
     ref = {}
     for dt in (torch.float32, torch.float64):
         bb, _ = O.build(cfg)
@@ -64,6 +61,19 @@ def test_backbone_forward_backward_vs_oracle(zeng):
         ((o["pf_hat_12"] * torch.tensor(g12, dtype=dt)).sum() + (o["pf_hat_21"] * torch.tensor(g21, dtype=dt)).sum()).backward()
         ref[dt] = ({k: o[k].detach().double() for k in ("pf_hat_12", "pf_hat_21")},
                    {n: p.grad.double() for n, p in bb.named_parameters()}, bb)
+    g64, g32 = ref[torch.float64][1], ref[torch.float32][1]
+    spread = (sum((g32[n] - g64[n]).pow(2).sum().item() for n in g64) / sum(g64[n].pow(2).sum().item() for n in g64)) ** 0.5
+    return ref, g12, g21, spread
+
+
+def check_backbone_forward_backward_vs_oracle(zeng, d, reference=None):
+    """Backbone alone on the patch pairs d["patch_1"], d["patch_2"] [B,1,h,w]: outputs against the float64 oracle; parameter gradients
+    against the float64 oracle with a tolerance tied to the oracle's own float32-vs-float64 spread (at a tiny batch a few
+    ReLU sign flips move some gradients by several percent even between two CPU precisions).  reference: backbone_reference(cfg, d), if
+    the caller has it already."""
+    cfg, model = zeng
+    B, _, h, w = d["patch_1"].shape
+    ref, g12, g21, _ = reference if reference is not None else backbone_reference(cfg, d)
     out64, grad64, bb64 = ref[torch.float64]
     out32, grad32, _ = ref[torch.float32]
     model.train()
@@ -71,7 +81,8 @@ def test_backbone_forward_backward_vs_oracle(zeng):
     data = {k: cuda(d[k]) for k in ("patch_1", "patch_2")}
     out = model[0](data)
     for k in ("pf_hat_12", "pf_hat_21"):
-        assert out[k].shape == (B, 2, 128, 128) and out[k].is_contiguous()
+        assert out[k].shape == (B, 2, h, w) and out[k].is_contiguous()
+        print("MEASURED backbone %dx%d %s: error %.3e of max |pf| (float32 oracle's own %.3e)" % (h, w, k, relerr(out[k].detach().cpu(), out64[k]), relerr(out32[k], out64[k])))
         assert relerr(out[k].detach().cpu(), out64[k]) < max(3 * relerr(out32[k], out64[k]), 1e-5), k
     for p in model[0].parameters():
         p.grad = None
@@ -89,6 +100,8 @@ def test_backbone_forward_backward_vs_oracle(zeng):
         den += r.pow(2).sum().item()
         if e > max(4 * spread, 3e-4):
             bad.append((name, e, spread))
+    print("MEASURED backbone %dx%d: whole-gradient relative L2 error %.3e (float32 oracle's own %.3e); %d tensors past their bound %s"
+          % (h, w, (num / den) ** 0.5, (num32 / den) ** 0.5, len(bad), bad[:4]))
     # whole-gradient relative L2 error: as close to float64 as the float32 CPU reference is (x3)
     assert (num / den) ** 0.5 <= max(3 * (num32 / den) ** 0.5, 1e-4), ((num / den) ** 0.5, (num32 / den) ** 0.5)
     # per tensor: a ReLU whose input is within rounding of zero can flip differently in two float32
@@ -97,6 +110,10 @@ def test_backbone_forward_backward_vs_oracle(zeng):
     # BatchNorm running statistics after the two per-direction updates
     assert relerr(model[0].layer1[1].running_mean.cpu(), bb64.layer1[1].running_mean) < 1e-5
     assert relerr(model[0].layer8[1].running_var.cpu(), bb64.layer8[1].running_var) < 1e-4
+
+
+def test_backbone_forward_backward_vs_oracle(zeng):
+    check_backbone_forward_backward_vs_oracle(zeng, synth.make_pairs(2, seed=3))
 
 
 def test_head_scenario_vs_golden(zeng, golden):

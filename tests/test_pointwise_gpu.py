@@ -23,7 +23,9 @@ def _rel(a, b):
 
 # (kind, N, H, W, Ci, Co): M = N H W >= 65536
 CASES = [("convT", 16, 64, 64, 32, 32), ("convT", 16, 64, 64, 32, 16), ("convT", 16, 64, 64, 64, 32), ("convT", 16, 64, 64, 64, 64),
-         ("convT", 18, 48, 80, 32, 32), ("1x1", 16, 64, 64, 32, 16), ("1x1", 16, 64, 64, 64, 32), ("1x1", 4, 128, 128, 32, 16)]
+         ("convT", 18, 48, 80, 32, 32), ("1x1", 16, 64, 64, 32, 16), ("1x1", 16, 64, 64, 64, 32), ("1x1", 4, 128, 128, 32, 16),
+         # rectangular maps: 48 x 80 decodes a pixel index with divisions, 32 x 128 with the shifts (w_shift 7, hw_shift 12)
+         ("1x1", 18, 48, 80, 32, 16), ("1x1", 16, 32, 128, 64, 32), ("convT", 16, 32, 128, 64, 32)]
 
 
 def _ref(kind, x, w, b):
@@ -95,20 +97,25 @@ def test_pointwise_deterministic_call_repeats_bitwise(K, kind, N, H, W, Ci, Co):
     assert (tab0 - tab1).abs().max().item() <= 1e-9 * tab1.abs().max().item() + 1e-6
 
 
-@pytest.mark.parametrize("N,H,Ci,Co", [(16, 64, 32, 16), (16, 64, 64, 32), (4, 128, 32, 16)])
+# (N, H, W, Ci, Co); square maps keep the ids they had as (N, H, Ci, Co)
+BN_CASES = [(16, 64, 64, 32, 16), (16, 64, 64, 64, 32), (4, 128, 128, 32, 16), (16, 32, 128, 64, 32), (18, 80, 48, 32, 16)]
+
+
+@pytest.mark.parametrize("N,H,W,Ci,Co", BN_CASES, ids=["%d-%d-%d-%d" % (N, H, Ci, Co) if H == W else "%d-%dx%d-%d-%d" % (N, H, W, Ci, Co) for (N, H, W, Ci, Co) in BN_CASES])
 @pytest.mark.parametrize("relu", [True, False])
-def test_pointwise_batchnorm_on_load(K, N, H, Ci, Co, relu):
+def test_pointwise_batchnorm_on_load(K, N, H, W, Ci, Co, relu):
     g = torch.Generator().manual_seed(H + Ci)
     groups = 2
-    z = (torch.randn(N, H, H, Ci, generator=g) * 1.5 + 0.3).cuda()
+    z = (torch.randn(N, H, W, Ci, generator=g) * 1.5 + 0.3).cuda()
     gamma, beta = (torch.rand(Ci, generator=g) + 0.5).cuda(), (torch.randn(Ci, generator=g) * 0.2).cuda()
     rm, rv = torch.zeros(Ci).cuda(), torch.ones(Ci).cuda()
     st = K.bn_stats_buffer(groups, Ci, "cuda")
     K.bn_stats(z, st, groups, Ci)
     rec = K.amax_record("cuda")
-    table = K.bn_fwd_coeffs(st, gamma, beta, rm, rv, groups, N * H * H // groups, Ci, 1e-5, 0.1, amax=rec)
+    table = K.bn_fwd_coeffs(st, gamma, beta, rm, rv, groups, N * H * W // groups, Ci, 1e-5, 0.1, amax=rec)
     lazy = K.BnOnLoad(z, table, groups, relu, amax=rec)
-    d = K.conv_desc(N, H, H, Ci, Co, 1, 1, 0, precision=4)
+    d = K.conv_desc(N, H, W, Ci, Co, 1, 1, 0, precision=4)
+    assert K.conv_variant(d, "fwd").startswith("pw_kernel<%d," % Ci), K.conv_variant(d, "fwd")
     w = (torch.randn(Co, 1, 1, Ci, generator=g) * 0.1).cuda()
     b = torch.randn(Co, generator=g).cuda()
     s = K.bn_stats_buffer(groups, Co, "cuda")
@@ -119,7 +126,7 @@ def test_pointwise_batchnorm_on_load(K, N, H, Ci, Co, relu):
     a = (zd - mu) / torch.sqrt(var + 1e-5) * gamma.double().cpu() + beta.double().cpu()
     if relu:
         a = a.clamp_min(0)
-    ref = a.reshape(N, H, H, Ci) @ w.double().cpu().reshape(Co, Ci).t() + b.double().cpu()
+    ref = a.reshape(N, H, W, Ci) @ w.double().cpu().reshape(Co, Ci).t() + b.double().cpu()
     assert _rel(y, ref) < 3e-6
     yd = ref.reshape(groups, -1, Co)
     tab = s.reshape(groups, Co, 2, -1)[..., 0].cpu()

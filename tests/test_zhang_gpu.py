@@ -172,18 +172,18 @@ def test_mask_gate_kernels(strength):
     assert relerr(g_y2.cpu(), yd2.grad) < 2e-5 and relerr(g_f2.cpu(), fd2.grad) < 1e-6
 
 
-@pytest.mark.parametrize("det", [False, True])
-def test_warp_adjoint_with_respect_to_the_image(det):
+def check_warp_adjoint_with_respect_to_the_image(det, h, w):
     """bh_warp_bwd_img is the transpose of bh_warp_fwd's bilinear gather: <warp(img), g> == <img, warp^T(g)> for random images and
     gradients under homographies that push part of the patch out of the image (zero padding), and equal to torch float64 autograd of
     grid_sample-style sampling through the forward kernel's linearity (finite differences are exact for a linear map)."""
     from bihome_amd import kernels as K
-    B, C, h = 3, 2, 64
+    from oracle import bihome_oracle as O
+    B, C = 3, 2
     g = torch.Generator().manual_seed(5)
     delta = (torch.rand(B, 4, 2, generator=g) - 0.5) * 40.0
-    H64, _ = K.h4pt_fwd(delta.cuda().contiguous(), h)
-    img = torch.randn(B, C, h, h, generator=g).cuda()
-    gout = torch.randn(B, C, h, h, generator=g).cuda()
+    H64, _ = K.h4pt_fwd(delta.cuda().contiguous(), (w, h))
+    img = torch.randn(B, C, h, w, generator=g).cuda()
+    gout = torch.randn(B, C, h, w, generator=g).cuda()
     with K.det_scope(det):
         warped, _ = K.warp_fwd(img, H64, 1, want_cov=False)
         gimg = K.warp_bwd_img(H64, gout)
@@ -202,6 +202,24 @@ def test_warp_adjoint_with_respect_to_the_image(det):
         assert abs(w_fwd[1, 0, 20, 33].item() - row[1, 0, yy, xx].item()) < 1e-6
     if det:
         assert torch.equal(gimg, gimg2)                                        # integer-limb accumulation: order-independent
+    # float64 autograd of the oracle's warp with respect to the image.  The bound is the forward warp's (test_head_kernels_gpu.py: 1e-4 of the
+    # reference's range): the adjoint spreads every gradient pixel with the four weights the forward blends with, weights made from float32
+    # coordinates (error ~ extent * 2^-24 * a few per weight), and an image pixel collects a handful of such terms
+    imt = img.double().cpu().requires_grad_(True)
+    (O.warp_image(imt, H64.cpu().reshape(B, 3, 3)) * gout.double().cpu()).sum().backward()
+    err, scale = (gimg.cpu().double() - imt.grad).abs().max().item(), imt.grad.abs().max().item()
+    print("MEASURED warp adjoint w.r.t. the image %dx%d det %d: max |hip - f64| %.3e = %.2e of max |g_img|" % (h, w, det, err, err / scale))
+    assert err <= 1e-4 * scale, (err, scale)
+
+
+@pytest.mark.parametrize("det", [False, True])
+def test_warp_adjoint_with_respect_to_the_image(det):
+    check_warp_adjoint_with_respect_to_the_image(det, 64, 64)
+
+
+@pytest.mark.parametrize("det", [False, True])
+def test_warp_adjoint_with_respect_to_the_image_rectangular(det):
+    check_warp_adjoint_with_respect_to_the_image(det, 48, 80)
 
 
 class _Rec:
