@@ -235,7 +235,9 @@ __host__ __device__ __forceinline__ int bh_f16_scale_exp(unsigned bound_bits) {
     const int e = (int)((bound_bits >> 23) & 0xFFu);          // biased exponent (0: zero / subnormal bound)
     int k = 14 - (e - 127);
     if (e == 0xFF) k = 0;                                      // inf / NaN bound: no scaling, the non-finite values propagate
-    return k > 100 ? 100 : (k < -100 ? -100 : k);
+    // The scale is the float with exponent field 127 + k: k <= 127 - exact down to a record of 2^-113, and a zero record multiplies zeros.
+    // Below, -100: a record past 2^114 overflows fp16 - inf / NaN in the result, loud.
+    return k > 127 ? 127 : (k < -100 ? -100 : k);
 }
 // all 64 lanes: the record's maximum (lanes 0..15 load one slot each)
 __device__ __forceinline__ unsigned bh_amax_read(const unsigned* __restrict__ rec, int lane) {

@@ -587,7 +587,7 @@ def _enqueue_wgrad(s, i, op, g, x, d):
         if s.ctx.precision == K.F16X2 and d.bh_wx3:
             # magnitude records the fp16-piece weight gradient reads: made (if missing) on the MAIN stream, in front of the
             # event - a record first measured on the side stream would be read by the main stream's dgrad without a wait
-            # (a still-zero record scales by 2^100)
+            # (a still-zero record scales by 2^127)
             K.amax_of(g)
             K.amax_of(x)
         ev = torch.cuda.Event()

@@ -392,7 +392,13 @@ typedef struct {
      * of max |element| as the maximum over its 16 slots (one per 128-byte line; non-negative floats): written by bh_absmax, by the
      * amax outputs of the BatchNorm entry points (measured) or by bh_bn_fwd_coeffs (|gamma| sqrt(rows) + |beta|).  A bound
      * that is too small overflows fp16 (inf / NaN in the result, never a silently wrong value); one that is too large by 2^j
-     * costs j of the 18 binades of full precision. */
+     * costs j of the 18 binades of full precision.
+     * Error per product a b of the two-piece form (csrc/common.h F16X2; held by tests/test_value_regimes_gpu.py on a gradient that is
+     * nonzero in one pixel, where every entry of the weight gradient is a single product):
+     *   |err| <= 1.25 * 2^-21 |a b| + 2^-39 (|a| bound_b + |b| bound_a)
+     * (2^-23 per operand's cut, 2^-22 for the dropped lo x lo, one fp32 rounding; the second term is the absolute floor of elements below
+     * 2^-18 of their tensor's record).  The fp32-input MFMA rounds a single product once, 2^-24: "no worse than 1.5 x the fp32-input
+     * MFMA kernel's error" is a statement about sums of 64 or more products, whose fp32 accumulation rounding dominates both forms. */
     const float* a_bound;
     const float* b_bound;
 } bh_conv_desc;
@@ -591,7 +597,15 @@ int bh_bn_stats_doubles(int groups, int C);
 int bh_bn_scratch_doubles(int groups, int C);
 /* C: a multiple of 4 (<= 1024, C/4 dividing 256), or 1 (round 3: the one-channel BatchNorms of the Zhang feature extractor /
  * mask predictor, ContentAware.py:24-26,68-70 - csrc/bn1.hip, same contract; BH_E_UNSUPPORTED with a magnitude record).
- * amax_y (NULL ok; BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |y| (precision 4 consumers). */
+ * amax_y (NULL ok; BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |y| (precision 4 consumers).
+ * Arithmetic of every BatchNorm apply (this entry point, the (scale, shift) table of bh_bn_fwd_coeffs, bh_bn_maxpool_fwd, bh_bn_join_fwd and
+ * the masks the adjoints recompute): the sums are float64; mean and 1 / sqrt(var + eps) are rounded to fp32, scale = gamma invstd and
+ * shift = beta - mean scale are fp32 operations, y = fma(x, scale, shift).  Against the float64 BatchNorm, per element,
+ *   |y - y64| <= 4 * 2^-24 (|x scale| + |mean scale| + |beta| + |y64|)
+ * (tests/test_value_regimes_gpu.py, tests/value_regimes.py bn_forward_bound): relative to |mean scale|, not to |shift| - where beta and
+ * mean scale cancel the shift carries the rounding of its two terms, as torch's float32 BatchNorm does; on a channel with
+ * |mean| / sigma = 2^10 that is 6e-5 absolute on outputs of order 1, which a consumer that applies the table on load (bh_conv_fwd_bnin)
+ * sees on every input: |out - out64| <= conv(that bound, |w|) + the conv's own rounding. */
 int bh_bn_fwd(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
               const float* res, float* y, double* stats, int groups, int rows, int C, float eps, float momentum,
               int flags, int use_running, float* amax_y, void* stream);

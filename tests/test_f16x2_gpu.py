@@ -108,10 +108,14 @@ def test_f16x2_packed_pieces_reconstruct_the_weights(K):
     assert ((back - wref).abs() <= tol).all()
 
 
-def check_wgrad_f16x2_kernel(K, N, H, W, Ci, Co):
+def check_wgrad_f16x2_kernel(K, N, H, W, Ci, Co, values=None):
+    """values (x, gy, generator) -> (x, gy): replaces the operands (host tensors) before the float64 reference and the launches see them."""
     g = torch.Generator().manual_seed(N + H + Ci)
-    x = torch.randn(N, H, W, Ci, generator=g).cuda()
-    gy = (torch.randn(N, H, W, Co, generator=g) * 3e-5).cuda()
+    x = torch.randn(N, H, W, Ci, generator=g)
+    gy = torch.randn(N, H, W, Co, generator=g) * 3e-5
+    if values is not None:
+        x, gy = values(x, gy, g)
+    x, gy = x.cuda(), gy.cuda()
     w = torch.zeros(Co, Ci, 3, 3, dtype=torch.float64, requires_grad=True)
     y = F.conv2d(x.double().cpu().permute(0, 3, 1, 2), w, None, 1, 1)
     ref = torch.autograd.grad(y, w, gy.double().cpu().permute(0, 3, 1, 2))[0].permute(0, 2, 3, 1)       # [Co][3][3][Ci]

@@ -130,27 +130,33 @@ def coordinate_ties(H, h, w):
     return tu | tv, (tu & edge(u, w)) | (tv & edge(v, h))
 
 
-def check_warp_fwd_bwd(K, B, C, h, w, pool, delta=None):
+def check_warp_fwd_bwd(K, B, C, h, w, pool, delta=None, image=None, H64=None, oracle=None):
     """Forward, coverage and adjoint of one shape (images of h rows and w columns) against the oracle; returns (cov, gH, the arguments of
-    warp_bwd) for further checks.  delta [B,4,2]: the corner offsets of the homographies (default: random, up to a quarter of the smaller extent)."""
+    warp_bwd) for further checks.  delta [B,4,2]: the corner offsets of the homographies (default: random, up to a quarter of the smaller extent).
+    image: a function of the seeded image [B,C,h,w] (numpy) that returns the image to warp instead; H64 [B,9] float64 on the device: the
+    homographies themselves, instead of those of `delta`; oracle(image, H): the reference warp in the dtype of `image` (default: O.warp_image)."""
+    warp_image = oracle or O.warp_image
     size = h if h == w else 1000 * h + w             # (seeds)
     rng = np.random.Generator(np.random.PCG64(B * 100 + size))
     img = rng.standard_normal((B, C, h, w)).astype(np.float32)
     # smooth the image a little so that bilinear gradients are O(1)
     img = F.avg_pool2d(torch.tensor(img), 3, 1, 1).numpy()
-    if delta is None:
-        delta = rand_delta(B, size, amp=min(h, w) / 4.0)
-    H64, _ = K.h4pt_fwd(dev(delta), (w, h))
+    if image is not None:
+        img = np.ascontiguousarray(image(img), dtype=np.float32)
+    if H64 is None:
+        if delta is None:
+            delta = rand_delta(B, size, amp=min(h, w) / 4.0)
+        H64, _ = K.h4pt_fwd(dev(delta), (w, h))
     out, cov = K.warp_fwd(dev(img), H64, pool)
     Ht = H64.cpu().reshape(B, 3, 3).clone().requires_grad_(True)
     imt = torch.tensor(img, dtype=torch.float64)
-    ref = O.warp_image(imt, Ht)
-    refcov = F.avg_pool2d(O.warp_image(torch.ones(B, 1, h, w, dtype=torch.float64), Ht), pool).squeeze(1)
+    ref = warp_image(imt, Ht)
+    refcov = F.avg_pool2d(warp_image(torch.ones(B, 1, h, w, dtype=torch.float64), Ht), pool).squeeze(1)
     # north_star: "fp32 warp ... within 1e-4 relative".  The kernel evaluates the map in float32 (like grid_sample's float32 grid):
     # coordinate rounding ~ size * 2^-24 * few -> value error ~ 1e-5 * local gradient.  Bound: 1e-4 of the reference's range, or - where the
     # reference's OWN float32 chain (torch.inverse twice, normalise, grid_sample) is further than that from float64 - 1.5 x that spread.
     o, r64 = out.cpu().double().numpy(), ref.detach().numpy()
-    ref32 = O.warp_image(torch.tensor(img), H64.cpu().reshape(B, 3, 3).float()).double().numpy()
+    ref32 = warp_image(torch.tensor(img), H64.cpu().reshape(B, 3, 3).float()).double().numpy()
     scale = np.abs(r64).max()
     err, spread = np.abs(o - r64).max(), np.abs(ref32 - r64).max()
     cerr = np.abs(cov.cpu().double().numpy() - refcov.detach().numpy()).max()
