@@ -595,10 +595,16 @@ __global__ void __launch_bounds__(256) tail_bwd_finalize_kernel(const float* __r
                 const int k = lane;
                 const double* mo = xmom + (size_t)grp * nm;
                 const double sk = red[0][6 + k] + red[1][6 + k] + red[2][6 + k] + red[3][6 + k];
-                double syx = ((b1 ? (double)b1[c] : 0.0) - mean) * mo[k];
-                for (int j = 0; j < CI; ++j) syx += (double)w1[c * CI + j] * mo[CI + j * CI + k];
-                syx *= invstd;
-                tw1 += A * (sk - kb * mo[k] - kg * syx);
+                if (use_running) {
+                    // (eval mode: no mean terms - and bh_tail_fwd wrote no moments into ws: 0 * whatever the buffer holds is NaN for a
+                    //  stale NaN / Inf)
+                    tw1 += A * sk;
+                } else {
+                    double syx = ((b1 ? (double)b1[c] : 0.0) - mean) * mo[k];
+                    for (int j = 0; j < CI; ++j) syx += (double)w1[c * CI + j] * mo[CI + j * CI + k];
+                    syx *= invstd;
+                    tw1 += A * (sk - kb * mo[k] - kg * syx);
+                }
             }
             if (lane == 0) {
                 float* cf = coef + ((size_t)grp * g.Cm + c) * 4;

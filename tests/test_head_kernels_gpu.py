@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from bihome_amd import synth
 from oracle import bihome_oracle as O
+from test_conv_kernels_gpu import grad_result, grad_start
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,7 @@ def test_h4pt_fwd_bwd(K):
     check_h4pt_fwd_bwd(K, 128)
 
 
-def check_dlt_fwd_bwd(K, n, P, pf):
+def check_dlt_fwd_bwd(K, n, P, pf, base=None):
     """pf [B,2,h,w]: the perspective field the hypotheses are fitted to (the corners of delta_hat are those of the field's own extents)."""
     B, _, h, w = pf.shape
     choice = O.sample_choice(h * w, B * n * P, torch.Generator().manual_seed(5)).reshape(B, n * P)
@@ -79,8 +80,18 @@ def check_dlt_fwd_bwd(K, n, P, pf):
     head.double()
     gd = np.random.Generator(np.random.PCG64(9)).standard_normal((B * n, 4, 2)).astype(np.float32)
     (dref.reshape(B * n, 4, 2) * torch.tensor(gd, dtype=torch.float64)).sum().backward()
-    gpf = K.dlt_bwd(dev(pf), choice.cuda(), eig, dev(gd), n, P)
     ref = pft.grad.numpy()
+    if base is None:
+        gpf = K.dlt_bwd(dev(pf), choice.cuda(), eig, dev(gd), n, P)
+    else:
+        # g_pf is a `+=` output (the wrapper hands the kernel a zeroed one): from a nonzero start, through the C entry point
+        import ctypes
+        from bihome_amd._lib import check, lib
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        args, buf = (dev(pf), choice.cuda(), dev(gd)), grad_start(base, ref)
+        check(lib.bh_dlt_bwd(ptr(args[0]), ptr(args[1]), ptr(eig), ptr(args[2]), None, B, n, P, h, w, ptr(buf), K._fdet(),
+                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_dlt_bwd")
+        gpf = grad_result(base, buf)
     print("MEASURED dlt n%d P%d %dx%d: max |Hdlt - f64| %.3e, |delta_hat - f64| %.3e, |g_pf - f64| %.3e of %.3e"
           % (n, P, h, w, np.abs(Hd.cpu().numpy().reshape(B, n, 3, 3) - Href.detach().numpy()).max(),
              np.abs(dh.cpu().numpy().reshape(B, n, 4, 2) - dref.detach().numpy()).max(), np.abs(gpf.cpu().numpy() - ref).max(), np.abs(ref).max()))
@@ -130,7 +141,7 @@ def coordinate_ties(H, h, w):
     return tu | tv, (tu & edge(u, w)) | (tv & edge(v, h))
 
 
-def check_warp_fwd_bwd(K, B, C, h, w, pool, delta=None, image=None, H64=None, oracle=None):
+def check_warp_fwd_bwd(K, B, C, h, w, pool, delta=None, image=None, H64=None, oracle=None, base=None):
     """Forward, coverage and adjoint of one shape (images of h rows and w columns) against the oracle; returns (cov, gH, the arguments of
     warp_bwd) for further checks.  delta [B,4,2]: the corner offsets of the homographies (default: random, up to a quarter of the smaller extent).
     image: a function of the seeded image [B,C,h,w] (numpy) that returns the image to warp instead; H64 [B,9] float64 on the device: the
@@ -176,8 +187,9 @@ def check_warp_fwd_bwd(K, B, C, h, w, pool, delta=None, image=None, H64=None, or
           % (B, C, h, w, pool, int(tie.sum()), tie.numel(), int(cov_tie.sum())))
     ((ref * torch.tensor(go, dtype=torch.float64)).sum() + (refcov * torch.tensor(gc, dtype=torch.float64)).sum()).backward()
     bwd_args = (dev(img), H64, dev(go), dev(gc), pool)
-    gH = K.warp_bwd(*bwd_args)
     r = Ht.grad.numpy().reshape(B, 9)
+    # (base: gH is a `+=` output - from a nonzero start, the start taken off again in float64)
+    gH = K.warp_bwd(*bwd_args) if base is None else grad_result(base, K.warp_bwd(*bwd_args, gH=grad_start(base, r, torch.float64))).cuda()
     gerr = np.abs(gH.cpu().double().numpy() - r).max() / np.abs(r).max()
     print("MEASURED warp adjoint B%d C%d %dx%d pool%d: max error %.3e of max|dL/dH|" % (B, C, h, w, pool, gerr))
     assert gerr <= WARP_ADJOINT_BOUND, gerr

@@ -65,7 +65,7 @@ def inputs(B, C, seed):
 
 
 @pytest.mark.parametrize("C", [1, 3])
-def test_photo_warp_fwd_and_adjoint_vs_float64(K, C):
+def test_photo_warp_fwd_and_adjoint_vs_float64(K, C, base=None):
     B = 8
     img, corners, delta = inputs(B, C, 100 + C)
     Hp64, _ = K.h4pt_fwd(cuda(delta), 128)
@@ -92,6 +92,10 @@ def test_photo_warp_fwd_and_adjoint_vs_float64(K, C):
     (restated(img, corners, d32, torch.float32) * torch.tensor(go)).sum().backward()
     spread = relerr(d32.grad, r)
     gH = K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), 128)
+    if base is not None:
+        # gH is a `+=` output: from a nonzero start (of the scale of the result itself), the start taken off again in float64
+        from test_conv_kernels_gpu import grad_result, grad_start
+        gH = grad_result(base, K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), 128, gH=grad_start(base, gH, torch.float64))).cuda()
     gd = K.h4pt_bwd(cuda(delta), Hp64, gH, 128)
     gerr = relerr(gd, r)
     print("MEASURED photo warp adjoint C%d: max error %.3e of max|dL/ddelta|; f32 oracle's own %.3e" % (C, gerr, spread))

@@ -24,7 +24,7 @@ def relerr(a, ref):
 
 @pytest.mark.parametrize("groups,N,H,relu,res,training", [(2, 4, 32, True, False, True), (1, 3, 17, False, True, True),
                                                           (2, 2, 16, True, True, True), (1, 2, 16, True, False, False)])
-def test_one_channel_batchnorm(groups, N, H, relu, res, training):
+def test_one_channel_batchnorm(groups, N, H, relu, res, training, base=None):
     """bh_bn_fwd / bh_bn_bwd with C = 1 (csrc/bn1.hip) against torch float64 autograd: output, running statistics, input / residual
     gradients, dgamma / dbeta; the mask recomputed from x where there is no residual."""
     from bihome_amd import kernels as K
@@ -54,10 +54,11 @@ def test_one_channel_batchnorm(groups, N, H, relu, res, training):
     assert relerr(y.cpu(), yref.detach()) < 2e-6
     if training:
         assert relerr(rmc.cpu(), rmd) < 1e-6 and relerr(rvc.cpu(), rvd) < 1e-6
-    gg, gb = torch.zeros(1, device="cuda"), torch.zeros(1, device="cuda")
+    from test_conv_kernels_gpu import grad_result, grad_start         # (base: ggamma / gbeta from a nonzero start, test_buffer_contracts_gpu.py)
+    gg, gb = grad_start(base, gd.grad), grad_start(base, bd.grad)
     gx, gres = K.bn_bwd(gy.cuda(), y, xc, gc, st, rmc, rvc, groups, 1e-5, relu, training, res, gg, gb, beta=bc)
     assert relerr(gx.cpu(), xd.grad) < 2e-5
-    assert relerr(gg.cpu(), gd.grad) < 2e-5 and relerr(gb.cpu(), bd.grad) < 2e-5
+    assert relerr(grad_result(base, gg), gd.grad) < 2e-5 and relerr(grad_result(base, gb), bd.grad) < 2e-5
     if res:
         assert relerr(gres.cpu(), rd.grad) < 1e-6
 
