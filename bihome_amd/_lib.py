@@ -128,6 +128,7 @@ SIGNATURES = {
     "bh_synth_pairs": [P] * 5 + [c_int] * 5 + [c_float, c_float, P, P, P],
     "bh_synth_batch": [P] * 5 + [c_int] * 6 + [c_float, c_float, P, P, P, P],
     "bh_synth_image": [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P, P],
+    "bh_synth_blobs": [P] * 7 + [c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_gap_fwd": [P, P, c_int, c_int, c_int, P],
@@ -159,6 +160,8 @@ def _load():
     lib.bh_stem7_wgrad_ws_bytes.restype = ctypes.c_size_t
     lib.bh_warp_bwd_img_scratch_doubles.argtypes = [c_int, c_int, c_int, c_int, c_int]
     lib.bh_warp_bwd_img_scratch_doubles.restype = ctypes.c_size_t
+    lib.bh_synth_blobs_scratch_floats.argtypes = [c_int, c_int]
+    lib.bh_synth_blobs_scratch_floats.restype = ctypes.c_size_t
     if TUNING:
         lib.bh_debug_force_tile.argtypes = [c_int, c_int]
         lib.bh_debug_force_tile.restype = c_int

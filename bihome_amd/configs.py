@@ -196,7 +196,13 @@ def get(name):
     counterpart - SURVEY.md 0).  'nguyen-orig' = config/s-coco/nguyen-orig-lr-5e-3.yaml (PhotometricHead); 'nguyen-orig-pds' =
     config/pds-coco/nguyen-orig-lr-5e-3.yaml, which upstream made a different experiment (NoOpHead + L1Loss), not a data variant.
     '*-ihome', '*-multihead', '*-ihome-cos' and '*-bihome-aware' are loss-branch variants without a yaml upstream (see their builders);
-    'zeng-ihome-proj', 'zeng-ihome-cos-proj' and 'detone-bihome-proj' add the trainable projection head to theirs (`_proj`)."""
+    'zeng-ihome-proj', 'zeng-ihome-cos-proj' and 'detone-bihome-proj' add the trainable projection head to theirs (`_proj`).
+    'zeng-bihome-pds-blobs' = 'zeng-bihome-pds' under CollatorWithBlobs (train.py:130-136,575-577) with the only values upstream shows
+    (src/data/coco/dataset.py:442): DATA.AUGMENT_BLOB_POROSITY 0.1, AUGMENT_BLOBINESS 0.2."""
+    if name == "zeng-bihome-pds-blobs":
+        cfg = get("zeng-bihome-pds")
+        cfg["DATA"].update(AUGMENT_BLOB_POROSITY=0.1, AUGMENT_BLOBINESS=0.2)
+        return cfg
     if name in ("zeng-ihome-proj", "zeng-ihome-cos-proj", "detone-bihome-proj"):
         return _proj(get(name[:-5]))
     if name == "zeng-bihome-rgb256":

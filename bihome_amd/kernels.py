@@ -1486,3 +1486,28 @@ def add_(a, b):
     if getattr(a, "_bh_amax", None) is not None:
         a._bh_amax = None           # the magnitude record described the old contents
     return a
+
+
+# ------------------------------------------------------------------------------------------------
+# pair generator: occlusion blobs
+# ------------------------------------------------------------------------------------------------
+def synth_blobs_scratch_floats(B, P):
+    return int(lib.bh_synth_blobs_scratch_floats(int(B), int(P)))
+
+
+def synth_blobs(noise, other, patch1, patch2, mask, sigma, porosity, field=None, scratch=None):
+    """CollatorWithBlobs on the device (include/bihome.h bh_synth_blobs): noise [B,P,P] in [0,1), other [B] int32, patch1 / patch2
+    [B,C,P,P]; patch2 is composited IN PLACE (patch1[other[b]] where the blob field of noise[b] lies below `porosity`).
+    Outputs are the caller's: mask [B,P,P] (1.0 / 0.0), field [B,P,P] or None, scratch of synth_blobs_scratch_floats(B, P) floats
+    (None where that is 0); bihome_amd.synth_gpu.apply_blobs allocates them."""
+    _chk(noise); _chk(other, torch.int32); _chk(patch1); _chk(patch2); _chk(mask); _chk(field); _chk(scratch)
+    if noise.dim() != 3 or patch1.dim() != 4 or patch1.shape != patch2.shape or noise.shape[1] != noise.shape[2] or \
+            tuple(noise.shape) != (patch1.shape[0],) + tuple(patch1.shape[2:]) or other.shape != (noise.shape[0],) or \
+            mask.shape != noise.shape or (field is not None and field.shape != noise.shape):
+        raise ValueError("synth_blobs: noise, mask and field [B,P,P], other [B], patch1 and patch2 [B,C,P,P]")
+    B, C, P = patch1.shape[0], patch1.shape[1], patch1.shape[2]
+    if (scratch.numel() if scratch is not None else 0) < synth_blobs_scratch_floats(B, P):
+        raise ValueError("synth_blobs: scratch needs synth_blobs_scratch_floats(B, P) = %d floats" % synth_blobs_scratch_floats(B, P))
+    check(lib.bh_synth_blobs(_p(noise), _p(other), _p(patch1), _p(patch2), _p(mask), _p(field), _p(scratch), B, C, P, float(sigma),
+                             float(porosity), _stream()), "bh_synth_blobs")
+    return mask, field

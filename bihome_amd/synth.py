@@ -192,14 +192,113 @@ def gray_standardize(patch, mean=0.443, std=0.129):
     return ((g[None].astype(np.float32) / 255) - mean) / std
 
 
-def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, channels=1, pool=4, target=False, image=False):
+# ---- occlusion blobs: CollatorWithBlobs (transforms.py:746-799; DATA.AUGMENT_BLOB_POROSITY / AUGMENT_BLOBINESS, train.py:130-136,575-577) ----
+
+def check_blob_options(blob_porosity, blobiness, batch=None):
+    """The rules of the two options: both or neither (train.py:130-131); 0 <= porosity <= 1; blobiness >= 0.1 (the blur radius
+    int(4 P / (40 blobiness) + 0.5) then stays <= P, which one reflection of the border serves); a batch of at least 2 (upstream's
+    `choice` on the empty list of other samples raises).  Returns True when blobs are on."""
+    if (blob_porosity is None) != (blobiness is None):
+        raise ValueError("blob_porosity and blobiness must be set together (or neither)")
+    if blob_porosity is None:
+        return False
+    if not 0.0 <= float(blob_porosity) <= 1.0:
+        raise ValueError("blob_porosity must lie in [0, 1], got %r" % (blob_porosity,))
+    if not float(blobiness) >= 0.1:
+        raise ValueError("blobiness must be >= 0.1 (blur radius <= patch size), got %r" % (blobiness,))
+    if batch is not None and batch < 2:
+        raise ValueError("blobs paste content of ANOTHER sample of the batch: the batch needs at least 2 samples")
+    return True
+
+
+def blob_sigma(patch, blobiness):
+    return patch / (40.0 * blobiness)
+
+
+def gaussian_blur_reflect(a, sigma):
+    """scipy.ndimage.gaussian_filter(a, sigma) for a 2-D array, restated: separable, radius r = int(4 sigma + 0.5), weights
+    exp(-0.5 (k / sigma)^2) normalised to sum 1, border mode 'reflect' (d c b a | a b c d | d c b a: numpy's 'symmetric').
+    Arithmetic in a's dtype (float64 is the reference; float32 measures what single precision costs)."""
+    a = np.asarray(a)
+    dt = a.dtype if a.dtype.kind == "f" else np.float64
+    r = int(4.0 * sigma + 0.5)
+    k = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-0.5 * (k / sigma) ** 2)
+    w = (w / w.sum()).astype(dt)
+    for axis in (0, 1):
+        if r > a.shape[axis]:
+            raise ValueError("blur radius %d exceeds the extent %d: more than one reflection" % (r, a.shape[axis]))
+        pad = [(0, 0), (0, 0)]
+        pad[axis] = (r, r)
+        p = np.pad(a.astype(dt), pad, mode="symmetric")
+        n = a.shape[axis]
+        out = np.zeros(a.shape, dt)
+        for j in range(2 * r + 1):
+            out += w[j] * (p[j:j + n] if axis == 0 else p[:, j:j + n])
+        a = out
+    return a
+
+
+def blob_field(noise, blobiness):
+    """noise[P,P] uniform in [0,1) -> u[P,P] in [0,1]: the continuous field porespy's `generators.blobs(shape, porosity, blobiness)`
+    thresholds at the porosity (`u < porosity`), the call CollatorWithBlobs makes (transforms.py:787).  The steps are RECALLED from
+    porespy, not read from its source, which is not available here (upstream's own `import porespy` is commented out, transforms.py:3):
+    sigma = P / (40 blobiness); g = gaussian_filter(noise, sigma); z = (g - mean g) / std g (population); u = 0.5 erfc(-z / sqrt 2),
+    then (u - min u) / (max u - min u).  A flat field (std g == 0 or max == min), where that arithmetic gives NaN and the comparison
+    selects nothing, is defined here as u = 1 everywhere: no blob at any porosity in [0, 1], and no NaN.  Arithmetic in noise's dtype."""
+    from math import erfc
+    noise = np.asarray(noise)
+    dt = noise.dtype if noise.dtype.kind == "f" else np.float64
+    g = gaussian_blur_reflect(noise.astype(dt), blob_sigma(noise.shape[-1], blobiness))
+    sd = g.std()
+    if not sd > 0 or not g.max() > g.min():
+        return np.ones(g.shape, dt)
+    z = ((g - g.mean()) / sd).astype(dt)
+    u = (0.5 * np.vectorize(erfc, otypes=[np.float64])(-z.astype(np.float64) / np.sqrt(2.0))).astype(dt)
+    if not u.max() > u.min():
+        return np.ones(g.shape, dt)
+    return ((u - u.min()) / (u.max() - u.min())).astype(dt)
+
+
+def blob_mask(noise, porosity, blobiness):
+    """[..., P, P] noise -> boolean blob masks (True: the pixel is replaced)."""
+    noise = np.asarray(noise)
+    if noise.ndim == 2:
+        return blob_field(noise, blobiness) < porosity
+    return np.stack([blob_mask(n, porosity, blobiness) for n in noise])
+
+
+def draw_other(rng, batch):
+    """other[b] uniform over the other batch - 1 samples (transforms.py:782-784): r = integers(0, B - 1), then r + (r >= b)."""
+    if batch < 2:
+        raise ValueError("blobs paste content of ANOTHER sample of the batch: the batch needs at least 2 samples")
+    r = rng.integers(0, batch - 1, batch)
+    return (r + (r >= np.arange(batch))).astype(np.int64)
+
+
+def apply_blobs(p1, p2, mask, other):
+    """patch_2[b, c] = where(mask[b], patch_1[other[b], c], patch_2[b, c]) for every channel (transforms.py:791-797); returns the new
+    patch_2.  Only patch_1 is read, which upstream never modifies, so its loop order over the batch does not matter.  A select, where
+    upstream multiplies by the mask and its complement and adds: identical for finite pixels (x * 1 + y * 0 == x)."""
+    p1, p2, mask = np.asarray(p1), np.asarray(p2), np.asarray(mask).astype(bool)
+    other = np.asarray(other)
+    if p1.shape[0] < 2:
+        raise ValueError("blobs paste content of ANOTHER sample of the batch: the batch needs at least 2 samples")
+    return np.where(mask[:, None], p1[other], p2)
+
+
+def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, channels=1, pool=4, target=False, image=False,
+               blob_porosity=None, blobiness=None):
     """Return dict of float32 arrays: patch_1, patch_2 [B,C,P,P] (standardised), delta [B,4,2]
     (ground-truth 4-point offsets, integers in [-rho, rho-1]), corners [B,4,2], homography [B,3,3].
     image=True (channels 1 only): also image_1 [B,1,h,w], the whole standardised grayscale image 1 that patch_1 is cropped from
-    (the photometric head's input, config/s-coco/nguyen-orig-lr-5e-3.yaml); no extra random draws, every other output unchanged."""
+    (the photometric head's input, config/s-coco/nguyen-orig-lr-5e-3.yaml); no extra random draws, every other output unchanged.
+    blob_porosity / blobiness (both or neither): CollatorWithBlobs on the finished batch - patch_2 is the composite, blob_mask
+    [B,1,P,P] and blob_other [B] say what was pasted from where; the two draws come after all others, every other output unchanged."""
     want_image = bool(image)          # (the loop below names the base image `image`)
     if want_image and channels != 1:
         raise ValueError("make_pairs(image=True) produces the grayscale image_1 of the photometric head: channels must be 1")
+    blobs = check_blob_options(blob_porosity, blobiness, batch)
     rng = np.random.Generator(np.random.PCG64(seed))
     h = max(240, patch + 2 * rho + 48)
     w = max(320, patch + 2 * rho + 128)
@@ -243,6 +342,12 @@ def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, chann
         c = np.array([[0, 0], [patch, 0], [patch, patch], [0, patch]], np.float64)
         out["target"] = np.stack([perspective_field(four_point_homography(c, c + deltas[b].astype(np.float64)), patch)
                                   for b in range(batch)]).astype(np.float32)
+    if blobs:
+        noise = rng.random((batch, patch, patch))
+        other = draw_other(rng, batch)
+        mask = blob_mask(noise, blob_porosity, blobiness)
+        out["patch_2"] = apply_blobs(p1, p2, mask, other)
+        out["blob_mask"], out["blob_other"] = mask[:, None].astype(np.float32), other
     return out
 
 

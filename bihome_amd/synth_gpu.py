@@ -43,15 +43,28 @@ def batch_spec(cfg):
     and the target come from DATA; the head decides what else its batch carries: PhotometricHead warps the whole image_1 (and
     its corners), NoOpHead's '4_points' predict_homography reads the corners."""
     data, head = cfg["DATA"], cfg["MODEL"]["HEAD"]["NAME"]
-    return {"patch": data["PATCH_SIZE"], "rho": data["RHO"], "photometric_max_delta": data.get("PHOTOMETRIC_MAX_DELTA", 0),
+    spec = {"patch": data["PATCH_SIZE"], "rho": data["RHO"], "photometric_max_delta": data.get("PHOTOMETRIC_MAX_DELTA", 0),
             "channels": data.get("PATCH_CHANNELS", 1), "target_gen": data.get("TARGET_GEN"),
             "image": head == "PhotometricHead", "corners": head in ("PhotometricHead", "NoOpHead")}
+    if "AUGMENT_BLOB_POROSITY" in data and "AUGMENT_BLOBINESS" in data:            # CollatorWithBlobs (train.py:130-136,575-577)
+        spec.update(blob_porosity=data["AUGMENT_BLOB_POROSITY"], blobiness=data["AUGMENT_BLOBINESS"])
+    return spec
+
+
+def apply_blobs(noise, other, patch1, patch2, sigma, porosity, want_field=False):
+    """K.synth_blobs with its outputs allocated here: patch2 [B,C,P,P] is composited in place; returns (mask [B,P,P], field [B,P,P] |
+    None - the continuous field, for tests)."""
+    mask = torch.empty(noise.shape, dtype=torch.float32, device=noise.device)
+    field = torch.empty(noise.shape, dtype=torch.float32, device=noise.device) if want_field else None
+    n = K.synth_blobs_scratch_floats(noise.shape[0], noise.shape[-1])
+    scratch = torch.empty(n, dtype=torch.float32, device=noise.device) if n else None
+    return K.synth_blobs(noise, other, patch1, patch2, mask, sigma, porosity, field=field, scratch=scratch)
 
 
 class GpuPairGenerator:
 
     def __init__(self, n_images=16, patch=128, rho=32, seed=42, photometric_max_delta=0, device="cuda", channels=1,
-                 target_gen=None, corners=False, photometric_draws="host", image=False):
+                 target_gen=None, corners=False, photometric_draws="host", image=False, blob_porosity=None, blobiness=None):
         if channels not in (1, 3):
             raise ValueError("channels must be 1 (grayscale) or 3 (RGB)")
         if target_gen not in (None, "4_points", "all_points"):
@@ -60,6 +73,8 @@ class GpuPairGenerator:
             raise ValueError("photometric_draws must be 'host' or 'device'")
         if image and channels != 1:
             raise ValueError("image=True produces the grayscale image_1 of the photometric head: channels must be 1")
+        self.blobs = synth.check_blob_options(blob_porosity, blobiness)
+        self.blob_porosity, self.blobiness = blob_porosity, blobiness
         rng = np.random.Generator(np.random.PCG64(seed))
         self.h = max(240, patch + 2 * rho + 48)
         self.w = max(320, patch + 2 * rho + 128)
@@ -80,7 +95,8 @@ class GpuPairGenerator:
 
     def draw(self, B):
         """Random sample parameters exactly as transforms.py:505-506,538 draw them (uniform integer position with a
-        rho margin, integer corner offsets in [-rho, rho-1])."""
+        rho margin, integer corner offsets in [-rho, rho-1]).  With blobs on, a fifth element (noise [B,P,P], other [B] int32) drawn
+        AFTER everything else: a seed yields the same idx / origin / delta / photo with and without blobs."""
         g, dev, half = self.gen, self.device, self.patch // 2
         idx = torch.randint(0, self.images.shape[0], (B,), generator=g, device=dev, dtype=torch.int32)
         px = torch.randint(self.rho + half, self.w - self.rho - half + 1, (B,), generator=g, device=dev)
@@ -98,10 +114,20 @@ class GpuPairGenerator:
             recs = np.stack([np.concatenate([synth.draw_photometric(self._rs, self.pmd), synth.draw_photometric(self._rs, self.pmd)])
                              for _ in range(B)])
             photo = torch.tensor(recs, dtype=torch.float32, device=dev).contiguous()
-        return idx, origin, delta, photo
+        if not self.blobs:
+            return idx, origin, delta, photo
+        if B < 2:
+            raise ValueError("blobs paste content of ANOTHER sample of the batch: the batch needs at least 2 samples")
+        # CollatorWithBlobs' draws (transforms.py:782-787): the field's noise, and a source uniform over the other B - 1 samples
+        noise = torch.rand((B, self.patch, self.patch), generator=g, device=dev)
+        r = torch.randint(0, B - 1, (B,), generator=g, device=dev)
+        other = (r + (r >= torch.arange(B, device=dev))).to(torch.int32)
+        return idx, origin, delta, photo, (noise, other)
 
-    def make(self, idx, origin, delta, photo=None, image=None):
-        """image=True: also image_1 [B,1,h,w] (the whole standardised grayscale image 1 under its photometric record, bh_synth_image:
+    def make(self, idx, origin, delta, photo=None, blobs=None, image=None):
+        """blobs = (noise, other), `draw`'s fifth element: patch_2 becomes CollatorWithBlobs' composite (bh_synth_blobs), and the batch
+        gains blob_mask [B,1,P,P] and blob_other [B]; every other entry is what it is without blobs.
+        image=True: also image_1 [B,1,h,w] (the whole standardised grayscale image 1 under its photometric record, bh_synth_image:
         its crop at the corners is patch_1 bitwise) and corners [B,4,2] - the batch of the photometric head (nguyen-orig).  Default:
         what the generator was constructed with."""
         image = self.image if image is None else image
@@ -119,6 +145,14 @@ class GpuPairGenerator:
                                  pv(field.data_ptr()) if field is not None else None,
                                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_synth_batch")
         out = {"patch_1": p1, "patch_2": p2, "delta": delta}
+        if blobs is not None:
+            if not self.blobs:
+                raise ValueError("make(blobs=...) needs a generator constructed with blob_porosity and blobiness")
+            noise, other = blobs
+            mask, _ = apply_blobs(noise, other, p1, p2, synth.blob_sigma(P, self.blobiness), self.blob_porosity)
+            out["blob_mask"], out["blob_other"] = mask.view(B, 1, P, P), other
+        elif self.blobs:
+            raise ValueError("this generator was constructed with blobs: make() needs draw()'s fifth element")
         if self.target_gen is not None:
             out["target"] = delta if self.target_gen == "4_points" else field            # transforms.py:628-633 / :635-685
         if image or self.corners:
@@ -134,4 +168,4 @@ class GpuPairGenerator:
         return out
 
     def next(self, B, image=None):
-        return self.make(*self.draw(B), image=image)
+        return self.make(*self.draw(B), image=image)        # (four or five draws: the fifth lands on `blobs`)

@@ -728,6 +728,22 @@ int bh_synth_batch(const float* images, const int* img_idx, const float* origin,
 int bh_synth_image(const float* images, const int* img_idx, const float* photo, int B, int n_images, int Hs, int Ws, float mean,
                    float std, float* image1, void* stream);
 
+/* Occlusion blobs of the pair generator: CollatorWithBlobs (src/data/transforms.py:746-799; DATA.AUGMENT_BLOB_POROSITY /
+ * AUGMENT_BLOBINESS, train.py:130-136,575-577) for B samples.  noise[B,P,P] uniform in [0,1) and other[B] (int32, the sample whose
+ * patch_1 is pasted, 0 <= other[b] < B; an index outside that range is read as b) are inputs: nothing is drawn here.  Per sample:
+ * g = Gaussian blur of noise (separable, radius int(4 sigma + 0.5), scipy's 'reflect' border), z = (g - mean) / std (population),
+ * u = 0.5 erfc(-z / sqrt 2) min-max normalised to [0,1], blob = u < porosity (what porespy's generators.blobs computes with
+ * sigma = P / (40 blobiness); bihome_amd/synth.py blob_field is the float64 restatement).  Outputs, all fully overwritten:
+ * mask[B,P,P] = 1.0 / 0.0; field[B,P,P] = u (NULL ok); patch2[B,C,P,P] in place: patch2[b,c] = patch1[other[b],c] where blob, every
+ * other element keeps its bits (patch1 is only read).  A flat plane (std == 0 or max == min, where upstream's arithmetic is NaN and
+ * selects nothing) gives field 1, mask 0, patch2 untouched.  scratch: bh_synth_blobs_scratch_floats(B, P) floats (0 for P <= 128),
+ * need not be initialised.  No atomics: two calls on the same inputs are bitwise equal.
+ * BH_E_BADARG: a NULL required pointer, B < 2, C not 1 or 3, sigma not positive and finite, porosity outside [0,1];
+ * BH_E_UNSUPPORTED: P % 16 != 0, P > 256, radius > P (blobiness < 0.1: more than one reflection). */
+size_t bh_synth_blobs_scratch_floats(int B, int P);
+int bh_synth_blobs(const float* noise, const int* other, const float* patch1, float* patch2, float* mask, float* field,
+                   float* scratch, int B, int C, int P, double sigma, double porosity, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation). */
 int bh_maxpool3s2_fwd(const float* x, float* y, unsigned char* argmax, int N, int Hi, int Wi, int C, void* stream);
