@@ -19,7 +19,7 @@ struct BnGeom {
 
 // det: 1 = this call accumulates / reads through the integer limbs (BH_BN_DETERMINISTIC), 0 = word 0 only, -1 = readers look
 static bool bn_geom(int groups, int rows, int C, BnGeom& g, int det) {
-    if (C % 4 || groups < 1 || rows < 1) return false;
+    if (C < 4 || C % 4 || groups < 1 || rows < 1) return false;      // (C < 4 first: 256 % (C / 4) below divides by zero for C == 0)
     g.groups = groups; g.rows = rows; g.C = C; g.C4 = C / 4; g.det = det;
     if (g.C4 > 256 || (256 % g.C4)) return false;
     g.LPR = g.C4; g.RPP = 256 / g.LPR;
@@ -724,6 +724,162 @@ __global__ void __launch_bounds__(256) bn_join_bwd_apply_kernel(const float* __r
     if (amax_b) { __syncthreads(); bh_amax_commit(amax_b, vmax_b, blockIdx.x + blockIdx.y * 5u, sm_amax); }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Groups of at most BN_SMALL_ROWS rows (training mode): the adjoint in double, one thread per channel.  Over two rows xhat = +-1 up to
+// eps and the input gradient A (d - mean d - xhat mean(d xhat)) is the residue (d1 - d2) / 2 * eps / (var + eps) of a cancellation between
+// terms of order d: formed in fp32 (the kernels above: mean, invstd and the two means rounded to fp32) it is one rounding of d, 1e-1 of
+// the result.  Here mean and variance are taken from the rows themselves (two passes), the sums and the expression stay in double and
+// the result is rounded once.  The ReLU mask is the forward's own decision: y where it is given, else the forward's fp32 expression.
+// grid ceil(C / 256); no scratch.
+// ---------------------------------------------------------------------------------------------
+#define BN_SMALL_ROWS 4
+__device__ __forceinline__ void bn_small_moments(const float* __restrict__ x, size_t base, int rows, int C, float eps, double& m, double& is) {
+    double s = 0;
+    for (int r = 0; r < rows; ++r) s += (double)x[base + (size_t)r * C];
+    m = s / rows;
+    double v = 0;
+    for (int r = 0; r < rows; ++r) { const double t = (double)x[base + (size_t)r * C] - m; v += t * t; }
+    is = 1.0 / sqrt(v / rows + (double)eps);
+}
+
+__global__ void __launch_bounds__(256) bn_bwd_small_kernel(const float* __restrict__ gy, const float* __restrict__ y, const float* __restrict__ x,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const double* __restrict__ stats, float* __restrict__ gx, float* __restrict__ gres,
+                                                           BnGeom g, float eps, int flags, float* __restrict__ ggamma, float* __restrict__ gbeta,
+                                                           unsigned* __restrict__ amax) {
+    __shared__ float sm_amax[4];
+    float vmax = 0.f;
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < g.C) {
+        const bool relu = flags & 1, mask_from_x = flags & 4;
+        const double gm = gamma ? (double)gamma[c] : 1.0;
+        double tb = 0, tg = 0;
+        for (int grp = 0; grp < g.groups; ++grp) {
+            float mean, invstd, sc, sh;
+            bn_coeffs(stats, gamma, beta, nullptr, nullptr, 0, g.groups, grp, g.C, c, eps, (double)g.rows, mean, invstd, sc, sh, g.det);
+            const size_t base = ((size_t)grp * g.rows) * g.C + c;
+            double m, is, d[BN_SMALL_ROWS], xh[BN_SMALL_ROWS], s1 = 0, s2 = 0;
+            bn_small_moments(x, base, g.rows, g.C, eps, m, is);
+            for (int r = 0; r < g.rows; ++r) {
+                const size_t off = base + (size_t)r * g.C;
+                const float a = x[off];
+                float dd = gy[off];
+                if (relu) {
+                    const float o = mask_from_x ? a * sc + sh : y[off];
+                    if (!(o > 0.f)) dd = 0.f;
+                }
+                d[r] = dd; xh[r] = ((double)a - m) * is;
+                s1 += d[r]; s2 += d[r] * xh[r];
+            }
+            const double kb = s1 / g.rows, kg = s2 / g.rows, A = gm * is;
+            for (int r = 0; r < g.rows; ++r) {
+                const size_t off = base + (size_t)r * g.C;
+                const float o = (float)(A * (d[r] - kb - xh[r] * kg));
+                gx[off] = o;
+                if (gres) gres[off] = (float)d[r];
+                vmax = fmaxf(vmax, fabsf(o));
+            }
+            tb += s1; tg += s2;
+        }
+        if (ggamma) ggamma[c] += (float)tg;
+        if (gbeta) gbeta[c] += (float)tb;
+    }
+    if (amax) bh_amax_commit(amax, vmax, blockIdx.x, sm_amax);
+}
+
+// the join's output over such groups: both normalisations in double from the rows themselves, one rounding (in fp32 the rounded
+// product mean * scale is an error of 2^-24 |mean scale|, and over a handful of rows var << mean^2 - a large scale - is no rare channel)
+__device__ __forceinline__ float bn_join_small_y(float a, float b, double gma, double ia, double ma, double ba, double gmb, double ib, double mb,
+                                                 double bb) {
+    return (float)(gma * ia * ((double)a - ma) + ba + (gmb * ib * ((double)b - mb) + bb));
+}
+
+__global__ void __launch_bounds__(256) bn_join_small_kernel(const float* __restrict__ xa, const float* __restrict__ xb, const float* __restrict__ gamma_a,
+                                                            const float* __restrict__ beta_a, const float* __restrict__ gamma_b,
+                                                            const float* __restrict__ beta_b, const double* __restrict__ stats_a,
+                                                            const double* __restrict__ stats_b, float* __restrict__ y, BnGeom g, float eps_a,
+                                                            float eps_b, int relu, float mom_a, float mom_b, float* __restrict__ rm_a,
+                                                            float* __restrict__ rv_a, float* __restrict__ rm_b, float* __restrict__ rv_b,
+                                                            unsigned* __restrict__ amax) {
+    __shared__ float sm_amax[4];
+    float vmax = 0.f;
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < g.C) {
+        const double gma = gamma_a ? (double)gamma_a[c] : 1.0, gmb = gamma_b ? (double)gamma_b[c] : 1.0;
+        const double ba = beta_a ? (double)beta_a[c] : 0.0, bb = beta_b ? (double)beta_b[c] : 0.0;
+        for (int grp = 0; grp < g.groups; ++grp) {
+            const size_t base = ((size_t)grp * g.rows) * g.C + c;
+            double ma, ia, mb, ib;
+            bn_small_moments(xa, base, g.rows, g.C, eps_a, ma, ia);
+            bn_small_moments(xb, base, g.rows, g.C, eps_b, mb, ib);
+            for (int r = 0; r < g.rows; ++r) {
+                const size_t off = base + (size_t)r * g.C;
+                float o = bn_join_small_y(xa[off], xb[off], gma, ia, ma, ba, gmb, ib, mb, bb);
+                if (relu) o = fmaxf(o, 0.f);
+                y[off] = o;
+                vmax = fmaxf(vmax, fabsf(o));
+            }
+        }
+    }
+    if (blockIdx.x == 0) {
+        if (rm_a) bn_update_running(stats_a, g, mom_a, rm_a, rv_a);
+        if (rm_b) bn_update_running(stats_b, g, mom_b, rm_b, rv_b);
+    }
+    if (amax) bh_amax_commit(amax, vmax, blockIdx.x, sm_amax);
+}
+
+// the same for the two-branch join: d = gy [y > 0], gxa = A_a (d - mean d - xhat_a mean(d xhat_a)), gxb likewise
+__global__ void __launch_bounds__(256) bn_join_bwd_small_kernel(const float* __restrict__ gy, const float* __restrict__ y, const float* __restrict__ xa,
+                                                                const float* __restrict__ xb, const float* __restrict__ gamma_a,
+                                                                const float* __restrict__ gamma_b, const float* __restrict__ beta_a,
+                                                                const float* __restrict__ beta_b, int remask, const double* __restrict__ stats_a,
+                                                                const double* __restrict__ stats_b, float* __restrict__ gxa, float* __restrict__ gxb,
+                                                                BnGeom g, float eps_a, float eps_b, int relu, float* __restrict__ gg_a,
+                                                                float* __restrict__ gb_a, float* __restrict__ gg_b, float* __restrict__ gb_b,
+                                                                unsigned* __restrict__ amax_a, unsigned* __restrict__ amax_b) {
+    __shared__ float sm_amax[4];
+    float vmax_a = 0.f, vmax_b = 0.f;
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c < g.C) {
+        const double gma = gamma_a ? (double)gamma_a[c] : 1.0, gmb = gamma_b ? (double)gamma_b[c] : 1.0;
+        const double ba = beta_a ? (double)beta_a[c] : 0.0, bb = beta_b ? (double)beta_b[c] : 0.0;
+        const double inv_rows = 1.0 / (double)g.rows;
+        double t1 = 0, t2a = 0, t2b = 0;
+        for (int grp = 0; grp < g.groups; ++grp) {
+            const size_t base = ((size_t)grp * g.rows) * g.C + c;
+            double ma, ia, mb, ib, d[BN_SMALL_ROWS], ha[BN_SMALL_ROWS], hb[BN_SMALL_ROWS], s1 = 0, s2a = 0, s2b = 0;
+            bn_small_moments(xa, base, g.rows, g.C, eps_a, ma, ia);
+            bn_small_moments(xb, base, g.rows, g.C, eps_b, mb, ib);
+            for (int r = 0; r < g.rows; ++r) {
+                const size_t off = base + (size_t)r * g.C;
+                const float a = xa[off], b = xb[off];
+                float dd = gy[off];
+                if (relu) {
+                    // (remask: the forward of such groups is bn_join_small_kernel - its expression, bit for bit)
+                    const float yi = remask ? bn_join_small_y(a, b, gma, ia, ma, ba, gmb, ib, mb, bb) : y[off];
+                    if (!(yi > 0.f)) dd = 0.f;
+                }
+                d[r] = dd; ha[r] = ((double)a - ma) * ia; hb[r] = ((double)b - mb) * ib;
+                s1 += d[r]; s2a += d[r] * ha[r]; s2b += d[r] * hb[r];
+            }
+            const double kb = s1 * inv_rows, kga = s2a * inv_rows, kgb = s2b * inv_rows;
+            for (int r = 0; r < g.rows; ++r) {
+                const size_t off = base + (size_t)r * g.C;
+                const float oa = (float)(gma * ia * (d[r] - kb - ha[r] * kga)), ob = (float)(gmb * ib * (d[r] - kb - hb[r] * kgb));
+                gxa[off] = oa; gxb[off] = ob;
+                vmax_a = fmaxf(vmax_a, fabsf(oa)); vmax_b = fmaxf(vmax_b, fabsf(ob));
+            }
+            t1 += s1; t2a += s2a; t2b += s2b;
+        }
+        if (gg_a) gg_a[c] += (float)t2a;
+        if (gb_a) gb_a[c] += (float)t1;
+        if (gg_b) gg_b[c] += (float)t2b;
+        if (gb_b) gb_b[c] += (float)t1;
+    }
+    if (amax_a) bh_amax_commit(amax_a, vmax_a, blockIdx.x, sm_amax);
+    if (amax_b) { __syncthreads(); bh_amax_commit(amax_b, vmax_b, blockIdx.x, sm_amax); }
+}
+
 BH_KNOB(g_bn_apply_cap, 512);        // workgroups per apply launch: two per CU that loop beat a one-shot grid of 2048 by 15-30 % (tools/bn_apply_sweep.py; tuning: bh_debug_force_tile(-20, n))
 #ifdef BH_TUNING
 void bh_bn_tune(int cap) { g_bn_apply_cap = cap; }
@@ -827,6 +983,14 @@ int bh_bn_bwd(const float* gy, const float* y, const float* x, const float* gamm
                                running_mean, running_var, bh_stream(stream));
     if (!bn_geom(groups, rows, C, g, (flags & BH_BN_DETERMINISTIC) ? 1 : 0)) return BH_E_UNSUPPORTED;
     hipStream_t s = bh_stream(stream);
+    // a handful of rows per group: the adjoint in double, from gy itself (flags bit4: the sums the dgrad epilogue left in `scratch` are
+    // not needed - they hold the same two sums with fp32 products)
+    if (!use_running && rows <= BN_SMALL_ROWS) {
+        hipLaunchKernelGGL(bn_bwd_small_kernel, dim3((C + 255) / 256), dim3(256), 0, s, gy, y, x, gamma, beta, stats, gx, gres, g, eps, flags,
+                           ggamma, gbeta, reinterpret_cast<unsigned*>(amax_gx));
+        BH_LAUNCH_CHECK();
+        return BH_OK;
+    }
     if (flags & 16) {            // scratch = padded sums accumulated by bh_conv_dgrad_bnreduce (training mode only)
         if (use_running) return BH_E_BADARG;
         hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(apply_blocks(g), groups), dim3(256), 0, s, gy, y, x, gamma, beta,
@@ -872,6 +1036,7 @@ int bh_bn_maxpool_fwd(const float* x, const float* gamma, const float* beta, flo
     if (use_running && (!running_mean || !running_var)) return BH_E_BADARG;
     const int rows = (N / groups) * Hi * Wi;
     if (!bn_geom(groups, rows, C, g, (flags & BH_BN_DETERMINISTIC) ? 1 : 0) || groups * C * 8 > 32768) return BH_E_UNSUPPORTED;
+    if (rows <= BN_SMALL_ROWS) return BH_E_UNSUPPORTED;      // (the fused adjoint has no double form: bh_bn_fwd + bh_maxpool3s2_fwd take such maps)
     hipStream_t s = bh_stream(stream);
     if (!use_running && !(flags & 8)) {                       // bit 3: the producer already accumulated the sums
         hipLaunchKernelGGL(bn_stats_kernel, dim3(g.nchunks, groups), dim3(256), 0, s, x, g, stats);
@@ -1058,6 +1223,7 @@ int bh_bn_maxpool_bwd(const float* gy, const unsigned char* idx, const float* x,
     if (use_running && (!running_mean || !running_var)) return BH_E_BADARG;
     const long long rows = (long long)(N / groups) * Hi * Wi;
     if (rows >= (1ll << 31) || !bn_geom(groups, (int)rows, C, g, (flags & BH_BN_DETERMINISTIC) ? 1 : 0)) return BH_E_UNSUPPORTED;
+    if (rows <= BN_SMALL_ROWS) return BH_E_UNSUPPORTED;      // (fp32 evaluation only: bh_maxpool3s2_bwd + bh_bn_bwd evaluate such groups in double)
     PoolGeom pg = {Hi, Wi, (Hi - 1) / 2 + 1, (Wi - 1) / 2 + 1, N / groups};
     hipStream_t s = bh_stream(stream);
     // scratch as in bh_bn_bwd: [groups][C] float4 coefficient table, then the per-chunk partial sums
@@ -1229,6 +1395,7 @@ int bh_bn_bwd_from_1x1(const float* gs, const float* w, int KC, const float* x, 
     if (!gs || !w || !x || !gx || !stats || !scratch) return BH_E_BADARG;
     if (KC != 16 && KC != 32) return BH_E_UNSUPPORTED;
     if (!bn_geom(groups, rows, C, g, (flags & BH_BN_DETERMINISTIC) ? 1 : 0)) return BH_E_UNSUPPORTED;
+    if (rows <= BN_SMALL_ROWS) return BH_E_UNSUPPORTED;      // (fp32 evaluation only: bh_conv_dgrad + bh_bn_bwd evaluate such groups in double)
     hipStream_t s = bh_stream(stream);
     float4* coef = reinterpret_cast<float4*>(scratch);
     double* part = scratch + (size_t)groups * C * 2;
@@ -1254,6 +1421,13 @@ int bh_bn_join_fwd(const float* xa, const float* xb, const float* gamma_a, const
     BnGeom g;
     if (!xa || !xb || !y || !stats_a || !stats_b) return BH_E_BADARG;
     if (!bn_geom(groups, rows, C, g, (flags & BH_BN_DETERMINISTIC) ? 1 : 0)) return BH_E_UNSUPPORTED;
+    if (rows <= BN_SMALL_ROWS) {                                         // a handful of rows per group: in double (bn_join_small_kernel)
+        hipLaunchKernelGGL(bn_join_small_kernel, dim3((C + 255) / 256), dim3(256), 0, bh_stream(stream), xa, xb, gamma_a, beta_a, gamma_b, beta_b,
+                           stats_a, stats_b, y, g, eps_a, eps_b, flags & 1, momentum_a, momentum_b, (rmean_a && rvar_a) ? rmean_a : nullptr, rvar_a,
+                           (rmean_b && rvar_b) ? rmean_b : nullptr, rvar_b, reinterpret_cast<unsigned*>(amax_y));
+        BH_LAUNCH_CHECK();
+        return BH_OK;
+    }
     hipLaunchKernelGGL(bn_join_apply_kernel, dim3(apply_blocks(g), groups), dim3(256), 0, bh_stream(stream), xa, xb, gamma_a, beta_a, gamma_b,
                        beta_b, stats_a, stats_b, y, g, eps_a, eps_b, flags & 1, momentum_a, momentum_b, (rmean_a && rvar_a) ? rmean_a : nullptr,
                        rvar_a, (rmean_b && rvar_b) ? rmean_b : nullptr, rvar_b, reinterpret_cast<unsigned*>(amax_y));
@@ -1270,6 +1444,13 @@ static int bn_join_bwd_impl(const float* gy, const float* y, const float* xa, co
     if (!gy || !xa || !xb || !gxa || !gxb || !stats_a || !stats_b || !scratch || ((flags & 1) && !remask && !y)) return BH_E_BADARG;
     if (!bn_geom(groups, rows, C, g, (flags & BH_BN_DETERMINISTIC) ? 1 : 0)) return BH_E_UNSUPPORTED;
     hipStream_t s = bh_stream(stream);
+    if (rows <= BN_SMALL_ROWS) {                                         // a handful of rows per group: the adjoint in double
+        hipLaunchKernelGGL(bn_join_bwd_small_kernel, dim3((C + 255) / 256), dim3(256), 0, s, gy, y, xa, xb, gamma_a, gamma_b, beta_a, beta_b, remask,
+                           stats_a, stats_b, gxa, gxb, g, eps_a, eps_b, flags & 1, ggamma_a, gbeta_a, ggamma_b, gbeta_b,
+                           reinterpret_cast<unsigned*>(amax_gxa), reinterpret_cast<unsigned*>(amax_gxb));
+        BH_LAUNCH_CHECK();
+        return BH_OK;
+    }
     float4* coef = reinterpret_cast<float4*>(scratch);
     double* part = scratch + (size_t)groups * C * 2;
     hipLaunchKernelGGL(bn_join_bwd_reduce_kernel, dim3(g.nchunks, groups), dim3(256), 0, s, gy, y, xa, xb, stats_a, stats_b, g, eps_a, eps_b,

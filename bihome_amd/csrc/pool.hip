@@ -124,7 +124,9 @@ static int nblocks(size_t work) {
 extern "C" {
 
 int bh_maxpool3s2_fwd(const float* x, float* y, unsigned char* argmax, int N, int Hi, int Wi, int C, void* stream) {
-    if (!x || !y || C % 4) return C % 4 ? BH_E_UNSUPPORTED : BH_E_BADARG;
+    if (!x || !y || N < 0 || Hi < 1 || Wi < 1 || C < 4) return BH_E_BADARG;      // (an empty map has no window: (0 - 1) / 2 + 1 == 1 output row)
+    if (C % 4) return BH_E_UNSUPPORTED;
+    if (N == 0) return BH_OK;
     const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
     hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(nblocks((size_t)N * Ho * Wo * (C / 4))), dim3(256), 0, bh_stream(stream), x,
                        y, argmax, N, Hi, Wi, C / 4, Ho, Wo);
@@ -133,7 +135,9 @@ int bh_maxpool3s2_fwd(const float* x, float* y, unsigned char* argmax, int N, in
 }
 
 int bh_maxpool3s2_bwd(const unsigned char* argmax, const float* gy, float* gx, int N, int Hi, int Wi, int C, void* stream) {
-    if (!argmax || !gy || !gx || C % 4) return C % 4 ? BH_E_UNSUPPORTED : BH_E_BADARG;
+    if (!argmax || !gy || !gx || N < 0 || Hi < 1 || Wi < 1 || C < 4) return BH_E_BADARG;
+    if (C % 4) return BH_E_UNSUPPORTED;
+    if (N == 0) return BH_OK;
     const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
     hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(nblocks((size_t)N * Hi * Wi * (C / 4))), dim3(256), 0, bh_stream(stream),
                        argmax, gy, gx, N, Hi, Wi, C / 4, Ho, Wo);
@@ -142,7 +146,7 @@ int bh_maxpool3s2_bwd(const unsigned char* argmax, const float* gy, float* gx, i
 }
 
 int bh_gap_fwd(const float* x, float* y, int N, int HW, int C, void* stream) {
-    if (!x || !y) return BH_E_BADARG;
+    if (!x || !y || N < 0 || HW < 1 || C < 1) return BH_E_BADARG;
     if (N == 0) return BH_OK;
     hipLaunchKernelGGL(gap_fwd_kernel, dim3(N), dim3(256), 0, bh_stream(stream), x, y, HW, C);
     BH_LAUNCH_CHECK();
@@ -150,7 +154,8 @@ int bh_gap_fwd(const float* x, float* y, int N, int HW, int C, void* stream) {
 }
 
 int bh_gap_bwd(const float* gy, float* gx, int N, int HW, int C, void* stream) {
-    if (!gy || !gx) return BH_E_BADARG;
+    if (!gy || !gx || N < 0 || HW < 1 || C < 1) return BH_E_BADARG;
+    if (N == 0) return BH_OK;
     hipLaunchKernelGGL(gap_bwd_kernel, dim3(nblocks((size_t)N * HW * C)), dim3(256), 0, bh_stream(stream), gy, gx, N, HW, C);
     BH_LAUNCH_CHECK();
     return BH_OK;

@@ -31,7 +31,8 @@ struct TailGeom {
 };
 
 static bool tail_geom(int groups, int rows, int hw, int Ci, int Cm, int Co, TailGeom& g) {
-    if (groups < 1 || rows < 1 || Ci % 4 || Ci > TAIL_MAXCI || Ci * Ci > 256 || Cm % 64 || Cm > 256 || Co < 1 || Co > 4 ||
+    // (hw < 1 first: rows % 0 is a division by zero on the host)
+    if (groups < 1 || rows < 1 || hw < 1 || Ci % 4 || Ci > TAIL_MAXCI || Ci * Ci > 256 || Cm < 64 || Cm % 64 || Cm > 256 || Co < 1 || Co > 4 ||
         rows % hw)
         return false;
     g.groups = groups; g.rows = rows; g.hw = hw; g.Ci = Ci; g.Cm = Cm; g.Co = Co;

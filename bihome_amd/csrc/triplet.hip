@@ -618,6 +618,7 @@ int bh_triplet_l1_fwd(const float* f1, const float* f2, const float* f1w, const 
 int bh_bihome_loss_fwd(const double* numden, const double* H1, const double* H2, int B, float mu, float* loss4,
                        void* stream) {
     if (!numden || !H1 || !H2 || !loss4 || B < 0) return BH_E_BADARG;
+    // (B == 0: one workgroup still runs and writes the sum of nothing - loss4 = {0, 0, 0, 0} - as the one-line forwards do)
     hipLaunchKernelGGL(bihome_loss_kernel, dim3(1), dim3(256), 0, bh_stream(stream), numden, H1, H2, B, mu, loss4);
     BH_LAUNCH_CHECK();
     return BH_OK;

@@ -323,7 +323,7 @@ void bh_warp_tune(int which, int n) {
 // what the warp kernels take: whole 16 x 16 tiles, whole pooling windows of a size the coverage reductions know, and a plane whose byte
 // offsets fit the tap's 32 bits
 static bool warp_shape_ok(int h, int w, int pool) {
-    return !(h % 16) && !(w % 16) && (pool == 1 || pool == 2 || pool == 4 || pool == 8 || pool == 16 || pool == 32) && !(h % pool) && !(w % pool) &&
+    return h > 0 && w > 0 && !(h % 16) && !(w % 16) && (pool == 1 || pool == 2 || pool == 4 || pool == 8 || pool == 16 || pool == 32) && !(h % pool) && !(w % pool) &&
            (long long)h * w < (1ll << 30);
 }
 

@@ -191,7 +191,8 @@ int bh_homography_refine_lm(const float* pf, const uint8_t* mask, int B, int h, 
  * + AvgPool2d(k) (src/heads/PerceptualHead.py:380-382,401,447-459) fused into the same pass.
  * ------------------------------------------------------------------------------------------- */
 /* img[B,C,h,w] (NULL => only the coverage is produced), H64[B,9]; out[B,C,h,w] (may be NULL when
- * img is NULL); cov[B,h/pool,w/pool] (NULL => skipped). h,w multiples of pool; pool in {1,2,4,8,16,32}.
+ * img is NULL); cov[B,h/pool,w/pool] (NULL => skipped). h,w positive multiples of 16 and of pool; pool in {1,2,4,8,16,32}
+ * (else BH_E_UNSUPPORTED, for all three warp entry points; B == 0: BH_OK, nothing launched).
  * flags: BH_F_DETERMINISTIC (matters for pool = 32) */
 int bh_warp_fwd(const float* img, const double* H64, int B, int C, int h, int w, int pool,
                 float* out, float* cov, int flags, void* stream);
@@ -231,7 +232,7 @@ int bh_triplet_l1_fwd(const float* f1, const float* f2, const float* f1w, const 
                       const float* m1w, const float* m2w, const float* m1, const float* m2,
                       int B, int hw, int C, float* M1, float* M2, double* numden, int flags, void* stream);
 /* loss4[4] = { loss, ln1, ln2, ln3 }: ln_k = sum_b num/max(den,1); ln3 = sum_b ||H1 H2 - I||_F^2;
- * loss = ln1 + ln2 + mu*ln3 (PerceptualHead.py:656-665) */
+ * loss = ln1 + ln2 + mu*ln3 (PerceptualHead.py:656-665).  B == 0: the sums of nothing, loss4 = { 0, 0, 0, 0 } (B < 0: BH_E_BADARG) */
 int bh_bihome_loss_fwd(const double* numden, const double* H1, const double* H2, int B, float mu,
                        float* loss4, void* stream);
 /* adjoint of both: g_loss[1] (device scalar) -> g_f1w,g_f2w [B,hw,C] (overwritten), g_m1w,g_m2w
@@ -595,7 +596,8 @@ int bh_conv_bias_grad(const float* gy, float* gbias, const bh_conv_desc* d, void
  * per-chunk partial sums, reduced deterministically). */
 int bh_bn_stats_doubles(int groups, int C);
 int bh_bn_scratch_doubles(int groups, int C);
-/* C: a multiple of 4 (<= 1024, C/4 dividing 256), or 1 (round 3: the one-channel BatchNorms of the Zhang feature extractor /
+/* groups >= 1, rows >= 1 (else BH_E_UNSUPPORTED, as every shape the BatchNorm entry points do not take).
+ * C: a multiple of 4 (4 <= C <= 1024, C/4 dividing 256), or 1 (round 3: the one-channel BatchNorms of the Zhang feature extractor /
  * mask predictor, ContentAware.py:24-26,68-70 - csrc/bn1.hip, same contract; BH_E_UNSUPPORTED with a magnitude record).
  * amax_y (NULL ok; BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |y| (precision 4 consumers).
  * Arithmetic of every BatchNorm apply (this entry point, the (scale, shift) table of bh_bn_fwd_coeffs, bh_bn_maxpool_fwd, bh_bn_join_fwd and
@@ -614,7 +616,11 @@ int bh_bn_fwd(const float* x, const float* gamma, const float* beta, float* runn
  * flags bit2 (only without residual): recompute the ReLU mask from x (y is not read, may be NULL).
  * flags bit4: `scratch` already holds the gradient sums (bh_bn_stats_doubles() layout) accumulated by
  * bh_conv_dgrad_bnreduce - one launch instead of three.
- * amax_gx (NULL ok; BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |gx|. */
+ * amax_gx (NULL ok; BH_AMAX_FLOATS floats, zeroed by the caller) receives the measured max |gx|.
+ * Groups of at most 4 rows (training mode, with or without flags bit4; bh_bn_join_fwd / _bwd / _remask likewise): evaluated in double
+ * from the rows themselves - over two rows the input gradient is the residue eps / (var + eps) of a cancellation that fp32 cannot hold.
+ * The fused forms bh_bn_maxpool_fwd / _bwd and bh_bn_bwd_from_1x1 have no such evaluation: groups of at most 4 rows are
+ * BH_E_UNSUPPORTED there (the unfused calls take them). */
 int bh_bn_bwd(const float* gy, const float* y, const float* x, const float* gamma, const float* beta, const double* stats,
               float* gx, float* gres, float* ggamma, float* gbeta, double* scratch,
               int groups, int rows, int C, float eps, int flags, int use_running,
@@ -674,8 +680,8 @@ int bh_bn_join_bwd_remask(const float* gy, const float* xa, const float* xb, con
 /* Fused tail of the Zeng backbone, `layer8` (src/backbones/Rethinking.py:145-147):
  *   Conv2d(Ci,Cm,1,bias) -> BatchNorm2d(Cm) -> ReLU -> Conv2d(Cm,Co,1,bias), NHWC x[groups*rows,Ci] -> NCHW out[N,Co,h,w]
  * (hw = h*w pixels per image, rows = pixels per group).  The Cm-channel intermediate is never materialised: its batch
- * statistics are derived from the first/second moments of x (a 1x1 conv is linear).  Ci in {8,16}, Cm multiple of
- * 64 (<= 256), Co <= 4.  ws: bh_tail_ws_doubles() doubles (kept for the adjoint); scratch: bh_tail_scratch_floats().
+ * statistics are derived from the first/second moments of x (a 1x1 conv is linear).  Ci in {8,16}, Cm a multiple of 64 (64 <= Cm <= 256),
+ * 1 <= Co <= 4, groups >= 1, hw >= 1 and rows a positive multiple of hw (else BH_E_UNSUPPORTED).  ws: bh_tail_ws_doubles() doubles (kept for the adjoint); scratch: bh_tail_scratch_floats().
  * route, per call (no process state): 0 = the library's choice - round 4: for Ci = 16, Co <= 2, rows % 32 == 0 and
  * hw % 32 == 0 the Ci -> Cm product runs on the matrix pipe in the exact three-bf16-piece arithmetic (tail_fwd_mfma_kernel);
  * bit 0 (BH_TAIL_ROUTE_VALU_FWD) keeps the per-pixel VALU kernel (tests compare the two, tools time them). */
@@ -745,10 +751,11 @@ int bh_synth_blobs(const float* noise, const int* other, const float* patch1, fl
                    float* scratch, int B, int C, int P, double sigma, double porosity, void* stream);
 
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
- * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation). */
+ * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
+ * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */
 int bh_maxpool3s2_fwd(const float* x, float* y, unsigned char* argmax, int N, int Hi, int Wi, int C, void* stream);
 int bh_maxpool3s2_bwd(const unsigned char* argmax, const float* gy, float* gx, int N, int Hi, int Wi, int C, void* stream);
-/* AdaptiveAvgPool2d(1) NHWC -> [N,C], and adjoint */
+/* AdaptiveAvgPool2d(1) NHWC -> [N,C], and adjoint.  BH_E_BADARG: a NULL pointer, N < 0, HW < 1, C < 1; N == 0: BH_OK, nothing launched. */
 int bh_gap_fwd(const float* x, float* y, int N, int HW, int C, void* stream);
 int bh_gap_bwd(const float* gy, float* gx, int N, int HW, int C, void* stream);
 /* out = a + b (elementwise, used to join gradient branches) */

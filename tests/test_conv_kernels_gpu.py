@@ -1178,9 +1178,10 @@ def test_conv3x3_halo_kernel_on_4x4_maps(K, N, Ci, Co, prec, groups):
     b = torch.randn(Co, generator=g).cuda()
     d = K.conv_desc(N, 4, 4, Ci, Co, 3, 1, 1, precision=prec, route=ROUTE_HALO_SMALL)
     dp = K._with_layout(d, K.packed_layout(prec))
-    assert K.conv_variant(dp, "fwd").endswith(",%d,true,false>" % K.SPLIT_PIECES[prec]) and K.conv_variant(dp, "dgrad").endswith(",%d,true,false>" % K.SPLIT_PIECES[prec])
+    tail = ",%d,true,%s>" % (K.SPLIT_PIECES[prec], "true" if prec == 4 else "false")       # (..., NP, MAP4, F16>; precision 4: tests/shape_edges.py)
+    assert K.conv_variant(dp, "fwd").endswith(tail) and K.conv_variant(dp, "dgrad").endswith(tail)
     assert K.packs_3x3(d)
-    pk = K.WeightPacker(split=K.SPLIT_PIECES[prec])
+    pk = K.packer_for_precision(prec)
     pf, pd = pk.get(w)
     pk.refresh()
     ref = F.conv2d(x.double().cpu().permute(0, 3, 1, 2), w.double().cpu(), b.double().cpu(), 1, 1).permute(0, 2, 3, 1)

