@@ -1511,3 +1511,18 @@ def synth_blobs(noise, other, patch1, patch2, mask, sigma, porosity, field=None,
     check(lib.bh_synth_blobs(_p(noise), _p(other), _p(patch1), _p(patch2), _p(mask), _p(field), _p(scratch), B, C, P, float(sigma),
                              float(porosity), _stream()), "bh_synth_blobs")
     return mask, field
+
+
+# ------------------------------------------------------------------------------------------------
+# pair generator: resident uint8 image bank
+# ------------------------------------------------------------------------------------------------
+def bank_gather_u8(bank, idx, out):
+    """Images idx [count] (int32) of a uint8 bank [N,H,W,3] as the float planes out [count,3,H,W], values 0..255 (include/bihome.h
+    bh_bank_gather_u8; an index outside [0, N) is clamped by the kernel).  `out` is the caller's: bihome_amd.bank.ImageBank.gather
+    allocates or reuses it."""
+    _chk(bank, torch.uint8); _chk(idx, torch.int32); _chk(out)
+    if bank.dim() != 4 or bank.shape[3] != 3 or idx.dim() != 1 or tuple(out.shape) != (idx.shape[0], 3, bank.shape[1], bank.shape[2]):
+        raise ValueError("bank_gather_u8: bank [N,H,W,3] uint8, idx [count] int32, out [count,3,H,W] float32")
+    check(lib.bh_bank_gather_u8(_p(bank), _p(idx), idx.shape[0], bank.shape[0], bank.shape[1], bank.shape[2], _p(out), _stream()),
+          "bh_bank_gather_u8")
+    return out

@@ -5,7 +5,9 @@ Same sample distribution as the host generator `bihome_amd.synth.make_pairs` (wh
 (`bh_synth_batch`) over base images that stay resident in HBM, so a training loop never waits for CPU workers.
 Grayscale or RGB patches, the 'all_points' perspective-field target of the supervised configurations, and - with
 `photometric_draws='device'` - the photometric records drawn on the device as well (`photometric_records`): nothing of a
-step's batch is then made on, or copied from, the host."""
+step's batch is then made on, or copied from, the host.  The base images are synthetic textures, or - `bank=` - a dataset: a
+`bihome_amd.bank.ImageBank` of uint8 images resident in HBM, whose batch is staged as float planes for the same kernels, and whose
+images a `BankSampler` picks in the reference's order (`epoch`)."""
 import ctypes
 
 import numpy as np
@@ -64,7 +66,9 @@ def apply_blobs(noise, other, patch1, patch2, sigma, porosity, want_field=False)
 class GpuPairGenerator:
 
     def __init__(self, n_images=16, patch=128, rho=32, seed=42, photometric_max_delta=0, device="cuda", channels=1,
-                 target_gen=None, corners=False, photometric_draws="host", image=False, blob_porosity=None, blobiness=None):
+                 target_gen=None, corners=False, photometric_draws="host", image=False, blob_porosity=None, blobiness=None, bank=None):
+        """bank: a `bihome_amd.bank.ImageBank` - the base images are the bank's (n_images = len(bank), h, w = bank.h, bank.w; the
+        `n_images` argument is not used), staged per batch as float planes by bh_bank_gather_u8.  None: synthetic textures."""
         if channels not in (1, 3):
             raise ValueError("channels must be 1 (grayscale) or 3 (RGB)")
         if target_gen not in (None, "4_points", "all_points"):
@@ -75,11 +79,20 @@ class GpuPairGenerator:
             raise ValueError("image=True produces the grayscale image_1 of the photometric head: channels must be 1")
         self.blobs = synth.check_blob_options(blob_porosity, blobiness)
         self.blob_porosity, self.blobiness = blob_porosity, blobiness
-        rng = np.random.Generator(np.random.PCG64(seed))
-        self.h = max(240, patch + 2 * rho + 48)
-        self.w = max(320, patch + 2 * rho + 128)
-        imgs = np.stack([synth.texture_image(rng, self.h, self.w).transpose(2, 0, 1) for _ in range(n_images)])
-        self.images = torch.tensor(imgs, dtype=torch.float32, device=device).contiguous()      # [NI,3,H,W] 0..255
+        self.bank = bank
+        if bank is not None:
+            if bank.h < patch + 2 * rho or bank.w < patch + 2 * rho:
+                # transforms.py:505-506 would draw the patch position from an empty range
+                raise ValueError("the bank's images are %d x %d: patch + 2 rho = %d does not fit" % (bank.h, bank.w, patch + 2 * rho))
+            self.h, self.w = bank.h, bank.w
+            self.images = None                            # (the batch's images are gathered from the bank in make())
+            self._arange = None
+        else:
+            rng = np.random.Generator(np.random.PCG64(seed))
+            self.h = max(240, patch + 2 * rho + 48)
+            self.w = max(320, patch + 2 * rho + 128)
+            imgs = np.stack([synth.texture_image(rng, self.h, self.w).transpose(2, 0, 1) for _ in range(n_images)])
+            self.images = torch.tensor(imgs, dtype=torch.float32, device=device).contiguous()      # [NI,3,H,W] 0..255
         self.patch, self.rho, self.pmd = patch, rho, photometric_max_delta
         self.channels, self.target_gen, self.corners, self.image = channels, target_gen, corners, image
         self.photometric_draws = photometric_draws
@@ -89,16 +102,40 @@ class GpuPairGenerator:
         self.device = device
 
     @classmethod
-    def from_config(cls, cfg, seed=42, n_images=16, device="cuda", photometric_draws="device"):
-        """The generator whose `next(B)` is the complete batch of the model `cfg` (a `configs.get(name)` dictionary) builds."""
-        return cls(n_images=n_images, seed=seed, device=device, photometric_draws=photometric_draws, **batch_spec(cfg))
+    def from_config(cls, cfg, seed=42, n_images=16, device="cuda", photometric_draws="device", bank=None):
+        """The generator whose `next(B)` is the complete batch of the model `cfg` (a `configs.get(name)` dictionary) builds.
+        bank: the dataset (an ImageBank, e.g. of DATA.DATASET_ROOT's .npy files) instead of synthetic textures."""
+        return cls(n_images=n_images, seed=seed, device=device, photometric_draws=photometric_draws, bank=bank, **batch_spec(cfg))
 
-    def draw(self, B):
+    @property
+    def n_images(self):
+        return len(self.bank) if self.bank is not None else self.images.shape[0]
+
+    def _given_idx(self, idx, B):
+        """A caller's image indices as the int32 [B] device tensor the kernels take.  Host values (a list, a numpy array, a CPU tensor) are
+        range-checked here; a device tensor is not read back (with a bank, an index outside it is clamped by the gather)."""
+        if isinstance(idx, torch.Tensor) and idx.device.type != "cpu":
+            if idx.shape != (B,) or idx.dtype.is_floating_point:
+                raise ValueError("idx must hold %d integers, got %s %s" % (B, tuple(idx.shape), idx.dtype))
+            return idx.to(device=self.device, dtype=torch.int32).contiguous()
+        a = np.asarray(idx)
+        if a.shape != (B,) or a.dtype.kind not in "iu":
+            raise ValueError("idx must hold %d integers, got %s %s" % (B, a.shape, a.dtype))
+        if B and (int(a.min()) < 0 or int(a.max()) >= self.n_images):
+            raise ValueError("idx must lie in [0, %d): got %d .. %d" % (self.n_images, a.min(), a.max()))
+        return torch.tensor(a.astype(np.int32), dtype=torch.int32, device=self.device)
+
+    def draw(self, B, idx=None):
         """Random sample parameters exactly as transforms.py:505-506,538 draw them (uniform integer position with a
         rho margin, integer corner offsets in [-rho, rho-1]).  With blobs on, a fifth element (noise [B,P,P], other [B] int32) drawn
-        AFTER everything else: a seed yields the same idx / origin / delta / photo with and without blobs."""
+        AFTER everything else: a seed yields the same idx / origin / delta / photo with and without blobs.
+        idx: the image of every sample ([B] integers, host or device - a sampler's batch) instead of the generator's own index draw,
+        which is still made and dropped: a seed yields the same origin / delta / photo / blobs with and without idx."""
         g, dev, half = self.gen, self.device, self.patch // 2
-        idx = torch.randint(0, self.images.shape[0], (B,), generator=g, device=dev, dtype=torch.int32)
+        given = self._given_idx(idx, B) if idx is not None else None            # (refused before anything is drawn or launched)
+        idx = torch.randint(0, self.n_images, (B,), generator=g, device=dev, dtype=torch.int32)
+        if given is not None:
+            idx = given
         px = torch.randint(self.rho + half, self.w - self.rho - half + 1, (B,), generator=g, device=dev)
         py = torch.randint(self.rho + half, self.h - self.rho - half + 1, (B,), generator=g, device=dev)
         origin = torch.stack([px - half, py - half], 1).to(torch.float32).contiguous()
@@ -139,8 +176,15 @@ class GpuPairGenerator:
         p2 = torch.empty_like(p1)
         field = torch.empty(B, 2, P, P, dtype=torch.float32, device=self.device) if self.target_gen == "all_points" else None
         pv = ctypes.c_void_p
-        check(lib.bh_synth_batch(pv(self.images.data_ptr()), pv(idx.data_ptr()), pv(origin.data_ptr()), pv(H64.data_ptr()),
-                                 pv(photo.data_ptr()) if photo is not None else None, B, self.images.shape[0], self.h,
+        images = self.images
+        if self.bank is not None:
+            # the batch's images leave the uint8 bank as the float planes the kernels read: image b of the staged batch is sample b's
+            images = self.bank.gather(idx)
+            if self._arange is None or self._arange.shape[0] != B:
+                self._arange = torch.arange(B, dtype=torch.int32, device=self.device)
+            idx = self._arange
+        check(lib.bh_synth_batch(pv(images.data_ptr()), pv(idx.data_ptr()), pv(origin.data_ptr()), pv(H64.data_ptr()),
+                                 pv(photo.data_ptr()) if photo is not None else None, B, images.shape[0], self.h,
                                  self.w, P, C, 0.443, 0.129, pv(p1.data_ptr()), pv(p2.data_ptr()),
                                  pv(field.data_ptr()) if field is not None else None,
                                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_synth_batch")
@@ -161,11 +205,17 @@ class GpuPairGenerator:
             out["corners"] = (origin[:, None, :] + sq).contiguous()
         if image:
             im = torch.empty(B, 1, self.h, self.w, dtype=torch.float32, device=self.device)
-            check(lib.bh_synth_image(pv(self.images.data_ptr()), pv(idx.data_ptr()), pv(photo.data_ptr()) if photo is not None else None,
-                                     B, self.images.shape[0], self.h, self.w, 0.443, 0.129, pv(im.data_ptr()),
+            check(lib.bh_synth_image(pv(images.data_ptr()), pv(idx.data_ptr()), pv(photo.data_ptr()) if photo is not None else None,
+                                     B, images.shape[0], self.h, self.w, 0.443, 0.129, pv(im.data_ptr()),
                                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "bh_synth_image")
             out["image_1"] = im
         return out
 
-    def next(self, B, image=None):
-        return self.make(*self.draw(B), image=image)        # (four or five draws: the fifth lands on `blobs`)
+    def next(self, B, idx=None, image=None):
+        return self.make(*self.draw(B, idx), image=image)        # (four or five draws: the fifth lands on `blobs`)
+
+    def epoch(self, sampler):
+        """One epoch of `sampler` (a `bihome_amd.bank.BankSampler`, or any iterable of index arrays): the batch of each of its index
+        batches, in its order."""
+        for batch in sampler:
+            yield self.next(len(batch), idx=batch)

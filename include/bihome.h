@@ -750,6 +750,19 @@ size_t bh_synth_blobs_scratch_floats(int B, int P);
 int bh_synth_blobs(const float* noise, const int* other, const float* patch1, float* patch2, float* mask, float* field,
                    float* scratch, int B, int C, int P, double sigma, double porosity, void* stream);
 
+/* Resident image bank of the pair generator: Dataset.load_image (src/data/coco/dataset.py:95-103: one np.load of a uint8 [H,W,3] RGB
+ * array per sample, written by preprocess_offline.py:22) as a gather on the device.  bank[n_images,Hs,Ws,3] uint8, interleaved RGB - the
+ * .npy layout, all images of one split in one tensor (82,783 x 240 x 320 x 3 = 19 GB for COCO train2014); img_idx[count] int32;
+ * out[count,3,Hs,Ws] float planar, values 0..255: out[b,c,y,x] = (float)bank[img_idx[b],y,x,c] - what bh_synth_batch / bh_synth_image
+ * take as `images` (with n_images = count and img_idx = 0..count-1).  Every element of out is overwritten and nothing outside it is
+ * touched; no atomics: two calls on the same inputs are bitwise equal.  Every offset is 64-bit (the bank may be far larger than 2^31
+ * bytes).  An index outside [0, n_images) is CLAMPED into that range in the kernel (a negative one reads image 0, one >= n_images the
+ * last image): nothing outside the bank is ever read.  Hs*Ws % 4 == 0 (every Ws % 4 == 0) with bank on a 4-byte and out on a 16-byte
+ * boundary takes the vector path (12-byte loads, float4 stores per plane), anything else a scalar path with the same results.
+ * BH_E_BADARG: a NULL pointer, count < 0, n_images < 1, Hs < 1, Ws < 1; count == 0: BH_OK, nothing launched;
+ * BH_E_UNSUPPORTED: more than 2^39 pixels per image.  Refusals return before any launch. */
+int bh_bank_gather_u8(const unsigned char* bank, const int* img_idx, int count, int n_images, int Hs, int Ws, float* out, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */

@@ -11,7 +11,12 @@ case:
                        worktree with `make -C bihome_amd/csrc`) against this build's, on the same inputs, launches only, the two
                        alternating round by round in this one process, and whether the two outputs are the same bits
 
+    bank               --bank (these rows only): zeng-bihome-pds' and nguyen-orig's batch from a uint8 240 x 320 ImageBank against the
+                       float layout over the same pixels, alternating in this one process; bh_bank_gather_u8 alone, its GB/s (bytes
+                       read + written) and those of a device copy that moves the same bytes
+
     python tools/datagen_bench.py [--other-lib ../parent/bihome_amd/libbihome_hip.so]
+    python tools/datagen_bench.py --bank [--bank-images 512]
 
 Device cases: `--warmup` batches, then `--rounds` rounds of `--reps` batches, each round between two device events with one synchronise
 at its end (so a round's time is the device's, host gaps included: what a training loop that waits for the batch sees); median, min and
@@ -88,8 +93,44 @@ def kernel_ab(other_path, B, reps, rounds, warmup):
     return res
 
 
+def bank_rows(n_images, B, reps, rounds, warmup, kernel_reps):
+    """--bank: `next(B)` of a generator on a uint8 240 x 320 ImageBank against a generator of the float layout over the same pixel values
+    (the two alternating round by round in this process), for zeng-bihome-pds (gray 128 x 128) and nguyen-orig (plus image_1); then
+    the gather kernel alone against a device copy that moves the same number of bytes (read + written)."""
+    from bihome_amd import configs
+    from bihome_amd.bank import ImageBank
+    dev = torch.cuda.get_device_name(0)
+    bank = ImageBank(torch.randint(0, 256, (n_images, 240, 320, 3), dtype=torch.uint8, device="cuda"))
+    planes = bank.data.permute(0, 3, 1, 2).float().contiguous()
+    for name in ("zeng-bihome-pds", "nguyen-orig"):
+        cfg = configs.get(name)
+        on_bank = GpuPairGenerator.from_config(cfg, seed=7, bank=bank)
+        on_float = GpuPairGenerator.from_config(cfg, seed=7, n_images=1)
+        on_float.images, on_float.h, on_float.w = planes, bank.h, bank.w
+        a, b = on_bank.next(B), on_float.next(B)
+        same = all(torch.equal(a[k], b[k]) for k in a)
+        r = device_rounds({"bank": lambda: on_bank.next(B), "float": lambda: on_float.next(B)}, reps, rounds, warmup)
+        print(json.dumps({"tool": "datagen_bench", "case": "bank: " + name, "batch": B, "device": dev, "reps": reps, "rounds": rounds,
+                          "bank_images": n_images, "bank_bytes": bank.nbytes, "float_layout_bytes": planes.numel() * 4,
+                          "uint8_bank": r["bank"], "float_layout": r["float"], "same_bits": bool(same),
+                          "bank_minus_float_median_us": round(r["bank"]["median_us"] - r["float"]["median_us"], 2)}), flush=True)
+    idx = torch.randint(0, n_images, (B,), dtype=torch.int32, device="cuda")
+    out = torch.empty(B, 3, bank.h, bank.w, device="cuda")
+    moved = B * bank.h * bank.w * 3 * (1 + 4)                            # bytes read from the bank + bytes written as floats
+    src = torch.empty(moved // 2, dtype=torch.uint8, device="cuda")
+    dst = torch.empty_like(src)
+    r = device_rounds({"gather": lambda: bank.gather(idx, out), "copy": lambda: dst.copy_(src)}, kernel_reps, rounds, warmup)
+    gbs = {k: round(moved / (r[k]["median_us"] * 1e-6) / 1e9, 1) for k in r}
+    print(json.dumps({"tool": "datagen_bench", "case": "bank: bh_bank_gather_u8 alone", "batch": B, "device": dev, "reps": kernel_reps,
+                      "rounds": rounds, "bytes_moved": moved, "gather": r["gather"], "gather_GBps": gbs["gather"],
+                      "device_copy_same_bytes": r["copy"], "copy_GBps": gbs["copy"],
+                      "gather_over_copy_bandwidth": round(gbs["gather"] / gbs["copy"], 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--bank", action="store_true", help="only the image-bank rows: uint8 bank against the float layout, and the gather kernel")
+    ap.add_argument("--bank-images", type=int, default=512)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=20)
@@ -98,6 +139,9 @@ def main():
     ap.add_argument("--other-lib", default=None, help="another build of libbihome_hip.so for the kernel A/B case")
     ap.add_argument("--kernel-reps", type=int, default=2000)
     args = ap.parse_args()
+    if args.bank:
+        bank_rows(args.bank_images, 64, args.reps, args.rounds, args.warmup, args.kernel_reps)
+        return
     dev = torch.cuda.get_device_name(0)
     cases = [
         ("gray", 64, dict(), dict()),
