@@ -130,6 +130,7 @@ SIGNATURES = {
     "bh_synth_image": [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P, P],
     "bh_synth_blobs": [P] * 7 + [c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, P],
     "bh_bank_gather_u8": [P, P, c_int, c_int, c_int, c_int, P, P],
+    "bh_bank_ingest_u8": [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_gap_fwd": [P, P, c_int, c_int, c_int, P],

@@ -1526,3 +1526,35 @@ def bank_gather_u8(bank, idx, out):
     check(lib.bh_bank_gather_u8(_p(bank), _p(idx), idx.shape[0], bank.shape[0], bank.shape[1], bank.shape[2], _p(out), _stream()),
           "bh_bank_gather_u8")
     return out
+
+
+def bank_ingest_u8(src, src_off, src_hw, bank, first=0):
+    """Rescale + CenterCrop of n raw-size images into slots first .. first+n-1 of a uint8 bank [N,H,W,3], one launch (include/bihome.h
+    bh_bank_ingest_u8).  src: uint8 [bytes] on the device, the images packed as interleaved RGB; src_off [n] int64: the byte offset of
+    each; src_hw [n,2] int32: its height and width.  src_off / src_hw on the HOST (numpy arrays or CPU tensors) are checked here - h, w
+    >= 1, every image inside src, a resized size that fits an int: ValueError - and then uploaded.  Device tensors are taken as they are
+    (nothing is copied: a captured launch), and what the kernel does with a bad entry is the header's: h < 1 or w < 1 leaves the slot
+    untouched, an offset outside src is read."""
+    _chk(src, torch.uint8); _chk(bank, torch.uint8)
+    off, hw = torch.as_tensor(src_off), torch.as_tensor(src_hw)
+    if src.dim() != 1 or bank.dim() != 4 or bank.shape[3] != 3 or off.dim() != 1 or tuple(hw.shape) != (off.shape[0], 2) or \
+            off.dtype != torch.int64 or hw.dtype != torch.int32 or off.is_cuda != hw.is_cuda:
+        raise ValueError("bank_ingest_u8: src [bytes] uint8, src_off [n] int64, src_hw [n,2] int32 (both on the host or both on the "
+                         "device), bank [N,H,W,3] uint8")
+    n, (N, H, W) = off.shape[0], bank.shape[:3]
+    if first < 0 or first + n > N:
+        raise ValueError("bank_ingest_u8: slots %d .. %d of a bank of %d" % (first, first + n - 1, N))
+    if n == 0:
+        return bank
+    if not off.is_cuda:
+        for k, (o, (h, w)) in enumerate(zip(off.tolist(), hw.tolist())):
+            if h < 1 or w < 1:
+                raise ValueError("bank_ingest_u8: image %d is %d x %d, an image has at least one pixel" % (k, h, w))
+            if o < 0 or o + h * w * 3 > src.numel():
+                raise ValueError("bank_ingest_u8: image %d (%d x %d at byte %d) does not lie inside src (%d bytes)" % (k, h, w, o, src.numel()))
+            if H * w >= h << 31 or W * h >= w << 31:
+                raise ValueError("bank_ingest_u8: image %d (%d x %d) rescaled to %d x %d does not fit an int" % (k, h, w, H, W))
+        off, hw = off.contiguous().to(bank.device), hw.contiguous().to(bank.device)
+    _chk(off, torch.int64); _chk(hw, torch.int32)
+    check(lib.bh_bank_ingest_u8(_p(src), _p(off), _p(hw), n, _p(bank), N, first, H, W, _stream()), "bh_bank_ingest_u8")
+    return bank

@@ -763,6 +763,28 @@ int bh_synth_blobs(const float* noise, const int* other, const float* patch1, fl
  * BH_E_UNSUPPORTED: more than 2^39 pixels per image.  Refusals return before any launch. */
 int bh_bank_gather_u8(const unsigned char* bank, const int* img_idx, int count, int n_images, int Hs, int Ws, float* out, void* stream);
 
+/* Filling the bank from raw-size images: Rescale((W, H)) then CenterCrop((W, H)) (src/data/transforms.py:24-46 and :103-122, which
+ * preprocess_offline.py runs through cv2.resize one image at a time on the host) for `count` images of DIFFERENT sizes in one launch.
+ * src: one packed device buffer of interleaved RGB uint8 images; src_off[count] int64: the byte offset of each image in src;
+ * src_hw[count,2] int32: its height and width; bank[n_slots,H,W,3] uint8: image b is written to slot first + b.  Every byte of slots
+ * first .. first+count-1 is written exactly once and nothing outside them is touched; no atomics, no scratch: two calls on the same
+ * inputs are bitwise equal.  Every byte offset is 64-bit, on the source and on the bank side.  Per image, in double: r = h / w; if
+ * r < H / W then (nw, nh) = (round(H / r), H) else (W, round(W r)), round half to even as numpy's; top = (nh - H) / 2,
+ * left = (nw - W) / 2; bank pixel (y, x) = resized pixel (y + top, x + left) - the resized image itself is never stored.  The resize is
+ * cv2.resize's default, INTER_LINEAR on 8-bit data, AS RECALLED (not read from OpenCV's source, and not compared with cv2):
+ * w == 2 nw and h == 2 nh: (s00 + s01 + s10 + s11 + 2) >> 2 over the 2x2 block; (nh, nw) == (h, w): a copy; otherwise two taps per
+ * axis at f = (float)((d + 0.5) (n / n_new) - 0.5), s = floor(f), f -= s, both clamped at the borders with f = 0, 11-bit coefficients
+ * rint((1 - f) 2048), rint(f 2048), rows S = s[sx] a0 + s[sx+1] a1 in int32, out = (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2.
+ * bihome_amd.bank.rescale_center_crop_host is the same arithmetic in numpy, and the kernel equals it bit for bit.
+ * src_hw is device memory, so this function cannot see it: an image with h < 1 or w < 1 (or whose resized size does not fit an int)
+ * leaves its slot UNTOUCHED, and an offset or size that points outside src is the caller's to exclude (bihome_amd.kernels.bank_ingest_u8
+ * checks both on the host before it uploads them).  W % 4 == 0 with bank on a 4-byte boundary takes dword stores, anything else byte
+ * stores with the same results.
+ * BH_E_BADARG: a NULL pointer, count < 0, n_slots < 1, H < 1, W < 1, first < 0, first + count > n_slots; count == 0: BH_OK, nothing
+ * launched; BH_E_UNSUPPORTED: H * W > 2^31 - 1 pixels per bank image.  Refusals return before any launch. */
+int bh_bank_ingest_u8(const unsigned char* src, const int64_t* src_off, const int* src_hw, int count, unsigned char* bank, int n_slots,
+                      int first, int H, int W, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */

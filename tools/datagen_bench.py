@@ -15,8 +15,14 @@ case:
                        float layout over the same pixels, alternating in this one process; bh_bank_gather_u8 alone, its GB/s (bytes
                        read + written) and those of a device copy that moves the same bytes
 
+    ingest             --ingest (these rows only): bh_bank_ingest_u8 alone (Rescale + CenterCrop of raw-size images into 240 x 320 bank
+                       slots, tables already on the device), 64 images per launch: 480 x 640 (the exact-halving path), 427 x 640 (the
+                       fixed-point path with a crop) and a mixed batch; its GB/s (source bytes inside the crop window + bank bytes
+                       written) and those of a device copy that moves the same bytes
+
     python tools/datagen_bench.py [--other-lib ../parent/bihome_amd/libbihome_hip.so]
     python tools/datagen_bench.py --bank [--bank-images 512]
+    python tools/datagen_bench.py --ingest
 
 Device cases: `--warmup` batches, then `--rounds` rounds of `--reps` batches, each round between two device events with one synchronise
 at its end (so a round's time is the device's, host gaps included: what a training loop that waits for the batch sees); median, min and
@@ -127,10 +133,41 @@ def bank_rows(n_images, B, reps, rounds, warmup, kernel_reps):
                       "gather_over_copy_bandwidth": round(gbs["gather"] / gbs["copy"], 3)}), flush=True)
 
 
+def ingest_rows(B, rounds, warmup, kernel_reps):
+    """--ingest: one bh_bank_ingest_u8 launch of B raw-size images into a [B,240,320,3] bank against a device copy that moves the same
+    number of bytes (read + written).  Bytes read: of every source image the part inside the crop window, h w 3 (H W) / (nh nw)."""
+    import numpy as np
+    from bihome_amd.bank import rescale_size
+    dev = torch.cuda.get_device_name(0)
+    W, H = 320, 240
+    cases = [("480x640 (exact halving)", [(480, 640)]), ("427x640 (fixed point, crop in x)", [(427, 640)]),
+             ("mixed", [(480, 640), (427, 640), (640, 480), (375, 500), (240, 320), (612, 612), (333, 500), (480, 360)])]
+    for name, sizes in cases:
+        hw = np.asarray([sizes[k % len(sizes)] for k in range(B)], np.int32)
+        nbytes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
+        off = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+        src = torch.randint(0, 256, (int(nbytes.sum()),), dtype=torch.uint8, device="cuda")
+        read = 0.0
+        for h, w in hw.tolist():
+            nh, nw, _, _ = rescale_size(h, w, (W, H))
+            read += h * w * 3 * (H * W) / (nh * nw)
+        moved = int(read) + B * H * W * 3
+        bank = torch.empty(B, H, W, 3, dtype=torch.uint8, device="cuda")
+        off_d, hw_d = torch.from_numpy(off).cuda(), torch.from_numpy(hw).cuda()
+        a, b = torch.empty(moved // 2, dtype=torch.uint8, device="cuda"), torch.empty(moved // 2, dtype=torch.uint8, device="cuda")
+        r = device_rounds({"ingest": lambda: K.bank_ingest_u8(src, off_d, hw_d, bank), "copy": lambda: b.copy_(a)}, kernel_reps, rounds, warmup)
+        gbs = {k: round(moved / (r[k]["median_us"] * 1e-6) / 1e9, 1) for k in r}
+        print(json.dumps({"tool": "datagen_bench", "case": "ingest: " + name, "batch": B, "device": dev, "reps": kernel_reps, "rounds": rounds,
+                          "source_bytes": int(nbytes.sum()), "bytes_moved": moved, "ingest": r["ingest"], "ingest_GBps": gbs["ingest"],
+                          "device_copy_same_bytes": r["copy"], "copy_GBps": gbs["copy"],
+                          "ingest_over_copy_bandwidth": round(gbs["ingest"] / gbs["copy"], 3)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--bank", action="store_true", help="only the image-bank rows: uint8 bank against the float layout, and the gather kernel")
     ap.add_argument("--bank-images", type=int, default=512)
+    ap.add_argument("--ingest", action="store_true", help="only the ingest rows: bh_bank_ingest_u8 (Rescale + CenterCrop into bank slots) against a device copy")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=20)
@@ -139,6 +176,9 @@ def main():
     ap.add_argument("--other-lib", default=None, help="another build of libbihome_hip.so for the kernel A/B case")
     ap.add_argument("--kernel-reps", type=int, default=2000)
     args = ap.parse_args()
+    if args.ingest:
+        ingest_rows(64, args.rounds, args.warmup, args.kernel_reps)
+        return
     if args.bank:
         bank_rows(args.bank_images, 64, args.reps, args.rounds, args.warmup, args.kernel_reps)
         return
