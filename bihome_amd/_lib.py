@@ -129,6 +129,7 @@ SIGNATURES = {
     "bh_synth_batch": [P] * 5 + [c_int] * 6 + [c_float, c_float, P, P, P, P],
     "bh_synth_image": [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P, P],
     "bh_synth_blobs": [P] * 7 + [c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, P],
+    "bh_synth_draw": [ctypes.c_size_t, ctypes.c_size_t] + [c_int] * 6 + [c_float] + [P] * 7,
     "bh_bank_gather_u8": [P, P, c_int, c_int, c_int, c_int, P, P],
     "bh_bank_ingest_u8": [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],

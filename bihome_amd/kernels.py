@@ -1513,6 +1513,24 @@ def synth_blobs(noise, other, patch1, patch2, mask, sigma, porosity, field=None,
     return mask, field
 
 
+def synth_draw(seed, first, n_images, h, w, patch, rho, max_delta, img_idx, origin, delta, photo=None, noise=None, other=None):
+    """Counter-based draws (include/bihome.h bh_synth_draw): the parameters of samples first .. first + B - 1 of the stream of `seed`,
+    one launch (two with blob noise).  Outputs are the caller's: img_idx [B] int32, origin [B,2], delta [B,4,2]; photo [B,2,6] (or
+    [B,12]) or None; noise [B,P,P] and other [B] int32, both or neither.  seed and first are taken modulo 2^64."""
+    _chk(img_idx, torch.int32); _chk(origin); _chk(delta); _chk(photo); _chk(noise); _chk(other, torch.int32)
+    B = img_idx.shape[0]
+    if img_idx.dim() != 1 or tuple(origin.shape) != (B, 2) or tuple(delta.shape) != (B, 4, 2) or \
+            (photo is not None and photo.numel() != 12 * B) or (noise is not None and tuple(noise.shape) != (B, patch, patch)) or \
+            (other is not None and tuple(other.shape) != (B,)):
+        raise ValueError("synth_draw: img_idx [B] int32, origin [B,2], delta [B,4,2], photo [B,2,6], noise [B,P,P], other [B] int32")
+    if (noise is None) != (other is None):
+        raise ValueError("synth_draw: noise and other are given together (or neither)")
+    m64 = (1 << 64) - 1
+    check(lib.bh_synth_draw(int(seed) & m64, int(first) & m64, B, int(n_images), int(h), int(w), int(patch), int(rho), float(max_delta),
+                            _p(img_idx), _p(origin), _p(delta), _p(photo), _p(noise), _p(other), _stream()), "bh_synth_draw")
+    return img_idx, origin, delta, photo, noise, other
+
+
 # ------------------------------------------------------------------------------------------------
 # pair generator: resident uint8 image bank
 # ------------------------------------------------------------------------------------------------

@@ -287,6 +287,98 @@ def apply_blobs(p1, p2, mask, other):
     return np.where(mask[:, None], p1[other], p2)
 
 
+# ---- counter-based draws: sample n of seed s is a pure function of (s, n) (include/bihome.h bh_synth_draw) ----
+#
+# The stream.  Word k (k = 0, 1, ...) of sample n for purpose p is element k % 4 of
+#     philox4x64_10(counter = (k // 4 + 1, n, 0, 0), key = (seed, p)),
+# which is np.random.Philox(key=[seed, p], counter=[0, n, 0, 0]).random_raw(K)[k]: numpy advances its counter before its first block,
+# hence the + 1.  Maps of a word: an integer in [0, r), r < 2**31, is (word * r) >> 64; a double uniform is (word >> 11) * 2**-53
+# (Generator.random()); a float32 noise value is (word >> 40) * 2**-24.
+# Purpose 0, the sample's parameters: word 0 image index int(n_images); words 1, 2 the patch centre px = rho + P//2 +
+# int(w - 2 rho - 2 (P//2) + 1), py likewise with h, origin = (px - P//2, py - P//2); word 3 the blob source r = int(B - 1),
+# other = r + (r >= b) - the only quantity that depends on the batch; words 4..11 delta[4,2] row-major, -rho + int(2 rho); words 12..22
+# the 11 uniforms of image 1's photometric record in the column order of synth_gpu.photometric_records, words 24..34 those of image 2
+# (23 and 35 are unused).  Purpose 1, blob noise: noise[y, x] is the float32 map of word y * P + x.
+
+_MASK64 = (1 << 64) - 1
+PHILOX_M = (0xD2E7470EE14C6C93, 0xCA5A826395121157)          # multipliers on counter[0], counter[2]
+PHILOX_W = (0x9E3779B97F4A7C15, 0xBB67AE8584CAA73B)          # key increments between rounds
+DRAW_PARAMS, DRAW_NOISE = 0, 1                                # the purposes
+
+
+def philox4x64_10(counter, key):
+    """The standard 10-round Philox function on 64-bit words (Salmon et al., SC'11), in Python integers: the definition the device's
+    __umul64hi form and np.random.Philox are both checked against.  counter: 4 words, key: 2 words; returns 4 words."""
+    c0, c1, c2, c3 = (int(c) & _MASK64 for c in counter)
+    k0, k1 = (int(k) & _MASK64 for k in key)
+    for _ in range(10):
+        p0, p1 = PHILOX_M[0] * c0, PHILOX_M[1] * c2
+        c0, c1, c2, c3 = (p1 >> 64) ^ c1 ^ k0, p1 & _MASK64, (p0 >> 64) ^ c3 ^ k1, p0 & _MASK64
+        k0, k1 = (k0 + PHILOX_W[0]) & _MASK64, (k1 + PHILOX_W[1]) & _MASK64
+    return c0, c1, c2, c3
+
+
+def counter_words(seed, purpose, n, count):
+    """Words 0 .. count-1 of sample n for a purpose, uint64 [count] (numpy's Philox)."""
+    bg = np.random.Philox(key=np.array([int(seed) & _MASK64, int(purpose)], np.uint64),
+                          counter=np.array([0, int(n) & _MASK64, 0, 0], np.uint64))
+    return bg.random_raw(int(count))
+
+
+def counter_photometric_records(u, max_delta):
+    """[..., 11] double uniforms -> [..., 6] float32 records: synth_gpu.photometric_records' formulas in numpy doubles, rounded once."""
+    u = np.asarray(u, np.float64)
+    on = u >= 0.5
+    md = float(max_delta)
+    lower, upper = 1.0 - md / 32 * 0.5, 1.0 + md / 32 * 0.5
+    one, zero = np.ones(u.shape[:-1]), np.zeros(u.shape[:-1])
+    br = np.where(on[..., 0], -md + 2 * md * u[..., 1], zero)
+    first = on[..., 2]
+    con = np.where(on[..., 3], lower + (upper - lower) * u[..., 4], one)
+    c1, c2 = np.where(first, con, one), np.where(first, one, con)
+    sat = np.where(on[..., 5], lower + (upper - lower) * u[..., 6], one)
+    hue = np.where(on[..., 7], -md / 2 + md * u[..., 8], zero)
+    perm = np.where(on[..., 9], np.minimum(np.floor(6 * u[..., 10]), 5.0), zero) if md > 0 else zero
+    return np.stack([br, c1, sat, hue, c2, perm], -1).astype(np.float32)
+
+
+def counter_draws(seed, first, B, n_images, h, w, patch, rho, max_delta=0, blobs=False):
+    """The numpy oracle of bh_synth_draw (needs no GPU): samples first .. first + B - 1 of the stream of `seed`.  Returns a dict of the
+    arrays the entry point writes, with its dtypes: img_idx [B] int32, origin [B,2], delta [B,4,2], photo [B,2,6] float32, and with
+    blobs noise [B,P,P] float32 and other [B] int32.  The integer maps are evaluated in Python integers.  max_delta is taken as the
+    float32 the C entry point receives."""
+    B, n_images, h, w, P, rho = int(B), int(n_images), int(h), int(w), int(patch), int(rho)
+    if B < 0 or n_images < 1 or rho < 1 or P < 1 or h < P + 2 * rho or w < P + 2 * rho:
+        raise ValueError("counter_draws: B >= 0, n_images >= 1, rho >= 1, patch >= 1 and an image of at least patch + 2 rho")
+    if blobs and 0 < B < 2:
+        raise ValueError("blobs paste content of ANOTHER sample of the batch: the batch needs at least 2 samples")
+    half = P // 2
+    xr, yr = w - 2 * rho - 2 * half + 1, h - 2 * rho - 2 * half + 1
+    md = float(np.float32(max_delta))
+    out = {"img_idx": np.zeros(B, np.int32), "origin": np.zeros((B, 2), np.float32), "delta": np.zeros((B, 4, 2), np.float32),
+           "photo": np.zeros((B, 2, 6), np.float32)}
+    if blobs:
+        out["noise"], out["other"] = np.zeros((B, P, P), np.float32), np.zeros(B, np.int32)
+
+    def integer(word, r):
+        return (int(word) * r) >> 64
+
+    for b in range(B):
+        n = (int(first) + b) & _MASK64
+        wd = counter_words(seed, DRAW_PARAMS, n, 36)
+        out["img_idx"][b] = integer(wd[0], n_images)
+        out["origin"][b] = (rho + integer(wd[1], xr), rho + integer(wd[2], yr))            # (px - P//2, py - P//2)
+        out["delta"][b] = np.array([-rho + integer(wd[4 + i], 2 * rho) for i in range(8)], np.float32).reshape(4, 2)
+        u = (wd >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+        out["photo"][b] = counter_photometric_records(np.stack([u[12:23], u[24:35]]), md)
+        if blobs:
+            r = integer(wd[3], B - 1)
+            out["other"][b] = r + (r >= b)
+            nz = counter_words(seed, DRAW_NOISE, n, P * P)
+            out["noise"][b] = ((nz >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)).reshape(P, P)
+    return out
+
+
 def make_pairs(batch, patch=128, rho=32, seed=42, photometric_max_delta=0, channels=1, pool=4, target=False, image=False,
                blob_porosity=None, blobiness=None):
     """Return dict of float32 arrays: patch_1, patch_2 [B,C,P,P] (standardised), delta [B,4,2]

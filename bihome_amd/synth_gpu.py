@@ -66,9 +66,20 @@ def apply_blobs(noise, other, patch1, patch2, sigma, porosity, want_field=False)
 class GpuPairGenerator:
 
     def __init__(self, n_images=16, patch=128, rho=32, seed=42, photometric_max_delta=0, device="cuda", channels=1,
-                 target_gen=None, corners=False, photometric_draws="host", image=False, blob_porosity=None, blobiness=None, bank=None):
+                 target_gen=None, corners=False, photometric_draws="host", image=False, blob_porosity=None, blobiness=None, bank=None,
+                 draws="torch", rank=0, world=1):
         """bank: a `bihome_amd.bank.ImageBank` - the base images are the bank's (n_images = len(bank), h, w = bank.h, bank.w; the
-        `n_images` argument is not used), staged per batch as float planes by bh_bank_gather_u8.  None: synthetic textures."""
+        `n_images` argument is not used), staged per batch as float planes by bh_bank_gather_u8.  None: synthetic textures.
+        draws: 'torch' - every random quantity comes from one torch.Generator, in sequence (the stream depends on the batch size of
+        every earlier call); 'counter' - sample n of `seed` gets its parameters as a pure function of (seed, n) from one bh_synth_draw
+        launch (`synth.counter_draws` is the definition), so a run can be resumed onto its stream (`state_dict`) and `world` ranks of B
+        samples see exactly the samples of one rank of world * B: rank r's call takes samples position + r B .. position + (r + 1) B - 1,
+        and every call moves `position` on by world * B.  photometric_draws is not consulted in counter mode."""
+        if draws not in ("torch", "counter"):
+            raise ValueError("draws must be 'torch' or 'counter', got %r" % (draws,))
+        if int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError("rank must lie in [0, world): got rank %r, world %r" % (rank, world))
+        self.draws, self.rank, self.world, self.seed, self.position = draws, int(rank), int(world), int(seed), 0
         if channels not in (1, 3):
             raise ValueError("channels must be 1 (grayscale) or 3 (RGB)")
         if target_gen not in (None, "4_points", "all_points"):
@@ -102,10 +113,11 @@ class GpuPairGenerator:
         self.device = device
 
     @classmethod
-    def from_config(cls, cfg, seed=42, n_images=16, device="cuda", photometric_draws="device", bank=None):
+    def from_config(cls, cfg, seed=42, n_images=16, device="cuda", photometric_draws="device", bank=None, draws="torch", rank=0, world=1):
         """The generator whose `next(B)` is the complete batch of the model `cfg` (a `configs.get(name)` dictionary) builds.
         bank: the dataset (an ImageBank, e.g. of DATA.DATASET_ROOT's .npy files) instead of synthetic textures."""
-        return cls(n_images=n_images, seed=seed, device=device, photometric_draws=photometric_draws, bank=bank, **batch_spec(cfg))
+        return cls(n_images=n_images, seed=seed, device=device, photometric_draws=photometric_draws, bank=bank, draws=draws, rank=rank,
+                   world=world, **batch_spec(cfg))
 
     @property
     def n_images(self):
@@ -125,14 +137,61 @@ class GpuPairGenerator:
             raise ValueError("idx must lie in [0, %d): got %d .. %d" % (self.n_images, a.min(), a.max()))
         return torch.tensor(a.astype(np.int32), dtype=torch.int32, device=self.device)
 
-    def draw(self, B, idx=None):
+    def state_dict(self):
+        """What `load_state_dict` needs to continue this generator's sample stream, to be saved next to a checkpoint.  Counter mode:
+        {"draws", "seed", "position"} is the whole state.  Torch mode: also the torch.Generator's state and the host RandomState's."""
+        state = {"draws": self.draws, "seed": self.seed, "position": self.position}
+        if self.draws == "torch":
+            state["torch_generator"] = self.gen.get_state()
+            state["random_state"] = self._rs.get_state()
+        return state
+
+    def load_state_dict(self, state):
+        """Continue the stream of a `state_dict()` of the same draw mode (another mode: ValueError).  The base images are the
+        constructor's: build the generator with the seed (or the bank) it was built with before."""
+        if state.get("draws") != self.draws:
+            raise ValueError("a state of draws=%r cannot be loaded into a generator with draws=%r" % (state.get("draws"), self.draws))
+        if self.draws == "torch":
+            self.gen.set_state(state["torch_generator"])
+            self._rs.set_state(state["random_state"])
+        self.seed, self.position = int(state["seed"]), int(state["position"])
+
+    def _draw_counter(self, B, idx, first):
+        """draw() with draws='counter': one K.synth_draw call makes every tensor."""
+        dev, P = self.device, self.patch
+        given = self._given_idx(idx, B) if idx is not None else None            # (refused before anything is launched)
+        if self.blobs and B < 2:
+            raise ValueError("blobs paste content of ANOTHER sample of the batch: the batch needs at least 2 samples")
+        advance = first is None
+        if advance:
+            first = self.position + self.rank * B
+        own = torch.empty(B, dtype=torch.int32, device=dev)
+        origin = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        delta = torch.empty(B, 4, 2, dtype=torch.float32, device=dev)
+        photo = torch.empty(B, 12, dtype=torch.float32, device=dev) if self.pmd > 0 else None
+        noise = torch.empty(B, P, P, dtype=torch.float32, device=dev) if self.blobs else None
+        other = torch.empty(B, dtype=torch.int32, device=dev) if self.blobs else None
+        K.synth_draw(self.seed, first, self.n_images, self.h, self.w, P, self.rho, self.pmd, own, origin, delta, photo, noise, other)
+        if advance:
+            self.position += self.world * B
+        idx = given if given is not None else own              # (the stream's own index is made and dropped, as in torch mode)
+        return (idx, origin, delta, photo) + (((noise, other),) if self.blobs else ())
+
+    def draw(self, B, idx=None, first=None):
         """Random sample parameters exactly as transforms.py:505-506,538 draw them (uniform integer position with a
         rho margin, integer corner offsets in [-rho, rho-1]).  With blobs on, a fifth element (noise [B,P,P], other [B] int32) drawn
         AFTER everything else: a seed yields the same idx / origin / delta / photo with and without blobs.
         idx: the image of every sample ([B] integers, host or device - a sampler's batch) instead of the generator's own index draw,
-        which is still made and dropped: a seed yields the same origin / delta / photo / blobs with and without idx."""
+        which is still made and dropped: a seed yields the same origin / delta / photo / blobs with and without idx.
+        first (draws='counter' only): the stream position of the call's first sample; None: position + rank * B, and position then moves
+        on by world * B.  An explicit `first` leaves `position` alone."""
+        if self.draws == "counter":
+            return self._draw_counter(B, idx, first)
+        if first is not None:
+            raise ValueError("first= names a position of the counter stream: it needs draws='counter'")
         g, dev, half = self.gen, self.device, self.patch // 2
         given = self._given_idx(idx, B) if idx is not None else None            # (refused before anything is drawn or launched)
+        self.position += B                                                      # (torch mode: the number of samples drawn so far)
         idx = torch.randint(0, self.n_images, (B,), generator=g, device=dev, dtype=torch.int32)
         if given is not None:
             idx = given

@@ -750,6 +750,41 @@ size_t bh_synth_blobs_scratch_floats(int B, int P);
 int bh_synth_blobs(const float* noise, const int* other, const float* patch1, float* patch2, float* mask, float* field,
                    float* scratch, int B, int C, int P, double sigma, double porosity, void* stream);
 
+/* Counter-based draws of the pair generator: every random quantity of sample n of a seed is a pure function of (seed, n), whatever the
+ * batch size, the rank count or the calls made before.  Sample b of a call is sample first + b of the stream (64-bit, wrapping).
+ *
+ * The stream.  philox4x64_10(counter[4], key[2]) is the standard 10-round Philox function on 64-bit words (Salmon et al., SC'11):
+ * multipliers 0xD2E7470EE14C6C93 on counter[0] and 0xCA5A826395121157 on counter[2]; one round gives {hi1 ^ c1 ^ k0, lo1,
+ * hi0 ^ c3 ^ k1, lo0} (hi / lo: the halves of the 128-bit products); between rounds the key grows by (0x9E3779B97F4A7C15,
+ * 0xBB67AE8584CAA73B).  Word k (k = 0, 1, ...) of sample n for purpose p is element k % 4 of
+ *     philox4x64_10(counter = (k / 4 + 1, n, 0, 0), key = (seed, p)),
+ * which is np.random.Philox(key=[seed, p], counter=[0, n, 0, 0]).random_raw(K)[k] (numpy advances its counter before its first block).
+ * Maps of a word: an integer in [0, r), r < 2^31, is (word * r) >> 64; a double uniform is (word >> 11) * 2^-53 (numpy's
+ * Generator.random()); a float noise value is (word >> 40) * 2^-24.
+ *
+ * Purpose 0, the sample's parameters:
+ *   word 0       img_idx = int(n_images)
+ *   words 1, 2   patch centre px = rho + P/2 + int(Ws - 2 rho - 2 (P/2) + 1), py likewise with Hs (transforms.py:505-506);
+ *                origin = (px - P/2, py - P/2)
+ *   word 3       blob source: r = int(B - 1), other = r + (r >= b) - the only quantity that depends on the batch (B, and the position b)
+ *   words 4..11  delta[4,2] row-major: -rho + int(2 rho) (transforms.py:538)
+ *   words 12..22 the 11 uniforms of image 1's photometric record, in the column order of bihome_amd.synth_gpu.photometric_records
+ *   words 24..34 the same for image 2 (words 23 and 35 are unused)
+ * A record is {brightness, contrast-first, saturation, hue, contrast-last, permutation index} (bh_synth_pairs' layout) by
+ * photometric_records' formulas - coins u >= 0.5, values lo + (hi - lo) u, the index floor(6 u) clamped to 5, permutation 0 at
+ * max_delta == 0 - evaluated in double without contraction and rounded once to float.
+ * Purpose 1, blob noise: noise[y, x] = the float map of word y * P + x.
+ *
+ * Outputs: img_idx[B], origin[B,2] and delta[B,4,2] always; photo[B,2,6] or NULL; noise[B,P,P] and other[B] both or neither.  Every
+ * element of every given output is written exactly once and nothing else is touched; no atomics, no scratch: two calls are bitwise
+ * equal.  At most two launches (parameters; noise), no allocation, no host synchronisation.  bihome_amd.synth.counter_draws is the
+ * same function in numpy, and every output equals it bit for bit.
+ * BH_E_BADARG: B < 0, n_images < 1, rho < 1, P < 1, Hs < P + 2 rho, Ws < P + 2 rho, only one of noise / other given; then B == 0:
+ * BH_OK, nothing launched; then BH_E_BADARG for a NULL img_idx / origin / delta, and for noise given with B < 2.  Refusals return
+ * before any launch. */
+int bh_synth_draw(size_t seed, size_t first, int B, int n_images, int Hs, int Ws, int P, int rho,
+                  float max_delta, int* img_idx, float* origin, float* delta, float* photo, float* noise, int* other, void* stream);
+
 /* Resident image bank of the pair generator: Dataset.load_image (src/data/coco/dataset.py:95-103: one np.load of a uint8 [H,W,3] RGB
  * array per sample, written by preprocess_offline.py:22) as a gather on the device.  bank[n_images,Hs,Ws,3] uint8, interleaved RGB - the
  * .npy layout, all images of one split in one tensor (82,783 x 240 x 320 x 3 = 19 GB for COCO train2014); img_idx[count] int32;

@@ -20,7 +20,13 @@ case:
                        fixed-point path with a crop) and a mixed batch; its GB/s (source bytes inside the crop window + bank bytes
                        written) and those of a device copy that moves the same bytes
 
+    draws              --draws counter (these rows only): `next(64)` with counter-based draws (draws='counter': one bh_synth_draw launch
+                       makes every parameter) against device draws (draws='torch', photometric_draws='device'), the two alternating
+                       in this one process, for zeng-bihome-pds, zeng-bihome-pds-blobs and zeng-bihome (gray s-coco); then
+                       bh_synth_draw alone with and without the blob noise
+
     python tools/datagen_bench.py [--other-lib ../parent/bihome_amd/libbihome_hip.so]
+    python tools/datagen_bench.py --draws counter
     python tools/datagen_bench.py --bank [--bank-images 512]
     python tools/datagen_bench.py --ingest
 
@@ -163,8 +169,39 @@ def ingest_rows(B, rounds, warmup, kernel_reps):
                           "ingest_over_copy_bandwidth": round(gbs["ingest"] / gbs["copy"], 3)}), flush=True)
 
 
+def draws_rows(B, reps, rounds, warmup, kernel_reps):
+    """--draws counter: `next(B)` of a generator with counter-based draws against one with device draws (the two alternating round by
+    round in this process), then the draw entry point alone (its outputs allocated once)."""
+    from bihome_amd import configs
+    dev = torch.cuda.get_device_name(0)
+    for name in ("zeng-bihome-pds", "zeng-bihome-pds-blobs", "zeng-bihome"):
+        cfg = configs.get(name)
+        counter = GpuPairGenerator.from_config(cfg, seed=7, draws="counter")
+        device = GpuPairGenerator.from_config(cfg, seed=7, draws="torch", photometric_draws="device")
+        r = device_rounds({"counter": lambda: counter.next(B), "device": lambda: device.next(B)}, reps, rounds, warmup)
+        diff = round(r["counter"]["median_us"] - r["device"]["median_us"], 2)
+        spread = max(r["counter"]["spread_us"], r["device"]["spread_us"])
+        print(json.dumps({"tool": "datagen_bench", "case": "draws: " + name, "batch": B, "device": dev, "reps": reps, "rounds": rounds,
+                          "counter_draws": r["counter"], "device_draws": r["device"], "counter_minus_device_median_us": diff,
+                          "counter_not_slower_than_spread": bool(diff <= spread)}), flush=True)
+    gen = GpuPairGenerator.from_config(configs.get("zeng-bihome-pds-blobs"), seed=7, draws="counter")
+    P = gen.patch
+    idx = torch.empty(B, dtype=torch.int32, device="cuda")
+    origin, delta, photo = torch.empty(B, 2, device="cuda"), torch.empty(B, 4, 2, device="cuda"), torch.empty(B, 2, 6, device="cuda")
+    noise, other = torch.empty(B, P, P, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+    geom = (gen.n_images, gen.h, gen.w, P, gen.rho, gen.pmd)
+    r = device_rounds({"params": lambda: K.synth_draw(7, 0, *geom, idx, origin, delta, photo),
+                       "params+noise": lambda: K.synth_draw(7, 0, *geom, idx, origin, delta, photo, noise, other)},
+                      kernel_reps, rounds, warmup)
+    print(json.dumps({"tool": "datagen_bench", "case": "draws: bh_synth_draw alone", "batch": B, "patch": P, "device": dev,
+                      "reps": kernel_reps, "rounds": rounds, "parameters_and_records": r["params"], "with_blob_noise": r["params+noise"],
+                      "noise_bytes": B * P * P * 4}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--draws", choices=["counter"], default=None,
+                    help="only the draw rows: counter-based draws against device draws, and bh_synth_draw alone")
     ap.add_argument("--bank", action="store_true", help="only the image-bank rows: uint8 bank against the float layout, and the gather kernel")
     ap.add_argument("--bank-images", type=int, default=512)
     ap.add_argument("--ingest", action="store_true", help="only the ingest rows: bh_bank_ingest_u8 (Rescale + CenterCrop into bank slots) against a device copy")
@@ -176,6 +213,9 @@ def main():
     ap.add_argument("--other-lib", default=None, help="another build of libbihome_hip.so for the kernel A/B case")
     ap.add_argument("--kernel-reps", type=int, default=2000)
     args = ap.parse_args()
+    if args.draws:
+        draws_rows(64, args.reps, args.rounds, args.warmup, args.kernel_reps)
+        return
     if args.ingest:
         ingest_rows(64, args.rounds, args.warmup, args.kernel_reps)
         return
