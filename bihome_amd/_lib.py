@@ -132,6 +132,8 @@ SIGNATURES = {
     "bh_synth_draw": [ctypes.c_size_t, ctypes.c_size_t] + [c_int] * 6 + [c_float] + [P] * 7,
     "bh_bank_gather_u8": [P, P, c_int, c_int, c_int, c_int, P, P],
     "bh_bank_ingest_u8": [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P],
+    "bh_align_prep_u8": [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_float, c_float, P, P, P],
+    "bh_warp_u8": [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_gap_fwd": [P, P, c_int, c_int, c_int, P],

@@ -1576,3 +1576,49 @@ def bank_ingest_u8(src, src_off, src_hw, bank, first=0):
     _chk(off, torch.int64); _chk(hw, torch.int32)
     check(lib.bh_bank_ingest_u8(_p(src), _p(off), _p(hw), n, _p(bank), N, first, H, W, _stream()), "bh_bank_ingest_u8")
     return bank
+
+
+# ------------------------------------------------------------------------------------------------
+# image alignment: uint8 images -> standardised patches, and the uint8 warp (bihome_amd/align.py)
+# ------------------------------------------------------------------------------------------------
+def _chk_images_u8(images, idx, B, what):
+    _chk(images, torch.uint8); _chk(idx, torch.int32)
+    if images.dim() != 4 or images.shape[3] != 3 or min(images.shape) < 1:
+        raise ValueError("%s: images [N,H,W,3] uint8 with N, H, W >= 1, got %s" % (what, tuple(images.shape)))
+    if idx is not None and tuple(idx.shape) != (B,):
+        raise ValueError("%s: idx [B] int32, got %s for B = %d" % (what, tuple(idx.shape), B))
+
+
+def align_prep_u8(images, patch, geom, mean, std, idx=None, roi=None):
+    """B samples of a uint8 bank [N,H,W,3] as the standardised patches patch [B,C,P,P] float32 by exact area averaging, and their
+    geometry records geom [B,4] float64 (sx, sy, tx, ty) (include/bihome.h bh_align_prep_u8).  Both outputs are the caller's
+    (bihome_amd.align.prepare allocates them).  idx [B] int32: each sample's image (None: sample b is image b; clamped by the kernel);
+    roi [B,4] float64 DEVICE tensor (x0, y0, rw, rh) in edge coordinates (None: whole images) - the kernel clamps what it derives from
+    it, range checks belong to the caller (bihome_amd.align.Aligner)."""
+    _chk(patch); _chk(geom, torch.float64); _chk(roi, torch.float64)
+    if patch.dim() != 4 or patch.shape[2] != patch.shape[3] or tuple(geom.shape) != (patch.shape[0], 4):
+        raise ValueError("align_prep_u8: patch [B,C,P,P] float32 and geom [B,4] float64, got %s and %s" % (tuple(patch.shape), tuple(geom.shape)))
+    B, C, P = patch.shape[:3]
+    _chk_images_u8(images, idx, B, "align_prep_u8")
+    if roi is not None and tuple(roi.shape) != (B, 4):
+        raise ValueError("align_prep_u8: roi [B,4] float64, got %s" % (tuple(roi.shape),))
+    check(lib.bh_align_prep_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(roi), B, P, C,
+                               float(mean), float(std), _p(patch), _p(geom), _stream()), "bh_align_prep_u8")
+    return patch, geom
+
+
+def warp_u8(images, H64, out, valid=None, idx=None):
+    """out [B,Ho,Wo,3] uint8 = round_half_up(bilinear images[idx[b]](H64[b] (x, y, 1))) with zero padding, and valid [B,Ho,Wo] uint8
+    (may be None) (include/bihome.h bh_warp_u8).  Both outputs are the caller's (bihome_amd.align.warp_u8 allocates them).  H64 [B,3,3]
+    or [B,9] float64: output index coordinates -> source index coordinates."""
+    _chk(H64, torch.float64); _chk(out, torch.uint8); _chk(valid, torch.uint8)
+    if H64.dim() < 2 or H64.numel() != 9 * H64.shape[0]:
+        raise ValueError("warp_u8: H64 [B,3,3] float64, got %s" % (tuple(H64.shape),))
+    B = H64.shape[0]
+    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (valid is not None and tuple(valid.shape) != tuple(out.shape[:3])):
+        raise ValueError("warp_u8: out [B,Ho,Wo,3] uint8 and valid [B,Ho,Wo] uint8 with B = %d, got %s and %s"
+                         % (B, tuple(out.shape), None if valid is None else tuple(valid.shape)))
+    _chk_images_u8(images, idx, B, "warp_u8")
+    check(lib.bh_warp_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(H64), B, out.shape[1], out.shape[2],
+                         _p(out), _p(valid), _stream()), "bh_warp_u8")
+    return out, valid

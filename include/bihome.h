@@ -820,6 +820,45 @@ int bh_bank_gather_u8(const unsigned char* bank, const int* img_idx, int count, 
 int bh_bank_ingest_u8(const unsigned char* src, const int64_t* src_off, const int* src_hw, int count, unsigned char* bank, int n_slots,
                       int first, int H, int W, void* stream);
 
+/* Image alignment: a trained model applied to two full-size uint8 images.  Upstream has this only at patch level and on the host
+ * (eval.py:249-255 builds four_point_to_homography(corners, delta_hat) and warps with kornia / cv2; src/data/utils.py:54-67 warp_image);
+ * the three steps around the model are stated here and, in numpy float64, in bihome_amd/align.py (prep_host, lift, warp_u8_host).
+ * INDEX coordinates: pixel j of an image sits at coordinate j and occupies [j - 0.5, j + 0.5) - the convention of csrc/warp_tap.h and of
+ * four_point_to_homography.  EDGE coordinates (regions only): pixel i spans [i, i + 1).
+ *
+ * Preparation (ToGrayscale / DictToGrayscale, src/data/transforms.py:333-354; DictStandardize, :369-378; the resize is new).
+ * images[n_images,H,W,3] uint8 interleaved RGB (a bank); idx[B] int32 picks each sample's image (NULL: sample b is image b; CLAMPED into
+ * [0, n_images) in the kernel); roi[B,4] double = (x0, y0, rw, rh) in edge coordinates (NULL: the whole image, (0, 0, W, H)).  With
+ * sx = rw / P, sy = rh / P, output pixel (y, x) is the exact area average of the source over
+ * [x0 + x sx, x0 + (x+1) sx) x [y0 + y sy, y0 + (y+1) sy):
+ *     patch[b,c,y,x] = ((1 / (sx sy)) sum_j sum_i ov_y(y,j) ov_x(x,i) v_c(j,i) / 255 - mean) / std,
+ * ov the length of the overlap of the output interval with pixel i's unit interval, v = 0.299 R + 0.587 G + 0.114 B for C = 1 and
+ * channel c for C = 3: one formula for shrinking, sx = 1 (the standardised image itself) and enlarging.  patch[B,C,P,P] float;
+ * geom[b] = (sx, sy, tx, ty) double with tx = x0 + 0.5 sx - 0.5, ty = y0 + 0.5 sy - 0.5: the affine map A from patch index coordinates
+ * to image index coordinates (evaluated in double without contraction: the bits of the numpy statement).  Interval ends are double, the
+ * overlaps and sums float.  roi is device memory, so this function cannot see it: every source index derived from it is clamped to the
+ * image - a wrong region gives wrong pixels, never a read outside the bank (bihome_amd.align.Aligner range-checks regions on the host).
+ * The offset of an image in the bank is 64-bit (the bank may be far larger than 2^31 bytes), offsets inside an image 32-bit.  One writer
+ * per output element, no atomics: two calls are bitwise equal.
+ * BH_E_BADARG: NULL images / patch / geom, B < 0, n_images < 1, H < 1, W < 1, P < 1, std zero or NaN; then BH_E_UNSUPPORTED: C not 1 or
+ * 3, P % 16 != 0, P > 256, H * W > 2^30 pixels; then B == 0: BH_OK, nothing launched.  Refusals return before any launch. */
+int bh_align_prep_u8(const uint8_t* images, const int* idx, int n_images, int H, int W, const double* roi,
+                     int B, int P, int C, float mean, float std, float* patch, double* geom, void* stream);
+
+/* The uint8 warp: out[b,y,x,:] = round_half_up(clamp(bilinear images[idx[b]](H64[b] (x, y, 1)), 0, 255)), taps outside the image
+ * contribute 0 - warp_image's net map with zero padding (src/data/utils.py:54-59) on interleaved uint8 RGB.  images[n_images,Hs,Ws,3],
+ * idx as above; H64[B,9] double maps index coordinates of the OUTPUT (Ho x Wo) to index coordinates of the source - for the lifted
+ * H_img = A_a H_p A_b^-1 (H_p = bh_h4pt_fwd(delta_hat, P), eval.py:252-254; the loss trains patch_1(H_p x) ~ patch_2(x),
+ * PerceptualHead.py:371) the source is image A and the output has image B's size.  out[B,Ho,Wo,3] uint8; valid[B,Ho,Wo] uint8 (NULL
+ * ok) = 1 where the projected point lies in [0, Ws - 1] x [0, Hs - 1] and the projection guard (|qz| <= 1e-8) did not fire, else 0.
+ * The projection and the placement of the taps are csrc/warp_tap.h's (tap_project / tap_place, float), as in every other warp here.
+ * Wo % 4 == 0 with out on a 4-byte boundary: four pixels and three dword stores per thread; anything else one pixel and byte stores,
+ * same results.  The offset of an image in the bank and every offset into out are 64-bit, offsets inside a source image 32-bit.  One writer per output element, no atomics: two calls are bitwise
+ * equal.  BH_E_BADARG: NULL images / H64 / out, B < 0, n_images < 1, Hs < 1, Ws < 1, Ho < 1, Wo < 1; then BH_E_UNSUPPORTED: Hs * Ws
+ * > 2^29 or Ho * Wo > 2^31 - 1 pixels; then B == 0: BH_OK, nothing launched.  Refusals return before any launch. */
+int bh_warp_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* H64,
+               int B, int Ho, int Wo, uint8_t* out, uint8_t* valid, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */
