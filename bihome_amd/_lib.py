@@ -134,6 +134,13 @@ SIGNATURES = {
     "bh_bank_ingest_u8": [P, P, P, c_int, P, c_int, c_int, c_int, c_int, P],
     "bh_align_prep_u8": [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_float, c_float, P, P, P],
     "bh_warp_u8": [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P],
+    "bh_gray_pyramid_layout": [c_int, c_int, c_int, P],
+    "bh_gray_pyramid_u8": [P, P, c_int, c_int, c_int, c_int, c_int, P, P],
+    "bh_ecc_sums_ws_doubles": [c_int, c_int, c_int, P],
+    "bh_ecc_sums": [P, c_int, c_int, c_int64, P, c_int, c_int, c_int64, P, P, c_int, P, P, P],
+    "bh_ecc_step": [P, P, c_int, c_int, P, c_int, P],
+    "bh_ecc_refine_ws_doubles": [c_int, c_int, c_int, P],
+    "bh_ecc_refine": [P, c_int, c_int, P, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_gap_fwd": [P, P, c_int, c_int, c_int, P],
@@ -182,6 +189,7 @@ ROUTE_C3_PC = 512
 ROUTE_WX3_PC = 1024       # include/bihome.h BH_ROUTE_WX3_PC
 ROUTE_WX3_SHARED = 2048   # include/bihome.h BH_ROUTE_WX3_SHARED             # ... the persistent kernel for every launch it supports (default: where it is the faster one)
 ROUTE_GEMM_X3 = 4096         # include/bihome.h BH_ROUTE_GEMM_X3: the generic kernel in three bf16 pieces (precision 2 / 4), opt-in
+ECC_SUMS, ECC_STATE = 66, 24   # include/bihome.h BH_ECC_SUMS / BH_ECC_STATE
 ROUTE_C3_TILE_WG = 256        # precision-4 3x3 fwd / dgrad on the one-workgroup-per-tile halo kernel instead of the persistent one
 
 

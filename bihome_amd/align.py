@@ -27,7 +27,13 @@ coordinates of image B to index coordinates of image A.
 
 uint8 warp: aligned[y,x,:] = round_half_up(clamp(bilinear A(H_img (x, y, 1)), 0, 255)) on B's grid, taps outside A contribute 0
 (warp_image's net map with zero padding, src/data/utils.py:54-59); valid = 1 where the projected point lies in [0, Wa-1] x [0, Ha-1].
-cv2.warpPerspective rounds half to even in fixed point with 1/32-pixel coordinates; this rounds half up in float."""
+cv2.warpPerspective rounds half to even in fixed point with 1/32-pixel coordinates; this rounds half up in float.
+
+Refinement (optional, `Aligner(..., refine="ecc")` / `ecc_refine`; csrc/ecc.hip): the lift multiplies the model's patch-level error by
+sx, sy, so H_img is polished on the two images themselves before the warp - the forward-additive enhanced-correlation-coefficient
+iteration (Evangelidis & Psarakis; what cv2.findTransformECC does on the host) on gray 2 x 2 box pyramids, coarse to fine, blind to a gain
+and a bias between the images, with the exact derivative of the bilinear interpolant at warp_tap.h's taps, a fixed number of passes per
+level and the best H so far kept.  Stated below as gray_pyramid_host / ecc_sums_host / ecc_step_host / ecc_level_host / ecc_refine_host."""
 import numpy as np
 import torch
 
@@ -126,6 +132,203 @@ def warp_u8_host(images, H, Ho, Wo):
             valid[b] = ~guard & (u >= 0) & (u <= Ws - 1) & (v >= 0) & (v <= Hs - 1)
         out[b] = np.floor(np.clip(acc, 0.0, 255.0) + 0.5).astype(np.uint8)
     return out, valid
+
+
+# ------------------------------------------------------------------------------------------------
+# ECC refinement, the definitions (numpy float64; include/bihome.h "ECC refinement" states the same in C terms)
+# ------------------------------------------------------------------------------------------------
+ECC_NZ, ECC_SUMS = 11, 66          # z = (j0..j7, iw, t, 1); the upper triangle of z z^T, row-major
+ECC_MIN_N = 16                     # fewer counting pixels than this: no step
+ECC_MAX_LEVELS, ECC_MIN_SIDE = 6, 8
+PYR_C = np.array([[2.0, 0.0, 0.5], [0.0, 2.0, 0.5], [0.0, 0.0, 1.0]])          # index coordinates of level l -> level l - 1
+_ECC_IU = np.triu_indices(ECC_NZ)
+
+
+def ecc_index(i, j):
+    """Where entry (i, j) of the 11 x 11 Gram matrix sits among the 66 sums (either order of i, j)."""
+    i, j = min(i, j), max(i, j)
+    return i * ECC_NZ - i * (i - 1) // 2 + (j - i)
+
+
+def pyramid_sizes(h, w, levels):
+    """[(h_l, w_l)] for l = 0 .. levels - 1; ValueError (naming the sizes) for a pyramid that is not built."""
+    if not 1 <= levels <= ECC_MAX_LEVELS:
+        raise ValueError("pyramid: levels is 1..%d, got %r" % (ECC_MAX_LEVELS, levels))
+    sizes = [(h >> l, w >> l) for l in range(levels)]
+    if min(sizes[-1]) < ECC_MIN_SIDE:
+        raise ValueError("pyramid: %d levels of a %d x %d (H x W) image end at %d x %d; the coarsest level has at least %d pixels on each "
+                         "side" % (levels, h, w, sizes[-1][0], sizes[-1][1], ECC_MIN_SIDE))
+    return sizes
+
+
+def pyramid_offsets(h, w, levels):
+    """offsets [levels + 1] of the levels inside a sample's packed row (bh_gray_pyramid_layout); the last is the row's length."""
+    return np.concatenate([[0], np.cumsum([a * b for a, b in pyramid_sizes(h, w, levels)])]).astype(np.int64)
+
+
+def gray_pyramid_host(images_u8, levels):
+    """uint8 [B,H,W,3] -> [levels] arrays [B,h_l,w_l] float64: level 0 the gray image 0.299 R + 0.587 G + 0.114 B, level l the 2 x 2 box
+    mean of level l - 1 (an odd last row / column dropped)."""
+    images = np.asarray(images_u8)
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
+        raise ValueError("gray_pyramid_host: images uint8 [B,H,W,3], got %s %s" % (images.dtype, images.shape))
+    sizes = pyramid_sizes(images.shape[1], images.shape[2], levels)
+    v = images.astype(np.float64)
+    out = [0.299 * v[..., 0] + 0.587 * v[..., 1] + 0.114 * v[..., 2]]
+    for h, w in sizes[1:]:
+        p = out[-1]
+        out.append(((p[:, 0:2 * h:2, 0:2 * w:2] + p[:, 0:2 * h:2, 1:2 * w:2]) + (p[:, 1:2 * h:2, 0:2 * w:2] + p[:, 1:2 * h:2, 1:2 * w:2])) * 0.25)
+    return out
+
+
+def mask_pyramid_host(mask, levels):
+    """uint8 [B,H,W] -> [levels] uint8 arrays: level l is 1 where all four bytes of the 2 x 2 block below are non-zero."""
+    m = (np.asarray(mask) != 0).astype(np.uint8)
+    out = [m]
+    for h, w in pyramid_sizes(m.shape[1], m.shape[2], levels)[1:]:
+        p = out[-1]
+        out.append(p[:, 0:2 * h:2, 0:2 * w:2] & p[:, 0:2 * h:2, 1:2 * w:2] & p[:, 1:2 * h:2, 0:2 * w:2] & p[:, 1:2 * h:2, 1:2 * w:2])
+    return out
+
+
+def h_level_down(H):
+    """H at level l -> level l - 1 (the finer one): C H C^-1, H[2,2] = 1."""
+    R = PYR_C @ np.asarray(H, np.float64).reshape(3, 3) @ np.linalg.inv(PYR_C)
+    return R / R[2, 2]
+
+
+def h_level_up(H):
+    """H at level l - 1 -> level l (the coarser one): C^-1 H C, H[2,2] = 1."""
+    R = np.linalg.inv(PYR_C) @ np.asarray(H, np.float64).reshape(3, 3) @ PYR_C
+    return R / R[2, 2]
+
+
+def ecc_terms_host(A_l, T_l, H, mask_l=None):
+    """The per-pixel terms of one pass: (z [11,Hb,Wb] float64 with z = (j0..j7, iw, t, 1), counts [Hb,Wb] bool).  H is used as H / H[2,2]."""
+    A, T = np.asarray(A_l, np.float64), np.asarray(T_l, np.float64)
+    h = np.asarray(H, np.float64).reshape(3, 3)
+    h = h / h[2, 2]
+    (Ha, Wa), (Hb, Wb) = A.shape, T.shape
+    ys, xs = np.mgrid[0:Hb, 0:Wb].astype(np.float64)
+    qz = h[2, 0] * xs + h[2, 1] * ys + h[2, 2]
+    with np.errstate(all="ignore"):
+        ok = qz > QZ_GUARD
+        iz = 1.0 / np.where(ok, qz, 1.0)
+        u, v = (h[0, 0] * xs + h[0, 1] * ys + h[0, 2]) * iz, (h[1, 0] * xs + h[1, 1] * ys + h[1, 2]) * iz
+        ok &= (u >= 0) & (u < Wa - 1) & (v >= 0) & (v < Ha - 1)
+    if mask_l is not None:
+        ok &= np.asarray(mask_l) != 0
+    u, v = np.where(ok, u, 0.0), np.where(ok, v, 0.0)
+    x0, y0 = np.floor(u).astype(np.int64), np.floor(v).astype(np.int64)
+    fx, fy = u - x0, v - y0
+    x1, y1 = np.minimum(x0 + 1, Wa - 1), np.minimum(y0 + 1, Ha - 1)          # (only where the pixel does not count)
+    a00, a01, a10, a11 = A[y0, x0], A[y0, x1], A[y1, x0], A[y1, x1]
+    iw = (1 - fy) * ((1 - fx) * a00 + fx * a01) + fy * ((1 - fx) * a10 + fx * a11)
+    gx = (1 - fy) * (a01 - a00) + fy * (a11 - a10)
+    gy = (1 - fx) * (a10 - a00) + fx * (a11 - a01)
+    m = -(gx * u + gy * v)
+    z = np.stack([gx * xs * iz, gx * ys * iz, gx * iz, gy * xs * iz, gy * ys * iz, gy * iz, m * xs * iz, m * ys * iz, iw, T, np.ones_like(T)])
+    return z * ok, ok
+
+
+def ecc_sums_host(A_l, T_l, H, mask_l=None):
+    """One pass: the 66 sums (upper triangle of sum z z^T over the counting pixels, row-major; `ecc_index`) of the gray planes A_l
+    (image A) and T_l (image B) at one level under H (B's index coordinates -> A's)."""
+    z, _ = ecc_terms_host(A_l, T_l, H, mask_l)
+    z = z.reshape(ECC_NZ, -1)
+    return (z @ z.T)[_ECC_IU]
+
+
+def ecc_step_host(sums):
+    """One step from the 66 sums: (rho, d).  rho is NaN where it cannot be measured (n < 16, a variance not positive); d [8] is None where
+    the step FAILS (that, a zero or NaN pivot, lambda's denominator not > 0, a d that is not finite).  Plain double operations in the
+    order the kernel performs them (csrc/ecc.hip ecc_step_kernel)."""
+    s = np.asarray(sums, np.float64).reshape(ECC_SUMS)
+    S = lambda i, j: float(s[ecc_index(i, j)])
+    n = S(10, 10)
+    if not n >= ECC_MIN_N:
+        return float("nan"), None
+    m_iw, m_t = S(8, 10) / n, S(9, 10) / n
+    v_iw, v_t, c_it = S(8, 8) - (n * m_iw) * m_iw, S(9, 9) - (n * m_t) * m_t, S(8, 9) - (n * m_iw) * m_t
+    if not (v_iw > 0 and v_t > 0):
+        return float("nan"), None
+    rho = c_it / float(np.sqrt(v_iw * v_t))
+    M = np.empty((8, 10))
+    for r in range(8):
+        for c in range(8):
+            M[r, c] = S(r, c) - (S(r, 10) * S(c, 10)) / n
+        M[r, 8], M[r, 9] = S(r, 8) - m_iw * S(r, 10), S(r, 9) - m_t * S(r, 10)
+    a, cc = M[:, 8].copy(), M[:, 9].copy()
+    with np.errstate(all="ignore"):
+        for k in range(8):
+            p, big = k, abs(M[k, k])
+            for q in range(k + 1, 8):
+                if abs(M[q, k]) > big:
+                    p, big = q, abs(M[q, k])
+            if not big > 0:
+                return rho, None
+            if p != k:
+                M[[k, p]] = M[[p, k]]
+            for r in range(k + 1, 8):
+                f = M[r, k] / M[k, k]
+                for c in range(k + 1, 10):
+                    M[r, c] = M[r, c] - f * M[k, c]
+        ya, yc = np.zeros(8), np.zeros(8)
+        for i in range(7, -1, -1):
+            sa, sc = M[i, 8], M[i, 9]
+            for j in range(i + 1, 8):
+                sa, sc = sa - M[i, j] * ya[j], sc - M[i, j] * yc[j]
+            ya[i], yc[i] = sa / M[i, i], sc / M[i, i]
+        da = dc = 0.0
+        for i in range(8):
+            da, dc = da + a[i] * ya[i], dc + cc[i] * ya[i]
+        lambda_n, lambda_d = v_iw - da, c_it - dc
+        if not lambda_d > 0:
+            return rho, None
+        d = (lambda_n / lambda_d) * yc - ya
+    return (rho, d) if np.isfinite(d).all() else (rho, None)
+
+
+def ecc_level_host(A_l, T_l, H, iters, mask_l=None):
+    """One level: iters + 1 passes from H -> (best [3,3], rho at the first pass, rho_best, accepted steps)."""
+    cur = np.asarray(H, np.float64).reshape(3, 3)
+    cur = cur / cur[2, 2]
+    best, rho_best, rho_first, frozen, accepted = cur.copy(), -np.inf, None, False, 0
+    for k in range(iters + 1):
+        rho, d = ecc_step_host(ecc_sums_host(A_l, T_l, cur, mask_l))          # (a frozen sample runs its passes too: fixed work)
+        rho_first = rho if k == 0 else rho_first
+        if frozen:
+            continue
+        if rho > rho_best:
+            best, rho_best = cur.copy(), rho
+            if k < iters and d is not None:
+                cur = (cur.reshape(9) + np.append(d, 0.0)).reshape(3, 3)
+                cur[2, 2] = 1.0
+                accepted += 1
+            else:
+                frozen = True
+        else:
+            cur, frozen = best.copy(), True
+    return best, rho_first, rho_best, accepted
+
+
+def ecc_refine_host(images_a, images_b, H, levels=3, iters=10, mask=None):
+    """images_* uint8 [B,H*,W*,3], H [B,3,3] (B's index coordinates -> A's), mask uint8 [B,Hb,Wb] or None -> (H [B,3,3] float64 with
+    H[2,2] = 1, stats [B,levels,3] = (rho at the level's first pass, rho_best, accepted steps), index 0 the FINEST level)."""
+    pa, pb = gray_pyramid_host(images_a, levels), gray_pyramid_host(images_b, levels)
+    pm = None if mask is None else mask_pyramid_host(mask, levels)
+    H = np.asarray(H, np.float64).reshape(-1, 3, 3)
+    out, stats = np.empty_like(H), np.empty((H.shape[0], levels, 3))
+    for b in range(H.shape[0]):
+        cur = H[b] / H[b, 2, 2]
+        for _ in range(levels - 1):
+            cur = h_level_up(cur)
+        for l in range(levels - 1, -1, -1):
+            cur, stats[b, l, 0], stats[b, l, 1], stats[b, l, 2] = ecc_level_host(pa[l][b], pb[l][b], cur, iters, None if pm is None else pm[l][b])
+            if l > 0:
+                cur = h_level_down(cur)
+        out[b] = cur
+    return out, stats
 
 
 # ------------------------------------------------------------------------------------------------
@@ -230,12 +433,113 @@ def warp_u8(images, H64, Ho, Wo, idx=None, want_valid=True):
     return K.warp_u8(images, H64, out, valid, idx=idx)
 
 
+def gray_pyramid(images, B, levels, idx=None):
+    """bh_gray_pyramid_u8 on an output allocated here: pyr [B,total] float32, the gray box pyramids of B samples of the uint8 bank
+    images [N,H,W,3] with the levels packed one after another (`pyramid_offsets`; `pyramid_level` views one).  idx [B] int32 DEVICE
+    tensor or None.  ValueError, before any launch, for levels the images are too small for."""
+    if not images.is_cuda:
+        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % images.device)
+    total = int(pyramid_offsets(images.shape[1], images.shape[2], levels)[-1])
+    pyr = torch.empty((B, total), dtype=torch.float32, device=images.device)
+    return K.gray_pyramid_u8(images, pyr, levels, idx=idx)
+
+
+def pyramid_level(pyr, h, w, levels, l):
+    """The [B,h_l,w_l] view of level l inside a packed pyramid [B,total] of h x w images (float planes or mask bytes)."""
+    off, (hl, wl) = pyramid_offsets(h, w, levels), pyramid_sizes(h, w, levels)[l]
+    return pyr[:, int(off[l]):int(off[l + 1])].view(pyr.shape[0], hl, wl)
+
+
+def mask_pyramid(mask, levels):
+    """mask [B,H,W] uint8 device tensor -> uint8 [B,total] in the pyramid's layout: level 0 is mask != 0, level l is 1 where all four
+    bytes of the 2 x 2 block below are (tensor slicing and & on the device)."""
+    B, h, w = mask.shape
+    sizes = pyramid_sizes(h, w, levels)
+    cur, parts = (mask != 0).to(torch.uint8), []
+    for l in range(levels):
+        if l:
+            hl, wl = sizes[l]
+            cur = cur[:, 0:2 * hl:2, 0:2 * wl:2] & cur[:, 0:2 * hl:2, 1:2 * wl:2] & cur[:, 1:2 * hl:2, 0:2 * wl:2] & cur[:, 1:2 * hl:2, 1:2 * wl:2]
+        parts.append(cur.reshape(B, -1))
+    return torch.cat(parts, 1).contiguous()
+
+
+def ecc_sums(a, t, H64, mask=None):
+    """bh_ecc_sums on buffers allocated here: a [B,Ha,Wa], t [B,Hb,Wb] float32 gray planes of one level (`pyramid_level` views),
+    H64 [B,3,3] float64, mask [B,Hb,Wb] uint8 or None -> sums [B,66] float64 (`ecc_sums_host`)."""
+    if not a.is_cuda:
+        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % a.device)
+    B = H64.shape[0]
+    partial = torch.empty((K.ecc_sums_ws_doubles(t.shape[1], t.shape[2], B),), dtype=torch.float64, device=a.device)
+    sums = torch.empty((B, ECC_SUMS), dtype=torch.float64, device=a.device)
+    return K.ecc_sums(a, t, H64, partial, sums, mask=mask)
+
+
+def ecc_state(H64):
+    """The state [B,24] float64 of a level that starts at H64 [B,3,3] (include/bihome.h bh_ecc_step): cur = best = H / H[2,2],
+    rho_best = -inf, nothing frozen, counters 0."""
+    B = H64.shape[0]
+    state = torch.zeros((B, K.ECC_STATE), dtype=torch.float64, device=H64.device)
+    h = H64.reshape(B, 9) / H64.reshape(B, 9)[:, 8:9]
+    state[:, 0:9], state[:, 9:18], state[:, 18] = h, h, float("-inf")
+    return state
+
+
+def ecc_step(sums, state, last=0):
+    """bh_ecc_step in place on `state`; -> (state, stats [B,3] float64 (written when last != 0))."""
+    stats = torch.zeros((state.shape[0], 3), dtype=torch.float64, device=state.device)
+    K.ecc_step(sums, state, last=last, stats=stats)
+    return state, stats
+
+
+def ecc_refine_pyramids(pyr_a, size_a, pyr_b, size_b, H64, levels, iters, mask_pyr=None):
+    """bh_ecc_refine on pyramids already built: -> (H [B,3,3] float64, stats [B,levels,3] float64); H64 itself is left as it is."""
+    B = H64.shape[0]
+    H = H64.reshape(B, 3, 3).clone()
+    stats = torch.empty((B, levels, 3), dtype=torch.float64, device=H64.device)
+    ws = torch.empty((K.ecc_refine_ws_doubles(size_b[0], size_b[1], B),), dtype=torch.float64, device=H64.device)
+    return K.ecc_refine(pyr_a, size_a, pyr_b, size_b, H, stats, ws, levels, iters, mask_pyr=mask_pyr)
+
+
+def _check_mask(mask, B, Hb, Wb, device):
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.device != device:
+        raise ValueError("ecc_refine: mask is a uint8 [B,Hb,Wb] tensor on the images' device")
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (B, Hb, Wb):
+        raise ValueError("ecc_refine: mask is uint8 [B,Hb,Wb] = [%d,%d,%d], got %s %s" % (B, Hb, Wb, mask.dtype, tuple(mask.shape)))
+    return mask.contiguous()
+
+
+def ecc_refine(images_a, images_b, H, levels=3, iters=10, idx_a=None, idx_b=None, mask=None):
+    """Coarse-to-fine ECC refinement on the device (`ecc_refine_host`): images_* uint8 [N,H*,W*,3] device tensors, H [B,3,3] float64 (B's
+    index coordinates -> A's), idx_* [B] int32 DEVICE tensors or None, mask [B,Hb,Wb] uint8 or None (non-zero: the pixel of B may count)
+    -> (H [B,3,3] float64 with H[2,2] = 1, stats [B,levels,3] = (rho at the level's first pass, rho_best, accepted steps), index 0 the
+    finest level).  ValueError, before any launch, for levels too deep for the images.  Nothing is copied to the host."""
+    if not (images_a.is_cuda and images_b.is_cuda and H.is_cuda):
+        raise RuntimeError("bihome_amd kernels need device tensors; there is no CPU path")
+    if H.dtype != torch.float64 or H.dim() < 2 or H.numel() != 9 * H.shape[0]:
+        raise ValueError("ecc_refine: H [B,3,3] float64, got %s %s" % (H.dtype, tuple(H.shape)))
+    if not iters >= 0:
+        raise ValueError("ecc_refine: iters >= 0, got %r" % (iters,))
+    B, (Ha, Wa), (Hb, Wb) = H.shape[0], images_a.shape[1:3], images_b.shape[1:3]
+    for h, w, what in ((Ha, Wa, "images_a"), (Hb, Wb, "images_b")):
+        try:
+            pyramid_sizes(h, w, levels)
+        except ValueError as e:
+            raise ValueError("ecc_refine: %s: %s" % (what, e)) from None
+    mask = _check_mask(mask, B, Hb, Wb, images_b.device)
+    pa, pb = gray_pyramid(images_a, B, levels, idx=idx_a), gray_pyramid(images_b, B, levels, idx=idx_b)
+    return ecc_refine_pyramids(pa, (Ha, Wa), pb, (Hb, Wb), H.contiguous(), levels, iters, mask_pyr=None if mask is None else mask_pyramid(mask, levels))
+
+
 class Aligner:
     """Aligner(model, patch=None, channels=None, mean=0.443, std=0.129): `model` is the Sequential(backbone, head) of step.build_model
     on the device.  patch / channels default to the model's PATCH_SIZE / PATCH_CHANNELS (channels to 1, upstream's grayscale pair,
     where the model does not say); mean / std are DictStandardize's (transforms.py:369-378).
 
-    aligner(images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True) -> dict
+    aligner(images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
+            refine_iters=10, mask_b=None) -> dict
         images_*: uint8 [N,H,W,3] device tensors or ImageBanks; the two may differ in size.
         idx_*: which image each of the B samples uses (host list: range-checked; int32 device tensor: clamped by the kernel;
                None: sample b is image b, so B = N).
@@ -246,6 +550,12 @@ class Aligner:
         'patch_1', 'patch_2'           what the model saw: [B,C,P,P] float32 of image A and of image B
         'geom_a', 'geom_b' [B,4]       the geometry records (sx, sy, tx, ty) of the two preparations
         'aligned' [B,Hb,Wb,3] uint8    image A resampled onto image B's grid; 'valid' [B,Hb,Wb] uint8 (both absent with warp=False)
+    refine="ecc" (default None: nothing below happens, the result is key for key the one above): between the lift and the warp the
+        homography is polished on the two images themselves by `ecc_refine` - refine_levels pyramid levels, refine_iters steps per level,
+        mask_b uint8 [B,Hb,Wb] on the device (non-zero: the pixel of B may count; moving objects, overlays) - and then
+        'H' is the refined matrix, 'H_model' the lifted one, 'rho' [B,2] the correlation coefficient at full size before and after,
+        'refine_stats' [B,levels,3] the whole table; 'aligned' / 'valid' come from the refined 'H'.  Levels too deep for the images
+        raise a ValueError that names the sizes, before any launch.
     The aligner copies nothing from the device to the host (host-given idx / roi values are uploaded).  What a model's own
     predict_homography does is the model's: NoOpHead '4_points' and PhotometricHead read the patch extent off 'corners' with .item()."""
 
@@ -278,8 +588,11 @@ class Aligner:
             self._square = c
         return c
 
-    def __call__(self, images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True):
+    def __call__(self, images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
+                 refine_iters=10, mask_b=None):
         from .step import predict
+        if refine not in (None, "ecc"):
+            raise ValueError("Aligner: refine is None or 'ecc', got %r" % (refine,))
         a, b = _images(images_a, "images_a"), _images(images_b, "images_b")
         if a.device != b.device:
             raise ValueError("Aligner: images_a is on %s, images_b on %s" % (a.device, b.device))
@@ -291,6 +604,17 @@ class Aligner:
         B, P = na, self.patch
         ra = _regions(roi_a, B, a.shape[1], a.shape[2], a.device, "roi_a")
         rb = _regions(roi_b, B, b.shape[1], b.shape[2], b.device, "roi_b")
+        if refine is not None:
+            for img, what in ((a, "images_a"), (b, "images_b")):
+                try:
+                    pyramid_sizes(img.shape[1], img.shape[2], refine_levels)
+                except ValueError as e:
+                    raise ValueError("Aligner: refine_levels, %s: %s" % (what, e)) from None
+            if not refine_iters >= 0:
+                raise ValueError("Aligner: refine_iters >= 0, got %r" % (refine_iters,))
+            mask_b = _check_mask(mask_b, B, b.shape[1], b.shape[2], b.device)
+        elif mask_b is not None:
+            raise ValueError("Aligner: mask_b restricts the pixels the refinement counts; pass refine='ecc' with it")
         with torch.cuda.device(a.device):
             p1, ga = prepare(a, B, P, self.channels, self.mean, self.std, idx=ia, roi=ra)
             p2, gb = prepare(b, B, P, self.channels, self.mean, self.std, idx=ib, roi=rb)
@@ -299,6 +623,9 @@ class Aligner:
             delta_hat = delta_hat.detach().reshape(B, 4, 2)
             H = lift_device(delta_hat, P, ga, gb)
             out = {"delta_hat": delta_hat, "H": H, "patch_1": p1, "patch_2": p2, "geom_a": ga, "geom_b": gb}
+            if refine is not None:
+                H, stats = ecc_refine(a, b, H, refine_levels, refine_iters, idx_a=ia, idx_b=ib, mask=mask_b)
+                out.update({"H_model": out["H"], "H": H, "refine_stats": stats, "rho": stats[:, 0, :2]})
             if warp:
                 out["aligned"], out["valid"] = warp_u8(a, H, b.shape[1], b.shape[2], idx=ia)
         return out

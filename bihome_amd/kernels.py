@@ -6,7 +6,7 @@ import os
 import torch
 
 from ._lib import (AMAX_FLOATS, BN_DETERMINISTIC, DSAC_METHODS, F_DETERMINISTIC, GEOMETRY_FIELDS, ROUTE_DETERMINISTIC, ROUTE_WX3_PC, ROUTE_WX3_SHARED, BhBnIn, BhBnReduce, BhConvDesc,
-                   BhPack3x3Job, check, lib)
+                   BhPack3x3Job, ECC_STATE, ECC_SUMS, check, lib)
 
 
 def _p(t):
@@ -1622,3 +1622,93 @@ def warp_u8(images, H64, out, valid=None, idx=None):
     check(lib.bh_warp_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(H64), B, out.shape[1], out.shape[2],
                          _p(out), _p(valid), _stream()), "bh_warp_u8")
     return out, valid
+
+
+# ------------------------------------------------------------------------------------------------
+# ECC refinement of the lifted homography (bihome_amd/align.py; csrc/ecc.hip).  Every buffer is the caller's.
+# ------------------------------------------------------------------------------------------------
+def _size_query(fn, name, *args):
+    out = ctypes.c_int64(0)
+    check(fn(*args, ctypes.byref(out)), name)
+    return int(out.value)
+
+
+def gray_pyramid_layout(H, W, levels):
+    """offsets [levels + 1] (floats) of the levels inside a sample's packed pyramid row; the last is the row's length (host only)."""
+    off = (ctypes.c_int64 * 8)()                         # (at most 6 levels; a refused call writes nothing)
+    check(lib.bh_gray_pyramid_layout(int(H), int(W), int(levels), off), "bh_gray_pyramid_layout")
+    return [int(v) for v in off[:levels + 1]]
+
+
+def ecc_sums_ws_doubles(Hb, Wb, B):
+    return _size_query(lib.bh_ecc_sums_ws_doubles, "bh_ecc_sums_ws_doubles", int(Hb), int(Wb), int(B))
+
+
+def ecc_refine_ws_doubles(Hb, Wb, B):
+    return _size_query(lib.bh_ecc_refine_ws_doubles, "bh_ecc_refine_ws_doubles", int(Hb), int(Wb), int(B))
+
+
+def gray_pyramid_u8(images, pyr, levels, idx=None):
+    """pyr [B,total] float32 = the gray box pyramids of B samples of the uint8 bank images [N,H,W,3], levels packed one after another
+    (include/bihome.h bh_gray_pyramid_u8; total = gray_pyramid_layout(H, W, levels)[-1]).  pyr is the caller's."""
+    _chk(pyr)
+    if pyr.dim() != 2:
+        raise ValueError("gray_pyramid_u8: pyr [B,total] float32, got %s" % (tuple(pyr.shape),))
+    B = pyr.shape[0]
+    _chk_images_u8(images, idx, B, "gray_pyramid_u8")
+    total = gray_pyramid_layout(images.shape[1], images.shape[2], levels)[-1]
+    if pyr.shape[1] != total:
+        raise ValueError("gray_pyramid_u8: %d levels of %d x %d take %d floats per sample, pyr has %d" % (levels, images.shape[1], images.shape[2], total, pyr.shape[1]))
+    check(lib.bh_gray_pyramid_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], B, int(levels), _p(pyr), _stream()),
+          "bh_gray_pyramid_u8")
+    return pyr
+
+
+def ecc_sums(a, t, H64, partial, sums, mask=None):
+    """One ECC pass at one level (include/bihome.h bh_ecc_sums): a [B,Ha,Wa], t [B,Hb,Wb] float32 gray planes (views of pyramid rows are
+    fine: the last two dimensions dense), H64 [B,3,3] float64, mask [B,Hb,Wb] uint8 or None -> sums [B,66] float64.  partial (float64,
+    ecc_sums_ws_doubles(Hb, Wb, B) elements) and sums are the caller's."""
+    _chk(H64, torch.float64); _chk(partial, torch.float64); _chk(sums, torch.float64); _chk(mask, torch.uint8)
+    for x in (a, t):                                     # (views: device and dtype here, the layout below)
+        if not x.is_cuda:
+            raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % x.device)
+        if x.dtype != torch.float32:
+            raise TypeError("expected %s, got %s" % (torch.float32, x.dtype))
+    B = H64.shape[0]
+    for x, what in ((a, "a"), (t, "t")):
+        if x.dim() != 3 or x.shape[0] != B or x.stride(2) != 1 or x.stride(1) != x.shape[2] or (B > 1 and x.stride(0) < x.shape[1] * x.shape[2]):
+            raise ValueError("ecc_sums: %s [B,H,W] float32 with dense planes and B = %d, got %s strides %s" % (what, B, tuple(x.shape), x.stride()))
+    if H64.numel() != 9 * B or tuple(sums.shape) != (B, ECC_SUMS) or (mask is not None and tuple(mask.shape) != tuple(t.shape)):
+        raise ValueError("ecc_sums: H64 [B,3,3], sums [B,66], mask [B,Hb,Wb]")
+    (Ha, Wa), (Hb, Wb) = a.shape[1:], t.shape[1:]
+    if partial.numel() < ecc_sums_ws_doubles(Hb, Wb, B):
+        raise ValueError("ecc_sums: partial has %d doubles, %d are needed" % (partial.numel(), ecc_sums_ws_doubles(Hb, Wb, B)))
+    sa, st = (a.stride(0), t.stride(0)) if B > 1 else (Ha * Wa, Hb * Wb)
+    check(lib.bh_ecc_sums(a.data_ptr(), Ha, Wa, sa, t.data_ptr(), Hb, Wb, st, _p(mask), _p(H64), B, _p(partial), _p(sums), _stream()), "bh_ecc_sums")
+    return sums
+
+
+def ecc_step(sums, state, last=0, stats=None):
+    """One ECC step and the books of its level on state [B,24] float64, in place (include/bihome.h bh_ecc_step); stats [B,3] float64 or
+    None receives (rho first, rho_best, accepted) when last != 0."""
+    _chk(sums, torch.float64); _chk(state, torch.float64); _chk(stats, torch.float64)
+    B = state.shape[0]
+    if tuple(state.shape) != (B, ECC_STATE) or tuple(sums.shape) != (B, ECC_SUMS) or (stats is not None and tuple(stats.shape) != (B, 3)):
+        raise ValueError("ecc_step: sums [B,66], state [B,24], stats [B,3] float64")
+    check(lib.bh_ecc_step(_p(sums), _p(state), B, int(last), _p(stats), 3, _stream()), "bh_ecc_step")
+    return state
+
+
+def ecc_refine(pyr_a, size_a, pyr_b, size_b, H64, stats, ws, levels, iters, mask_pyr=None):
+    """The whole coarse-to-fine refinement, enqueued on the current stream (include/bihome.h bh_ecc_refine): H64 [B,3,3] float64 is the
+    start and becomes the result; stats [B,levels,3] float64; ws float64 with ecc_refine_ws_doubles(Hb, Wb, B) elements.  All the caller's."""
+    _chk(pyr_a); _chk(pyr_b); _chk(H64, torch.float64); _chk(stats, torch.float64); _chk(ws, torch.float64); _chk(mask_pyr, torch.uint8)
+    B, (Ha, Wa), (Hb, Wb) = H64.shape[0], size_a, size_b
+    ta, tb = gray_pyramid_layout(Ha, Wa, levels)[-1], gray_pyramid_layout(Hb, Wb, levels)[-1]
+    if tuple(pyr_a.shape) != (B, ta) or tuple(pyr_b.shape) != (B, tb) or (mask_pyr is not None and tuple(mask_pyr.shape) != (B, tb)):
+        raise ValueError("ecc_refine: pyr_a [B,%d], pyr_b [B,%d] (and mask_pyr like pyr_b) with B = %d, got %s, %s" % (ta, tb, B, tuple(pyr_a.shape), tuple(pyr_b.shape)))
+    if H64.numel() != 9 * B or tuple(stats.shape) != (B, levels, 3) or ws.numel() < ecc_refine_ws_doubles(Hb, Wb, B):
+        raise ValueError("ecc_refine: H64 [B,3,3], stats [B,levels,3], ws of ecc_refine_ws_doubles() float64")
+    check(lib.bh_ecc_refine(_p(pyr_a), Ha, Wa, _p(pyr_b), Hb, Wb, _p(mask_pyr), B, int(levels), int(iters), _p(H64), _p(stats), _p(ws), _stream()),
+          "bh_ecc_refine")
+    return H64, stats

@@ -859,6 +859,67 @@ int bh_align_prep_u8(const uint8_t* images, const int* idx, int n_images, int H,
 int bh_warp_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* H64,
                int B, int Ho, int Wo, uint8_t* out, uint8_t* valid, void* stream);
 
+/* ECC refinement: a photometric polish of the lifted homography on the two images themselves, coarse to fine - the forward-additive
+ * enhanced-correlation-coefficient iteration (Evangelidis & Psarakis 2008; what cv2.findTransformECC does on the host), which does not
+ * see a gain or a bias between the images.  Fixed work, no early exit, no atomics: two calls give equal bits.  The numpy float64
+ * statements are bihome_amd/align.py's gray_pyramid_host, ecc_sums_host, ecc_step_host, ecc_refine_host.  Index coordinates throughout.
+ *
+ * Pyramid.  Level 0 is g = fmaf(0.114, B, fmaf(0.587, G, 0.299 R)) of the uint8 image (float, 0..255); level l is the 2 x 2 box mean
+ * ((a + b) + (c + d)) * 0.25 of level l - 1 and has (h >> 1, w >> 1) pixels (an odd last row / column is dropped); pixel x of level l
+ * sits at 2 x + 0.5 of level l - 1, so with C = [[2,0,.5],[0,2,.5],[0,0,1]] a homography moves a level down (finer) as C H C^-1 and up
+ * as C^-1 H C, rescaled to H[8] = 1.  pyr[B, total] float holds a sample's levels one after another: bh_gray_pyramid_layout writes
+ * offsets[levels + 1] (HOST memory, in floats; offsets[levels] = total).  images / idx / n_images as in bh_align_prep_u8 (idx clamped,
+ * 64-bit image offsets).  One writer per element; bitwise a float32 restatement.
+ * BH_E_BADARG: a NULL images / pyr / offsets, B < 0, n_images < 1, H < 1, W < 1; then BH_E_UNSUPPORTED: levels outside 1..6, a coarsest
+ * level under 8 pixels on a side, H * W > 2^29; then B == 0: BH_OK, nothing launched.  Refusals return before any launch. */
+#define BH_ECC_SUMS 66
+#define BH_ECC_STATE 24
+int bh_gray_pyramid_layout(int H, int W, int levels, int64_t* offsets);
+int bh_gray_pyramid_u8(const uint8_t* images, const int* idx, int n_images, int H, int W, int B, int levels, float* pyr, void* stream);
+
+/* One pass at one level.  a: B gray planes Ha x Wa of image A, a_stride floats apart; t: B planes Hb x Wb of image B, t_stride floats
+ * apart; mask[B,Hb,Wb] uint8 (NULL ok); H64[B,9] double maps t's index coordinates to a's and is used as H / H[8].  For every pixel
+ * (x, y) of t: q = H (x, y, 1), (u, v) = (qx, qy) / qz by csrc/warp_tap.h's tap_project / tap_place - the taps bh_warp_u8 takes.  The
+ * pixel COUNTS iff qz > 1e-8, 0 <= u < Wa - 1, 0 <= v < Ha - 1 (all four taps a00 a01 a10 a11 inside a) and its mask byte is non-zero.
+ * With the fractions fx, fy: iw = the bilinear value, gx = (1-fy)(a01-a00) + fy(a11-a10), gy = (1-fx)(a10-a00) + fx(a11-a01) (the
+ * exact derivative of the interpolant), m = -(gx u + gy v), j = (gx x, gx y, gx, gy x, gy y, gy, m x, m y) / qz = d iw / d H[0..7].
+ * sums[B,66] double = the upper triangle, row-major (entry (i, j), i <= j, at 11 i - i (i - 1) / 2 + j - i), of sum z z^T over the
+ * counting pixels, z = (j0..j7, iw, t, 1): entry 65 is n, (8,10) sum iw, (9,10) sum t, (8,8) (9,9) (8,9) the second moments, (i,10)
+ * sum j_i, (i,8) sum j_i iw, (i,9) sum j_i t.  Per-pixel terms are float and no float accumulator carries more than 16 pixels; beyond
+ * that the sums are double.  partial: scratch of bh_ecc_sums_ws_doubles() doubles (written to HOST memory by that query), one block of
+ * 66 per workgroup, overwritten, then added in block-index order.
+ * BH_E_BADARG: a NULL a / t / H64 / partial / sums (doubles for the query), B < 0, Ha, Wa, Hb, Wb < 1, a stride shorter than its plane;
+ * then BH_E_UNSUPPORTED: Ha * Wa or Hb * Wb > 2^29; then B == 0: BH_OK, nothing launched. */
+int bh_ecc_sums_ws_doubles(int Hb, int Wb, int B, int64_t* doubles);
+int bh_ecc_sums(const float* a, int Ha, int Wa, int64_t a_stride, const float* t, int Hb, int Wb, int64_t t_stride, const uint8_t* mask,
+                const double* H64, int B, double* partial, double* sums, void* stream);
+
+/* One step and the books of a level, all double.  With n, the means m_iw = sum iw / n, m_t = sum t / n, |iw'|^2 = sum iw^2 - n m_iw^2,
+ * |t'|^2 likewise, <iw',t'> = sum iw t - n m_iw m_t: rho = <iw',t'> / sqrt(|iw'|^2 |t'|^2); G = sum j j^T - (sum j)(sum j)^T / n,
+ * a = sum j iw - m_iw sum j, c = sum j t - m_t sum j; G (ya, yc) = (a, c) by 8 x 8 Gaussian elimination with partial pivoting;
+ * lambda = (|iw'|^2 - a.ya) / (<iw',t'> - c.ya); d = lambda yc - ya.  The step FAILS for n < 16, a variance not positive, a zero or NaN
+ * pivot, a denominator of lambda not > 0, or a d that is not finite.
+ * state[B, BH_ECC_STATE] double: 0..8 cur, 9..17 best, 18 rho_best (-inf at the start of a level), 19 frozen (0 / 1), 20 rho at the
+ * level's first pass, 21 accepted steps, 22 passes done, 23 unused.  A sample that is not frozen and whose rho rose above rho_best
+ * takes best = cur, rho_best = rho and then, if last == 0 and the step did not fail, cur[0..7] += d, cur[8] = 1 - else it freezes; one
+ * whose rho did not rise (or is NaN) takes cur = best and freezes; a frozen sample changes nothing.  last = 1, the level's final pass:
+ * cur = best, and stats (NULL ok; sample b at stats + b * stats_stride) = (rho first, rho_best, accepted steps).  last = 2: as 1, then
+ * cur = best = C cur C^-1 (a level down) with the books reset.
+ * BH_E_BADARG: a NULL sums / state, B < 0, last outside 0..2, stats with stats_stride < 3; B == 0: BH_OK, nothing launched. */
+int bh_ecc_step(const double* sums, double* state, int B, int last, double* stats, int stats_stride, void* stream);
+
+/* The whole refinement on one stream, without allocation or host synchronisation (capturable): H64[B,9] (in: the start at level 0, out:
+ * the result, H[8] = 1) is taken to level levels - 1; every level runs iters + 1 passes (iters steps at most) and hands its best to
+ * the next finer one.  pyr_a / pyr_b: pyramids of bh_gray_pyramid_u8 for Ha x Wa and Hb x Wb with the same `levels`; mask_pyr (NULL ok)
+ * uint8 [B, total of B's pyramid] in the same layout, non-zero = the pixel of B may count.  stats[B, levels, 3] = (rho at the level's
+ * first pass, rho_best, accepted steps), index 0 the FINEST level.  ws: bh_ecc_refine_ws_doubles() doubles (HOST memory query).
+ * BH_E_BADARG: a NULL pyr_a / pyr_b / H64 / stats / ws (doubles for the query), B < 0, a size < 1, iters < 0; then BH_E_UNSUPPORTED:
+ * levels outside 1..6 or a coarsest level of either image under 8 pixels on a side, more than 2^29 pixels; then B == 0: BH_OK, nothing
+ * launched.  Refusals return before any launch. */
+int bh_ecc_refine_ws_doubles(int Hb, int Wb, int B, int64_t* doubles);
+int bh_ecc_refine(const float* pyr_a, int Ha, int Wa, const float* pyr_b, int Hb, int Wb, const uint8_t* mask_pyr, int B, int levels, int iters,
+                  double* H64, double* stats, double* ws, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */
