@@ -33,7 +33,17 @@ Refinement (optional, `Aligner(..., refine="ecc")` / `ecc_refine`; csrc/ecc.hip)
 sx, sy, so H_img is polished on the two images themselves before the warp - the forward-additive enhanced-correlation-coefficient
 iteration (Evangelidis & Psarakis; what cv2.findTransformECC does on the host) on gray 2 x 2 box pyramids, coarse to fine, blind to a gain
 and a bias between the images, with the exact derivative of the bilinear interpolant at warp_tap.h's taps, a fixed number of passes per
-level and the best H so far kept.  Stated below as gray_pyramid_host / ecc_sums_host / ecc_step_host / ecc_level_host / ecc_refine_host."""
+level and the best H so far kept.  Stated below as gray_pyramid_host / ecc_sums_host / ecc_step_host / ecc_level_host / ecc_refine_host.
+
+Cascade (optional, `aligner(..., cascade=K)`; csrc/cascade.hip): the models are trained on corner displacements of at most P / 4 patch
+pixels and their error grows with the displacement, so the model is run again on A SEEN THROUGH the current H - stage k reads
+patch_1 = A through H_prev on B's patch grid (bh_align_prep_warp_u8: the mean of nx x ny bilinear samples per patch pixel, no full-size
+intermediate image) and patch_2 = B's patch, predicts only the residual delta_k, and the stages compose: patch coordinate q of that
+patch_1 is A's coordinate H_prev A_b q, hence H_k = H_prev A_b H_p(delta_k) A_b^-1, still B's index coordinates -> A's.  A stage is kept
+only where it raises the zero-mean normalised correlation of the two patches over the fully covered pixels (bh_patch_ncc), decided per
+sample on the device.  Stated below as sample_host / grid_map / prep_warp_host / patch_ncc_host / cascade_compose."""
+import operator
+
 import numpy as np
 import torch
 
@@ -132,6 +142,105 @@ def warp_u8_host(images, H, Ho, Wo):
             valid[b] = ~guard & (u >= 0) & (u <= Ws - 1) & (v >= 0) & (v <= Hs - 1)
         out[b] = np.floor(np.clip(acc, 0.0, 255.0) + 0.5).astype(np.uint8)
     return out, valid
+
+
+# ------------------------------------------------------------------------------------------------
+# cascaded re-prediction, the definitions (numpy float64; include/bihome.h "Cascaded re-prediction" states the same in C terms)
+# ------------------------------------------------------------------------------------------------
+def _sample_host(images, H, Ho, Wo):
+    """(values float64 [B,Ho,Wo,3], valid bool [B,Ho,Wo], guard bool [B,Ho,Wo]): warp_u8_host's arithmetic up to its rounding."""
+    images = np.asarray(images)
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
+        raise ValueError("sample_host: images uint8 [B,Hs,Ws,3], got %s %s" % (images.dtype, images.shape))
+    H = np.asarray(H, np.float64).reshape(-1, 3, 3)
+    B, Hs, Ws = images.shape[:3]
+    out, valid, guards = np.empty((B, Ho, Wo, 3)), np.empty((B, Ho, Wo), bool), np.empty((B, Ho, Wo), bool)
+    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(np.float64)
+    for b in range(B):
+        h, img = H[b], images[b].astype(np.float64)
+        qz = h[2, 0] * xs + h[2, 1] * ys + h[2, 2]
+        guard = ~(np.abs(qz) > QZ_GUARD)
+        iz = 1.0 / np.where(guard, 1.0, qz)
+        u, v = (h[0, 0] * xs + h[0, 1] * ys + h[0, 2]) * iz, (h[1, 0] * xs + h[1, 1] * ys + h[1, 2]) * iz
+        with np.errstate(invalid="ignore"):
+            x0f, y0f = np.floor(u), np.floor(v)
+            fx, fy = u - x0f, v - y0f
+            x0 = np.clip(np.nan_to_num(x0f, nan=-2.0), -2, Ws).astype(np.int64)
+            y0 = np.clip(np.nan_to_num(y0f, nan=-2.0), -2, Hs).astype(np.int64)
+            acc = np.zeros((Ho, Wo, 3))
+            for dy, wy in ((0, 1 - fy), (1, fy)):
+                for dx, wx in ((0, 1 - fx), (1, fx)):
+                    xi, yi = x0 + dx, y0 + dy
+                    ok = (xi >= 0) & (xi < Ws) & (yi >= 0) & (yi < Hs)
+                    w = np.where(ok, wy * wx, 0.0)
+                    acc += img[np.clip(yi, 0, Hs - 1), np.clip(xi, 0, Ws - 1)] * np.nan_to_num(w)[..., None]
+            valid[b] = ~guard & (u >= 0) & (u <= Ws - 1) & (v >= 0) & (v <= Hs - 1)
+        out[b], guards[b] = acc, guard
+    return out, valid, guards
+
+
+def sample_host(images, H, Ho, Wo):
+    """images uint8 [B,Hs,Ws,3], H [B,3,3] (output index coordinates -> source index coordinates) -> (values float64 [B,Ho,Wo,3], the
+    bilinear samples with zero padding, NOT rounded or clamped; valid uint8 [B,Ho,Wo]): `warp_u8_host` without its rounding."""
+    values, valid, _ = _sample_host(images, H, Ho, Wo)
+    return values, valid.astype(np.uint8)
+
+
+def grid_map(geom, nx, ny):
+    """geom [B,4], the sub-samples per patch pixel -> A S [B,3,3]: index coordinates of the P ny x P nx sub-sample grid -> image index
+    coordinates.  Grid column X = x nx + i is the sub-sample at patch coordinate x + (i + 0.5) / nx - 0.5: S = [[1/nx, 0, 0.5/nx - 0.5],
+    [0, 1/ny, 0.5/ny - 0.5], [0, 0, 1]]."""
+    S = np.array([[1.0 / nx, 0.0, 0.5 / nx - 0.5], [0.0, 1.0 / ny, 0.5 / ny - 0.5], [0.0, 0.0, 1.0]])
+    return _affine(geom) @ S
+
+
+def prep_warp_host(images, Hg, P=128, C=1, nx=1, ny=1, mean=0.443, std=0.129):
+    """images uint8 [B,Hs,Ws,3], Hg [B,3,3] (index coordinates of the P ny x P nx sub-sample grid -> image index coordinates) ->
+    (patch [B,C,P,P] float64, cover [B,P,P] float64): patch pixel (y, x) is the mean over grid rows y ny .. y ny + ny - 1 and columns
+    x nx .. x nx + nx - 1 of the bilinear sample (taps outside the image 0; a sample under the guard |qz| <= 1e-8 is 0), as gray
+    0.299 R + 0.587 G + 0.114 B (C = 1) or per channel (C = 3), then (v / 255 - mean) / std; cover is the share of its sub-samples that
+    are valid by warp_u8_host's rule - 1.0 exactly where all are."""
+    if C not in (1, 3):
+        raise ValueError("prep_warp_host: C is 1 (grayscale) or 3 (RGB), got %r" % (C,))
+    values, valid, guard = _sample_host(images, Hg, P * ny, P * nx)
+    B = values.shape[0]
+    values = np.where(guard[..., None], 0.0, values)
+    m = values.reshape(B, P, ny, P, nx, 3).sum(axis=(2, 4)) / (nx * ny)                     # [B,P,P,3]
+    v = (0.299 * m[..., 0] + 0.587 * m[..., 1] + 0.114 * m[..., 2])[:, None] if C == 1 else m.transpose(0, 3, 1, 2)
+    cover = valid.reshape(B, P, ny, P, nx).sum(axis=(2, 4)) / float(nx * ny)
+    return (v / 255.0 - mean) / std, cover
+
+
+def patch_ncc_host(w, t, cover=None):
+    """w, t [B,C,P,P], cover [B,P,P] or None -> [B,8] float64 (n, sum w, sum t, sum ww, sum tt, sum wt, rho, 0) over all channels of the
+    pixels with cover == 1 (None: all): rho = (n sum wt - sum w sum t) / sqrt((n sum ww - (sum w)^2)(n sum tt - (sum t)^2)) for
+    n >= ECC_MIN_N and both variances positive, else -inf."""
+    w, t = np.asarray(w, np.float64), np.asarray(t, np.float64)
+    B, C = w.shape[:2]
+    out = np.zeros((B, 8))
+    for b in range(B):
+        keep = np.ones(w.shape[2:], bool) if cover is None else np.asarray(cover[b]) == 1.0
+        a, c = w[b][:, keep].ravel(), t[b][:, keep].ravel()
+        n, sw, st, sww, stt, swt = float(a.size), a.sum(), c.sum(), (a * a).sum(), (c * c).sum(), (a * c).sum()
+        num, va, vt = n * swt - sw * st, n * sww - sw * sw, n * stt - st * st
+        rho = num / np.sqrt(va * vt) if (n >= ECC_MIN_N and va > 0 and vt > 0) else -np.inf
+        out[b] = n, sw, st, sww, stt, swt, rho, 0.0
+    return out
+
+
+def cascade_compose(H_prev, delta, P, geom_b):
+    """H_prev [B,3,3] (B's index coordinates -> A's), delta [B,4,2] predicted on (A seen through H_prev on B's patch grid, B's patch),
+    geom_b [B,4] -> H_prev A_b H_p(delta) A_b^-1 [B,3,3] scaled to H[2,2] = 1, H_p = four_point_to_homography of the patch square as in
+    `lift`: patch coordinate q of the warped patch is A's coordinate H_prev A_b q, so the product still maps B's coordinates to A's."""
+    Hp = np.asarray(H_prev, np.float64).reshape(-1, 3, 3)
+    d = np.asarray(delta, np.float64).reshape(-1, 4, 2)
+    Ab = _affine(geom_b)
+    c = patch_corners(P)
+    H = np.empty_like(Hp)
+    for b in range(Hp.shape[0]):
+        Hb = Hp[b] @ Ab[b] @ synth.four_point_homography(c, c + d[b]) @ np.linalg.inv(Ab[b])
+        H[b] = Hb / Hb[2, 2]
+    return H
 
 
 # ------------------------------------------------------------------------------------------------
@@ -433,6 +542,53 @@ def warp_u8(images, H64, Ho, Wo, idx=None, want_valid=True):
     return K.warp_u8(images, H64, out, valid, idx=idx)
 
 
+def prepare_warped(images, Hg, B, patch, channels, nx, ny, mean=0.443, std=0.129, idx=None):
+    """bh_align_prep_warp_u8 on outputs allocated here: (patch [B,C,P,P] float32, cover [B,P,P] float32) of B samples of the uint8 bank
+    images [N,Hs,Ws,3] seen through Hg [B,3,3] float64 (`prep_warp_host`; Hg = H @ grid_map(geom_b, nx, ny)); idx [B] int32 DEVICE tensor
+    or None (kernels.align_prep_warp_u8)."""
+    if not images.is_cuda:
+        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % images.device)
+    out = torch.empty((B, channels, patch, patch), dtype=torch.float32, device=images.device)
+    cover = torch.empty((B, patch, patch), dtype=torch.float32, device=images.device)
+    return K.align_prep_warp_u8(images, Hg, out, cover, nx, ny, mean, std, idx=idx)
+
+
+def patch_ncc(w, t, cover=None):
+    """bh_patch_ncc on an output allocated here: w, t [B,C,P,P] float32, cover [B,P,P] float32 or None -> [B,8] float64
+    (n, sum w, sum t, sum ww, sum tt, sum wt, rho, 0) (`patch_ncc_host`)."""
+    if not w.is_cuda:
+        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % w.device)
+    out = torch.empty((w.shape[0], 8), dtype=torch.float64, device=w.device)
+    return K.patch_ncc(w, t, cover, out)
+
+
+def cascade_compose_device(H_prev, delta, P, geom_b):
+    """`cascade_compose` on the device: H_prev [B,3,3] float64, delta [B,4,2] float32, geom_b [B,4] float64 -> H [B,3,3] float64.  The
+    8 x 8 solve is bh_h4pt_fwd's, the rest batched [B,3,3] double arithmetic, as in `lift_device`."""
+    B = delta.shape[0]
+    Hp = K.h4pt_fwd(delta.reshape(B, 4, 2).to(torch.float32).contiguous(), P)[0].view(B, 3, 3)
+    H = H_prev @ _affine_dev(geom_b) @ Hp @ _affine_dev(geom_b, inverse=True)
+    return (H / H[:, 2:3, 2:3]).contiguous()
+
+
+def _cascade_samples(samples, roi_b, Hb, Wb, P):
+    """(nx, ny): given, or min(8, max(1, ceil(s))) per axis with s the largest rw_b / P (rh_b / P) of the batch - host values only."""
+    if samples is not None:
+        try:
+            nx, ny = (operator.index(v) for v in samples)
+        except (TypeError, ValueError):
+            raise ValueError("Aligner: cascade_samples is (nx, ny), two integers in 1..8, got %r" % (samples,)) from None
+        if not (1 <= nx <= 8 and 1 <= ny <= 8):
+            raise ValueError("Aligner: cascade_samples is (nx, ny), two integers in 1..8, got %r" % (samples,))
+        return nx, ny
+    if roi_b is None:
+        rw, rh = float(Wb), float(Hb)
+    else:
+        r = np.asarray(roi_b.numpy() if isinstance(roi_b, torch.Tensor) else roi_b, np.float64).reshape(-1, 4)
+        rw, rh = float(r[:, 2].max()), float(r[:, 3].max())
+    return tuple(min(8, max(1, int(np.ceil(s / P)))) for s in (rw, rh))
+
+
 def gray_pyramid(images, B, levels, idx=None):
     """bh_gray_pyramid_u8 on an output allocated here: pyr [B,total] float32, the gray box pyramids of B samples of the uint8 bank
     images [N,H,W,3] with the levels packed one after another (`pyramid_offsets`; `pyramid_level` views one).  idx [B] int32 DEVICE
@@ -539,7 +695,7 @@ class Aligner:
     where the model does not say); mean / std are DictStandardize's (transforms.py:369-378).
 
     aligner(images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
-            refine_iters=10, mask_b=None) -> dict
+            refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25) -> dict
         images_*: uint8 [N,H,W,3] device tensors or ImageBanks; the two may differ in size.
         idx_*: which image each of the B samples uses (host list: range-checked; int32 device tensor: clamped by the kernel;
                None: sample b is image b, so B = N).
@@ -556,6 +712,17 @@ class Aligner:
         'H' is the refined matrix, 'H_model' the lifted one, 'rho' [B,2] the correlation coefficient at full size before and after,
         'refine_stats' [B,levels,3] the whole table; 'aligned' / 'valid' come from the refined 'H'.  Levels too deep for the images
         raise a ValueError that names the sizes, before any launch.
+    cascade=K (default 0: nothing below happens, no further launch, the result is key for key and bit for bit the one above),
+        cascade_samples=None, cascade_min_cover=0.25: after the lift the model predicts K more times, each time on A seen through the best
+        H so far (`prepare_warped`, nx x ny bilinear samples per patch pixel: cascade_samples=(nx, ny), or min(8, max(1, ceil(s))) per
+        axis with s the largest rw_b / P, rh_b / P of the batch) against patch_2, and the candidate `cascade_compose_device` makes of it
+        replaces the best where its score - the correlation of the two patches over the fully covered pixels, `patch_ncc` - is higher
+        and counts at least cascade_min_cover C P P elements.  Every sample runs every stage; the choice is torch.where on the device.
+        'H' is then the best candidate, 'H_stages' [B,K+1,3,3] all of them (index 0 the lift), 'delta_stages' [B,K+1,4,2] the prediction
+        of each stage, 'score' [B,K+1] float64 their correlations, 'accepted' [B,K+1] uint8 (index 0 always 1), 'patch_1_warped' A
+        through 'H' as the model last saw it; 'delta_hat', 'patch_1', 'geom_*' stay stage 0's.  With refine="ecc" the refinement starts
+        from the cascade's 'H', and 'H_model' is that matrix.  A cascade that is no integer >= 0, samples outside 1..8 and a
+        cascade_min_cover outside [0, 1] raise a ValueError before any launch.
     The aligner copies nothing from the device to the host (host-given idx / roi values are uploaded).  What a model's own
     predict_homography does is the model's: NoOpHead '4_points' and PhotometricHead read the patch extent off 'corners' with .item()."""
 
@@ -588,11 +755,51 @@ class Aligner:
             self._square = c
         return c
 
+    def _cascade(self, predict, a, ia, p2, gb, H0, delta0, stages, nx, ny, min_cover):
+        """The stages after the lift, all on the device: every sample runs every stage, a candidate replaces the best so far where its
+        score is higher on enough elements (torch.where; False for a NaN or -inf score).  -> the keys the cascade adds or replaces."""
+        B, P, dev = H0.shape[0], self.patch, H0.device
+        G = _affine_dev(gb)                                                    # `grid_map`, A_b S written out (no upload): sub-sample grid ->
+        G[:, 0, 2] += G[:, 0, 0] * (0.5 / nx - 0.5)                            # B's index coordinates
+        G[:, 1, 2] += G[:, 1, 1] * (0.5 / ny - 0.5)
+        G[:, 0, 0] *= 1.0 / nx
+        G[:, 1, 1] *= 1.0 / ny
+        need = float(min_cover) * self.channels * P * P
+
+        def seen(Hc):                                                          # A through Hc as the model's patch, and its score
+            W, cov = prepare_warped(a, (Hc @ G).contiguous(), B, P, self.channels, nx, ny, self.mean, self.std, idx=ia)
+            return W, patch_ncc(W, p2, cov)
+        H_best = H0
+        W_best, o = seen(H_best)
+        s_best = o[:, 6]
+        Hs, deltas, scores, accepted = [H0], [delta0], [s_best], [torch.ones(B, dtype=torch.uint8, device=dev)]
+        for _ in range(stages):
+            d = predict(self.model, {self.patch_keys[0]: W_best, self.patch_keys[1]: p2, "corners": self._corners(B, dev)})
+            d = d.detach().reshape(B, 4, 2)
+            H_c = cascade_compose_device(H_best, d, P, gb)
+            W_c, o = seen(H_c)
+            take = (o[:, 6] > s_best) & (o[:, 0] >= need)
+            H_best = torch.where(take[:, None, None], H_c, H_best)
+            W_best = torch.where(take[:, None, None, None], W_c, W_best)
+            s_best = torch.where(take, o[:, 6], s_best)
+            Hs.append(H_c); deltas.append(d); scores.append(o[:, 6]); accepted.append(take.to(torch.uint8))
+        return {"H": H_best, "H_stages": torch.stack(Hs, 1), "delta_stages": torch.stack(deltas, 1), "score": torch.stack(scores, 1),
+                "accepted": torch.stack(accepted, 1), "patch_1_warped": W_best}
+
     def __call__(self, images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
-                 refine_iters=10, mask_b=None):
+                 refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25):
         from .step import predict
         if refine not in (None, "ecc"):
             raise ValueError("Aligner: refine is None or 'ecc', got %r" % (refine,))
+        try:
+            stages = operator.index(cascade)
+        except TypeError:
+            stages = -1
+        if stages < 0:
+            raise ValueError("Aligner: cascade is the number of re-prediction stages, an integer >= 0, got %r" % (cascade,))
+        if not 0.0 <= cascade_min_cover <= 1.0:                                # (False for a NaN too)
+            raise ValueError("Aligner: cascade_min_cover is a share in [0, 1], got %r" % (cascade_min_cover,))
+        samples = None if cascade_samples is None else _cascade_samples(cascade_samples, None, 0, 0, 1)
         a, b = _images(images_a, "images_a"), _images(images_b, "images_b")
         if a.device != b.device:
             raise ValueError("Aligner: images_a is on %s, images_b on %s" % (a.device, b.device))
@@ -615,6 +822,7 @@ class Aligner:
             mask_b = _check_mask(mask_b, B, b.shape[1], b.shape[2], b.device)
         elif mask_b is not None:
             raise ValueError("Aligner: mask_b restricts the pixels the refinement counts; pass refine='ecc' with it")
+        nx, ny = samples or _cascade_samples(None, roi_b, b.shape[1], b.shape[2], P)
         with torch.cuda.device(a.device):
             p1, ga = prepare(a, B, P, self.channels, self.mean, self.std, idx=ia, roi=ra)
             p2, gb = prepare(b, B, P, self.channels, self.mean, self.std, idx=ib, roi=rb)
@@ -623,6 +831,9 @@ class Aligner:
             delta_hat = delta_hat.detach().reshape(B, 4, 2)
             H = lift_device(delta_hat, P, ga, gb)
             out = {"delta_hat": delta_hat, "H": H, "patch_1": p1, "patch_2": p2, "geom_a": ga, "geom_b": gb}
+            if stages:
+                out.update(self._cascade(predict, a, ia, p2, gb, H, delta_hat, stages, nx, ny, cascade_min_cover))
+                H = out["H"]
             if refine is not None:
                 H, stats = ecc_refine(a, b, H, refine_levels, refine_iters, idx_a=ia, idx_b=ib, mask=mask_b)
                 out.update({"H_model": out["H"], "H": H, "refine_stats": stats, "rho": stats[:, 0, :2]})

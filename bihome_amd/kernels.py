@@ -1712,3 +1712,37 @@ def ecc_refine(pyr_a, size_a, pyr_b, size_b, H64, stats, ws, levels, iters, mask
     check(lib.bh_ecc_refine(_p(pyr_a), Ha, Wa, _p(pyr_b), Hb, Wb, _p(mask_pyr), B, int(levels), int(iters), _p(H64), _p(stats), _p(ws), _stream()),
           "bh_ecc_refine")
     return H64, stats
+
+
+# ------------------------------------------------------------------------------------------------
+# cascaded re-prediction: image A through a homography as the model's patch, and the score of a stage (bihome_amd/align.py; csrc/cascade.hip)
+# ------------------------------------------------------------------------------------------------
+def align_prep_warp_u8(images, Hg, patch, cover, nx, ny, mean, std, idx=None):
+    """B samples of a uint8 bank [N,Hs,Ws,3] seen through Hg [B,3,3] / [B,9] float64 (index coordinates of the P ny x P nx sub-sample
+    grid -> index coordinates of the image) as the standardised patches patch [B,C,P,P] float32: the mean of nx x ny bilinear samples per
+    patch pixel; cover [B,P,P] float32 (may be None) the share of them that is valid (include/bihome.h bh_align_prep_warp_u8).  Both
+    outputs are the caller's (bihome_amd.align.prepare_warped allocates them).  idx [B] int32 as in align_prep_u8."""
+    _chk(Hg, torch.float64); _chk(patch); _chk(cover)
+    if patch.dim() != 4 or patch.shape[2] != patch.shape[3] or Hg.dim() < 2 or Hg.numel() != 9 * patch.shape[0] or Hg.shape[0] != patch.shape[0]:
+        raise ValueError("align_prep_warp_u8: patch [B,C,P,P] float32 and Hg [B,3,3] float64, got %s and %s" % (tuple(patch.shape), tuple(Hg.shape)))
+    B, C, P = patch.shape[:3]
+    if cover is not None and tuple(cover.shape) != (B, P, P):
+        raise ValueError("align_prep_warp_u8: cover [B,P,P] float32 = [%d,%d,%d], got %s" % (B, P, P, tuple(cover.shape)))
+    _chk_images_u8(images, idx, B, "align_prep_warp_u8")
+    check(lib.bh_align_prep_warp_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(Hg), B, P, C, int(nx), int(ny),
+                                    float(mean), float(std), _p(patch), _p(cover), _stream()), "bh_align_prep_warp_u8")
+    return patch, cover
+
+
+def patch_ncc(w, t, cover, out):
+    """out [B,8] float64 = (n, sum w, sum t, sum ww, sum tt, sum wt, rho, 0) of the patches w, t [B,C,P,P] float32 over all channels of the
+    pixels with cover [B,P,P] float32 == 1 (None: all pixels) (include/bihome.h bh_patch_ncc).  out is the caller's."""
+    _chk(w); _chk(t); _chk(cover); _chk(out, torch.float64)
+    if w.dim() != 4 or w.shape[2] != w.shape[3] or t.shape != w.shape:
+        raise ValueError("patch_ncc: w and t [B,C,P,P] float32 of one shape, got %s and %s" % (tuple(w.shape), tuple(t.shape)))
+    B, C, P = w.shape[:3]
+    if tuple(out.shape) != (B, 8) or (cover is not None and tuple(cover.shape) != (B, P, P)):
+        raise ValueError("patch_ncc: out [B,8] float64 and cover [B,P,P] float32 with B = %d, P = %d, got %s and %s"
+                         % (B, P, tuple(out.shape), None if cover is None else tuple(cover.shape)))
+    check(lib.bh_patch_ncc(_p(w), _p(t), _p(cover), B, C, P, _p(out), _stream()), "bh_patch_ncc")
+    return out

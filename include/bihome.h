@@ -920,6 +920,39 @@ int bh_ecc_refine_ws_doubles(int Hb, int Wb, int B, int64_t* doubles);
 int bh_ecc_refine(const float* pyr_a, int Ha, int Wa, const float* pyr_b, int Hb, int Wb, const uint8_t* mask_pyr, int B, int levels, int iters,
                   double* H64, double* stats, double* ws, void* stream);
 
+/* Cascaded re-prediction: the model is run again on image A seen through the current homography, so that a stage only predicts the
+ * residual, and the stages are composed.  Upstream makes one prediction (eval.py:249-255) and warps whole images on the host
+ * (src/data/utils.py:54-67); the direction is the loss's, patch_1(H_p x) ~ patch_2(x) (PerceptualHead.py:371).  Two passes are stated
+ * here and, in numpy float64, in bihome_amd/align.py (prep_warp_host, patch_ncc_host; grid_map and cascade_compose hold the algebra).
+ *
+ * The warped preparation.  The sub-sample grid is a virtual integer grid of P ny rows and P nx columns: patch pixel (y, x) owns columns
+ * x nx .. x nx + nx - 1 and rows y ny .. y ny + ny - 1.  Hg[B,9] double maps the grid's index coordinates to index coordinates of
+ * images[idx[b]] (the caller folds everything into it: Hg = H A_b S with A_b the affine map of B's preparation and
+ * S = [[1/nx, 0, 0.5/nx - 0.5], [0, 1/ny, 0.5/ny - 0.5], [0, 0, 1]]).  Every sub-sample (X, Y) is bh_warp_u8's bilinear sample at
+ * Hg (X, Y, 1) - csrc/warp_tap.h's make_tap4, tap_weights, tap_blend on the three channels, taps outside the image contribute 0 - and a
+ * sub-sample under the projection guard (|qz| <= 1e-8) contributes 0.  With m_c the sum over the nx ny sub-samples divided by nx ny:
+ *     patch[b,c,y,x] = (v / 255 - mean) / std,  v = 0.299 m_R + 0.587 m_G + 0.114 m_B for C = 1, m_c for C = 3,
+ * without a full-size intermediate image and without its rounding to uint8.  cover[B,P,P] float (NULL ok) = (number of VALID
+ * sub-samples) / (nx ny), valid by bh_warp_u8's rule (no guard, 0 <= u <= Ws - 1, 0 <= v <= Hs - 1): exactly 1.0f if and only if every
+ * sub-sample is valid.  images / idx / n_images as in bh_align_prep_u8 (idx CLAMPED, 64-bit image offsets, 32-bit offsets inside an
+ * image).  One thread per patch pixel, one writer per element, no atomics, no scratch: two calls are bitwise equal.
+ * BH_E_BADARG: NULL images / Hg / patch, a negative B, n_images < 1, Hs < 1, Ws < 1, P < 1, std zero or NaN; then BH_E_UNSUPPORTED: C
+ * not 1 or 3, P % 16 != 0, P > 256, nx or ny outside 1..8, Hs * Ws > 2^29 pixels; then B == 0: BH_OK, nothing launched.  Refusals
+ * return before any launch. */
+int bh_align_prep_warp_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* Hg,
+                          int B, int P, int C, int nx, int ny, float mean, float std,
+                          float* patch, float* cover, void* stream);
+
+/* The score of a stage: the zero-mean normalised correlation of the warped patch w[B,C,P,P] and B's patch t[B,C,P,P] over all C
+ * channels of the pixels with cover[b,y,x] == 1.0f (cover[B,P,P]; NULL: every pixel counts).  out[B,8] double = (n, sum w, sum t,
+ * sum w w, sum t t, sum w t, rho, 0) with num = n sum wt - sum w sum t, va = n sum ww - (sum w)^2, vt = n sum tt - (sum t)^2 and
+ * rho = num / sqrt(va vt) when n >= 16, va > 0 and vt > 0, else rho = -inf.  One workgroup of 256 threads per sample; products and
+ * accumulators are double, reduced inside a wavefront by shuffles and across the four wavefronts through LDS in a fixed order: no
+ * atomics, no workspace, two calls are bitwise equal.
+ * BH_E_BADARG: NULL w / t / out, a negative B, P < 1; then BH_E_UNSUPPORTED: C not 1 or 3, P % 16 != 0, P > 256; then B == 0: BH_OK,
+ * nothing launched.  Refusals return before any launch. */
+int bh_patch_ncc(const float* w, const float* t, const float* cover, int B, int C, int P, double* out, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */
