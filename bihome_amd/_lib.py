@@ -143,6 +143,7 @@ SIGNATURES = {
     "bh_ecc_refine": [P, c_int, c_int, P, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P],
     "bh_align_prep_warp_u8": [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P],
     "bh_patch_ncc": [P, P, P, c_int, c_int, c_int, P, P],
+    "bh_mosaic_u8": [P, P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_float, c_int, P, P, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_gap_fwd": [P, P, c_int, c_int, c_int, P],

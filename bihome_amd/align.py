@@ -41,7 +41,18 @@ patch_1 = A through H_prev on B's patch grid (bh_align_prep_warp_u8: the mean of
 intermediate image) and patch_2 = B's patch, predicts only the residual delta_k, and the stages compose: patch coordinate q of that
 patch_1 is A's coordinate H_prev A_b q, hence H_k = H_prev A_b H_p(delta_k) A_b^-1, still B's index coordinates -> A's.  A stage is kept
 only where it raises the zero-mean normalised correlation of the two patches over the fully covered pixels (bh_patch_ncc), decided per
-sample on the device.  Stated below as sample_host / grid_map / prep_warp_host / patch_ncc_host / cascade_compose."""
+sample on the device.  Stated below as sample_host / grid_map / prep_warp_host / patch_ncc_host / cascade_compose.
+
+Mosaic (optional, `aligner(..., mosaic="b")` / `mosaic=(Hc, Wc)` / `mosaic`; csrc/mosaic.hip): the warp alone gives "A on B's grid" - what
+of A falls outside B's frame is lost and inside it the two are never combined.  bh_mosaic_u8 puts both on one canvas in one pass: with T
+from canvas index coordinates to B's (the identity for canvas "b"; else `mosaic_frame_host`: the bounding box of B's extent and of A's
+corners projected through H^-1 - clamped to `limit` image sizes around B, so that a garbage H cannot shrink B to a dot - scaled and centred
+onto the Hc x Wc canvas with the aspect ratio kept) each canvas pixel takes warp_u8_host's sample of A through H T and of B through T, and
+an image is PRESENT where warp_u8_host's `valid` holds.  Its weight is min(distance of the projected point to the border of the image, in
+its own pixels, + 1, feather); mode "feather" gives (wa a' + wb b) / (wa + wb) over the images present, "b_over_a" / "a_over_b" put one
+image on top, nothing present gives 0, then round half up; cover = (A present) | (B present) << 1.  a' = g a + o is A after the optional
+gain / bias match: the ECC step is blind to both by design, so the blend handles them - `exposure_host` is the least-squares line of B's
+gray on A's through H from the sums ecc_sums_host already makes.  Stated below as mosaic_frame_host / mosaic_host / exposure_host."""
 import operator
 
 import numpy as np
@@ -142,6 +153,110 @@ def warp_u8_host(images, H, Ho, Wo):
             valid[b] = ~guard & (u >= 0) & (u <= Ws - 1) & (v >= 0) & (v <= Hs - 1)
         out[b] = np.floor(np.clip(acc, 0.0, 255.0) + 0.5).astype(np.uint8)
     return out, valid
+
+
+# ------------------------------------------------------------------------------------------------
+# mosaic, the definitions (numpy float64; include/bihome.h "Mosaic" states the same in C terms)
+# ------------------------------------------------------------------------------------------------
+MOSAIC_MODES = ("feather", "b_over_a", "a_over_b")
+
+
+def mosaic_frame_host(H, size_a, size_b, canvas, limit=2.0):
+    """H [B,3,3] (B's index coordinates -> A's), size_a = (Ha, Wa), size_b = (Hb, Wb), canvas = (Hc, Wc) -> (T [B,3,3] float64: canvas
+    index coordinates -> B's, a scale and a translation; bbox [B,4] = (xmin, ymin, xmax, ymax) in B's index coordinates; fitted [B]
+    uint8): the Mosaic frame of the module docstring.  H^-1 is adjugate / determinant, written out."""
+    H = np.asarray(H, np.float64).reshape(-1, 3, 3)
+    (Ha, Wa), (Hb, Wb), (Hc, Wc) = size_a, size_b, canvas
+    if min(Hc, Wc) < 2:
+        raise ValueError("mosaic_frame: a canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (Hc, Wc))
+    if not limit > 0:
+        raise ValueError("mosaic_frame: limit > 0, got %r" % (limit,))
+    a, b, c, d, e, f, g, h, i = (H[:, r, k] for r in range(3) for k in range(3))
+    with np.errstate(all="ignore"):
+        adj = ((e * i - f * h, c * h - b * i, b * f - c * e), (f * g - d * i, a * i - c * g, c * d - a * f), (d * h - e * g, b * g - a * h, a * e - b * d))
+        det = a * adj[0][0] + b * adj[1][0] + c * adj[2][0]
+        inv = [[adj[r][k] / det for k in range(3)] for r in range(3)]
+        corners = ((0.0, 0.0), (Wa - 1.0, 0.0), (Wa - 1.0, Ha - 1.0), (0.0, Ha - 1.0))
+        qx, qy, qz = (np.stack([inv[r][0] * x + inv[r][1] * y + inv[r][2] for x, y in corners], 1) for r in range(3))          # [B,4]
+        px, py = qx / qz, qy / qz
+        usable = np.isfinite(det) & (det != 0) & np.isfinite(qz).all(1) & ((qz > 0).all(1) | (qz < 0).all(1)) & (np.abs(qz) > QZ_GUARD).all(1)
+        usable &= np.isfinite(px).all(1) & np.isfinite(py).all(1)
+        x0 = np.minimum(np.clip(px.min(1), -limit * Wb, (1 + limit) * Wb - 1), 0.0)
+        x1 = np.maximum(np.clip(px.max(1), -limit * Wb, (1 + limit) * Wb - 1), Wb - 1.0)
+        y0 = np.minimum(np.clip(py.min(1), -limit * Hb, (1 + limit) * Hb - 1), 0.0)
+        y1 = np.maximum(np.clip(py.max(1), -limit * Hb, (1 + limit) * Hb - 1), Hb - 1.0)
+    x0, x1, y0, y1 = np.where(usable, x0, 0.0), np.where(usable, x1, Wb - 1.0), np.where(usable, y0, 0.0), np.where(usable, y1, Hb - 1.0)
+    s = np.maximum((x1 - x0) / (Wc - 1), (y1 - y0) / (Hc - 1))
+    s = np.where(s == 0, 1.0, s)
+    T = np.zeros((H.shape[0], 3, 3))
+    T[:, 0, 0], T[:, 1, 1], T[:, 2, 2] = s, s, 1.0
+    T[:, 0, 2], T[:, 1, 2] = (x0 + x1) * 0.5 - s * (0.5 * (Wc - 1)), (y0 + y1) * 0.5 - s * (0.5 * (Hc - 1))
+    return T, np.stack([x0, y0, x1, y1], 1), usable.astype(np.uint8)
+
+
+def _project_host(M, Ho, Wo):
+    """(u, v) float64 [Ho,Wo] of the output grid through M [3,3]: `_sample_host`'s expressions (1 / qz is 1 under the guard)."""
+    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(np.float64)
+    qz = M[2, 0] * xs + M[2, 1] * ys + M[2, 2]
+    iz = 1.0 / np.where(~(np.abs(qz) > QZ_GUARD), 1.0, qz)
+    return (M[0, 0] * xs + M[0, 1] * ys + M[0, 2]) * iz, (M[1, 0] * xs + M[1, 1] * ys + M[1, 2]) * iz
+
+
+def mosaic_host(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather", gain=None):
+    """images_a uint8 [B,Ha,Wa,3], images_b uint8 [B,Hb,Wb,3], Ma / Mb [B,3,3] (canvas index coordinates -> A's / B's; the caller passes
+    Ma = H T, Mb = T), gain [B,2] = (g, o) or None -> (out uint8 [B,Hc,Wc,3], cover uint8 [B,Hc,Wc] = (A present) | (B present) << 1):
+    the Mosaic of the module docstring."""
+    if mode not in MOSAIC_MODES:
+        raise ValueError("mosaic_host: mode is one of %s, got %r" % (MOSAIC_MODES, mode))
+    if not (feather >= 1 and np.isfinite(feather)):
+        raise ValueError("mosaic_host: feather is finite and at least 1, got %r" % (feather,))
+    Ma, Mb = np.asarray(Ma, np.float64).reshape(-1, 3, 3), np.asarray(Mb, np.float64).reshape(-1, 3, 3)
+    B = Ma.shape[0]
+    gain = np.tile(np.array([[1.0, 0.0]]), (B, 1)) if gain is None else np.asarray(gain, np.float64).reshape(B, 2)
+    va, pa, _ = _sample_host(images_a, Ma, Hc, Wc)
+    vb, pb, _ = _sample_host(images_b, Mb, Hc, Wc)
+    va = gain[:, 0, None, None, None] * va + gain[:, 1, None, None, None]
+    out = np.empty((B, Hc, Wc, 3), np.uint8)
+    for b in range(B):
+        w = []
+        for img, M in ((images_a, Ma[b]), (images_b, Mb[b])):
+            Hx, Wx = np.asarray(img).shape[1:3]
+            with np.errstate(all="ignore"):
+                u, v = _project_host(M, Hc, Wc)
+                w.append(np.minimum(np.minimum(np.minimum(u, Wx - 1 - u), np.minimum(v, Hx - 1 - v)) + 1.0, feather))
+        a, t, A, T = va[b], vb[b], pa[b][..., None], pb[b][..., None]
+        if mode == "feather":
+            wa, wb = np.where(pa[b], w[0], 0.0)[..., None], np.where(pb[b], w[1], 0.0)[..., None]
+            num = np.where(A, wa * np.where(A, a, 0.0), 0.0) + np.where(T, wb * np.where(T, t, 0.0), 0.0)
+            den = wa + wb
+            val = np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
+        elif mode == "b_over_a":
+            val = np.where(T, t, np.where(A, a, 0.0))
+        else:
+            val = np.where(A, a, np.where(T, t, 0.0))
+        out[b] = np.floor(np.clip(np.where(A | T, val, 0.0), 0.0, 255.0) + 0.5).astype(np.uint8)
+    return out, (pa.astype(np.uint8) | (pb.astype(np.uint8) << 1)).astype(np.uint8)
+
+
+def exposure_host(sums):
+    """The 66 sums of `ecc_sums_host` at level 0 ([66], or [B,66]) -> (g, o) ([2], or [B,2]) float64: the least-squares line of B's gray
+    on A's gray seen through H over the counting pixels, t ~ g iw + o; (1, 0) for n < ECC_MIN_N, a variance of iw that is not > 0, or a
+    g that is not finite and positive."""
+    s = np.asarray(sums, np.float64)
+    rows = s.reshape(-1, ECC_SUMS)
+    out = np.empty((rows.shape[0], 2))
+    for k, r in enumerate(rows):
+        S = lambda i, j: float(r[ecc_index(i, j)])
+        g, o, n = 1.0, 0.0, S(10, 10)
+        if n >= ECC_MIN_N:
+            m_iw, m_t = S(8, 10) / n, S(9, 10) / n
+            v_iw, c_it = S(8, 8) - (n * m_iw) * m_iw, S(8, 9) - (n * m_iw) * m_t
+            if v_iw > 0:
+                gg = c_it / v_iw
+                if np.isfinite(gg) and gg > 0:
+                    g, o = gg, m_t - gg * m_iw
+        out[k] = g, o
+    return out[0] if s.ndim == 1 else out
 
 
 # ------------------------------------------------------------------------------------------------
@@ -689,13 +804,173 @@ def ecc_refine(images_a, images_b, H, levels=3, iters=10, idx_a=None, idx_b=None
     return ecc_refine_pyramids(pa, (Ha, Wa), pb, (Hb, Wb), H.contiguous(), levels, iters, mask_pyr=None if mask is None else mask_pyramid(mask, levels))
 
 
+# ------------------------------------------------------------------------------------------------
+# mosaic, the device path
+# ------------------------------------------------------------------------------------------------
+def mosaic_frame_device(H, size_a, size_b, canvas, limit=2.0):
+    """`mosaic_frame_host` on the device: H [B,3,3] float64 -> (T [B,3,3] float64, bbox [B,4] float64, fitted [B] uint8), batched double
+    tensor arithmetic with the adjugate written out - no solve, nothing copied to the host."""
+    (Ha, Wa), (Hb, Wb), (Hc, Wc) = size_a, size_b, canvas
+    if min(Hc, Wc) < 2:
+        raise ValueError("mosaic_frame: a canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (Hc, Wc))
+    if not limit > 0:
+        raise ValueError("mosaic_frame: limit > 0, got %r" % (limit,))
+    B = H.shape[0]
+    a, b, c, d, e, f, g, h, i = H.reshape(B, 9).unbind(1)
+    adj = ((e * i - f * h, c * h - b * i, b * f - c * e), (f * g - d * i, a * i - c * g, c * d - a * f), (d * h - e * g, b * g - a * h, a * e - b * d))
+    det = a * adj[0][0] + b * adj[1][0] + c * adj[2][0]
+    inv = [[adj[r][k] / det for k in range(3)] for r in range(3)]
+    corners = ((0.0, 0.0), (Wa - 1.0, 0.0), (Wa - 1.0, Ha - 1.0), (0.0, Ha - 1.0))
+    qx, qy, qz = (torch.stack([inv[r][0] * x + inv[r][1] * y + inv[r][2] for x, y in corners], 1) for r in range(3))              # [B,4]
+    px, py = qx / qz, qy / qz
+    usable = torch.isfinite(det) & (det != 0) & torch.isfinite(qz).all(1) & ((qz > 0).all(1) | (qz < 0).all(1)) & (qz.abs() > QZ_GUARD).all(1)
+    usable = usable & torch.isfinite(px).all(1) & torch.isfinite(py).all(1)
+    zero = torch.zeros_like(det)
+    x0 = torch.minimum(px.amin(1).clamp(-limit * Wb, (1 + limit) * Wb - 1), zero)
+    x1 = torch.maximum(px.amax(1).clamp(-limit * Wb, (1 + limit) * Wb - 1), zero + (Wb - 1.0))
+    y0 = torch.minimum(py.amin(1).clamp(-limit * Hb, (1 + limit) * Hb - 1), zero)
+    y1 = torch.maximum(py.amax(1).clamp(-limit * Hb, (1 + limit) * Hb - 1), zero + (Hb - 1.0))
+    x0, x1, y0, y1 = torch.where(usable, x0, zero), torch.where(usable, x1, zero + (Wb - 1.0)), torch.where(usable, y0, zero), torch.where(usable, y1, zero + (Hb - 1.0))
+    s = torch.maximum((x1 - x0) / (Wc - 1), (y1 - y0) / (Hc - 1))
+    s = torch.where(s == 0, zero + 1.0, s)
+    T = torch.zeros((B, 3, 3), dtype=torch.float64, device=H.device)
+    T[:, 0, 0], T[:, 1, 1], T[:, 2, 2] = s, s, 1.0
+    T[:, 0, 2], T[:, 1, 2] = (x0 + x1) * 0.5 - s * (0.5 * (Wc - 1)), (y0 + y1) * 0.5 - s * (0.5 * (Hc - 1))
+    return T, torch.stack([x0, y0, x1, y1], 1), usable.to(torch.uint8)
+
+
+def exposure_device(sums):
+    """`exposure_host` on the device: sums [B,66] float64 (`ecc_sums` at level 0) -> [B,2] float64 (g, o), the fallbacks by torch.where."""
+    S = lambda i, j: sums[:, ecc_index(i, j)]
+    n = S(10, 10)
+    m_iw, m_t = S(8, 10) / n, S(9, 10) / n
+    v_iw, c_it = S(8, 8) - (n * m_iw) * m_iw, S(8, 9) - (n * m_iw) * m_t
+    g = c_it / v_iw
+    ok = (n >= ECC_MIN_N) & (v_iw > 0) & torch.isfinite(g) & (g > 0)
+    return torch.stack([torch.where(ok, g, torch.ones_like(g)), torch.where(ok, m_t - g * m_iw, torch.zeros_like(g))], 1)
+
+
+def mosaic_u8(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather", gain=None, idx_a=None, idx_b=None, want_cover=True):
+    """bh_mosaic_u8 on outputs allocated here: (out [B,Hc,Wc,3] uint8, cover [B,Hc,Wc] uint8 or None) (kernels.mosaic_u8; `mosaic_host`)."""
+    if not (images_a.is_cuda and images_b.is_cuda):
+        raise RuntimeError("bihome_amd kernels need device tensors (got %s and %s); there is no CPU path" % (images_a.device, images_b.device))
+    B = Ma.shape[0]
+    out = torch.empty((B, Hc, Wc, 3), dtype=torch.uint8, device=images_a.device)
+    cover = torch.empty((B, Hc, Wc), dtype=torch.uint8, device=images_a.device) if want_cover else None
+    return K.mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=gain, idx_a=idx_a, idx_b=idx_b)
+
+
+def _mosaic_args(canvas, feather, mode, exposure, limit, size_a, size_b, who):
+    """The host-side argument rules of `mosaic` and Aligner(mosaic=), checked before any launch -> (Hc, Wc) or None for canvas 'b'."""
+    size = None
+    if not (isinstance(canvas, str) and canvas == "b"):
+        try:
+            size = tuple(operator.index(v) for v in canvas)
+        except (TypeError, ValueError):
+            size = ()
+        if len(size) != 2:
+            raise ValueError("%s: the mosaic canvas is 'b' (image B's grid) or (Hc, Wc), got %r" % (who, canvas))
+        if min(size) < 2:
+            raise ValueError("%s: a mosaic canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (who, size[0], size[1]))
+    try:
+        feather_ok = bool(1.0 <= float(feather) < float("inf"))                # (False for a NaN too)
+    except (TypeError, ValueError):
+        feather_ok = False
+    if not feather_ok:
+        raise ValueError("%s: the mosaic feather is finite and at least 1 (pixels), got %r" % (who, feather))
+    if not (isinstance(mode, str) and mode in MOSAIC_MODES):
+        raise ValueError("%s: the mosaic mode is one of %s, got %r" % (who, ", ".join(MOSAIC_MODES), mode))
+    if isinstance(exposure, torch.Tensor):
+        if not exposure.is_cuda or exposure.dtype != torch.float64 or exposure.dim() != 2 or exposure.shape[1] != 2:
+            raise ValueError("%s: the mosaic exposure as a tensor is [B,2] float64 (g, o) on the device, got %s %s on %s"
+                             % (who, exposure.dtype, tuple(exposure.shape), exposure.device))
+    elif exposure == "gain":
+        for (h, w), what in ((size_a, "images_a"), (size_b, "images_b")):
+            if min(h, w) < ECC_MIN_SIDE:
+                raise ValueError("%s: the mosaic exposure 'gain' measures on the gray images, which need at least %d pixels on each side; "
+                                 "%s is %d x %d (H x W)" % (who, ECC_MIN_SIDE, what, h, w))
+    elif exposure is not None:
+        raise ValueError("%s: the mosaic exposure is None, 'gain' or a [B,2] float64 device tensor (g, o), got %r" % (who, exposure))
+    try:
+        limit_ok = bool(float(limit) > 0)
+    except (TypeError, ValueError):
+        limit_ok = False
+    if not limit_ok:
+        raise ValueError("%s: the mosaic limit (image sizes around B that the frame may reach) is > 0, got %r" % (who, limit))
+    return size
+
+
+def _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b):
+    """The mosaic stage on checked arguments (a, b: uint8 banks on the device, ia / ib: int32 device tensors or None) -> its six keys."""
+    B, dev, (Ha, Wa), (Hb, Wb) = H.shape[0], H.device, a.shape[1:3], b.shape[1:3]
+    H = H.reshape(B, 3, 3).contiguous()
+    if size is None:
+        Hc, Wc = Hb, Wb
+        T = torch.zeros((B, 3, 3), dtype=torch.float64, device=dev)
+        T[:, 0, 0] = T[:, 1, 1] = T[:, 2, 2] = 1.0
+        bbox = torch.zeros((B, 4), dtype=torch.float64, device=dev)
+        bbox[:, 2], bbox[:, 3] = Wb - 1.0, Hb - 1.0
+        fitted = torch.zeros((B,), dtype=torch.uint8, device=dev)
+        Ma = H
+    else:
+        Hc, Wc = size
+        T, bbox, fitted = mosaic_frame_device(H, (Ha, Wa), (Hb, Wb), (Hc, Wc), limit)
+        Ma = (H @ T).contiguous()
+    if isinstance(exposure, torch.Tensor):
+        gain = exposure.contiguous()
+    elif exposure == "gain":
+        pa, pb = gray_pyramid(a, B, 1, idx=ia), gray_pyramid(b, B, 1, idx=ib)
+        gain = exposure_device(ecc_sums(pyramid_level(pa, Ha, Wa, 1, 0), pyramid_level(pb, Hb, Wb, 1, 0), H, mask=mask_b)).contiguous()
+    else:
+        gain = None
+    out, cover = mosaic_u8(a, b, Ma, T, Hc, Wc, feather, mode, gain=gain, idx_a=ia, idx_b=ib)
+    if gain is None:
+        gain = torch.zeros((B, 2), dtype=torch.float64, device=dev)
+        gain[:, 0] = 1.0
+    return {"mosaic": out, "mosaic_cover": cover, "mosaic_T": T, "mosaic_bbox": bbox, "mosaic_fitted": fitted, "mosaic_gain": gain}
+
+
+def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", exposure=None, limit=2.0, idx_a=None, idx_b=None, mask_b=None):
+    """Both images on one canvas, for a caller who has H [B,3,3] float64 (B's index coordinates -> A's) from anywhere: images_* uint8
+    [N,H*,W*,3] device tensors or ImageBanks, idx_* as in `Aligner`.  canvas="b": the canvas is B's grid (T the identity);
+    canvas=(Hc, Wc): the frame `mosaic_frame_device` fits around B and A's projected corners, `limit` image sizes around B at most.
+    feather / mode: `mosaic_host`.  exposure: None, "gain" (A's gray is matched to B's by the least-squares line through H over the
+    pixels the ECC pass counts - one-level `gray_pyramid` of both, `ecc_sums` (mask_b uint8 [B,Hb,Wb]: non-zero, the pixel of B may
+    count), `exposure_device`) or a [B,2] float64 device tensor (g, o).  -> dict: 'mosaic' [B,Hc,Wc,3] uint8, 'mosaic_cover'
+    [B,Hc,Wc] uint8 (0 empty, 1 only A, 2 only B, 3 both), 'mosaic_T' [B,3,3] float64 (canvas -> B), 'mosaic_bbox' [B,4] float64
+    (xmin, ymin, xmax, ymax in B's coordinates), 'mosaic_fitted' [B] uint8 (A's corners took part in the frame), 'mosaic_gain' [B,2]
+    float64.  ValueError before any launch for arguments outside these; nothing is copied to the host."""
+    a, b = _images(images_a, "images_a"), _images(images_b, "images_b")
+    if not isinstance(H, torch.Tensor) or not H.is_cuda:
+        raise RuntimeError("bihome_amd kernels need device tensors; there is no CPU path")
+    if a.device != b.device or H.device != a.device:
+        raise ValueError("mosaic: images_a is on %s, images_b on %s, H on %s" % (a.device, b.device, H.device))
+    if H.dtype != torch.float64 or H.dim() < 2 or H.numel() != 9 * H.shape[0]:
+        raise ValueError("mosaic: H [B,3,3] float64, got %s %s" % (H.dtype, tuple(H.shape)))
+    B = H.shape[0]
+    size = _mosaic_args(canvas, feather, mode, exposure, limit, a.shape[1:3], b.shape[1:3], "mosaic")
+    if isinstance(exposure, torch.Tensor) and exposure.shape[0] != B:
+        raise ValueError("mosaic: exposure [B,2] with B = %d, got %s" % (B, tuple(exposure.shape)))
+    ia, na = _index(idx_a, a.shape[0], a.device, "idx_a")
+    ib, nb = _index(idx_b, b.shape[0], b.device, "idx_b")
+    for n, what in ((a.shape[0] if na is None else na, "images_a"), (b.shape[0] if nb is None else nb, "images_b")):
+        if n != B:
+            raise ValueError("mosaic: %d samples of %s, H has %d" % (n, what, B))
+    if mask_b is not None and not (isinstance(exposure, str) and exposure == "gain"):
+        raise ValueError("mosaic: mask_b restricts the pixels the exposure measurement counts; pass exposure='gain' with it")
+    mask_b = _check_mask(mask_b, B, b.shape[1], b.shape[2], b.device)
+    with torch.cuda.device(a.device):
+        return _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b)
+
+
 class Aligner:
     """Aligner(model, patch=None, channels=None, mean=0.443, std=0.129): `model` is the Sequential(backbone, head) of step.build_model
     on the device.  patch / channels default to the model's PATCH_SIZE / PATCH_CHANNELS (channels to 1, upstream's grayscale pair,
     where the model does not say); mean / std are DictStandardize's (transforms.py:369-378).
 
     aligner(images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
-            refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25) -> dict
+            refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25, mosaic=None, mosaic_feather=32.0,
+            mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0) -> dict
         images_*: uint8 [N,H,W,3] device tensors or ImageBanks; the two may differ in size.
         idx_*: which image each of the B samples uses (host list: range-checked; int32 device tensor: clamped by the kernel;
                None: sample b is image b, so B = N).
@@ -723,6 +998,17 @@ class Aligner:
         through 'H' as the model last saw it; 'delta_hat', 'patch_1', 'geom_*' stay stage 0's.  With refine="ecc" the refinement starts
         from the cascade's 'H', and 'H_model' is that matrix.  A cascade that is no integer >= 0, samples outside 1..8 and a
         cascade_min_cover outside [0, 1] raise a ValueError before any launch.
+    mosaic="b" or (Hc, Wc) (default None: nothing below happens, no further launch, the result is key for key and bit for bit the one
+        above), mosaic_feather=32.0, mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0: from the final 'H' - after the cascade
+        and the refinement - both images are put on one canvas by `mosaic` (bh_mosaic_u8, one pass): "b" is image B's grid, (Hc, Wc) the
+        frame fitted around B and A's projected corners (`mosaic_frame_device`, at most mosaic_limit image sizes around B).
+        mosaic_mode "feather" blends by the distance to each image's border capped at mosaic_feather pixels, "b_over_a" / "a_over_b" put
+        one image on top; mosaic_exposure "gain" matches A's gray to B's by a least-squares gain and bias first (`exposure_device`;
+        mask_b, where refine="ecc" was given one, restricts the pixels it counts), a [B,2] float64 device tensor gives (g, o).  Added:
+        'mosaic' [B,Hc,Wc,3] uint8, 'mosaic_cover' [B,Hc,Wc] uint8 (0 empty, 1 only A, 2 only B, 3 both), 'mosaic_T' [B,3,3] float64
+        (canvas index coordinates -> B's), 'mosaic_bbox' [B,4] float64, 'mosaic_fitted' [B] uint8, 'mosaic_gain' [B,2] float64.  A
+        mosaic that is neither of the two, a canvas side below 2, a feather that is NaN, infinite or below 1, an unknown mode or
+        exposure, 'gain' on an image side below 8 and a limit that is not > 0 raise a ValueError before any launch.
     The aligner copies nothing from the device to the host (host-given idx / roi values are uploaded).  What a model's own
     predict_homography does is the model's: NoOpHead '4_points' and PhotometricHead read the patch extent off 'corners' with .item()."""
 
@@ -787,7 +1073,8 @@ class Aligner:
                 "accepted": torch.stack(accepted, 1), "patch_1_warped": W_best}
 
     def __call__(self, images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
-                 refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25):
+                 refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25, mosaic=None, mosaic_feather=32.0,
+                 mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0):
         from .step import predict
         if refine not in (None, "ecc"):
             raise ValueError("Aligner: refine is None or 'ecc', got %r" % (refine,))
@@ -823,6 +1110,10 @@ class Aligner:
         elif mask_b is not None:
             raise ValueError("Aligner: mask_b restricts the pixels the refinement counts; pass refine='ecc' with it")
         nx, ny = samples or _cascade_samples(None, roi_b, b.shape[1], b.shape[2], P)
+        if mosaic is not None:
+            canvas = _mosaic_args(mosaic, mosaic_feather, mosaic_mode, mosaic_exposure, mosaic_limit, a.shape[1:3], b.shape[1:3], "Aligner")
+            if isinstance(mosaic_exposure, torch.Tensor) and mosaic_exposure.shape[0] != B:
+                raise ValueError("Aligner: mosaic_exposure [B,2] with B = %d, got %s" % (B, tuple(mosaic_exposure.shape)))
         with torch.cuda.device(a.device):
             p1, ga = prepare(a, B, P, self.channels, self.mean, self.std, idx=ia, roi=ra)
             p2, gb = prepare(b, B, P, self.channels, self.mean, self.std, idx=ib, roi=rb)
@@ -839,4 +1130,6 @@ class Aligner:
                 out.update({"H_model": out["H"], "H": H, "refine_stats": stats, "rho": stats[:, 0, :2]})
             if warp:
                 out["aligned"], out["valid"] = warp_u8(a, H, b.shape[1], b.shape[2], idx=ia)
+            if mosaic is not None:
+                out.update(_mosaic(a, b, H, canvas, mosaic_feather, mosaic_mode, mosaic_exposure, mosaic_limit, ia, ib, mask_b))
         return out

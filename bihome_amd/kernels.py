@@ -1746,3 +1746,39 @@ def patch_ncc(w, t, cover, out):
                          % (B, P, tuple(out.shape), None if cover is None else tuple(cover.shape)))
     check(lib.bh_patch_ncc(_p(w), _p(t), _p(cover), B, C, P, _p(out), _stream()), "bh_patch_ncc")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# mosaic: both images of an aligned pair on one canvas, feathered, in one pass (bihome_amd/align.py; csrc/mosaic.hip)
+# ------------------------------------------------------------------------------------------------
+MOSAIC_MODES = {"feather": 0, "b_over_a": 1, "a_over_b": 2}          # include/bihome.h BH_MOSAIC_*
+
+
+def mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=None, idx_a=None, idx_b=None):
+    """out [B,Hc,Wc,3] uint8 = the mosaic of images_a[idx_a[b]] and images_b[idx_b[b]] (uint8 banks [N,H,W,3]) on a canvas whose index
+    coordinates Ma / Mb [B,3,3] or [B,9] float64 map to A's / B's, cover [B,Hc,Wc] uint8 (may be None) = (A present) | (B present) << 1
+    (include/bihome.h bh_mosaic_u8).  feather >= 1 caps the border-distance weights; mode is 'feather', 'b_over_a' or 'a_over_b' (or
+    its BH_MOSAIC_* number); gain [B,2] float64 (g, o) turns A's value into g a + o (None: unchanged).  Both outputs are the caller's
+    (bihome_amd.align.mosaic_u8 allocates them)."""
+    _chk(Ma, torch.float64); _chk(Mb, torch.float64); _chk(gain, torch.float64); _chk(out, torch.uint8); _chk(cover, torch.uint8)
+    for M, what in ((Ma, "Ma"), (Mb, "Mb")):
+        if M.dim() < 2 or M.numel() != 9 * M.shape[0]:
+            raise ValueError("mosaic_u8: %s [B,3,3] float64, got %s" % (what, tuple(M.shape)))
+    B = Ma.shape[0]
+    if Mb.shape[0] != B or (gain is not None and tuple(gain.shape) != (B, 2)):
+        raise ValueError("mosaic_u8: Ma and Mb [B,3,3] and gain [B,2] float64 with one B, got %s, %s and %s"
+                         % (tuple(Ma.shape), tuple(Mb.shape), None if gain is None else tuple(gain.shape)))
+    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (cover is not None and tuple(cover.shape) != tuple(out.shape[:3])):
+        raise ValueError("mosaic_u8: out [B,Hc,Wc,3] uint8 and cover [B,Hc,Wc] uint8 with B = %d, got %s and %s"
+                         % (B, tuple(out.shape), None if cover is None else tuple(cover.shape)))
+    if isinstance(mode, str):
+        if mode not in MOSAIC_MODES:
+            raise ValueError("mosaic_u8: mode is one of %s, got %r" % (sorted(MOSAIC_MODES), mode))
+        mode = MOSAIC_MODES[mode]
+    _chk_images_u8(images_a, idx_a, B, "mosaic_u8")
+    _chk_images_u8(images_b, idx_b, B, "mosaic_u8")
+    check(lib.bh_mosaic_u8(_p(images_a), _p(idx_a), images_a.shape[0], images_a.shape[1], images_a.shape[2],
+                           _p(images_b), _p(idx_b), images_b.shape[0], images_b.shape[1], images_b.shape[2],
+                           _p(Ma), _p(Mb), _p(gain), B, out.shape[1], out.shape[2], float(feather), int(mode), _p(out), _p(cover), _stream()),
+          "bh_mosaic_u8")
+    return out, cover

@@ -953,6 +953,39 @@ int bh_align_prep_warp_u8(const uint8_t* images, const int* idx, int n_images, i
  * nothing launched.  Refusals return before any launch. */
 int bh_patch_ncc(const float* w, const float* t, const float* cover, int B, int C, int P, double* out, void* stream);
 
+/* Mosaic: both images of an aligned pair on one canvas, combined in one pass - what an inter-image homography is usually computed for
+ * (panoramas, frame stacks, before / after composites).  The numpy float64 statement is bihome_amd/align.py's mosaic_host
+ * (mosaic_frame_host places the canvas, exposure_host gives the gain / bias).  Index coordinates throughout.
+ *
+ * images_a[n_a,Ha,Wa,3], images_b[n_b,Hb,Wb,3] uint8 interleaved RGB banks, idx_a / idx_b[B] int32 as in bh_align_prep_u8 (NULL: sample b
+ * is image b; CLAMPED into the bank in the kernel).  Ma[B,9], Mb[B,9] double map index coordinates of the CANVAS (Hc x Wc) to index
+ * coordinates of A and of B: with H from B to A and T from the canvas to B, Ma = H T and Mb = T.  For image X in {A, B} at canvas pixel
+ * (x, y): (u, v) and the bilinear value (taps outside the image contribute 0) are bh_warp_u8's, by csrc/warp_tap.h's make_tap4 /
+ * tap_weights / tap_blend in float; X is PRESENT where bh_warp_u8's valid holds (no projection guard, 0 <= u <= Wx - 1,
+ * 0 <= v <= Hx - 1); its weight is w = min(min(u, Wx - 1 - u, v, Hx - 1 - v) + 1, feather) where present: the distance to the border
+ * of the image in its own pixels, plus 1, capped - feather = 1 is the plain average.  gain[B,2] double = (g, o) (NULL: (1, 0)) turns
+ * A's value a into a' = fmaf(g, a, o) per channel, in grey levels, before the blend.  Then, by mode,
+ *     BH_MOSAIC_FEATHER   v = (wa a' + wb b) / (wa + wb) over the images present,
+ *     BH_MOSAIC_B_OVER_A  v = b where B is present, else a' where A is present,
+ *     BH_MOSAIC_A_OVER_B  the reverse,
+ * v = 0 where neither is, and out[b,y,x,:] = round_half_up(clamp(v, 0, 255)) as in bh_warp_u8.  An image that is not present is
+ * selected out, not multiplied by 0 (its sample is unspecified under the guard).  out[B,Hc,Wc,3] uint8; cover[B,Hc,Wc] uint8 (NULL ok)
+ * = (A present) | (B present) << 1: 0 empty, 1 only A, 2 only B, 3 both.  Floating point is float apart from reading the matrices.
+ * Wc % 4 == 0 with out on a 4-byte boundary: four pixels and three dword stores per thread (cover: one dword when it is on a 4-byte
+ * boundary, else four bytes); anything else one pixel and byte stores, same results.  64-bit image offsets and offsets into out, 32-bit
+ * offsets inside an image.  One pass, one writer per output element, no atomics, no scratch: two calls are bitwise equal.
+ * BH_E_BADARG: NULL images_a / images_b / Ma / Mb / out, B < 0, n_a, n_b, Ha, Wa, Hb, Wb, Hc or Wc < 1, a feather that is NaN, infinite
+ * or below 1, an unknown mode; then BH_E_UNSUPPORTED: Ha * Wa or Hb * Wb > 2^29 or Hc * Wc > 2^31 - 1 pixels; then B == 0: BH_OK,
+ * nothing launched.  Refusals return before any launch. */
+#define BH_MOSAIC_FEATHER 0
+#define BH_MOSAIC_B_OVER_A 1
+#define BH_MOSAIC_A_OVER_B 2
+int bh_mosaic_u8(const uint8_t* images_a, const int* idx_a, int n_a, int Ha, int Wa,
+                 const uint8_t* images_b, const int* idx_b, int n_b, int Hb, int Wb,
+                 const double* Ma, const double* Mb, const double* gain,
+                 int B, int Hc, int Wc, float feather, int mode,
+                 uint8_t* out, uint8_t* cover, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */

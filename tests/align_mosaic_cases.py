@@ -1,0 +1,233 @@
+"""Shared by tests/test_align_mosaic_cpu.py and tests/test_align_mosaic_gpu.py: the inputs of the mosaic cases (the generators of
+tests/test_align_gpu.py, copied), their float64 references (computed once), a float32 numpy restatement of the kernel's arithmetic, the
+stub model and the 1/16-pixel delta construction of test_align_gpu.py's test_direction_and_lift_end_to_end."""
+import functools
+
+import numpy as np
+import torch
+
+from bihome_amd import align, synth
+
+NEAR = 1e-3                      # cover is compared where the float64 point is at least this far (px) from a border line of the image
+GAIN = (0.9, 6.0)
+# every combination the kernel cases run: the feather matters to the blend only
+COMBOS = [("feather", f, g) for f in (1.0, 8.0, 64.0) for g in (None, GAIN)] + [(m, 8.0, g) for m in ("b_over_a", "a_over_b") for g in (None, GAIN)]
+
+# name -> (Ha, Wa, Hb, Wb, canvas or None for B's grid, samples)
+CASES = {
+    "17x23-scalar": (17, 23, 17, 23, None, 2),
+    "48x80-vector": (48, 80, 48, 80, None, 2),
+    "48x80-and-40x56-fitted-64x96-vector": (48, 80, 40, 56, (64, 96), 2),
+    "48x80-and-40x56-fitted-37x53-scalar": (48, 80, 40, 56, (37, 53), 2),
+    "240x320-fitted-240x320": (240, 320, 240, 320, (240, 320), 1),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def pixels(n, h, w, seed=0):
+    a = np.random.RandomState(seed).randint(0, 256, (n, h, w, 3)).astype(np.uint8)
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def textures(n, h, w, seed=0):
+    """uint8 [n,h,w,3]: synth.texture_image clipped and rounded to uint8, made once per shape and shared (tests/test_align_gpu.py's)."""
+    rng = np.random.default_rng(seed)
+    a = np.stack([np.floor(np.clip(synth.texture_image(rng, h, w), 0, 255) + 0.5).astype(np.uint8) for _ in range(n)])
+    a.setflags(write=False)
+    return a
+
+
+def corner_homography(seed, Hs, Ws, Ho, Wo, frac=0.2):
+    """tests/test_align_gpu.py's: the corners of the Ho x Wo output onto the corners of the Hs x Ws source moved by up to frac of each side."""
+    rs = np.random.RandomState(seed)
+    co = np.array([[0, 0], [Wo - 1, 0], [Wo - 1, Ho - 1], [0, Ho - 1]], np.float64)
+    cs = np.array([[0, 0], [Ws - 1, 0], [Ws - 1, Hs - 1], [0, Hs - 1]], np.float64)
+    return synth.four_point_homography(co, cs + rs.uniform(-frac, frac, (4, 2)) * np.array([Ws, Hs]))
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """(A uint8 [n,Ha,Wa,3], B uint8 [n,Hb,Wb,3], Ma [n,3,3], Mb [n,3,3], Hc, Wc): textures of seeds 1 and 2, H = corner_homography(11 + b)
+    from B's grid to A, T the identity (B's grid) or mosaic_frame_host's."""
+    Ha, Wa, Hb, Wb, canvas, n = CASES[name]
+    A, B = textures(2, Ha, Wa, seed=1)[:n], textures(2, Hb, Wb, seed=2)[:n]
+    H = np.stack([corner_homography(11 + b, Ha, Wa, Hb, Wb) for b in range(n)])
+    if canvas is None:
+        Hc, Wc, T = Hb, Wb, np.stack([np.eye(3)] * n)
+    else:
+        (Hc, Wc), T = canvas, align.mosaic_frame_host(H, (Ha, Wa), (Hb, Wb), canvas)[0]
+    Ma = H @ T
+    for x in (Ma, T):
+        x.setflags(write=False)
+    return A, B, Ma, T, Hc, Wc
+
+
+def gain_of(g, n):
+    return None if g is None else np.tile(np.array([g], np.float64), (n, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, mode, feather, gain):
+    """mosaic_host of the case: (out uint8 [n,Hc,Wc,3], cover uint8 [n,Hc,Wc])."""
+    A, B, Ma, Mb, Hc, Wc = case(name)
+    return align.mosaic_host(A, B, Ma, Mb, Hc, Wc, feather, mode, gain_of(gain, len(A)))
+
+
+def near_border(M, Ho, Wo, Hs, Ws):
+    """bool [B,Ho,Wo]: the float64 point of the canvas pixel lies within NEAR px of one of the four border lines of the Hs x Ws image."""
+    M = np.asarray(M, np.float64).reshape(-1, 3, 3)
+    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(np.float64)
+    out = np.zeros((M.shape[0], Ho, Wo), bool)
+    for b, h in enumerate(M):
+        with np.errstate(all="ignore"):
+            qz = h[2, 0] * xs + h[2, 1] * ys + h[2, 2]
+            u, v = (h[0, 0] * xs + h[0, 1] * ys + h[0, 2]) / qz, (h[1, 0] * xs + h[1, 1] * ys + h[1, 2]) / qz
+            out[b] = np.minimum.reduce([np.abs(u), np.abs(u - (Ws - 1)), np.abs(v), np.abs(v - (Hs - 1))]) < NEAR
+    return out
+
+
+def differing_share(got, want):
+    """(largest difference in grey levels, share of the pixels that differ at all)."""
+    d = np.abs(np.asarray(got).astype(np.int32) - np.asarray(want).astype(np.int32))
+    return int(d.max()), float((d.max(-1) > 0).mean())
+
+
+# ------------------------------------------------------------------------------------------------
+# the kernel's arithmetic in float32 numpy
+# ------------------------------------------------------------------------------------------------
+def f32_fma(a, b, c):
+    """float32 fma: the product of two floats is exact in double, one double addition, one rounding to float."""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def sample_f32(image, M, Ho, Wo, feather):
+    """csrc/mosaic.hip mosaic_sample in float32 numpy: warp_tap.h's tap_project / tap_place / tap_weights / tap_blend, the presence test and
+    the weight.  (The kernel's reciprocal is within an ulp of the division used here.)  -> (value float32 [Ho,Wo,3], weight, present)"""
+    f = np.float32
+    Hs, Ws = image.shape[:2]
+    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(f)
+    h = np.asarray(M, np.float64).reshape(9).astype(f)
+    img = image.astype(f)
+    with np.errstate(all="ignore"):
+        qx, qy, qz = (f32_fma(np.full_like(xs, h[3 * r]), xs, f32_fma(np.full_like(ys, h[3 * r + 1]), ys, h[3 * r + 2])) for r in range(3))
+        guard = ~(np.abs(qz) > f(1e-8))
+        iz = (f(1) / np.where(guard, f(1), qz)).astype(f)
+        u, v = qx * iz, qy * iz
+        x0f, y0f = np.floor(u), np.floor(v)
+        fx, fy = u - x0f, v - y0f
+        x0 = np.clip(np.nan_to_num(x0f, nan=-2.0), -2, Ws).astype(np.int64)
+        y0 = np.clip(np.nan_to_num(y0f, nan=-2.0), -2, Hs).astype(np.int64)
+        vx0, vx1, vy0, vy1 = (x0 >= 0) & (x0 < Ws), (x0 + 1 >= 0) & (x0 + 1 < Ws), (y0 >= 0) & (y0 < Hs), (y0 + 1 >= 0) & (y0 + 1 < Hs)
+        wx0, wx1 = np.where(vx0, f(1) - fx, f(0)), np.where(vx1, fx, f(0))
+        wy0, wy1 = np.where(vy0, f(1) - fy, f(0)), np.where(vy1, fy, f(0))
+        present = ~guard & (u >= 0) & (u <= f(Ws - 1)) & (v >= 0) & (v <= f(Hs - 1))
+        weight = np.minimum(np.minimum(np.minimum(u, f(Ws - 1) - u), np.minimum(v, f(Hs - 1) - v)) + f(1), f(feather))
+        px = lambda dy, dx: img[np.clip(y0 + dy, 0, Hs - 1), np.clip(x0 + dx, 0, Ws - 1)]          # (a tap outside weighs 0)
+        w00, w01, w10, w11 = (wx0 * wy0)[..., None], (wx1 * wy0)[..., None], (wx0 * wy1)[..., None], (wx1 * wy1)[..., None]
+        val = f32_fma(px(1, 1), w11, f32_fma(px(1, 0), w10, f32_fma(px(0, 1), w01, px(0, 0) * w00)))
+    assert val.dtype == f and weight.dtype == f
+    return val, weight, present
+
+
+def mosaic_f32(images_a, images_b, Ma, Mb, Hc, Wc, feather, mode, gain=None):
+    """csrc/mosaic.hip mosaic_kernel in float32 numpy -> (out uint8 [B,Hc,Wc,3], cover uint8 [B,Hc,Wc])."""
+    f = np.float32
+    B = len(Ma)
+    out, cover = np.empty((B, Hc, Wc, 3), np.uint8), np.empty((B, Hc, Wc), np.uint8)
+    for b in range(B):
+        a, wa, pa = sample_f32(images_a[b], Ma[b], Hc, Wc, feather)
+        t, wb, pb = sample_f32(images_b[b], Mb[b], Hc, Wc, feather)
+        g, o = (f(1), f(0)) if gain is None else (f(gain[b][0]), f(gain[b][1]))
+        with np.errstate(all="ignore"):
+            a = f32_fma(np.full_like(a, g), a, o)
+            A, T = pa[..., None], pb[..., None]
+            if mode == "feather":
+                num = np.where(A, wa[..., None] * a, f(0)) + np.where(T, wb[..., None] * t, f(0))
+                den = (np.where(pa, wa, f(0)) + np.where(pb, wb, f(0)))[..., None]
+                val = np.where(den > 0, num / np.where(den > 0, den, f(1)), f(0))
+            elif mode == "b_over_a":
+                val = np.where(T, t, np.where(A, a, f(0)))
+            else:
+                val = np.where(A, a, np.where(T, t, f(0)))
+            assert val.dtype == f
+            out[b] = (np.minimum(np.maximum(np.nan_to_num(val, nan=0.0), f(0)), f(255)) + f(0.5)).astype(np.uint8)
+        cover[b] = pa.astype(np.uint8) | (pb.astype(np.uint8) << 1)
+    return out, cover
+
+
+# ------------------------------------------------------------------------------------------------
+# the integer translation: every sample is a pixel, so the comparison is bitwise
+# ------------------------------------------------------------------------------------------------
+def translation_case(h=17, w=23):
+    """A on a canvas shifted by (+5, -3), B by (-4, +6): strips of only A, only B, both and nothing; every sample is a pixel."""
+    A, B = pixels(1, h, w, seed=3), pixels(1, h, w, seed=4)
+    Ma = np.array([[[1.0, 0, 5], [0, 1, -3], [0, 0, 1]]])          # canvas (x, y) reads A(x + 5, y - 3)
+    Mb = np.array([[[1.0, 0, -4], [0, 1, 6], [0, 0, 1]]])          # ... and B(x - 4, y + 6)
+    pa, pb = np.zeros((h, w), bool), np.zeros((h, w), bool)
+    a, b = np.zeros((h, w, 3)), np.zeros((h, w, 3))
+    pa[3:, :w - 5], pb[:h - 6, 4:] = True, True
+    a[3:, :w - 5], b[:h - 6, 4:] = A[0, :h - 3, 5:], B[0, 6:, :w - 4]
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    da = np.minimum(np.minimum(xs + 5, w - 1 - (xs + 5)), np.minimum(ys - 3, h - 1 - (ys - 3))) + 1
+    db = np.minimum(np.minimum(xs - 4, w - 1 - (xs - 4)), np.minimum(ys + 6, h - 1 - (ys + 6))) + 1
+    return A, B, Ma, Mb, pa, pb, a, b, da, db
+
+
+def translation_want(mode, feather, gain, pa, pb, a, b, da, db):
+    g, o = (1.0, 0.0) if gain is None else gain
+    a = g * a + o
+    if mode == "feather":
+        wa, wb = np.where(pa, np.minimum(da, feather), 0.0)[..., None], np.where(pb, np.minimum(db, feather), 0.0)[..., None]
+        val = (wa * a + wb * b) / np.maximum(wa + wb, 1e-300)
+    elif mode == "b_over_a":
+        val = np.where(pb[..., None], b, a)
+    else:
+        val = np.where(pa[..., None], a, b)
+    val = np.where((pa | pb)[..., None], val, 0.0)
+    return np.floor(np.clip(val, 0, 255) + 0.5).astype(np.uint8), (pa.astype(np.uint8) | (pb.astype(np.uint8) << 1))
+
+
+# ------------------------------------------------------------------------------------------------
+# the exposure case and the aligner's pair
+# ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def darkened_pair(h=120, w=160, seed=5, g=0.8, o=10.0):
+    """(A, B) uint8 [1,h,w,3]: a texture and B = round_half_up(g A + o) per channel."""
+    A = textures(1, h, w, seed=seed)
+    B = np.floor(g * A.astype(np.float64) + o + 0.5).astype(np.uint8)
+    B.setflags(write=False)
+    return A, B
+
+
+class StubHead(torch.nn.Module):
+    """tests/test_align_gpu.py's: a 'model' whose prediction is given."""
+
+    def __init__(self, delta):
+        super().__init__()
+        self.delta, self.seen = delta, None
+
+    def predict_homography(self, data):
+        self.seen = data
+        return self.delta, None
+
+
+def whole_geom(h, w, P):
+    sx, sy = w / P, h / P
+    return np.array([[sx, sy, 0.5 * sx - 0.5, 0.5 * sy - 0.5]])
+
+
+@functools.lru_cache(maxsize=None)
+def aligner_pair(size_a=(120, 160), size_b=(96, 128), P=32, g=1.0, o=0.0):
+    """test_direction_and_lift_end_to_end's construction: A a texture, H_true = lift(delta) with delta on the 1/16-pixel grid (so the
+    float32 delta the stub returns is exact), B = round_half_up(g warp_u8_host(A, H_true) + o).  -> (A, B, delta [1,4,2], H_true [1,3,3])"""
+    (Ha, Wa), (Hb, Wb) = size_a, size_b
+    A = textures(1, Ha, Wa, seed=5)
+    delta = np.round(np.random.RandomState(3).uniform(-0.12 * P, 0.12 * P, (1, 4, 2)) * 16) / 16
+    H_true = align.lift(delta, P, whole_geom(Ha, Wa, P), whole_geom(Hb, Wb, P))
+    B, _ = align.warp_u8_host(A, H_true, Hb, Wb)
+    B = np.floor(g * B.astype(np.float64) + o + 0.5).astype(np.uint8)
+    for x in (B, delta, H_true):
+        x.setflags(write=False)
+    return A, B, delta, H_true
