@@ -111,33 +111,46 @@ def patch_corners(P):
     return np.array([[0, 0], [P, 0], [P, P], [0, P]], np.float64)
 
 
-def lift(delta_hat, P, geom_a, geom_b):
-    """delta_hat [B,4,2] (patch pixels), the geometry records of both preparations -> H [B,3,3] float64 with H[2,2] = 1: index
-    coordinates of image B -> index coordinates of image A (the Lift of the module docstring)."""
-    d = np.asarray(delta_hat, np.float64).reshape(-1, 4, 2)
-    Aa, Ab = _affine(geom_a), _affine(geom_b)
+def _compose(left, delta, P, geom_b):
+    """left [B,3,3], delta [B,4,2] (patch pixels), geom_b [B,4] -> left H_p(delta) A_b^-1 [B,3,3] float64 scaled to H[2,2] = 1, H_p =
+    four_point_to_homography of the patch square: what `lift` (left = A_a) and `cascade_compose` (left = H_prev A_b) share."""
+    d = np.asarray(delta, np.float64).reshape(-1, 4, 2)
+    Ab = _affine(geom_b)
     c = patch_corners(P)
     H = np.empty((d.shape[0], 3, 3))
     for b in range(d.shape[0]):
-        Hb = Aa[b] @ synth.four_point_homography(c, c + d[b]) @ np.linalg.inv(Ab[b])
+        Hb = left[b] @ synth.four_point_homography(c, c + d[b]) @ np.linalg.inv(Ab[b])
         H[b] = Hb / Hb[2, 2]
     return H
 
 
-def warp_u8_host(images, H, Ho, Wo):
-    """images uint8 [B,Hs,Ws,3], H [B,3,3] (output index coordinates -> source index coordinates) -> (out uint8 [B,Ho,Wo,3],
-    valid uint8 [B,Ho,Wo]): the uint8 warp of the module docstring."""
+def lift(delta_hat, P, geom_a, geom_b):
+    """delta_hat [B,4,2] (patch pixels), the geometry records of both preparations -> H [B,3,3] float64 with H[2,2] = 1: index
+    coordinates of image B -> index coordinates of image A (the Lift of the module docstring)."""
+    return _compose(_affine(geom_a), delta_hat, P, geom_b)
+
+
+def _project_host(M, Ho, Wo):
+    """(u, v float64 [Ho,Wo], guard bool [Ho,Wo]) of the output grid through M [3,3]; 1 / qz is 1 under the guard."""
+    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(np.float64)
+    qz = M[2, 0] * xs + M[2, 1] * ys + M[2, 2]
+    guard = ~(np.abs(qz) > QZ_GUARD)
+    iz = 1.0 / np.where(guard, 1.0, qz)
+    return (M[0, 0] * xs + M[0, 1] * ys + M[0, 2]) * iz, (M[1, 0] * xs + M[1, 1] * ys + M[1, 2]) * iz, guard
+
+
+def _sample_host(images, H, Ho, Wo):
+    """(values float64 [B,Ho,Wo,3], valid bool [B,Ho,Wo], guard bool [B,Ho,Wo]): the uint8 warp of the module docstring up to its
+    rounding."""
     images = np.asarray(images)
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
+        raise ValueError("sample_host: images uint8 [B,Hs,Ws,3], got %s %s" % (images.dtype, images.shape))
     H = np.asarray(H, np.float64).reshape(-1, 3, 3)
     B, Hs, Ws = images.shape[:3]
-    out, valid = np.empty((B, Ho, Wo, 3), np.uint8), np.empty((B, Ho, Wo), np.uint8)
-    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(np.float64)
+    out, valid, guards = np.empty((B, Ho, Wo, 3)), np.empty((B, Ho, Wo), bool), np.empty((B, Ho, Wo), bool)
     for b in range(B):
-        h, img = H[b], images[b].astype(np.float64)
-        qz = h[2, 0] * xs + h[2, 1] * ys + h[2, 2]
-        guard = ~(np.abs(qz) > QZ_GUARD)
-        iz = 1.0 / np.where(guard, 1.0, qz)
-        u, v = (h[0, 0] * xs + h[0, 1] * ys + h[0, 2]) * iz, (h[1, 0] * xs + h[1, 1] * ys + h[1, 2]) * iz
+        img = images[b].astype(np.float64)
+        u, v, guard = _project_host(H[b], Ho, Wo)
         with np.errstate(invalid="ignore"):
             x0f, y0f = np.floor(u), np.floor(v)
             fx, fy = u - x0f, v - y0f
@@ -151,8 +164,15 @@ def warp_u8_host(images, H, Ho, Wo):
                     w = np.where(ok, wy * wx, 0.0)
                     acc += img[np.clip(yi, 0, Hs - 1), np.clip(xi, 0, Ws - 1)] * np.nan_to_num(w)[..., None]
             valid[b] = ~guard & (u >= 0) & (u <= Ws - 1) & (v >= 0) & (v <= Hs - 1)
-        out[b] = np.floor(np.clip(acc, 0.0, 255.0) + 0.5).astype(np.uint8)
-    return out, valid
+        out[b], guards[b] = acc, guard
+    return out, valid, guards
+
+
+def warp_u8_host(images, H, Ho, Wo):
+    """images uint8 [B,Hs,Ws,3], H [B,3,3] (output index coordinates -> source index coordinates) -> (out uint8 [B,Ho,Wo,3],
+    valid uint8 [B,Ho,Wo]): the uint8 warp of the module docstring."""
+    values, valid, _ = _sample_host(images, H, Ho, Wo)
+    return np.floor(np.clip(values, 0.0, 255.0) + 0.5).astype(np.uint8), valid.astype(np.uint8)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -194,14 +214,6 @@ def mosaic_frame_host(H, size_a, size_b, canvas, limit=2.0):
     return T, np.stack([x0, y0, x1, y1], 1), usable.astype(np.uint8)
 
 
-def _project_host(M, Ho, Wo):
-    """(u, v) float64 [Ho,Wo] of the output grid through M [3,3]: `_sample_host`'s expressions (1 / qz is 1 under the guard)."""
-    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(np.float64)
-    qz = M[2, 0] * xs + M[2, 1] * ys + M[2, 2]
-    iz = 1.0 / np.where(~(np.abs(qz) > QZ_GUARD), 1.0, qz)
-    return (M[0, 0] * xs + M[0, 1] * ys + M[0, 2]) * iz, (M[1, 0] * xs + M[1, 1] * ys + M[1, 2]) * iz
-
-
 def mosaic_host(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather", gain=None):
     """images_a uint8 [B,Ha,Wa,3], images_b uint8 [B,Hb,Wb,3], Ma / Mb [B,3,3] (canvas index coordinates -> A's / B's; the caller passes
     Ma = H T, Mb = T), gain [B,2] = (g, o) or None -> (out uint8 [B,Hc,Wc,3], cover uint8 [B,Hc,Wc] = (A present) | (B present) << 1):
@@ -222,7 +234,7 @@ def mosaic_host(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather"
         for img, M in ((images_a, Ma[b]), (images_b, Mb[b])):
             Hx, Wx = np.asarray(img).shape[1:3]
             with np.errstate(all="ignore"):
-                u, v = _project_host(M, Hc, Wc)
+                u, v, _ = _project_host(M, Hc, Wc)
                 w.append(np.minimum(np.minimum(np.minimum(u, Wx - 1 - u), np.minimum(v, Hx - 1 - v)) + 1.0, feather))
         a, t, A, T = va[b], vb[b], pa[b][..., None], pb[b][..., None]
         if mode == "feather":
@@ -262,38 +274,6 @@ def exposure_host(sums):
 # ------------------------------------------------------------------------------------------------
 # cascaded re-prediction, the definitions (numpy float64; include/bihome.h "Cascaded re-prediction" states the same in C terms)
 # ------------------------------------------------------------------------------------------------
-def _sample_host(images, H, Ho, Wo):
-    """(values float64 [B,Ho,Wo,3], valid bool [B,Ho,Wo], guard bool [B,Ho,Wo]): warp_u8_host's arithmetic up to its rounding."""
-    images = np.asarray(images)
-    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] != 3:
-        raise ValueError("sample_host: images uint8 [B,Hs,Ws,3], got %s %s" % (images.dtype, images.shape))
-    H = np.asarray(H, np.float64).reshape(-1, 3, 3)
-    B, Hs, Ws = images.shape[:3]
-    out, valid, guards = np.empty((B, Ho, Wo, 3)), np.empty((B, Ho, Wo), bool), np.empty((B, Ho, Wo), bool)
-    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(np.float64)
-    for b in range(B):
-        h, img = H[b], images[b].astype(np.float64)
-        qz = h[2, 0] * xs + h[2, 1] * ys + h[2, 2]
-        guard = ~(np.abs(qz) > QZ_GUARD)
-        iz = 1.0 / np.where(guard, 1.0, qz)
-        u, v = (h[0, 0] * xs + h[0, 1] * ys + h[0, 2]) * iz, (h[1, 0] * xs + h[1, 1] * ys + h[1, 2]) * iz
-        with np.errstate(invalid="ignore"):
-            x0f, y0f = np.floor(u), np.floor(v)
-            fx, fy = u - x0f, v - y0f
-            x0 = np.clip(np.nan_to_num(x0f, nan=-2.0), -2, Ws).astype(np.int64)
-            y0 = np.clip(np.nan_to_num(y0f, nan=-2.0), -2, Hs).astype(np.int64)
-            acc = np.zeros((Ho, Wo, 3))
-            for dy, wy in ((0, 1 - fy), (1, fy)):
-                for dx, wx in ((0, 1 - fx), (1, fx)):
-                    xi, yi = x0 + dx, y0 + dy
-                    ok = (xi >= 0) & (xi < Ws) & (yi >= 0) & (yi < Hs)
-                    w = np.where(ok, wy * wx, 0.0)
-                    acc += img[np.clip(yi, 0, Hs - 1), np.clip(xi, 0, Ws - 1)] * np.nan_to_num(w)[..., None]
-            valid[b] = ~guard & (u >= 0) & (u <= Ws - 1) & (v >= 0) & (v <= Hs - 1)
-        out[b], guards[b] = acc, guard
-    return out, valid, guards
-
-
 def sample_host(images, H, Ho, Wo):
     """images uint8 [B,Hs,Ws,3], H [B,3,3] (output index coordinates -> source index coordinates) -> (values float64 [B,Ho,Wo,3], the
     bilinear samples with zero padding, NOT rounded or clamped; valid uint8 [B,Ho,Wo]): `warp_u8_host` without its rounding."""
@@ -348,14 +328,7 @@ def cascade_compose(H_prev, delta, P, geom_b):
     geom_b [B,4] -> H_prev A_b H_p(delta) A_b^-1 [B,3,3] scaled to H[2,2] = 1, H_p = four_point_to_homography of the patch square as in
     `lift`: patch coordinate q of the warped patch is A's coordinate H_prev A_b q, so the product still maps B's coordinates to A's."""
     Hp = np.asarray(H_prev, np.float64).reshape(-1, 3, 3)
-    d = np.asarray(delta, np.float64).reshape(-1, 4, 2)
-    Ab = _affine(geom_b)
-    c = patch_corners(P)
-    H = np.empty_like(Hp)
-    for b in range(Hp.shape[0]):
-        Hb = Hp[b] @ Ab[b] @ synth.four_point_homography(c, c + d[b]) @ np.linalg.inv(Ab[b])
-        H[b] = Hb / Hb[2, 2]
-    return H
+    return _compose([h @ a for h, a in zip(Hp, _affine(geom_b))], delta, P, geom_b)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -616,6 +589,19 @@ def _regions(roi, B, H, W, device, what):
     return torch.from_numpy(np.ascontiguousarray(r)).to(device)
 
 
+def _need_device(*tensors, name=True):
+    """RuntimeError unless every argument is a device tensor (name: the message says where they are)."""
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors):
+        got = " (got %s)" % " and ".join(str(t.device) for t in tensors) if name else ""
+        raise RuntimeError("bihome_amd kernels need device tensors%s; there is no CPU path" % got)
+
+
+def _need_h(H, who):
+    """ValueError unless H is [B,3,3] (or [B,9]) float64."""
+    if H.dtype != torch.float64 or H.dim() < 2 or H.numel() != 9 * H.shape[0]:
+        raise ValueError("%s: H [B,3,3] float64, got %s %s" % (who, H.dtype, tuple(H.shape)))
+
+
 def _affine_dev(geom, inverse=False):
     """geom [B,4] float64 device tensor -> A [B,3,3] (or A^-1), batched tensor arithmetic only."""
     A = torch.zeros((geom.shape[0], 3, 3), dtype=torch.float64, device=geom.device)
@@ -628,20 +614,24 @@ def _affine_dev(geom, inverse=False):
     return A
 
 
-def lift_device(delta_hat, P, geom_a, geom_b):
-    """`lift` on the device: delta_hat [B,4,2] float32, geom_* [B,4] float64 -> H [B,3,3] float64.  The 8 x 8 solve is bh_h4pt_fwd's
-    (double), the conjugation batched [B,3,3] double arithmetic; nothing is copied to the host."""
-    B = delta_hat.shape[0]
-    Hp = K.h4pt_fwd(delta_hat.reshape(B, 4, 2).to(torch.float32).contiguous(), P)[0].view(B, 3, 3)
-    H = _affine_dev(geom_a) @ Hp @ _affine_dev(geom_b, inverse=True)
+def _compose_device(left, delta, P, geom_b):
+    """`_compose` on the device: left [B,3,3] float64, delta [B,4,2] float32, geom_b [B,4] float64 -> H [B,3,3] float64.  The 8 x 8 solve
+    is bh_h4pt_fwd's (double), the rest batched [B,3,3] double arithmetic; nothing is copied to the host."""
+    B = delta.shape[0]
+    Hp = K.h4pt_fwd(delta.reshape(B, 4, 2).to(torch.float32).contiguous(), P)[0].view(B, 3, 3)
+    H = left @ Hp @ _affine_dev(geom_b, inverse=True)
     return (H / H[:, 2:3, 2:3]).contiguous()
+
+
+def lift_device(delta_hat, P, geom_a, geom_b):
+    """`lift` on the device: delta_hat [B,4,2] float32, geom_* [B,4] float64 -> H [B,3,3] float64 (`_compose_device`, left = A_a)."""
+    return _compose_device(_affine_dev(geom_a), delta_hat, P, geom_b)
 
 
 def prepare(images, B, patch, channels, mean=0.443, std=0.129, idx=None, roi=None):
     """bh_align_prep_u8 on outputs allocated here: (patch [B,C,P,P] float32, geom [B,4] float64) of B samples of the uint8 bank
     images [N,H,W,3]; idx [B] int32 and roi [B,4] float64 are DEVICE tensors or None (kernels.align_prep_u8)."""
-    if not images.is_cuda:
-        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % images.device)
+    _need_device(images)
     out = torch.empty((B, channels, patch, patch), dtype=torch.float32, device=images.device)
     geom = torch.empty((B, 4), dtype=torch.float64, device=images.device)
     return K.align_prep_u8(images, out, geom, mean, std, idx=idx, roi=roi)
@@ -649,8 +639,7 @@ def prepare(images, B, patch, channels, mean=0.443, std=0.129, idx=None, roi=Non
 
 def warp_u8(images, H64, Ho, Wo, idx=None, want_valid=True):
     """bh_warp_u8 on outputs allocated here: (out [B,Ho,Wo,3] uint8, valid [B,Ho,Wo] uint8 or None) (kernels.warp_u8)."""
-    if not images.is_cuda:
-        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % images.device)
+    _need_device(images)
     B = H64.shape[0]
     out = torch.empty((B, Ho, Wo, 3), dtype=torch.uint8, device=images.device)
     valid = torch.empty((B, Ho, Wo), dtype=torch.uint8, device=images.device) if want_valid else None
@@ -661,8 +650,7 @@ def prepare_warped(images, Hg, B, patch, channels, nx, ny, mean=0.443, std=0.129
     """bh_align_prep_warp_u8 on outputs allocated here: (patch [B,C,P,P] float32, cover [B,P,P] float32) of B samples of the uint8 bank
     images [N,Hs,Ws,3] seen through Hg [B,3,3] float64 (`prep_warp_host`; Hg = H @ grid_map(geom_b, nx, ny)); idx [B] int32 DEVICE tensor
     or None (kernels.align_prep_warp_u8)."""
-    if not images.is_cuda:
-        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % images.device)
+    _need_device(images)
     out = torch.empty((B, channels, patch, patch), dtype=torch.float32, device=images.device)
     cover = torch.empty((B, patch, patch), dtype=torch.float32, device=images.device)
     return K.align_prep_warp_u8(images, Hg, out, cover, nx, ny, mean, std, idx=idx)
@@ -671,19 +659,15 @@ def prepare_warped(images, Hg, B, patch, channels, nx, ny, mean=0.443, std=0.129
 def patch_ncc(w, t, cover=None):
     """bh_patch_ncc on an output allocated here: w, t [B,C,P,P] float32, cover [B,P,P] float32 or None -> [B,8] float64
     (n, sum w, sum t, sum ww, sum tt, sum wt, rho, 0) (`patch_ncc_host`)."""
-    if not w.is_cuda:
-        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % w.device)
+    _need_device(w)
     out = torch.empty((w.shape[0], 8), dtype=torch.float64, device=w.device)
     return K.patch_ncc(w, t, cover, out)
 
 
 def cascade_compose_device(H_prev, delta, P, geom_b):
-    """`cascade_compose` on the device: H_prev [B,3,3] float64, delta [B,4,2] float32, geom_b [B,4] float64 -> H [B,3,3] float64.  The
-    8 x 8 solve is bh_h4pt_fwd's, the rest batched [B,3,3] double arithmetic, as in `lift_device`."""
-    B = delta.shape[0]
-    Hp = K.h4pt_fwd(delta.reshape(B, 4, 2).to(torch.float32).contiguous(), P)[0].view(B, 3, 3)
-    H = H_prev @ _affine_dev(geom_b) @ Hp @ _affine_dev(geom_b, inverse=True)
-    return (H / H[:, 2:3, 2:3]).contiguous()
+    """`cascade_compose` on the device: H_prev [B,3,3] float64, delta [B,4,2] float32, geom_b [B,4] float64 -> H [B,3,3] float64
+    (`_compose_device`, left = H_prev A_b)."""
+    return _compose_device(H_prev @ _affine_dev(geom_b), delta, P, geom_b)
 
 
 def _cascade_samples(samples, roi_b, Hb, Wb, P):
@@ -708,8 +692,7 @@ def gray_pyramid(images, B, levels, idx=None):
     """bh_gray_pyramid_u8 on an output allocated here: pyr [B,total] float32, the gray box pyramids of B samples of the uint8 bank
     images [N,H,W,3] with the levels packed one after another (`pyramid_offsets`; `pyramid_level` views one).  idx [B] int32 DEVICE
     tensor or None.  ValueError, before any launch, for levels the images are too small for."""
-    if not images.is_cuda:
-        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % images.device)
+    _need_device(images)
     total = int(pyramid_offsets(images.shape[1], images.shape[2], levels)[-1])
     pyr = torch.empty((B, total), dtype=torch.float32, device=images.device)
     return K.gray_pyramid_u8(images, pyr, levels, idx=idx)
@@ -738,8 +721,7 @@ def mask_pyramid(mask, levels):
 def ecc_sums(a, t, H64, mask=None):
     """bh_ecc_sums on buffers allocated here: a [B,Ha,Wa], t [B,Hb,Wb] float32 gray planes of one level (`pyramid_level` views),
     H64 [B,3,3] float64, mask [B,Hb,Wb] uint8 or None -> sums [B,66] float64 (`ecc_sums_host`)."""
-    if not a.is_cuda:
-        raise RuntimeError("bihome_amd kernels need device tensors (got %s); there is no CPU path" % a.device)
+    _need_device(a)
     B = H64.shape[0]
     partial = torch.empty((K.ecc_sums_ws_doubles(t.shape[1], t.shape[2], B),), dtype=torch.float64, device=a.device)
     sums = torch.empty((B, ECC_SUMS), dtype=torch.float64, device=a.device)
@@ -787,10 +769,8 @@ def ecc_refine(images_a, images_b, H, levels=3, iters=10, idx_a=None, idx_b=None
     index coordinates -> A's), idx_* [B] int32 DEVICE tensors or None, mask [B,Hb,Wb] uint8 or None (non-zero: the pixel of B may count)
     -> (H [B,3,3] float64 with H[2,2] = 1, stats [B,levels,3] = (rho at the level's first pass, rho_best, accepted steps), index 0 the
     finest level).  ValueError, before any launch, for levels too deep for the images.  Nothing is copied to the host."""
-    if not (images_a.is_cuda and images_b.is_cuda and H.is_cuda):
-        raise RuntimeError("bihome_amd kernels need device tensors; there is no CPU path")
-    if H.dtype != torch.float64 or H.dim() < 2 or H.numel() != 9 * H.shape[0]:
-        raise ValueError("ecc_refine: H [B,3,3] float64, got %s %s" % (H.dtype, tuple(H.shape)))
+    _need_device(images_a, images_b, H, name=False)
+    _need_h(H, "ecc_refine")
     if not iters >= 0:
         raise ValueError("ecc_refine: iters >= 0, got %r" % (iters,))
     B, (Ha, Wa), (Hb, Wb) = H.shape[0], images_a.shape[1:3], images_b.shape[1:3]
@@ -852,8 +832,7 @@ def exposure_device(sums):
 
 def mosaic_u8(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather", gain=None, idx_a=None, idx_b=None, want_cover=True):
     """bh_mosaic_u8 on outputs allocated here: (out [B,Hc,Wc,3] uint8, cover [B,Hc,Wc] uint8 or None) (kernels.mosaic_u8; `mosaic_host`)."""
-    if not (images_a.is_cuda and images_b.is_cuda):
-        raise RuntimeError("bihome_amd kernels need device tensors (got %s and %s); there is no CPU path" % (images_a.device, images_b.device))
+    _need_device(images_a, images_b)
     B = Ma.shape[0]
     out = torch.empty((B, Hc, Wc, 3), dtype=torch.uint8, device=images_a.device)
     cover = torch.empty((B, Hc, Wc), dtype=torch.uint8, device=images_a.device) if want_cover else None
@@ -941,12 +920,10 @@ def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", expo
     (xmin, ymin, xmax, ymax in B's coordinates), 'mosaic_fitted' [B] uint8 (A's corners took part in the frame), 'mosaic_gain' [B,2]
     float64.  ValueError before any launch for arguments outside these; nothing is copied to the host."""
     a, b = _images(images_a, "images_a"), _images(images_b, "images_b")
-    if not isinstance(H, torch.Tensor) or not H.is_cuda:
-        raise RuntimeError("bihome_amd kernels need device tensors; there is no CPU path")
+    _need_device(H, name=False)
     if a.device != b.device or H.device != a.device:
         raise ValueError("mosaic: images_a is on %s, images_b on %s, H on %s" % (a.device, b.device, H.device))
-    if H.dtype != torch.float64 or H.dim() < 2 or H.numel() != 9 * H.shape[0]:
-        raise ValueError("mosaic: H [B,3,3] float64, got %s %s" % (H.dtype, tuple(H.shape)))
+    _need_h(H, "mosaic")
     B = H.shape[0]
     size = _mosaic_args(canvas, feather, mode, exposure, limit, a.shape[1:3], b.shape[1:3], "mosaic")
     if isinstance(exposure, torch.Tensor) and exposure.shape[0] != B:

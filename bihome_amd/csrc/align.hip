@@ -4,27 +4,19 @@
 // bh_align_prep_u8: uint8 interleaved RGB image (a region of it) -> the standardised P x P patch the model reads, as an exact area
 // average.  One thread per output pixel, all channels: it walks the source rows of its interval and, inside a row, the run of pixels its
 // interval covers (neighbouring lanes read neighbouring runs).  Interval ends in double (the same expressions as the host statement),
-// the overlaps (relative to the first pixel of the run) and the sums in float.  A pixel is one 4-byte load of any alignment (warp_tap.h
+// the overlaps (relative to the first pixel of the run) and the sums in float.  A pixel is one 4-byte load of any alignment (u8_image.h
 // ld_rgb_u8).
 //
-// bh_warp_u8: out(x, y) = bilinear image(H (x, y, 1)) on interleaved uint8, zero padding, round half up, with the validity mask.  The
-// projection and the placement of the four taps are warp_tap.h's.  Wo % 4 == 0 and out on a 4-byte boundary: a thread makes four pixels
-// and stores three dwords (consecutive lanes on consecutive 12 bytes, bank.hip's layout); anything else: one pixel, three byte stores.
+// bh_warp_u8: out(x, y) = bilinear image(H (x, y, 1)) on interleaved uint8, zero padding, round half up, with the validity mask: the
+// sample, its `valid` and the stores are u8_image.h's (u8_sample, u8_round, u8_store_pixels / u8_store_flags).  Wo % 4 == 0 and out on a
+// 4-byte boundary: a thread makes four pixels and stores three dwords; anything else: one pixel, three byte stores.
 //
 // The offset of an image in the bank is 64-bit (image 9,321 of a 240 x 320 bank starts past 2^31 bytes; inside an image offsets are
-// 32-bit), the image index is clamped, and every source pixel index is clamped to its image.  No atomics, no scratch, one writer per output element.
-#include "warp_tap.h"
+// 32-bit), the image index is clamped, and every source pixel index is clamped to its image (u8_image.h u8_image).  No atomics, no
+// scratch, one writer per output element.
+#include "u8_image.h"
 
 #define ALIGN_THREADS 256
-#define ALIGN_MAX_GRID_Y 65535
-
-struct __attribute__((aligned(4))) AlignDwords3 { unsigned a, b, c; };
-
-// sample b's image: idx[b], or b itself without an index list, clamped into [0, n_images)
-__device__ __forceinline__ size_t align_image(const int* __restrict__ idx, int b, int n_images) {
-    const int i = idx ? idx[b] : b;
-    return (size_t)(i < 0 ? 0 : (i >= n_images ? n_images - 1 : i));
-}
 
 // floor / ceil results as indices inside [0, n - 1], whatever the double is (NaN -> 0)
 __device__ __forceinline__ int align_index(double f, int n) { return (int)fmin(fmax(f, 0.0), (double)(n - 1)); }
@@ -65,7 +57,7 @@ __device__ __forceinline__ float prep_overlap(float lo, float hi, int k) {
     return fmaxf(fminf(hi, (float)(k + 1)) - fmaxf(lo, (float)k), 0.0f);
 }
 
-// grid (ceil(P * P / ALIGN_THREADS), min(B, ALIGN_MAX_GRID_Y)); H * W <= 2^30
+// grid (ceil(P * P / ALIGN_THREADS), u8_grid_y(B)); H * W <= 2^30
 template <int C, bool BYTES>
 __global__ void __launch_bounds__(ALIGN_THREADS) align_prep_kernel(const unsigned char* __restrict__ images, const int* __restrict__ idx, int n_images,
                                                                    int H, int W, const double* __restrict__ roi, int B, int P, double per_p,
@@ -84,15 +76,13 @@ __global__ void __launch_bounds__(ALIGN_THREADS) align_prep_kernel(const unsigne
         const int j0 = align_index(floor(yl), H), j1 = align_index(ceil(yh) - 1.0, H);
         // the interval relative to the first pixel of the run: the per-pixel overlaps are float arithmetic on small numbers
         const float fxl = (float)(xl - (double)i0), fxh = (float)(xh - (double)i0), fyl = (float)(yl - (double)j0), fyh = (float)(yh - (double)j0);
-        const size_t img = align_image(idx, b, n_images);
-        const unsigned char* image = images + img * n * 3;
-        const unsigned lim = u8_load_limit(img, n_images, n);
+        const U8Image im = u8_image(images, idx, b, n_images, n);
         float ar = 0.f, ag = 0.f, ab = 0.f;
         for (int j = j0; j <= j1; ++j) {
             const unsigned row = (unsigned)j * (unsigned)W;
             float rr = 0.f, rg = 0.f, rb = 0.f;
             for (int i = i0; i <= i1; ++i) {
-                const unsigned v = ld_rgb_u8<BYTES>(image, row + (unsigned)i, n, lim);
+                const unsigned v = ld_rgb_u8<BYTES>(im, row + (unsigned)i);
                 const float wx = prep_overlap(fxl, fxh, i - i0);
                 rr = __builtin_fmaf(wx, (float)(v & 255u), rr);
                 rg = __builtin_fmaf(wx, (float)((v >> 8) & 255u), rg);
@@ -104,23 +94,18 @@ __global__ void __launch_bounds__(ALIGN_THREADS) align_prep_kernel(const unsigne
             ab = __builtin_fmaf(wy, rb, ab);
         }
         const float inv = 1.0f / ((float)g.sx * (float)g.sy * 255.0f);
-        float* dst = patch + (size_t)b * C * P * P + u;
-        if constexpr (C == 1) {
-            dst[0] = ((0.299f * ar + 0.587f * ag + 0.114f * ab) * inv - mean) / std;
-        } else {
-            const size_t pp = (size_t)P * P;
-            dst[0] = (ar * inv - mean) / std;
-            dst[pp] = (ag * inv - mean) / std;
-            dst[2 * pp] = (ab * inv - mean) / std;
-        }
+        u8_store_patch<C>(patch + (size_t)b * C * P * P + u, (size_t)P * P, ar, ag, ab, inv, mean, std);
     }
 }
 
-// grid (ceil(Ho * (Wo / PX) / ALIGN_THREADS), min(B, ALIGN_MAX_GRID_Y)); PX = 4: Wo % 4 == 0 and out % 4 == 0 (valid_vec: valid % 4 == 0 too)
+// grid (ceil(Ho * (Wo / PX) / ALIGN_THREADS), u8_grid_y(B)); PX = 4: Wo % 4 == 0 and out % 4 == 0 (valid_vec: valid % 4 == 0 too).
+// The four-pixel form is a gather whose time is the latency of its sixteen loads: with five waves per SIMD as the target the compiler
+// keeps eight of them in flight (77-81 registers), with the default of eight it takes 52 registers, waits for every load before it
+// issues the next and 64 pairs of 480 x 640 take 80 us instead of 66.
 template <int PX, bool BYTES>
-__global__ void __launch_bounds__(ALIGN_THREADS) align_warp_kernel(const unsigned char* __restrict__ images, const int* __restrict__ idx, int n_images,
-                                                                   int Hs, int Ws, const double* __restrict__ H64, int B, int Ho, int Wo,
-                                                                   unsigned char* __restrict__ out, unsigned char* __restrict__ valid, int valid_vec) {
+__global__ void __launch_bounds__(ALIGN_THREADS) __attribute__((amdgpu_waves_per_eu(1, PX == 4 ? 5 : 8)))
+align_warp_kernel(const unsigned char* __restrict__ images, const int* __restrict__ idx, int n_images, int Hs, int Ws, const double* __restrict__ H64,
+                  int B, int Ho, int Wo, unsigned char* __restrict__ out, unsigned char* __restrict__ valid, int valid_vec) {
     const unsigned upr = (unsigned)Wo / PX;                                    // units per output row
     const unsigned u = blockIdx.x * ALIGN_THREADS + threadIdx.x;
     if (u >= upr * (unsigned)Ho) return;
@@ -129,46 +114,18 @@ __global__ void __launch_bounds__(ALIGN_THREADS) align_warp_kernel(const unsigne
     const float xmax = (float)(Ws - 1), ymax = (float)(Hs - 1);
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
         const Hf Hm = load_h(H64 + 9 * (size_t)b);
-        const size_t img = align_image(idx, b, n_images);
-        const unsigned char* image = images + img * n * 3;
-        const unsigned lim = u8_load_limit(img, n_images, n);
+        const U8Image im = u8_image(images, idx, b, n_images, n);
         unsigned o[PX * 3], ok[PX];
 #pragma unroll
         for (int p = 0; p < PX; ++p) {
-            const Tap4 t = make_tap4(Hm, x + p, y, Ws, Hs);
-            float w00, w01, w10, w11, wsum;
-            tap_weights(t, w00, w01, w10, w11, wsum);
-            // no branch around the loads: a tap outside the image reads pixel 0 and weighs 0
-            const unsigned p00 = ld_rgb_u8<BYTES>(image, tap_u8_pixel(t.o00), n, lim), p01 = ld_rgb_u8<BYTES>(image, tap_u8_pixel(t.o01), n, lim);
-            const unsigned p10 = ld_rgb_u8<BYTES>(image, tap_u8_pixel(t.o10), n, lim), p11 = ld_rgb_u8<BYTES>(image, tap_u8_pixel(t.o11), n, lim);
+            const U8Sample s = u8_sample<BYTES>(im, Hm, x + p, y, Ws, Hs, xmax, ymax);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v = tap_blend((float)((p00 >> (8 * c)) & 255u), (float)((p01 >> (8 * c)) & 255u), (float)((p10 >> (8 * c)) & 255u),
-                                          (float)((p11 >> (8 * c)) & 255u), w00, w01, w10, w11);
-                o[p * 3 + c] = (unsigned)(fminf(fmaxf(v, 0.0f), 255.0f) + 0.5f);      // (fmaxf drops a NaN: 0) round half up: the conversion truncates
-            }
-            ok[p] = (!t.guard && t.u >= 0.0f && t.u <= xmax && t.v >= 0.0f && t.v <= ymax) ? 1u : 0u;
+            for (int c = 0; c < 3; ++c) o[p * 3 + c] = u8_round(s.c[c]);
+            ok[p] = s.valid ? 1u : 0u;
         }
         const size_t at = ((size_t)b * Ho + y) * Wo + x;
-        unsigned char* dst = out + at * 3;
-        if constexpr (PX == 4) {
-            AlignDwords3 d;
-            d.a = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
-            d.b = o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24);
-            d.c = o[8] | (o[9] << 8) | (o[10] << 16) | (o[11] << 24);
-            *reinterpret_cast<AlignDwords3*>(dst) = d;
-            if (valid) {
-                if (valid_vec) *reinterpret_cast<unsigned*>(valid + at) = ok[0] | (ok[1] << 8) | (ok[2] << 16) | (ok[3] << 24);
-                else {
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) valid[at + p] = (unsigned char)ok[p];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) dst[i] = (unsigned char)o[i];
-            if (valid) valid[at] = (unsigned char)ok[0];
-        }
+        u8_store_pixels<PX>(out + at * 3, o);
+        if (valid) u8_store_flags<PX>(valid + at, ok, valid_vec);
     }
 }
 
@@ -182,13 +139,12 @@ int bh_align_prep_u8(const uint8_t* images, const int* idx, int n_images, int H,
     if (!images || !patch || !geom || align_extents_bad(B, n_images, H, W) || P < 1 || !(std != 0.0f) || std != std) return BH_E_BADARG;
     if ((C != 1 && C != 3) || P % 16 != 0 || P > 256 || (long long)H * W > (1ll << 30)) return BH_E_UNSUPPORTED;      // (32-bit offsets inside an image)
     if (B == 0) return BH_OK;
-    const dim3 grid((unsigned)(P * P + ALIGN_THREADS - 1) / ALIGN_THREADS, (unsigned)(B < ALIGN_MAX_GRID_Y ? B : ALIGN_MAX_GRID_Y));
+    const dim3 grid((unsigned)(P * P + ALIGN_THREADS - 1) / ALIGN_THREADS, u8_grid_y(B));
     hipStream_t st = bh_stream(stream);
     const bool bytes = (long long)H * W < 2;                                    // a single-pixel image: no room for 4-byte loads
-#define PREP_LAUNCH(C_, BYTES_) hipLaunchKernelGGL((align_prep_kernel<C_, BYTES_>), grid, dim3(ALIGN_THREADS), 0, st, images, idx, n_images, H, W, roi, B, P, 1.0 / (double)P, mean, std, patch, geom)
-    if (C == 1) { if (bytes) PREP_LAUNCH(1, true); else PREP_LAUNCH(1, false); }
-    else { if (bytes) PREP_LAUNCH(3, true); else PREP_LAUNCH(3, false); }
-#undef PREP_LAUNCH
+    u8_flags([&](auto gray, auto by) {
+        hipLaunchKernelGGL((align_prep_kernel<gray ? 1 : 3, by>), grid, dim3(ALIGN_THREADS), 0, st, images, idx, n_images, H, W, roi, B, P, 1.0 / (double)P, mean, std, patch, geom);
+    }, C == 1, bytes);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }
@@ -202,13 +158,12 @@ int bh_warp_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int 
     const bool vec = Wo % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0;
     const int valid_vec = valid && reinterpret_cast<uintptr_t>(valid) % 4 == 0;
     const unsigned units = (unsigned)Ho * ((unsigned)Wo / (vec ? 4 : 1));
-    const dim3 grid((units + ALIGN_THREADS - 1) / ALIGN_THREADS, (unsigned)(B < ALIGN_MAX_GRID_Y ? B : ALIGN_MAX_GRID_Y));
+    const dim3 grid((units + ALIGN_THREADS - 1) / ALIGN_THREADS, u8_grid_y(B));
     hipStream_t st = bh_stream(stream);
     const bool bytes = (long long)Hs * Ws < 2;                                  // a single-pixel image: no room for 4-byte loads
-#define WARP_LAUNCH(PX_, BYTES_) hipLaunchKernelGGL((align_warp_kernel<PX_, BYTES_>), grid, dim3(ALIGN_THREADS), 0, st, images, idx, n_images, Hs, Ws, H64, B, Ho, Wo, out, valid, valid_vec)
-    if (vec) { if (bytes) WARP_LAUNCH(4, true); else WARP_LAUNCH(4, false); }
-    else { if (bytes) WARP_LAUNCH(1, true); else WARP_LAUNCH(1, false); }
-#undef WARP_LAUNCH
+    u8_flags([&](auto four, auto by) {
+        hipLaunchKernelGGL((align_warp_kernel<four ? 4 : 1, by>), grid, dim3(ALIGN_THREADS), 0, st, images, idx, n_images, Hs, Ws, H64, B, Ho, Wo, out, valid, valid_vec);
+    }, vec, bytes);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

@@ -8,27 +8,19 @@
 // 12-byte load, consecutive lanes on consecutive 12 bytes) and stores one float4 into each of the three planes (consecutive lanes on
 // consecutive 16 bytes).  Scalar path (anything else): a thread takes one pixel, three byte loads and three float stores.  Every byte
 // offset is 64-bit: image 9,321 of a 240 x 320 bank already starts past 2^31.  No atomics, every output element written exactly once.
-#include "common.h"
+// Which image a sample reads (an index outside [0, n_images) is clamped into it), the 12-byte struct and the pixel store are u8_image.h's.
+#include "u8_image.h"
 
 #define BANK_THREADS 256
-#define BANK_MAX_GRID_Y 65535
 
-struct __attribute__((aligned(4))) BankDwords3 { unsigned a, b, c; };
-
-// an index outside [0, n_images) is clamped into it: nothing outside the bank is ever read
-__device__ __forceinline__ size_t bank_image(const int* __restrict__ img_idx, int b, int n_images) {
-    const int i = img_idx[b];
-    return (size_t)(i < 0 ? 0 : (i >= n_images ? n_images - 1 : i));
-}
-
-// grid (ceil(n/4 / BANK_THREADS), min(count, BANK_MAX_GRID_Y)), n = Hs*Ws pixels per image, n % 4 == 0
+// grid (ceil(n/4 / BANK_THREADS), u8_grid_y(count)), n = Hs*Ws pixels per image, n % 4 == 0
 __global__ void __launch_bounds__(BANK_THREADS) bank_gather_vec4_kernel(const unsigned char* __restrict__ bank, const int* __restrict__ img_idx,
                                                                         int count, int n_images, size_t n, float* __restrict__ out) {
     const size_t u = (size_t)blockIdx.x * BANK_THREADS + threadIdx.x;          // unit = pixels 4u .. 4u+3
     if (u >= n / 4) return;
     for (int b = blockIdx.y; b < count; b += gridDim.y) {
-        const unsigned char* src = bank + bank_image(img_idx, b, n_images) * n * 3;
-        const BankDwords3 d = reinterpret_cast<const BankDwords3*>(src)[u];
+        const unsigned char* src = bank + u8_image_index(img_idx, b, n_images) * n * 3;
+        const Dwords3 d = reinterpret_cast<const Dwords3*>(src)[u];
         // bytes, lowest first: d.a = r0 g0 b0 r1, d.b = g1 b1 r2 g2, d.c = b2 r3 g3 b3
         const float4 r = make_float4((float)(d.a & 255u), (float)(d.a >> 24), (float)((d.b >> 16) & 255u), (float)((d.c >> 8) & 255u));
         const float4 g = make_float4((float)((d.a >> 8) & 255u), (float)(d.b & 255u), (float)(d.b >> 24), (float)((d.c >> 16) & 255u));
@@ -40,13 +32,13 @@ __global__ void __launch_bounds__(BANK_THREADS) bank_gather_vec4_kernel(const un
     }
 }
 
-// grid (ceil(n / BANK_THREADS), min(count, BANK_MAX_GRID_Y)): any n, any alignment
+// grid (ceil(n / BANK_THREADS), u8_grid_y(count)): any n, any alignment
 __global__ void __launch_bounds__(BANK_THREADS) bank_gather_scalar_kernel(const unsigned char* __restrict__ bank, const int* __restrict__ img_idx,
                                                                           int count, int n_images, size_t n, float* __restrict__ out) {
     const size_t p = (size_t)blockIdx.x * BANK_THREADS + threadIdx.x;
     if (p >= n) return;
     for (int b = blockIdx.y; b < count; b += gridDim.y) {
-        const unsigned char* src = bank + (bank_image(img_idx, b, n_images) * n + p) * 3;
+        const unsigned char* src = bank + (u8_image_index(img_idx, b, n_images) * n + p) * 3;
         float* dst = out + (size_t)b * 3 * n + p;
         dst[0] = (float)src[0];
         dst[n] = (float)src[1];
@@ -127,7 +119,7 @@ __device__ __forceinline__ unsigned long long ingest_taps6(const unsigned char* 
     return edge ? v >> 24 : v;
 }
 
-// grid (ceil(H * (W / PX) / BANK_THREADS), min(count, BANK_MAX_GRID_Y)); PX = 4: W % 4 == 0 and bank % 4 == 0; H * W < 2^31
+// grid (ceil(H * (W / PX) / BANK_THREADS), u8_grid_y(count)); PX = 4: W % 4 == 0 and bank % 4 == 0; H * W < 2^31
 template <int PX>
 __global__ void __launch_bounds__(BANK_THREADS) bank_ingest_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ src_off,
                                                                    const int* __restrict__ src_hw, int count, unsigned char* __restrict__ bank,
@@ -171,17 +163,7 @@ __global__ void __launch_bounds__(BANK_THREADS) bank_ingest_kernel(const unsigne
 #pragma unroll
             for (int i = 0; i < PX * 3; ++i) o[i] = r0[i];
         }
-        unsigned char* dst = bank + (((size_t)(first + b) * H + y) * W + x) * 3;
-        if constexpr (PX == 4) {
-            BankDwords3 d;
-            d.a = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
-            d.b = o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24);
-            d.c = o[8] | (o[9] << 8) | (o[10] << 16) | (o[11] << 24);
-            *reinterpret_cast<BankDwords3*>(dst) = d;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) dst[i] = (unsigned char)o[i];
-        }
+        u8_store_pixels<PX>(bank + (((size_t)(first + b) * H + y) * W + x) * 3, o);
     }
 }
 
@@ -195,7 +177,7 @@ int bh_bank_ingest_u8(const unsigned char* src, const int64_t* src_off, const in
     if ((long long)H * W > 0x7fffffffll) return BH_E_UNSUPPORTED;              // (more than 2^31 - 1 pixels in one bank image)
     const bool vec = W % 4 == 0 && reinterpret_cast<uintptr_t>(bank) % 4 == 0;
     const unsigned units = (unsigned)H * ((unsigned)W / (vec ? 4 : 1));
-    const dim3 grid((units + BANK_THREADS - 1) / BANK_THREADS, (unsigned)(count < BANK_MAX_GRID_Y ? count : BANK_MAX_GRID_Y));
+    const dim3 grid((units + BANK_THREADS - 1) / BANK_THREADS, u8_grid_y(count));
     hipStream_t st = bh_stream(stream);
     if (vec) hipLaunchKernelGGL(bank_ingest_kernel<4>, grid, dim3(BANK_THREADS), 0, st, src, src_off, src_hw, count, bank, first, H, W);
     else hipLaunchKernelGGL(bank_ingest_kernel<1>, grid, dim3(BANK_THREADS), 0, st, src, src_off, src_hw, count, bank, first, H, W);
@@ -211,7 +193,7 @@ int bh_bank_gather_u8(const unsigned char* bank, const int* img_idx, int count, 
     const size_t units = vec ? n / 4 : n;
     const size_t gx = (units + BANK_THREADS - 1) / BANK_THREADS;
     if (gx > 0x7fffffffull) return BH_E_UNSUPPORTED;                         // (more than 2^39 pixels in one image)
-    const dim3 grid((unsigned)gx, (unsigned)(count < BANK_MAX_GRID_Y ? count : BANK_MAX_GRID_Y));
+    const dim3 grid((unsigned)gx, u8_grid_y(count));
     hipStream_t st = bh_stream(stream);
     if (vec) hipLaunchKernelGGL(bank_gather_vec4_kernel, grid, dim3(BANK_THREADS), 0, st, bank, img_idx, count, n_images, n, out);
     else hipLaunchKernelGGL(bank_gather_scalar_kernel, grid, dim3(BANK_THREADS), 0, st, bank, img_idx, count, n_images, n, out);

@@ -3,53 +3,35 @@
 //
 // bh_align_prep_warp_u8: image A seen through a homography, as the standardised P x P patch the model reads, without a full-size
 // intermediate image.  One thread per patch pixel: it walks the ny x nx sub-sample points of its cell on a virtual integer grid of
-// P ny x P nx points, each one bh_warp_u8's bilinear sample (warp_tap.h make_tap4 / tap_weights / tap_blend, ld_rgb_u8), and writes their
-// mean and the share of them that is valid.  The sub-samples are taken four at a time without a branch between them, so a thread has
+// P ny x P nx points, each one bh_warp_u8's bilinear sample with its `valid` (u8_image.h u8_sample), and writes their mean
+// (u8_store_patch) and the share of them that is valid.  The sub-samples are taken four at a time without a branch between them, so a thread has
 // sixteen independent pixel loads in flight (a gather: neighbouring lanes read neighbouring cells, nothing coalesces beyond a cache
 // line); what is left of nx ny after the groups of four is taken one by one.  Sums are float, in the fixed order of the walk.
 //
 // bh_patch_ncc: the zero-mean normalised correlation of two patches over the fully covered pixels.  One workgroup per sample, double
 // accumulators, a butterfly inside each wavefront and a fixed-order sum of the four wavefronts through LDS.
 //
-// The offset of an image in the bank is 64-bit, the image index is clamped, every pixel index is clamped to its image (ld_rgb_u8).  No
+// The offset of an image in the bank is 64-bit, the image index is clamped, every pixel index is clamped to its image (u8_image.h).  No
 // atomics, no scratch, one writer per output element.
-#include "warp_tap.h"
+#include "u8_image.h"
 
 #define CASCADE_THREADS 256
-#define CASCADE_MAX_GRID_Y 65535
 #define CASCADE_MAX_SUB 8
 #define CASCADE_MIN_N 16.0           // fewer counting elements than this: no score (bihome_amd.align.ECC_MIN_N)
-
-// sample b's image: idx[b], or b itself without an index list, clamped into [0, n_images)
-__device__ __forceinline__ size_t cascade_image(const int* __restrict__ idx, int b, int n_images) {
-    const int i = idx ? idx[b] : b;
-    return (size_t)(i < 0 ? 0 : (i >= n_images ? n_images - 1 : i));
-}
 
 struct SubAcc { float r, g, b; unsigned ok; };
 
 // one sub-sample: grid point (X, Y) -> its bilinear value on the three channels (0 under the guard) and its validity
 template <bool BYTES>
-__device__ __forceinline__ void cascade_sub(SubAcc& a, const Hf& Hm, int X, int Y, const unsigned char* __restrict__ image, unsigned n, unsigned lim,
-                                            int Ws, int Hs, float xmax, float ymax) {
-    const Tap4 t = make_tap4(Hm, X, Y, Ws, Hs);
-    float w00, w01, w10, w11, wsum;
-    tap_weights(t, w00, w01, w10, w11, wsum);
-    // no branch around the loads: a tap outside the image reads pixel 0 and weighs 0
-    const unsigned p00 = ld_rgb_u8<BYTES>(image, tap_u8_pixel(t.o00), n, lim), p01 = ld_rgb_u8<BYTES>(image, tap_u8_pixel(t.o01), n, lim);
-    const unsigned p10 = ld_rgb_u8<BYTES>(image, tap_u8_pixel(t.o10), n, lim), p11 = ld_rgb_u8<BYTES>(image, tap_u8_pixel(t.o11), n, lim);
-    float v[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-        v[c] = tap_blend((float)((p00 >> (8 * c)) & 255u), (float)((p01 >> (8 * c)) & 255u), (float)((p10 >> (8 * c)) & 255u),
-                         (float)((p11 >> (8 * c)) & 255u), w00, w01, w10, w11);
-    a.r += t.guard ? 0.0f : v[0];
-    a.g += t.guard ? 0.0f : v[1];
-    a.b += t.guard ? 0.0f : v[2];
-    a.ok += (!t.guard && t.u >= 0.0f && t.u <= xmax && t.v >= 0.0f && t.v <= ymax) ? 1u : 0u;
+__device__ __forceinline__ void cascade_sub(SubAcc& a, const U8Image& im, const Hf& Hm, int X, int Y, int Ws, int Hs, float xmax, float ymax) {
+    const U8Sample s = u8_sample<BYTES>(im, Hm, X, Y, Ws, Hs, xmax, ymax);
+    a.r += s.guard ? 0.0f : s.c[0];
+    a.g += s.guard ? 0.0f : s.c[1];
+    a.b += s.guard ? 0.0f : s.c[2];
+    a.ok += s.valid ? 1u : 0u;
 }
 
-// grid (ceil(P * P / CASCADE_THREADS), min(B, CASCADE_MAX_GRID_Y)); Hs * Ws <= 2^29, 1 <= nx, ny <= CASCADE_MAX_SUB
+// grid (ceil(P * P / CASCADE_THREADS), u8_grid_y(B)); Hs * Ws <= 2^29, 1 <= nx, ny <= CASCADE_MAX_SUB
 template <int C, bool BYTES>
 __global__ void __launch_bounds__(CASCADE_THREADS) align_prep_warp_kernel(const unsigned char* __restrict__ images, const int* __restrict__ idx, int n_images,
                                                                           int Hs, int Ws, const double* __restrict__ Hg, int B, int P, int nx, int ny,
@@ -63,9 +45,7 @@ __global__ void __launch_bounds__(CASCADE_THREADS) align_prep_warp_kernel(const 
     const float inv = 1.0f / ((float)subs * 255.0f);
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
         const Hf Hm = load_h(Hg + 9 * (size_t)b);
-        const size_t img = cascade_image(idx, b, n_images);
-        const unsigned char* image = images + img * n * 3;
-        const unsigned lim = u8_load_limit(img, n_images, n);
+        const U8Image im = u8_image(images, idx, b, n_images, n);
         SubAcc a = {0.f, 0.f, 0.f, 0u};
         int s = 0, sx = 0, sy = 0;          // sub-sample s sits at column sx, row sy of the cell: row-major
         for (; s + 4 <= subs; s += 4) {
@@ -76,21 +56,13 @@ __global__ void __launch_bounds__(CASCADE_THREADS) align_prep_warp_kernel(const 
                 if (++sx == nx) { sx = 0; ++sy; }
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) cascade_sub<BYTES>(a, Hm, X[k], Y[k], image, n, lim, Ws, Hs, xmax, ymax);
+            for (int k = 0; k < 4; ++k) cascade_sub<BYTES>(a, im, Hm, X[k], Y[k], Ws, Hs, xmax, ymax);
         }
         for (; s < subs; ++s) {
-            cascade_sub<BYTES>(a, Hm, X0 + sx, Y0 + sy, image, n, lim, Ws, Hs, xmax, ymax);
+            cascade_sub<BYTES>(a, im, Hm, X0 + sx, Y0 + sy, Ws, Hs, xmax, ymax);
             if (++sx == nx) { sx = 0; ++sy; }
         }
-        float* dst = patch + (size_t)b * C * P * P + u;
-        if constexpr (C == 1) {
-            dst[0] = ((0.299f * a.r + 0.587f * a.g + 0.114f * a.b) * inv - mean) / std;
-        } else {
-            const size_t pp = (size_t)P * P;
-            dst[0] = (a.r * inv - mean) / std;
-            dst[pp] = (a.g * inv - mean) / std;
-            dst[2 * pp] = (a.b * inv - mean) / std;
-        }
+        u8_store_patch<C>(patch + (size_t)b * C * P * P + u, (size_t)P * P, a.r, a.g, a.b, inv, mean, std);
         if (cover) cover[(size_t)b * P * P + u] = (float)a.ok / (float)subs;          // exactly 1.0f iff every sub-sample is valid
     }
 }
@@ -147,13 +119,12 @@ int bh_align_prep_warp_u8(const uint8_t* images, const int* idx, int n_images, i
     // (tap_place's offsets are ints of 4 bytes per pixel, byte offsets inside an image 32-bit)
     if (cascade_patch_unsupported(C, P) || nx < 1 || nx > CASCADE_MAX_SUB || ny < 1 || ny > CASCADE_MAX_SUB || (long long)Hs * Ws > (1ll << 29)) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
-    const dim3 grid((unsigned)(P * P + CASCADE_THREADS - 1) / CASCADE_THREADS, (unsigned)(B < CASCADE_MAX_GRID_Y ? B : CASCADE_MAX_GRID_Y));
+    const dim3 grid((unsigned)(P * P + CASCADE_THREADS - 1) / CASCADE_THREADS, u8_grid_y(B));
     hipStream_t st = bh_stream(stream);
     const bool bytes = (long long)Hs * Ws < 2;                                  // a single-pixel image: no room for 4-byte loads
-#define PREP_WARP_LAUNCH(C_, BYTES_) hipLaunchKernelGGL((align_prep_warp_kernel<C_, BYTES_>), grid, dim3(CASCADE_THREADS), 0, st, images, idx, n_images, Hs, Ws, Hg, B, P, nx, ny, mean, std, patch, cover)
-    if (C == 1) { if (bytes) PREP_WARP_LAUNCH(1, true); else PREP_WARP_LAUNCH(1, false); }
-    else { if (bytes) PREP_WARP_LAUNCH(3, true); else PREP_WARP_LAUNCH(3, false); }
-#undef PREP_WARP_LAUNCH
+    u8_flags([&](auto gray, auto by) {
+        hipLaunchKernelGGL((align_prep_warp_kernel<gray ? 1 : 3, by>), grid, dim3(CASCADE_THREADS), 0, st, images, idx, n_images, Hs, Ws, Hg, B, P, nx, ny, mean, std, patch, cover);
+    }, C == 1, bytes);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

@@ -1,7 +1,7 @@
 // Coarse-to-fine ECC refinement of a homography on two image pyramids (include/bihome.h "ECC refinement"; bihome_amd/align.py holds the
 // numpy float64 statements gray_pyramid_host / ecc_sums_host / ecc_step_host / ecc_refine_host the kernels are tested against).
 //
-// bh_gray_pyramid_u8: uint8 interleaved RGB -> gray float planes, level l the 2 x 2 box mean of level l - 1, one launch per level, one
+// bh_gray_pyramid_u8: uint8 interleaved RGB (u8_image.h u8_image / ld_rgb_u8) -> gray float planes, level l the 2 x 2 box mean of level l - 1, one launch per level, one
 // thread and one writer per element.  The gray value is two written-out fused multiply-adds, the box mean plain float operations without
 // contraction: the bits of a float32 numpy restatement.
 //
@@ -18,13 +18,12 @@
 // ecc_step_host in its order.
 //
 // bh_ecc_refine: the whole schedule on one stream - per level iters + 1 times (sums, partial reduction + step in one launch).
-#include "warp_tap.h"
+#include "u8_image.h"
 
 #define ECC_THREADS 256
 #define ECC_PX 16                                       // pixels a float accumulator carries before it is added to a double
 #define ECC_ROUNDS 4
 #define ECC_BLOCK_PIXELS (ECC_THREADS * ECC_PX * ECC_ROUNDS)
-#define ECC_MAX_GRID_Y 65535
 #define ECC_NZ 11
 #define ECC_NS BH_ECC_SUMS
 #define ECC_STEP_THREADS 128
@@ -36,16 +35,10 @@ static_assert(ECC_NS == ECC_NZ * (ECC_NZ + 1) / 2, "the upper triangle of z z^T"
 // index of entry (i, j), i <= j, of the row-major upper triangle of the 11 x 11 Gram matrix (include/bihome.h)
 __host__ __device__ constexpr int ecc_at(int i, int j) { return i * ECC_NZ - i * (i - 1) / 2 + (j - i); }
 
-// sample b's image: idx[b], or b itself without an index list, clamped into [0, n_images)   (align.hip's rule)
-__device__ __forceinline__ size_t ecc_image(const int* __restrict__ idx, int b, int n_images) {
-    const int i = idx ? idx[b] : b;
-    return (size_t)(i < 0 ? 0 : (i >= n_images ? n_images - 1 : i));
-}
-
 // ------------------------------------------------------------------------------------------------
 // the pyramid
 // ------------------------------------------------------------------------------------------------
-// grid (ceil(H * W / ECC_THREADS), min(B, ECC_MAX_GRID_Y)); H * W >= 64
+// grid (ceil(H * W / ECC_THREADS), u8_grid_y(B)); H * W >= 64
 __global__ void __launch_bounds__(ECC_THREADS) ecc_gray_kernel(const unsigned char* __restrict__ images, const int* __restrict__ idx, int n_images,
                                                                int H, int W, int B, size_t total, float* __restrict__ pyr) {
 #pragma clang fp contract(off)
@@ -53,8 +46,7 @@ __global__ void __launch_bounds__(ECC_THREADS) ecc_gray_kernel(const unsigned ch
     const unsigned u = blockIdx.x * ECC_THREADS + threadIdx.x;
     if (u >= n) return;
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
-        const size_t img = ecc_image(idx, b, n_images);
-        const unsigned v = ld_rgb_u8<false>(images + img * n * 3, u, n, u8_load_limit(img, n_images, n));
+        const unsigned v = ld_rgb_u8<false>(u8_image(images, idx, b, n_images, n), u);
         const float r = (float)(v & 255u), g = (float)((v >> 8) & 255u), bl = (float)((v >> 16) & 255u);
         pyr[(size_t)b * total + u] = __builtin_fmaf(0.114f, bl, __builtin_fmaf(0.587f, g, 0.299f * r));
     }
@@ -109,7 +101,7 @@ __device__ __forceinline__ void ecc_pixel(const float* __restrict__ A, int Wa, i
     z[8] = c ? iw : 0.0f; z[9] = c ? tv : 0.0f; z[10] = c ? 1.0f : 0.0f;
 }
 
-// grid (ceil(Hb * Wb / ECC_BLOCK_PIXELS), min(B, ECC_MAX_GRID_Y)); partial[B, gridDim.x, 66].  A thread's pixels lie ECC_THREADS apart, so
+// grid (ceil(Hb * Wb / ECC_BLOCK_PIXELS), u8_grid_y(B)); partial[B, gridDim.x, 66].  A thread's pixels lie ECC_THREADS apart, so
 // (x, y) advances by (ECC_THREADS % Wb, ECC_THREADS / Wb) with one carry: one division per thread, none per pixel.
 template <bool MASK>
 __global__ void __launch_bounds__(ECC_THREADS) ecc_sums_kernel(const float* __restrict__ a, int Ha, int Wa, size_t a_stride, const float* __restrict__ t,
@@ -350,7 +342,7 @@ static int ecc_layout(int H, int W, int levels, int64_t* off) {
 }
 
 static unsigned ecc_blocks(int Hb, int Wb) { return (unsigned)(((long long)Hb * Wb + ECC_BLOCK_PIXELS - 1) / ECC_BLOCK_PIXELS); }
-static dim3 ecc_grid(unsigned x, int B) { return dim3(x, (unsigned)(B < ECC_MAX_GRID_Y ? B : ECC_MAX_GRID_Y)); }
+static dim3 ecc_grid(unsigned x, int B) { return dim3(x, u8_grid_y(B)); }
 
 static void ecc_launch_sums(const float* a, int Ha, int Wa, size_t a_stride, const float* t, int Hb, int Wb, size_t t_stride, const uint8_t* mask,
                             size_t m_stride, const double* H64, int h_stride, int B, double* partial, hipStream_t st) {

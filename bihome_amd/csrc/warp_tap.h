@@ -97,27 +97,6 @@ __device__ __forceinline__ float tap_blend(float p00, float p01, float p10, floa
     return acc;
 }
 
-// Interleaved uint8 RGB images (csrc/align.hip): the taps are placed by tap_place as in a float plane (offset = 4 * pixel index), and a
-// pixel is read as ONE 4-byte load of any alignment, without a branch: bytes 3 p .. 3 p + 3.  The fourth byte belongs to the next pixel -
-// of the next image for the last pixel of an image, and outside the buffer for the last pixel of the LAST image, which is therefore read
-// one byte lower and shifted: `lim` is the highest byte offset inside the image at which four bytes may be read.  Offsets are 32-bit and
-// relative to the image (3 n < 2^32; the image's own base is a 64-bit pointer).  Images of a single pixel take byte loads (BYTES: the
-// caller's compile-time choice, so that the common path has no branch at all).
-// -> r | g << 8 | b << 16 in bits 0..23; bits 24..31 are NOT pixel data
-__device__ __forceinline__ unsigned tap_u8_pixel(unsigned o) { return o == TAP_OUTSIDE ? 0u : o >> 2; }      // a tap outside: pixel 0, weight 0
-__device__ __forceinline__ unsigned u8_load_limit(size_t image, int n_images, unsigned n) {
-    return image + 1 < (size_t)n_images ? 3u * n - 3u : 3u * n - 4u;      // (n >= 2)
-}
-template <bool BYTES>
-__device__ __forceinline__ unsigned ld_rgb_u8(const unsigned char* __restrict__ image, unsigned pixel, unsigned n, unsigned lim) {
-    pixel = pixel < n ? pixel : n - 1u;                // (never past the image, whatever the caller derived the index from)
-    if constexpr (BYTES) return (unsigned)image[3u * pixel] | ((unsigned)image[3u * pixel + 1u] << 8) | ((unsigned)image[3u * pixel + 2u] << 16);
-    const unsigned off = 3u * pixel, o = off < lim ? off : lim;
-    unsigned v;
-    __builtin_memcpy(&v, image + o, 4);
-    return v >> (8u * (off - o));
-}
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const float* p, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, bytes, 0x00020000);
 }

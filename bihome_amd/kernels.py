@@ -1581,6 +1581,11 @@ def bank_ingest_u8(src, src_off, src_hw, bank, first=0):
 # ------------------------------------------------------------------------------------------------
 # image alignment: uint8 images -> standardised patches, and the uint8 warp (bihome_amd/align.py)
 # ------------------------------------------------------------------------------------------------
+def _is_h(M):
+    """M is [B,3,3] or [B,9]: the shape of a batch of homographies (the dtype is _chk's)."""
+    return M.dim() >= 2 and M.numel() == 9 * M.shape[0]
+
+
 def _chk_images_u8(images, idx, B, what):
     _chk(images, torch.uint8); _chk(idx, torch.int32)
     if images.dim() != 4 or images.shape[3] != 3 or min(images.shape) < 1:
@@ -1612,7 +1617,7 @@ def warp_u8(images, H64, out, valid=None, idx=None):
     (may be None) (include/bihome.h bh_warp_u8).  Both outputs are the caller's (bihome_amd.align.warp_u8 allocates them).  H64 [B,3,3]
     or [B,9] float64: output index coordinates -> source index coordinates."""
     _chk(H64, torch.float64); _chk(out, torch.uint8); _chk(valid, torch.uint8)
-    if H64.dim() < 2 or H64.numel() != 9 * H64.shape[0]:
+    if not _is_h(H64):
         raise ValueError("warp_u8: H64 [B,3,3] float64, got %s" % (tuple(H64.shape),))
     B = H64.shape[0]
     if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (valid is not None and tuple(valid.shape) != tuple(out.shape[:3])):
@@ -1723,7 +1728,7 @@ def align_prep_warp_u8(images, Hg, patch, cover, nx, ny, mean, std, idx=None):
     patch pixel; cover [B,P,P] float32 (may be None) the share of them that is valid (include/bihome.h bh_align_prep_warp_u8).  Both
     outputs are the caller's (bihome_amd.align.prepare_warped allocates them).  idx [B] int32 as in align_prep_u8."""
     _chk(Hg, torch.float64); _chk(patch); _chk(cover)
-    if patch.dim() != 4 or patch.shape[2] != patch.shape[3] or Hg.dim() < 2 or Hg.numel() != 9 * patch.shape[0] or Hg.shape[0] != patch.shape[0]:
+    if patch.dim() != 4 or patch.shape[2] != patch.shape[3] or not _is_h(Hg) or Hg.shape[0] != patch.shape[0]:
         raise ValueError("align_prep_warp_u8: patch [B,C,P,P] float32 and Hg [B,3,3] float64, got %s and %s" % (tuple(patch.shape), tuple(Hg.shape)))
     B, C, P = patch.shape[:3]
     if cover is not None and tuple(cover.shape) != (B, P, P):
@@ -1762,7 +1767,7 @@ def mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=None, 
     (bihome_amd.align.mosaic_u8 allocates them)."""
     _chk(Ma, torch.float64); _chk(Mb, torch.float64); _chk(gain, torch.float64); _chk(out, torch.uint8); _chk(cover, torch.uint8)
     for M, what in ((Ma, "Ma"), (Mb, "Mb")):
-        if M.dim() < 2 or M.numel() != 9 * M.shape[0]:
+        if not _is_h(M):
             raise ValueError("mosaic_u8: %s [B,3,3] float64, got %s" % (what, tuple(M.shape)))
     B = Ma.shape[0]
     if Mb.shape[0] != B or (gain is not None and tuple(gain.shape) != (B, 2)):

@@ -851,7 +851,8 @@ int bh_align_prep_u8(const uint8_t* images, const int* idx, int n_images, int H,
  * H_img = A_a H_p A_b^-1 (H_p = bh_h4pt_fwd(delta_hat, P), eval.py:252-254; the loss trains patch_1(H_p x) ~ patch_2(x),
  * PerceptualHead.py:371) the source is image A and the output has image B's size.  out[B,Ho,Wo,3] uint8; valid[B,Ho,Wo] uint8 (NULL
  * ok) = 1 where the projected point lies in [0, Ws - 1] x [0, Hs - 1] and the projection guard (|qz| <= 1e-8) did not fire, else 0.
- * The projection and the placement of the taps are csrc/warp_tap.h's (tap_project / tap_place, float), as in every other warp here.
+ * The projection and the placement of the taps are csrc/warp_tap.h's (tap_project / tap_place, float), as in every other warp here; the
+ * sample of the uint8 image and its valid are csrc/u8_image.h's u8_sample, the one bh_align_prep_warp_u8 and bh_mosaic_u8 call too.
  * Wo % 4 == 0 with out on a 4-byte boundary: four pixels and three dword stores per thread; anything else one pixel and byte stores,
  * same results.  The offset of an image in the bank and every offset into out are 64-bit, offsets inside a source image 32-bit.  One writer per output element, no atomics: two calls are bitwise
  * equal.  BH_E_BADARG: NULL images / H64 / out, B < 0, n_images < 1, Hs < 1, Ws < 1, Ho < 1, Wo < 1; then BH_E_UNSUPPORTED: Hs * Ws
@@ -929,7 +930,7 @@ int bh_ecc_refine(const float* pyr_a, int Ha, int Wa, const float* pyr_b, int Hb
  * x nx .. x nx + nx - 1 and rows y ny .. y ny + ny - 1.  Hg[B,9] double maps the grid's index coordinates to index coordinates of
  * images[idx[b]] (the caller folds everything into it: Hg = H A_b S with A_b the affine map of B's preparation and
  * S = [[1/nx, 0, 0.5/nx - 0.5], [0, 1/ny, 0.5/ny - 0.5], [0, 0, 1]]).  Every sub-sample (X, Y) is bh_warp_u8's bilinear sample at
- * Hg (X, Y, 1) - csrc/warp_tap.h's make_tap4, tap_weights, tap_blend on the three channels, taps outside the image contribute 0 - and a
+ * Hg (X, Y, 1) - csrc/u8_image.h's u8_sample, the function bh_warp_u8 calls; taps outside the image contribute 0 - and a
  * sub-sample under the projection guard (|qz| <= 1e-8) contributes 0.  With m_c the sum over the nx ny sub-samples divided by nx ny:
  *     patch[b,c,y,x] = (v / 255 - mean) / std,  v = 0.299 m_R + 0.587 m_G + 0.114 m_B for C = 1, m_c for C = 3,
  * without a full-size intermediate image and without its rounding to uint8.  cover[B,P,P] float (NULL ok) = (number of VALID
@@ -960,8 +961,8 @@ int bh_patch_ncc(const float* w, const float* t, const float* cover, int B, int 
  * images_a[n_a,Ha,Wa,3], images_b[n_b,Hb,Wb,3] uint8 interleaved RGB banks, idx_a / idx_b[B] int32 as in bh_align_prep_u8 (NULL: sample b
  * is image b; CLAMPED into the bank in the kernel).  Ma[B,9], Mb[B,9] double map index coordinates of the CANVAS (Hc x Wc) to index
  * coordinates of A and of B: with H from B to A and T from the canvas to B, Ma = H T and Mb = T.  For image X in {A, B} at canvas pixel
- * (x, y): (u, v) and the bilinear value (taps outside the image contribute 0) are bh_warp_u8's, by csrc/warp_tap.h's make_tap4 /
- * tap_weights / tap_blend in float; X is PRESENT where bh_warp_u8's valid holds (no projection guard, 0 <= u <= Wx - 1,
+ * (x, y): (u, v) and the bilinear value (taps outside the image contribute 0) are bh_warp_u8's, by the function it calls
+ * (csrc/u8_image.h's u8_sample, float); X is PRESENT where bh_warp_u8's valid holds (no projection guard, 0 <= u <= Wx - 1,
  * 0 <= v <= Hx - 1); its weight is w = min(min(u, Wx - 1 - u, v, Hx - 1 - v) + 1, feather) where present: the distance to the border
  * of the image in its own pixels, plus 1, capped - feather = 1 is the plain average.  gain[B,2] double = (g, o) (NULL: (1, 0)) turns
  * A's value a into a' = fmaf(g, a, o) per channel, in grey levels, before the blend.  Then, by mode,

@@ -4,7 +4,8 @@ import functools
 
 import numpy as np
 
-from bihome_amd import align, synth
+from align_cases import corner_homography, f32_fma, near_border_points, pixels, sample_f32, textures, whole_geom
+from bihome_amd import align
 
 MEAN, STD = 0.443, 0.129
 PREP_BOUND = 1e-4 / STD          # the project's fp32 bound on a prepared patch: 1e-4 of the output range 1 / std (tests/test_align_gpu.py)
@@ -14,34 +15,6 @@ NEAR = 1e-3                      # cover is compared on patch pixels none of who
 WARP_CASES = [(37, 53, 29, 41, 16, 1, 1), (37, 53, 29, 41, 16, 3, 2), (37, 53, 29, 41, 16, 8, 8), (48, 80, 40, 56, 32, 2, 2)]
 WARP_IDS = ["37x53-from-29x41-1x1", "37x53-from-29x41-3x2", "37x53-from-29x41-8x8", "48x80-from-40x56-P32-2x2"]
 IDX, IDX_CLAMPED = (2, 0, 7), (2, 0, 3)          # a permuted index list into a bank of four; 7 lies outside and is clamped to 3
-
-
-@functools.lru_cache(maxsize=None)
-def pixels(n, h, w, seed=0):
-    a = np.random.RandomState(seed).randint(0, 256, (n, h, w, 3)).astype(np.uint8)
-    a.setflags(write=False)
-    return a
-
-
-@functools.lru_cache(maxsize=None)
-def textures(n, h, w, seed=0):
-    rng = np.random.default_rng(seed)
-    a = np.stack([np.floor(np.clip(synth.texture_image(rng, h, w), 0, 255) + 0.5).astype(np.uint8) for _ in range(n)])
-    a.setflags(write=False)
-    return a
-
-
-def whole_geom(h, w, P, n=1):
-    sx, sy = w / P, h / P
-    return np.tile(np.array([[sx, sy, 0.5 * sx - 0.5, 0.5 * sy - 0.5]]), (n, 1))
-
-
-def corner_homography(seed, Hs, Ws, Ho, Wo, frac=0.2):
-    """tests/test_align_gpu.py's: the corners of the Ho x Wo output onto the corners of the Hs x Ws source moved by up to frac of each side."""
-    rs = np.random.RandomState(seed)
-    co = np.array([[0, 0], [Wo - 1, 0], [Wo - 1, Ho - 1], [0, Ho - 1]], np.float64)
-    cs = np.array([[0, 0], [Ws - 1, 0], [Ws - 1, Hs - 1], [0, Hs - 1]], np.float64)
-    return synth.four_point_homography(co, cs + rs.uniform(-frac, frac, (4, 2)) * np.array([Ws, Hs]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -63,56 +36,23 @@ def warp_reference(case, C):
 
 def near_border(Hg, P, nx, ny, Hs, Ws):
     """bool [B,P,P]: a sub-sample of the patch pixel has its float64 point within NEAR px of one of the four border lines."""
-    Hg = np.asarray(Hg, np.float64).reshape(-1, 3, 3)
-    ys, xs = np.mgrid[0:P * ny, 0:P * nx].astype(np.float64)
-    out = np.zeros((Hg.shape[0], P, P), bool)
-    for b, h in enumerate(Hg):
-        with np.errstate(all="ignore"):
-            qz = h[2, 0] * xs + h[2, 1] * ys + h[2, 2]
-            u, v = (h[0, 0] * xs + h[0, 1] * ys + h[0, 2]) / qz, (h[1, 0] * xs + h[1, 1] * ys + h[1, 2]) / qz
-            near = np.minimum.reduce([np.abs(u), np.abs(u - (Ws - 1)), np.abs(v), np.abs(v - (Hs - 1))]) < NEAR
-        out[b] = near.reshape(P, ny, P, nx).any(axis=(1, 3))
-    return out
+    near = near_border_points(Hg, P * ny, P * nx, Hs, Ws, NEAR)
+    return near.reshape(-1, P, ny, P, nx).any(axis=(2, 4))
 
 
 # ------------------------------------------------------------------------------------------------
 # the kernel's arithmetic in float32 numpy
 # ------------------------------------------------------------------------------------------------
-def f32_fma(a, b, c):
-    """float32 fma: the product of two floats is exact in double, one double addition, one rounding to float."""
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
-
-
 def prep_warp_f32(images, Hg, P, C, nx, ny, mean=MEAN, std=STD):
-    """csrc/cascade.hip align_prep_warp_kernel in float32 numpy: warp_tap.h's tap_project / tap_place / tap_weights / tap_blend per
-    sub-sample, float32 sums in the order of the walk (rows of the cell, columns inside a row), the kernel's epilogue.  (The kernel's
-    reciprocal is within an ulp of the division used here.)  -> (patch float32 [B,C,P,P], cover float32 [B,P,P])"""
+    """csrc/cascade.hip align_prep_warp_kernel in float32 numpy: csrc/u8_image.h's u8_sample per sub-sample (align_cases.sample_f32),
+    float32 sums in the order of the walk (rows of the cell, columns inside a row), the epilogue (u8_store_patch).
+    -> (patch float32 [B,C,P,P], cover float32 [B,P,P])"""
     f = np.float32
     images = np.asarray(images)
-    B, Hs, Ws = images.shape[:3]
-    Hh, Wh = P * ny, P * nx
-    ys, xs = np.mgrid[0:Hh, 0:Wh].astype(f)
+    B = images.shape[0]
     patch, cover = np.empty((B, C, P, P), f), np.empty((B, P, P), f)
     for b in range(B):
-        h = np.asarray(Hg[b], np.float64).reshape(9).astype(f)
-        img = images[b].astype(f)
-        with np.errstate(all="ignore"):
-            qx, qy, qz = (f32_fma(np.full_like(xs, h[3 * r]), xs, f32_fma(np.full_like(ys, h[3 * r + 1]), ys, h[3 * r + 2])) for r in range(3))
-            guard = ~(np.abs(qz) > f(1e-8))
-            iz = (f(1) / np.where(guard, f(1), qz)).astype(f)
-            u, v = qx * iz, qy * iz
-            x0f, y0f = np.floor(u), np.floor(v)
-            fx, fy = u - x0f, v - y0f
-            x0 = np.clip(np.nan_to_num(x0f, nan=-2.0), -2, Ws).astype(np.int64)
-            y0 = np.clip(np.nan_to_num(y0f, nan=-2.0), -2, Hs).astype(np.int64)
-            vx0, vx1, vy0, vy1 = (x0 >= 0) & (x0 < Ws), (x0 + 1 >= 0) & (x0 + 1 < Ws), (y0 >= 0) & (y0 < Hs), (y0 + 1 >= 0) & (y0 + 1 < Hs)
-            wx0, wx1 = np.where(vx0, f(1) - fx, f(0)), np.where(vx1, fx, f(0))
-            wy0, wy1 = np.where(vy0, f(1) - fy, f(0)), np.where(vy1, fy, f(0))
-            ok = ~guard & (u >= 0) & (u <= f(Ws - 1)) & (v >= 0) & (v <= f(Hs - 1))
-        px = lambda dy, dx: img[np.clip(y0 + dy, 0, Hs - 1), np.clip(x0 + dx, 0, Ws - 1)]          # (a tap outside weighs 0)
-        w00, w01, w10, w11 = (wx0 * wy0)[..., None], (wx1 * wy0)[..., None], (wx0 * wy1)[..., None], (wx1 * wy1)[..., None]
-        val = f32_fma(px(1, 1), w11, f32_fma(px(1, 0), w10, f32_fma(px(0, 1), w01, px(0, 0) * w00)))
-        assert val.dtype == f
+        val, _, _, guard, ok = sample_f32(images[b], Hg[b], P * ny, P * nx)
         val = np.where(guard[..., None], f(0), val).reshape(P, ny, P, nx, 3)
         acc = np.zeros((P, P, 3), f)
         for sy in range(ny):

@@ -13,30 +13,14 @@ import pytest
 import torch
 
 import poisoned_alloc
-from bihome_amd import align, configs, synth
+from align_cases import corner_homography, near_border_points, pixels, textures
+from bihome_amd import align, configs
 
 pytestmark = pytest.mark.gpu
 
 MEAN, STD = 0.443, 0.129
 PREP_BOUND = 1e-4 / STD
 N_BIG = 9400        # 240 x 320 x 3 bytes per image: image 9,321 is the first that starts past 2^31 bytes (tests/test_bank_gpu.py)
-
-
-@functools.lru_cache(maxsize=None)
-def pixels(n, h, w, seed=0):
-    """uint8 [n,h,w,3] random bytes on the host, made once per shape and shared; callers do not modify it."""
-    a = np.random.RandomState(seed).randint(0, 256, (n, h, w, 3)).astype(np.uint8)
-    a.setflags(write=False)
-    return a
-
-
-@functools.lru_cache(maxsize=None)
-def textures(n, h, w, seed=0):
-    """uint8 [n,h,w,3]: synth.texture_image clipped and rounded to uint8, made once per shape and shared."""
-    rng = np.random.default_rng(seed)
-    a = np.stack([np.floor(np.clip(synth.texture_image(rng, h, w), 0, 255) + 0.5).astype(np.uint8) for _ in range(n)])
-    a.setflags(write=False)
-    return a
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,14 +34,6 @@ def cuda(a, dtype=None):
     return t if dtype is None else t.to(dtype)
 
 
-def corner_homography(seed, Hs, Ws, Ho, Wo, frac=0.2):
-    """The homography that sends the corners of the Ho x Wo output onto the corners of the Hs x Ws source moved by up to `frac` of each side."""
-    rs = np.random.RandomState(seed)
-    co = np.array([[0, 0], [Wo - 1, 0], [Wo - 1, Ho - 1], [0, Ho - 1]], np.float64)
-    cs = np.array([[0, 0], [Ws - 1, 0], [Ws - 1, Hs - 1], [0, Hs - 1]], np.float64)
-    return synth.four_point_homography(co, cs + rs.uniform(-frac, frac, (4, 2)) * np.array([Ws, Hs]))
-
-
 def check_u8(got, want, what):
     d = np.abs(got.astype(np.int32) - want.astype(np.int32))
     share = float((d.max(-1) > 0).mean())
@@ -67,14 +43,7 @@ def check_u8(got, want, what):
 
 def check_valid(got, want, H, Hs, Ws, what):
     B, Ho, Wo = want.shape
-    ys, xs = np.mgrid[0:Ho, 0:Wo].astype(np.float64)
-    near = np.zeros(want.shape, bool)
-    for b in range(B):
-        h = np.asarray(H[b], np.float64).reshape(3, 3)
-        qz = h[2, 0] * xs + h[2, 1] * ys + h[2, 2]
-        with np.errstate(all="ignore"):
-            u, v = (h[0, 0] * xs + h[0, 1] * ys + h[0, 2]) / qz, (h[1, 0] * xs + h[1, 1] * ys + h[1, 2]) / qz
-            near[b] = np.minimum.reduce([np.abs(u), np.abs(u - (Ws - 1)), np.abs(v), np.abs(v - (Hs - 1))]) < 1e-3
+    near = near_border_points(H, Ho, Wo, Hs, Ws, 1e-3)
     print("%s: valid compared on all but %.2e of the pixels" % (what, near.mean()))
     assert near.mean() <= 1e-3, (what, near.mean())
     assert np.array_equal(got[~near], want[~near]), what
