@@ -52,7 +52,17 @@ an image is PRESENT where warp_u8_host's `valid` holds.  Its weight is min(dista
 its own pixels, + 1, feather); mode "feather" gives (wa a' + wb b) / (wa + wb) over the images present, "b_over_a" / "a_over_b" put one
 image on top, nothing present gives 0, then round half up; cover = (A present) | (B present) << 1.  a' = g a + o is A after the optional
 gain / bias match: the ECC step is blind to both by design, so the blend handles them - `exposure_host` is the least-squares line of B's
-gray on A's through H from the sums ecc_sums_host already makes.  Stated below as mosaic_frame_host / mosaic_host / exposure_host."""
+gray on A's through H from the sums ecc_sums_host already makes.  Stated below as mosaic_frame_host / mosaic_host / exposure_host.
+
+Panorama (`aligner.sequence(images, idx, ..., canvas=...)` / `panorama`; csrc/pano.hip): a SEQUENCE of n frames (1..255) of one size and
+one bank, chosen by idx [B,n].  Frame r is the reference and G[b,k] maps the reference's index coordinates to frame k's (the pair
+convention with B = the reference; G[b,r] = I).  The n - 1 neighbouring pairs (`pairs_of`: pair j connects frames j and j + 1, b the
+one nearer to the reference) go through the aligner in ONE call, `chain_host` composes them outwards from the reference - G[a] = H_pair
+G[b], divided by its [2,2] entry; the exposure lines compose alongside - `pano_frame_host` is the mosaic's frame rule per frame (the
+reference's extent united with the clamped corners of every usable frame), and `pano_host` the mosaic's blend over the frames present:
+'feather' sum w v / sum w in frame order, 'first' / 'last' the lowest / highest frame present, count = the number present.  For n = 2 all
+three equal the pair's definitions bit for bit.  bh_pano_u8 makes the canvas in one pass, and a wavefront none of whose pixels has a
+frame present takes no tap of it."""
 import operator
 
 import numpy as np
@@ -181,23 +191,18 @@ def warp_u8_host(images, H, Ho, Wo):
 MOSAIC_MODES = ("feather", "b_over_a", "a_over_b")
 
 
-def mosaic_frame_host(H, size_a, size_b, canvas, limit=2.0):
-    """H [B,3,3] (B's index coordinates -> A's), size_a = (Ha, Wa), size_b = (Hb, Wb), canvas = (Hc, Wc) -> (T [B,3,3] float64: canvas
-    index coordinates -> B's, a scale and a translation; bbox [B,4] = (xmin, ymin, xmax, ymax) in B's index coordinates; fitted [B]
-    uint8): the Mosaic frame of the module docstring.  H^-1 is adjugate / determinant, written out."""
-    H = np.asarray(H, np.float64).reshape(-1, 3, 3)
-    (Ha, Wa), (Hb, Wb), (Hc, Wc) = size_a, size_b, canvas
-    if min(Hc, Wc) < 2:
-        raise ValueError("mosaic_frame: a canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (Hc, Wc))
-    if not limit > 0:
-        raise ValueError("mosaic_frame: limit > 0, got %r" % (limit,))
+def _corner_box(H, size_a, size_b, limit):
+    """H [K,3,3] (B's index coordinates -> A's) -> (x0, x1, y0, y1 [K] float64, usable [K] bool): B's extent united with A's four corners
+    through H^-1 (adjugate / determinant, written out) clamped to `limit` image sizes around B; B's extent alone where H is not usable.
+    What `mosaic_frame_host` and `pano_frame_host` share."""
+    (Ha, Wa), (Hb, Wb) = size_a, size_b
     a, b, c, d, e, f, g, h, i = (H[:, r, k] for r in range(3) for k in range(3))
     with np.errstate(all="ignore"):
         adj = ((e * i - f * h, c * h - b * i, b * f - c * e), (f * g - d * i, a * i - c * g, c * d - a * f), (d * h - e * g, b * g - a * h, a * e - b * d))
         det = a * adj[0][0] + b * adj[1][0] + c * adj[2][0]
         inv = [[adj[r][k] / det for k in range(3)] for r in range(3)]
         corners = ((0.0, 0.0), (Wa - 1.0, 0.0), (Wa - 1.0, Ha - 1.0), (0.0, Ha - 1.0))
-        qx, qy, qz = (np.stack([inv[r][0] * x + inv[r][1] * y + inv[r][2] for x, y in corners], 1) for r in range(3))          # [B,4]
+        qx, qy, qz = (np.stack([inv[r][0] * x + inv[r][1] * y + inv[r][2] for x, y in corners], 1) for r in range(3))          # [K,4]
         px, py = qx / qz, qy / qz
         usable = np.isfinite(det) & (det != 0) & np.isfinite(qz).all(1) & ((qz > 0).all(1) | (qz < 0).all(1)) & (np.abs(qz) > QZ_GUARD).all(1)
         usable &= np.isfinite(px).all(1) & np.isfinite(py).all(1)
@@ -205,13 +210,36 @@ def mosaic_frame_host(H, size_a, size_b, canvas, limit=2.0):
         x1 = np.maximum(np.clip(px.max(1), -limit * Wb, (1 + limit) * Wb - 1), Wb - 1.0)
         y0 = np.minimum(np.clip(py.min(1), -limit * Hb, (1 + limit) * Hb - 1), 0.0)
         y1 = np.maximum(np.clip(py.max(1), -limit * Hb, (1 + limit) * Hb - 1), Hb - 1.0)
-    x0, x1, y0, y1 = np.where(usable, x0, 0.0), np.where(usable, x1, Wb - 1.0), np.where(usable, y0, 0.0), np.where(usable, y1, Hb - 1.0)
+    return np.where(usable, x0, 0.0), np.where(usable, x1, Wb - 1.0), np.where(usable, y0, 0.0), np.where(usable, y1, Hb - 1.0), usable
+
+
+def _fit_canvas(x0, x1, y0, y1, canvas):
+    """The box [x0, x1] x [y0, y1] ([K] each) -> T [K,3,3]: canvas index coordinates -> the box's, one scale (the aspect ratio kept; 1 for
+    a box without extent) and the box centred."""
+    Hc, Wc = canvas
     s = np.maximum((x1 - x0) / (Wc - 1), (y1 - y0) / (Hc - 1))
     s = np.where(s == 0, 1.0, s)
-    T = np.zeros((H.shape[0], 3, 3))
+    T = np.zeros((x0.shape[0], 3, 3))
     T[:, 0, 0], T[:, 1, 1], T[:, 2, 2] = s, s, 1.0
     T[:, 0, 2], T[:, 1, 2] = (x0 + x1) * 0.5 - s * (0.5 * (Wc - 1)), (y0 + y1) * 0.5 - s * (0.5 * (Hc - 1))
-    return T, np.stack([x0, y0, x1, y1], 1), usable.astype(np.uint8)
+    return T
+
+
+def _frame_args(canvas, limit, who):
+    if min(canvas) < 2:
+        raise ValueError("%s: a canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (who, canvas[0], canvas[1]))
+    if not limit > 0:
+        raise ValueError("%s: limit > 0, got %r" % (who, limit))
+
+
+def mosaic_frame_host(H, size_a, size_b, canvas, limit=2.0):
+    """H [B,3,3] (B's index coordinates -> A's), size_a = (Ha, Wa), size_b = (Hb, Wb), canvas = (Hc, Wc) -> (T [B,3,3] float64: canvas
+    index coordinates -> B's, a scale and a translation; bbox [B,4] = (xmin, ymin, xmax, ymax) in B's index coordinates; fitted [B]
+    uint8): the Mosaic frame of the module docstring.  H^-1 is adjugate / determinant, written out."""
+    H = np.asarray(H, np.float64).reshape(-1, 3, 3)
+    _frame_args(canvas, limit, "mosaic_frame")
+    x0, x1, y0, y1, usable = _corner_box(H, size_a, size_b, limit)
+    return _fit_canvas(x0, x1, y0, y1, canvas), np.stack([x0, y0, x1, y1], 1), usable.astype(np.uint8)
 
 
 def mosaic_host(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather", gain=None):
@@ -248,6 +276,109 @@ def mosaic_host(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather"
             val = np.where(A, a, np.where(T, t, 0.0))
         out[b] = np.floor(np.clip(np.where(A | T, val, 0.0), 0.0, 255.0) + 0.5).astype(np.uint8)
     return out, (pa.astype(np.uint8) | (pb.astype(np.uint8) << 1)).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------
+# panorama, the definitions (numpy float64; include/bihome.h "Panorama" states the same in C terms)
+# ------------------------------------------------------------------------------------------------
+PANO_MODES = ("feather", "first", "last")
+PANO_MAX_FRAMES = 255              # count is a byte
+
+
+def pairs_of(n, ref):
+    """The n - 1 pairs (a, b) of a chain of n frames around the reference `ref`: pair j connects frames j and j + 1, and b is the one
+    nearer to the reference - (j + 1, j) for j >= ref, (j, j + 1) for j < ref."""
+    if not (1 <= n <= PANO_MAX_FRAMES and 0 <= ref < n):
+        raise ValueError("pairs_of: 1 <= n <= %d and 0 <= ref < n, got n = %r, ref = %r" % (PANO_MAX_FRAMES, n, ref))
+    return [(j, j + 1) if j < ref else (j + 1, j) for j in range(n - 1)]
+
+
+def chain_host(H_pairs, ref, gain_pairs=None):
+    """H_pairs [B,n-1,3,3] (pair j of `pairs_of`: b's index coordinates -> a's), gain_pairs [B,n-1,2] = (g, o) with v_b ~ g v_a + o, or
+    None -> G [B,n,3,3] float64 (the reference's index coordinates -> frame k's, G[ref] = I, every G scaled to G[2,2] = 1 by an unguarded
+    division), and with gains also gain [B,n,2] (frame k's line to the reference, (1, 0) for the reference): the Panorama chain."""
+    Hp = np.asarray(H_pairs, np.float64)
+    if Hp.ndim != 4 or Hp.shape[2:] != (3, 3):
+        raise ValueError("chain_host: H_pairs [B,n-1,3,3], got %s" % (Hp.shape,))
+    B, n = Hp.shape[0], Hp.shape[1] + 1
+    order = pairs_of(n, ref)
+    G = np.empty((B, n, 3, 3))
+    G[:, ref] = np.eye(3)
+    gp = None if gain_pairs is None else np.asarray(gain_pairs, np.float64).reshape(B, n - 1, 2)
+    gain = np.empty((B, n, 2))
+    gain[:, ref] = 1.0, 0.0
+    with np.errstate(all="ignore"):
+        for j in list(range(ref, n - 1)) + list(range(ref - 1, -1, -1)):
+            a, b = order[j]
+            P = Hp[:, j] @ G[:, b]
+            G[:, a] = P / P[:, 2:3, 2:3]
+            if gp is not None:
+                gain[:, a, 0] = gain[:, b, 0] * gp[:, j, 0]
+                gain[:, a, 1] = gain[:, b, 0] * gp[:, j, 1] + gain[:, b, 1]
+    return G if gp is None else (G, gain)
+
+
+def pano_frame_host(G, size, canvas, limit=2.0, use=None):
+    """G [B,n,3,3] (the reference's index coordinates -> frame k's), size = (Hs, Ws) of every frame, canvas = (Hc, Wc), use [B,n] or None
+    -> (T [B,3,3] float64: canvas index coordinates -> the reference's; bbox [B,4] = (xmin, ymin, xmax, ymax) in the reference's index
+    coordinates; fitted [B,n] uint8): `mosaic_frame_host`'s rule per frame - the reference's extent united with the clamped corners of
+    every frame that is usable and in use."""
+    G = np.asarray(G, np.float64)
+    if G.ndim != 4 or G.shape[2:] != (3, 3) or not 1 <= G.shape[1] <= PANO_MAX_FRAMES:
+        raise ValueError("pano_frame: G [B,n,3,3] with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, G.shape))
+    _frame_args(canvas, limit, "pano_frame")
+    B, n = G.shape[:2]
+    Hs, Ws = size
+    x0, x1, y0, y1, usable = (v.reshape(B, n) for v in _corner_box(G.reshape(B * n, 3, 3), size, size, limit))
+    fitted = usable if use is None else usable & (np.asarray(use).reshape(B, n) != 0)
+    x0, x1 = np.where(fitted, x0, 0.0).min(1), np.where(fitted, x1, Ws - 1.0).max(1)
+    y0, y1 = np.where(fitted, y0, 0.0).min(1), np.where(fitted, y1, Hs - 1.0).max(1)
+    return _fit_canvas(x0, x1, y0, y1, canvas), np.stack([x0, y0, x1, y1], 1), fitted.astype(np.uint8)
+
+
+def pano_host(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, use=None):
+    """images uint8 [N,Hs,Ws,3], idx [B,n] (frame k of sample b is images[idx[b,k]]), M [B,n,3,3] (canvas index coordinates -> frame
+    k's; the caller passes G T), gain [B,n,2] = (g, o) or None, use [B,n] or None -> (out uint8 [B,Hc,Wc,3], count uint8 [B,Hc,Wc]): frame
+    k is PRESENT at a canvas pixel where warp_u8_host's `valid` holds and use[b,k] != 0, its value is g v + o and its weight
+    `mosaic_host`'s; 'feather' is sum w v / sum w over the frames present, accumulated in the order k = 0..n-1, 'first' / 'last' the value
+    of the lowest / highest k present, nothing present 0; then round half up.  count is the number of frames present."""
+    if mode not in PANO_MODES:
+        raise ValueError("pano_host: mode is one of %s, got %r" % (PANO_MODES, mode))
+    if not (feather >= 1 and np.isfinite(feather)):
+        raise ValueError("pano_host: feather is finite and at least 1, got %r" % (feather,))
+    images, idx = np.asarray(images), np.asarray(idx)
+    M = np.asarray(M, np.float64)
+    if idx.ndim != 2 or not 1 <= idx.shape[1] <= PANO_MAX_FRAMES or M.shape != idx.shape + (3, 3):
+        raise ValueError("pano_host: idx [B,n] with 1 <= n <= %d and M [B,n,3,3], got %s and %s" % (PANO_MAX_FRAMES, idx.shape, M.shape))
+    B, n = idx.shape
+    gain = np.tile(np.array([1.0, 0.0]), (B, n, 1)) if gain is None else np.asarray(gain, np.float64).reshape(B, n, 2)
+    use = np.ones((B, n), bool) if use is None else np.asarray(use).reshape(B, n) != 0
+    Hs, Ws = images.shape[1:3]
+    num, den, val = np.zeros((B, Hc, Wc, 3)), np.zeros((B, Hc, Wc, 1)), np.zeros((B, Hc, Wc, 3))
+    count = np.zeros((B, Hc, Wc), np.uint8)
+    for k in range(n):
+        v, present, _ = _sample_host(images[idx[:, k]], M[:, k], Hc, Wc)
+        present = present & use[:, k, None, None]
+        v = gain[:, k, 0, None, None, None] * v + gain[:, k, 1, None, None, None]
+        P = present[..., None]
+        if mode == "feather":
+            w = np.empty((B, Hc, Wc))
+            for b in range(B):
+                with np.errstate(all="ignore"):
+                    pu, pv, _ = _project_host(M[b, k], Hc, Wc)
+                    w[b] = np.minimum(np.minimum(np.minimum(pu, Ws - 1 - pu), np.minimum(pv, Hs - 1 - pv)) + 1.0, feather)
+            w = np.where(present, w, 0.0)[..., None]
+            num = num + np.where(P, w * np.where(P, v, 0.0), 0.0)
+            den = den + w
+        elif mode == "first":
+            val = np.where(P & (count == 0)[..., None], v, val)
+        else:
+            val = np.where(P, v, val)
+        count = count + present.astype(np.uint8)
+    if mode == "feather":
+        val = np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
+    out = np.floor(np.clip(np.where((count > 0)[..., None], val, 0.0), 0.0, 255.0) + 0.5).astype(np.uint8)
+    return out, count
 
 
 def exposure_host(sums):
@@ -940,6 +1071,169 @@ def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", expo
         return _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b)
 
 
+# ------------------------------------------------------------------------------------------------
+# panorama, the device path
+# ------------------------------------------------------------------------------------------------
+def chain_device(H_pairs, ref, gain_pairs=None):
+    """bh_pano_chain on outputs allocated here (`chain_host`): H_pairs [B,n-1,3,3] float64, gain_pairs [B,n-1,2] float64 or None ->
+    (G [B,n,3,3] float64, gain [B,n,2] float64 or None)."""
+    _need_device(H_pairs)
+    if H_pairs.dim() != 4 or tuple(H_pairs.shape[2:]) != (3, 3):
+        raise ValueError("chain_device: H_pairs [B,n-1,3,3] float64, got %s" % (tuple(H_pairs.shape),))
+    B, n = H_pairs.shape[0], H_pairs.shape[1] + 1
+    G = torch.empty((B, n, 3, 3), dtype=torch.float64, device=H_pairs.device)
+    gain = None if gain_pairs is None else torch.empty((B, n, 2), dtype=torch.float64, device=H_pairs.device)
+    return K.pano_chain(H_pairs.contiguous(), ref, G, None if gain_pairs is None else gain_pairs.contiguous(), gain)
+
+
+def pano_frame_device(G, size, canvas, limit=2.0, use=None):
+    """bh_pano_frame on outputs allocated here (`pano_frame_host`): G [B,n,3,3] float64, use [B,n] uint8 or None -> (T [B,3,3] float64,
+    bbox [B,4] float64, fitted [B,n] uint8, M [B,n,3,3] float64 = G T): one launch."""
+    _need_device(G)
+    _frame_args(canvas, limit, "pano_frame")
+    if G.dim() != 4:
+        raise ValueError("pano_frame: G [B,n,3,3] float64, got %s" % (tuple(G.shape),))
+    B, n = G.shape[:2]
+    T = torch.empty((B, 3, 3), dtype=torch.float64, device=G.device)
+    bbox = torch.empty((B, 4), dtype=torch.float64, device=G.device)
+    fitted = torch.empty((B, n), dtype=torch.uint8, device=G.device)
+    M = torch.empty((B, n, 3, 3), dtype=torch.float64, device=G.device)
+    return K.pano_frame(G.contiguous(), size, canvas, limit, T, bbox, fitted, M, use=use)
+
+
+def pano_u8(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, use=None, want_count=True):
+    """bh_pano_u8 on outputs allocated here: (out [B,Hc,Wc,3] uint8, count [B,Hc,Wc] uint8 or None) (kernels.pano_u8; `pano_host`)."""
+    _need_device(images)
+    B = M.shape[0]
+    out = torch.empty((B, Hc, Wc, 3), dtype=torch.uint8, device=images.device)
+    count = torch.empty((B, Hc, Wc), dtype=torch.uint8, device=images.device) if want_count else None
+    return K.pano_u8(images, idx, M, out, count, feather, mode, gain=gain, use=use)
+
+
+def _frames_index(idx, n_images, device, who):
+    """idx -> int32 [B,n] device tensor.  None: one sample of all the bank's images in order; host values are range-checked here, a
+    device tensor is the kernel's to clamp."""
+    if idx is None:
+        if n_images > PANO_MAX_FRAMES:
+            raise ValueError("%s: idx=None takes the whole bank as one sequence, at most %d frames; the bank has %d" % (who, PANO_MAX_FRAMES, n_images))
+        return torch.arange(n_images, dtype=torch.int32, device=device).reshape(1, n_images)
+    if isinstance(idx, torch.Tensor) and idx.is_cuda:
+        if idx.dim() != 2 or idx.dtype != torch.int32 or not 1 <= idx.shape[1] <= PANO_MAX_FRAMES:
+            raise ValueError("%s: idx on the device is an int32 [B,n] tensor with 1 <= n <= %d, got %s %s" % (who, PANO_MAX_FRAMES, idx.dtype, tuple(idx.shape)))
+        return idx.contiguous()
+    host = np.asarray(idx.numpy() if isinstance(idx, torch.Tensor) else idx)
+    if host.ndim != 2 or not np.issubdtype(host.dtype, np.integer) or not 1 <= host.shape[1] <= PANO_MAX_FRAMES:
+        raise ValueError("%s: idx is [B,n] image indices with 1 <= n <= %d, got %s %s" % (who, PANO_MAX_FRAMES, host.dtype, host.shape))
+    for b, row in enumerate(host.tolist()):
+        for k, i in enumerate(row):
+            if not 0 <= i < n_images:
+                raise ValueError("%s: idx of sample %d, frame %d is %d, outside [0, %d)" % (who, b, k, i, n_images))
+    return torch.from_numpy(host.astype(np.int32)).to(device)
+
+
+def _pano_args(canvas, feather, mode, limit, who):
+    """The host-side argument rules of `panorama` and Aligner.sequence(canvas=), checked before any launch -> (Hc, Wc) or None for 'ref'."""
+    size = None
+    if not (isinstance(canvas, str) and canvas == "ref"):
+        try:
+            size = tuple(operator.index(v) for v in canvas)
+        except (TypeError, ValueError):
+            size = ()
+        if len(size) != 2:
+            raise ValueError("%s: the panorama canvas is 'ref' (the reference frame's grid) or (Hc, Wc), got %r" % (who, canvas))
+        if min(size) < 2:
+            raise ValueError("%s: a panorama canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (who, size[0], size[1]))
+    try:
+        feather_ok = bool(1.0 <= float(feather) < float("inf"))                # (False for a NaN too)
+    except (TypeError, ValueError):
+        feather_ok = False
+    if not feather_ok:
+        raise ValueError("%s: the panorama feather is finite and at least 1 (pixels), got %r" % (who, feather))
+    if not (isinstance(mode, str) and mode in PANO_MODES):
+        raise ValueError("%s: the panorama mode is one of %s, got %r" % (who, ", ".join(PANO_MODES), mode))
+    try:
+        limit_ok = bool(float(limit) > 0)
+    except (TypeError, ValueError):
+        limit_ok = False
+    if not limit_ok:
+        raise ValueError("%s: the panorama limit (image sizes around the reference that the frame may reach) is > 0, got %r" % (who, limit))
+    return size
+
+
+def _pano_tensor(t, shape, dtype, what, who):
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape:
+        got = "%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if isinstance(t, torch.Tensor) else repr(t)
+        raise ValueError("%s: the panorama %s is a %s %s device tensor, got %s" % (who, what, dtype, list(shape), got))
+    return t.contiguous()
+
+
+def _panorama(images, idx, G, size, feather, mode, gain, use, limit):
+    """The panorama stage on checked arguments -> its seven keys."""
+    B, n = G.shape[:2]
+    dev, (Hs, Ws) = G.device, images.shape[1:3]
+    if size is None:
+        Hc, Wc = Hs, Ws
+        T = torch.zeros((B, 3, 3), dtype=torch.float64, device=dev)
+        T[:, 0, 0] = T[:, 1, 1] = T[:, 2, 2] = 1.0
+        bbox = torch.zeros((B, 4), dtype=torch.float64, device=dev)
+        bbox[:, 2], bbox[:, 3] = Ws - 1.0, Hs - 1.0
+        fitted = torch.zeros((B, n), dtype=torch.uint8, device=dev)
+        M = G
+    else:
+        Hc, Wc = size
+        T, bbox, fitted, M = pano_frame_device(G, (Hs, Ws), (Hc, Wc), limit, use=use)
+    out, count = pano_u8(images, idx, M, Hc, Wc, feather, mode, gain=gain, use=use)
+    if gain is None:
+        gain = torch.zeros((B, n, 2), dtype=torch.float64, device=dev)
+        gain[:, :, 0] = 1.0
+    return {"panorama": out, "panorama_count": count, "panorama_T": T, "panorama_bbox": bbox, "panorama_fitted": fitted, "panorama_M": M,
+            "panorama_gain": gain}
+
+
+def panorama(images, G, idx=None, canvas="ref", feather=32.0, mode="feather", gain=None, use=None, limit=2.0):
+    """The n frames of a sequence on one canvas, for a caller who has G [B,n,3,3] float64 (the reference's index coordinates -> frame
+    k's, the identity for the reference) from anywhere: images a uint8 [N,Hs,Ws,3] device tensor or an ImageBank, idx [B,n] (host values:
+    range-checked; int32 device tensor: clamped by the kernel; None: one sample of all N images in order).  canvas="ref": the canvas is
+    the reference's grid (T the identity, M = G, no frame launch); canvas=(Hc, Wc): the frame `pano_frame_device` fits around the
+    reference and every usable frame's projected corners, `limit` image sizes around the reference at most.  feather / mode: `pano_host`.
+    gain [B,n,2] float64 device tensor (g, o) per frame, use [B,n] uint8 device tensor (0: the frame is left out), or None.  -> dict:
+    'panorama' [B,Hc,Wc,3] uint8, 'panorama_count' [B,Hc,Wc] uint8 (frames present), 'panorama_T' [B,3,3] float64 (canvas -> reference),
+    'panorama_bbox' [B,4] float64, 'panorama_fitted' [B,n] uint8, 'panorama_M' [B,n,3,3] float64 (canvas -> frame k), 'panorama_gain'
+    [B,n,2] float64.  ValueError before any launch for arguments outside these; nothing is copied to the host."""
+    data = _images(images, "images")
+    _need_device(G, name=False)
+    if G.device != data.device:
+        raise ValueError("panorama: images is on %s, G on %s" % (data.device, G.device))
+    if G.dtype != torch.float64 or G.dim() != 4 or tuple(G.shape[2:]) != (3, 3) or not 1 <= G.shape[1] <= PANO_MAX_FRAMES:
+        raise ValueError("panorama: G [B,n,3,3] float64 with 1 <= n <= %d, got %s %s" % (PANO_MAX_FRAMES, G.dtype, tuple(G.shape)))
+    B, n = G.shape[:2]
+    size = _pano_args(canvas, feather, mode, limit, "panorama")
+    ix = _frames_index(idx, data.shape[0], data.device, "panorama")
+    if tuple(ix.shape) != (B, n):
+        raise ValueError("panorama: idx names %d samples of %d frames, G has %d of %d" % (ix.shape[0], ix.shape[1], B, n))
+    gain = _pano_tensor(gain, (B, n, 2), torch.float64, "gain", "panorama")
+    use = _pano_tensor(use, (B, n), torch.uint8, "use", "panorama")
+    with torch.cuda.device(data.device):
+        return _panorama(data, ix, G.contiguous(), size, feather, mode, gain, use, limit)
+
+
+def _stage_args(refine, cascade, cascade_min_cover, cascade_samples):
+    """The rules of Aligner's refine / cascade arguments that need no image, checked before any launch -> (stages, (nx, ny) or None)."""
+    if refine not in (None, "ecc"):
+        raise ValueError("Aligner: refine is None or 'ecc', got %r" % (refine,))
+    try:
+        stages = operator.index(cascade)
+    except TypeError:
+        stages = -1
+    if stages < 0:
+        raise ValueError("Aligner: cascade is the number of re-prediction stages, an integer >= 0, got %r" % (cascade,))
+    if not 0.0 <= cascade_min_cover <= 1.0:                                # (False for a NaN too)
+        raise ValueError("Aligner: cascade_min_cover is a share in [0, 1], got %r" % (cascade_min_cover,))
+    return stages, None if cascade_samples is None else _cascade_samples(cascade_samples, None, 0, 0, 1)
+
+
 class Aligner:
     """Aligner(model, patch=None, channels=None, mean=0.443, std=0.129): `model` is the Sequential(backbone, head) of step.build_model
     on the device.  patch / channels default to the model's PATCH_SIZE / PATCH_CHANNELS (channels to 1, upstream's grayscale pair,
@@ -986,6 +1280,8 @@ class Aligner:
         (canvas index coordinates -> B's), 'mosaic_bbox' [B,4] float64, 'mosaic_fitted' [B] uint8, 'mosaic_gain' [B,2] float64.  A
         mosaic that is neither of the two, a canvas side below 2, a feather that is NaN, infinite or below 1, an unknown mode or
         exposure, 'gain' on an image side below 8 and a limit that is not > 0 raise a ValueError before any launch.
+    aligner.sequence(images, idx=None, ref=None, ..., canvas=None) registers n frames of one bank to a reference frame through this
+        call and blends them on one canvas (`chain_device`, `pano_frame_device`, `pano_u8`): see its docstring.
     The aligner copies nothing from the device to the host (host-given idx / roi values are uploaded).  What a model's own
     predict_homography does is the model's: NoOpHead '4_points' and PhotometricHead read the patch extent off 'corners' with .item()."""
 
@@ -1053,17 +1349,7 @@ class Aligner:
                  refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25, mosaic=None, mosaic_feather=32.0,
                  mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0):
         from .step import predict
-        if refine not in (None, "ecc"):
-            raise ValueError("Aligner: refine is None or 'ecc', got %r" % (refine,))
-        try:
-            stages = operator.index(cascade)
-        except TypeError:
-            stages = -1
-        if stages < 0:
-            raise ValueError("Aligner: cascade is the number of re-prediction stages, an integer >= 0, got %r" % (cascade,))
-        if not 0.0 <= cascade_min_cover <= 1.0:                                # (False for a NaN too)
-            raise ValueError("Aligner: cascade_min_cover is a share in [0, 1], got %r" % (cascade_min_cover,))
-        samples = None if cascade_samples is None else _cascade_samples(cascade_samples, None, 0, 0, 1)
+        stages, samples = _stage_args(refine, cascade, cascade_min_cover, cascade_samples)
         a, b = _images(images_a, "images_a"), _images(images_b, "images_b")
         if a.device != b.device:
             raise ValueError("Aligner: images_a is on %s, images_b on %s" % (a.device, b.device))
@@ -1109,4 +1395,100 @@ class Aligner:
                 out["aligned"], out["valid"] = warp_u8(a, H, b.shape[1], b.shape[2], idx=ia)
             if mosaic is not None:
                 out.update(_mosaic(a, b, H, canvas, mosaic_feather, mosaic_mode, mosaic_exposure, mosaic_limit, ia, ib, mask_b))
+        return out
+
+    def sequence(self, images, idx=None, ref=None, roi=None, refine=None, refine_levels=3, refine_iters=10, mask=None, cascade=0,
+                 cascade_samples=None, cascade_min_cover=0.25, canvas=None, feather=32.0, mode="feather", exposure=None, limit=2.0, use=None):
+        """Register a sequence of n frames (1 <= n <= 255) to one of them and, with a canvas, blend them all on it.
+            images: one uint8 [N,Hs,Ws,3] device tensor or ImageBank; every frame has this size.
+            idx: [B,n], frame k of sample b (host values: range-checked; int32 device tensor: clamped by the kernels; None: one sample
+                 of all N images in order).  ref: the reference frame, default n // 2.
+            roi: the region the model looks at, host values (x0, y0, rw, rh) for every frame or [B,4] per sample; None: whole frames.
+        The B (n - 1) neighbouring pairs `pairs_of(n, ref)` - (a, b) with b the frame nearer to the reference - go through the aligner
+        ONCE (`self(images, images, idx_a=, idx_b=, warp=False, ...)`, sample b (n - 1) + j is pair j of sample b; refine, refine_levels,
+        refine_iters, cascade, cascade_samples and cascade_min_cover are that call's and apply per pair; mask uint8 [B,n,Hs,Ws] on the
+        device gives the pixels of each frame that may count where the frame is a pair's b), and `chain_device` composes them outwards
+        from the reference.  -> dict: 'G' [B,n,3,3] float64 (the reference's index coordinates -> frame k's, G[ref] = I), 'H_pairs'
+        [B,n-1,3,3] float64, 'pairs' (the host list of (a, b)), 'pair' (the pair call's dict; empty for n = 1, which runs no model).
+        canvas="ref" or (Hc, Wc) (default None: no further launch) adds `panorama`'s keys with feather, mode, limit and use [B,n] uint8 on
+        the device (0: the frame is left out of the blend and of the frame fit); exposure=None, "gain" (each pair's least-squares line of
+        b's gray on a's through its H - one-level `gray_pyramid`, `ecc_sums`, `exposure_device`, counting the pixels `mask` allows -
+        composed along the chain) or a [B,n,2] float64 device tensor (g, o) per frame.  The chain accumulates every pair's error: it
+        drifts with n, and nothing here closes a loop.  Arguments outside these rules raise a ValueError before any launch; nothing is
+        copied to the host."""
+        who = "Aligner.sequence"
+        _stage_args(refine, cascade, cascade_min_cover, cascade_samples)
+        data = _images(images, "images")
+        dev, (Hs, Ws) = data.device, data.shape[1:3]
+        ix = _frames_index(idx, data.shape[0], dev, who)
+        B, n = ix.shape
+        if ref is None:
+            ref = n // 2
+        try:
+            ref = operator.index(ref)
+        except TypeError:
+            ref = -1
+        if not 0 <= ref < n:
+            raise ValueError("%s: ref is a frame of the sequence, an integer in [0, %d), got %r" % (who, n, ref))
+        pairs = pairs_of(n, ref)
+        if roi is not None:
+            if not (isinstance(roi, torch.Tensor) and roi.is_cuda):           # (a device tensor is `_regions`' to refuse)
+                roi = np.asarray(roi.numpy() if isinstance(roi, torch.Tensor) else roi, np.float64)
+                if roi.shape not in ((4,), (B, 4)):
+                    raise ValueError("%s: roi is (x0, y0, rw, rh) or [B,4] of them with B = %d, got shape %s" % (who, B, roi.shape))
+                if roi.ndim == 2:
+                    roi = np.repeat(roi, n - 1, axis=0)                        # one region per sample -> one per pair
+            _regions(roi, B * (n - 1), Hs, Ws, torch.device("cpu"), "roi")
+        if refine is not None:
+            try:
+                pyramid_sizes(Hs, Ws, refine_levels)
+            except ValueError as e:
+                raise ValueError("%s: refine_levels: %s" % (who, e)) from None
+            if not refine_iters >= 0:
+                raise ValueError("%s: refine_iters >= 0, got %r" % (who, refine_iters))
+        if canvas is None:
+            if exposure is not None or use is not None:
+                raise ValueError("%s: exposure and use belong to the panorama; pass canvas='ref' or (Hc, Wc) with them" % who)
+            size = None
+        else:
+            size = _pano_args(canvas, feather, mode, limit, who)
+        measure = isinstance(exposure, str) and exposure == "gain"
+        if measure:
+            if min(Hs, Ws) < ECC_MIN_SIDE:
+                raise ValueError("%s: the panorama exposure 'gain' measures on the gray frames, which need at least %d pixels on each side; "
+                                 "the frames are %d x %d (H x W)" % (who, ECC_MIN_SIDE, Hs, Ws))
+        elif isinstance(exposure, torch.Tensor):
+            exposure = _pano_tensor(exposure, (B, n, 2), torch.float64, "exposure", who)
+        elif exposure is not None:
+            raise ValueError("%s: the panorama exposure is None, 'gain' or a [B,n,2] float64 device tensor (g, o), got %r" % (who, exposure))
+        use = _pano_tensor(use, (B, n), torch.uint8, "use", who)
+        if mask is not None:
+            if refine is None and not measure:
+                raise ValueError("%s: mask restricts the pixels the refinement and the exposure measurement count; pass refine='ecc' or "
+                                 "exposure='gain' with it" % who)
+            mask = _pano_tensor(mask, (B, n, Hs, Ws), torch.uint8, "mask", who)
+        with torch.cuda.device(dev):
+            out = {"pairs": pairs, "pair": {}}
+            gain_pairs = None
+            if n > 1:
+                ia = ix[:, [a for a, _ in pairs]].reshape(-1).contiguous()
+                ib = ix[:, [b for _, b in pairs]].reshape(-1).contiguous()
+                mask_b = None if mask is None else mask[:, [b for _, b in pairs]].reshape(B * (n - 1), Hs, Ws).contiguous()
+                r = self(data, data, idx_a=ia, idx_b=ib, roi_a=roi, roi_b=roi, warp=False, refine=refine, refine_levels=refine_levels,
+                         refine_iters=refine_iters, mask_b=mask_b if refine is not None else None, cascade=cascade,
+                         cascade_samples=cascade_samples, cascade_min_cover=cascade_min_cover)
+                out["pair"] = r
+                H_pairs = r["H"].reshape(B, n - 1, 3, 3).contiguous()
+                if measure:
+                    pa, pb = gray_pyramid(data, B * (n - 1), 1, idx=ia), gray_pyramid(data, B * (n - 1), 1, idx=ib)
+                    sums = ecc_sums(pyramid_level(pa, Hs, Ws, 1, 0), pyramid_level(pb, Hs, Ws, 1, 0), r["H"], mask=mask_b)
+                    gain_pairs = exposure_device(sums).reshape(B, n - 1, 2).contiguous()
+            else:
+                H_pairs = torch.empty((B, 0, 3, 3), dtype=torch.float64, device=dev)
+                if measure:
+                    gain_pairs = torch.empty((B, 0, 2), dtype=torch.float64, device=dev)
+            G, gain = chain_device(H_pairs, ref, gain_pairs)
+            out.update({"G": G, "H_pairs": H_pairs})
+            if canvas is not None:
+                out.update(_panorama(data, ix, G, size, feather, mode, exposure if isinstance(exposure, torch.Tensor) else gain, use, limit))
         return out

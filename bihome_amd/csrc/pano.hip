@@ -1,0 +1,281 @@
+// Panorama: the n frames of a registered sequence on one canvas, in one pass (include/bihome.h "Panorama"; bihome_amd/align.py holds the
+// numpy float64 statements chain_host / pano_frame_host / pano_host the kernels are tested against).  Upstream has nothing like it.
+//
+// bh_pano_chain: the n - 1 pair homographies of a sequence composed into G[k], the reference's index coordinates -> frame k's, outwards
+// from the reference; one thread per sample, double.
+// bh_pano_frame: the canvas around the reference's extent and every frame's projected corners - adjugate, corners, the usable test and
+// the clamp per frame (thread k), a min / max reduction over the workgroup, then T, the box and M[k] = G[k] T; one workgroup per sample,
+// one launch where mosaic_frame_device spends some sixty tensor launches per pair.
+// bh_pano_u8: mosaic.hip's kernel with a run-time loop over the frames.  Per frame a thread first projects its pixels (u8_image.h's
+// u8_point / u8_valid: arithmetic only), and when no lane of the wavefront has the frame present the wavefront goes on to the next frame
+// without a single load (PANO_SKIP) - in a pan most canvas pixels see 0 to 3 of the n frames.  That cannot change a result: a frame
+// that is not present at a pixel is selected out, never multiplied by 0.  Else the four taps of each pixel (u8_gather), the gain, the
+// border weight and num += w v, den += w (or first / last) in registers, in the order k = 0..n-1 with every product rounded before it
+// is added: for n = 2 the result is bit for bit bh_mosaic_u8's.  Stores, offsets and clamps are mosaic.hip's; the pixels of a wavefront
+// are a compact tile, not a run of one row, because a tile is absent from more frames (PANO_TILE).  No LDS, no atomics, no scratch, one
+// writer per output element.
+#include "u8_image.h"
+
+#define PANO_THREADS 256
+#define PANO_MAX_FRAMES 255
+// A/B switches for tools/pano_bench.py (make ab ABFLAGS=-DPANO_SKIP=0 / -DPANO_TILE=0); DESIGN.md section 8 "Panorama" has the figures
+#ifndef PANO_SKIP
+#define PANO_SKIP 1        // 0: every frame takes its taps at every pixel
+#endif
+#ifndef PANO_TILE
+#define PANO_TILE 1        // 1: a wavefront makes 8 units x 8 rows of the canvas (a unit: 4 pixels, or 1), a workgroup 32 units x 8 rows - the
+#endif                     // compact tile is absent from more frames; 0: mosaic.hip's 64 consecutive units of one row (longer store runs)
+
+// ------------------------------------------------------------------------------------------------
+// the chain
+// ------------------------------------------------------------------------------------------------
+// grid ceil(B / PANO_THREADS)
+__global__ void __launch_bounds__(PANO_THREADS) pano_chain_kernel(const double* __restrict__ Hpair, const double* __restrict__ gain_pair, int B, int n, int ref,
+                                                                  double* __restrict__ G, double* __restrict__ gain) {
+#pragma clang fp contract(off)
+    const size_t b = (size_t)blockIdx.x * PANO_THREADS + threadIdx.x;
+    if (b >= (size_t)B) return;
+    double* Gb = G + 9 * b * n;
+    const double* Hb = Hpair + 9 * b * (n - 1);
+    const bool lines = gain && (gain_pair || n == 1);                           // (a single frame has no pair: its line is (1, 0))
+    double* gb = lines ? gain + 2 * b * n : nullptr;
+    const double* pb = lines ? gain_pair + 2 * b * (n - 1) : nullptr;
+    for (int i = 0; i < 9; ++i) Gb[9 * ref + i] = (i % 4 == 0) ? 1.0 : 0.0;
+    if (lines) { gb[2 * ref] = 1.0; gb[2 * ref + 1] = 0.0; }
+    for (int step = 0; step < n - 1; ++step) {
+        const int j = step < n - 1 - ref ? ref + step : n - 2 - step;          // ref .. n - 2, then ref - 1 .. 0
+        const int fa = j >= ref ? j + 1 : j, fb = j >= ref ? j : j + 1;         // the pair (a, b): b is nearer to the reference and done
+        const double* H = Hb + 9 * j;
+        double L[9], P[9];
+        for (int i = 0; i < 9; ++i) L[i] = Gb[9 * fb + i];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) P[3 * r + c] = (H[3 * r] * L[c] + H[3 * r + 1] * L[3 + c]) + H[3 * r + 2] * L[6 + c];
+        for (int i = 0; i < 9; ++i) Gb[9 * fa + i] = P[i] / P[8];
+        if (lines) {
+            const double g_b = gb[2 * fb], o_b = gb[2 * fb + 1];
+            gb[2 * fa] = g_b * pb[2 * j];
+            gb[2 * fa + 1] = g_b * pb[2 * j + 1] + o_b;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// the frame
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double pano_wave_min(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ double pano_clip(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+
+// grid B, PANO_THREADS threads: thread k is frame k (n <= PANO_MAX_FRAMES)
+__global__ void __launch_bounds__(PANO_THREADS) pano_frame_kernel(const double* __restrict__ G, const unsigned char* __restrict__ use, int n, int Hs, int Ws,
+                                                                  int Hc, int Wc, double limit, double* __restrict__ T, double* __restrict__ bbox,
+                                                                  unsigned char* __restrict__ fitted, double* __restrict__ M) {
+#pragma clang fp contract(off)
+    __shared__ double red[4][PANO_THREADS / 64];
+    __shared__ double Ts[3];                                                   // s, tx, ty
+    const size_t b = blockIdx.x;
+    const int k = threadIdx.x;
+    const double W1 = (double)Ws - 1.0, H1 = (double)Hs - 1.0;
+    double x0 = 0.0, x1 = W1, y0 = 0.0, y1 = H1, g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (k < n) {
+        const double* Gk = G + 9 * (b * n + k);
+        for (int i = 0; i < 9; ++i) g[i] = Gk[i];
+        const double a = g[0], bb = g[1], c = g[2], d = g[3], e = g[4], f = g[5], gg = g[6], h = g[7], i = g[8];
+        const double adj[9] = {e * i - f * h, c * h - bb * i, bb * f - c * e, f * gg - d * i, a * i - c * gg, c * d - a * f, d * h - e * gg, bb * gg - a * h, a * e - bb * d};
+        const double det = (a * adj[0] + bb * adj[3]) + c * adj[6];
+        double inv[9];
+        for (int q = 0; q < 9; ++q) inv[q] = adj[q] / det;
+        const double cx[4] = {0.0, W1, W1, 0.0}, cy[4] = {0.0, 0.0, H1, H1};
+        bool usable = isfinite(det) && det != 0.0, pos = true, neg = true;
+        double pxmin = 0, pxmax = 0, pymin = 0, pymax = 0;
+        for (int q = 0; q < 4; ++q) {
+            const double qx = (inv[0] * cx[q] + inv[1] * cy[q]) + inv[2], qy = (inv[3] * cx[q] + inv[4] * cy[q]) + inv[5], qz = (inv[6] * cx[q] + inv[7] * cy[q]) + inv[8];
+            const double px = qx / qz, py = qy / qz;
+            usable = usable && isfinite(qz) && fabs(qz) > 1e-8 && isfinite(px) && isfinite(py);
+            pos = pos && qz > 0.0;
+            neg = neg && qz < 0.0;
+            pxmin = q ? fmin(pxmin, px) : px; pxmax = q ? fmax(pxmax, px) : px;
+            pymin = q ? fmin(pymin, py) : py; pymax = q ? fmax(pymax, py) : py;
+        }
+        usable = usable && (pos || neg) && !(use && use[b * n + k] == 0);
+        if (usable) {
+            const double W = (double)Ws, H = (double)Hs;
+            x0 = fmin(pano_clip(pxmin, -limit * W, (1.0 + limit) * W - 1.0), 0.0);
+            x1 = fmax(pano_clip(pxmax, -limit * W, (1.0 + limit) * W - 1.0), W1);
+            y0 = fmin(pano_clip(pymin, -limit * H, (1.0 + limit) * H - 1.0), 0.0);
+            y1 = fmax(pano_clip(pymax, -limit * H, (1.0 + limit) * H - 1.0), H1);
+        }
+        if (fitted) fitted[b * n + k] = usable ? 1 : 0;
+    }
+    // min / max are exact: the order of the reduction does not show
+    x0 = pano_wave_min(x0); x1 = -pano_wave_min(-x1); y0 = pano_wave_min(y0); y1 = -pano_wave_min(-y1);
+    if ((k & 63) == 0) { red[0][k >> 6] = x0; red[1][k >> 6] = x1; red[2][k >> 6] = y0; red[3][k >> 6] = y1; }
+    __syncthreads();
+    if (k == 0) {
+        for (int w = 1; w < PANO_THREADS / 64; ++w) { x0 = fmin(x0, red[0][w]); x1 = fmax(x1, red[1][w]); y0 = fmin(y0, red[2][w]); y1 = fmax(y1, red[3][w]); }
+        double s = fmax((x1 - x0) / (double)(Wc - 1), (y1 - y0) / (double)(Hc - 1));
+        s = s == 0.0 ? 1.0 : s;
+        const double tx = (x0 + x1) * 0.5 - s * (0.5 * (double)(Wc - 1)), ty = (y0 + y1) * 0.5 - s * (0.5 * (double)(Hc - 1));
+        Ts[0] = s; Ts[1] = tx; Ts[2] = ty;
+        double* Tb = T + 9 * b;
+        Tb[0] = s; Tb[1] = 0.0; Tb[2] = tx; Tb[3] = 0.0; Tb[4] = s; Tb[5] = ty; Tb[6] = 0.0; Tb[7] = 0.0; Tb[8] = 1.0;
+        if (bbox) { bbox[4 * b] = x0; bbox[4 * b + 1] = y0; bbox[4 * b + 2] = x1; bbox[4 * b + 3] = y1; }
+    }
+    __syncthreads();
+    if (M && k < n) {                                                          // G T with T = (s 0 tx; 0 s ty; 0 0 1)
+        const double s = Ts[0], tx = Ts[1], ty = Ts[2];
+        double* Mk = M + 9 * (b * n + k);
+        for (int r = 0; r < 3; ++r) {
+            Mk[3 * r] = g[3 * r] * s;
+            Mk[3 * r + 1] = g[3 * r + 1] * s;
+            Mk[3 * r + 2] = (g[3 * r] * tx + g[3 * r + 1] * ty) + g[3 * r + 2];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// the blend
+// ------------------------------------------------------------------------------------------------
+// mosaic.hip's mosaic_weight: min(distance of the projected point to the border of the frame + 1, feather); meaningful where present
+__device__ __forceinline__ float pano_weight(const U8Sample& s, float xmax, float ymax, float feather) {
+#pragma clang fp contract(off)
+    return fminf(fminf(fminf(s.u, xmax - s.u), fminf(s.v, ymax - s.v)) + 1.0f, feather);
+}
+
+// the thread's unit of PX pixels -> (x, y) of its first pixel; false: outside the canvas
+template <int PX>
+__device__ __forceinline__ bool pano_unit(int Hc, int Wc, int& x, int& y) {
+    const unsigned upr = (unsigned)Wc / PX;                                    // units per canvas row
+#if PANO_TILE
+    const unsigned tiles_x = (upr + 31u) / 32u, by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
+    const unsigned ux = bx * 32u + (threadIdx.x >> 6) * 8u + (threadIdx.x & 7u), uy = by * 8u + ((threadIdx.x >> 3) & 7u);
+    if (ux >= upr || uy >= (unsigned)Hc) return false;
+    x = (int)ux * PX; y = (int)uy;
+#else
+    const unsigned u = blockIdx.x * PANO_THREADS + threadIdx.x;
+    if (u >= upr * (unsigned)Hc) return false;
+    y = (int)(u / upr); x = (int)(u - (unsigned)y * upr) * PX;
+#endif
+    return true;
+}
+static unsigned pano_grid_x(int Hc, int Wc, int px) {
+    const unsigned upr = (unsigned)Wc / px;
+#if PANO_TILE
+    return ((upr + 31u) / 32u) * (((unsigned)Hc + 7u) / 8u);
+#else
+    return (upr * (unsigned)Hc + PANO_THREADS - 1) / PANO_THREADS;
+#endif
+}
+
+// grid (pano_grid_x, u8_grid_y(B)); PX = 4: Wc % 4 == 0 and out % 4 == 0 (count_vec: count % 4 == 0 too)
+template <int PX, bool BYTES>
+__global__ void __launch_bounds__(PANO_THREADS) pano_kernel(const unsigned char* __restrict__ images, const int* __restrict__ idx, int n_images, int Hs, int Ws,
+                                                            const double* __restrict__ M64, const double* __restrict__ gain, const unsigned char* __restrict__ use,
+                                                            int B, int n, int Hc, int Wc, float feather, int mode,
+                                                            unsigned char* __restrict__ out, unsigned char* __restrict__ count, int count_vec) {
+#pragma clang fp contract(off)
+    int x, y;
+    if (!pano_unit<PX>(Hc, Wc, x, y)) return;
+    const unsigned npix = (unsigned)Hs * (unsigned)Ws;
+    const float xmax = (float)(Ws - 1), ymax = (float)(Hs - 1);
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        float num[PX * 3], den[PX];
+        unsigned cnt[PX];
+#pragma unroll
+        for (int p = 0; p < PX; ++p) { num[p * 3] = num[p * 3 + 1] = num[p * 3 + 2] = den[p] = 0.0f; cnt[p] = 0u; }
+        for (int k = 0; k < n; ++k) {
+            const size_t f = (size_t)b * n + k;
+            if (use && use[f] == 0) continue;                                  // (the same for every lane)
+            const Hf M = load_h(M64 + 9 * f);
+            Tap4 t[PX];
+            bool present[PX], any = false;
+#pragma unroll
+            for (int p = 0; p < PX; ++p) {
+                t[p] = u8_point(M, x + p, y, Ws, Hs);
+                present[p] = u8_valid(t[p], xmax, ymax);
+                any = any || present[p];
+            }
+#if PANO_SKIP
+            if (!__any(any)) continue;                                         // absent from the whole wavefront: no load at all
+#endif
+            const float g = gain ? (float)gain[2 * f] : 1.0f, o = gain ? (float)gain[2 * f + 1] : 0.0f;
+            const U8Image im = u8_image(images, idx ? idx + (size_t)b * n : nullptr, k, n_images, npix);
+#pragma unroll
+            for (int p = 0; p < PX; ++p) {
+                const U8Sample s = u8_gather<BYTES>(im, t[p], xmax, ymax);
+                const float w = pano_weight(s, xmax, ymax, feather);
+                const bool first = cnt[p] == 0u;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float v = __builtin_fmaf(g, s.c[c], o), wv = w * v, acc = num[p * 3 + c];
+                    const float next = mode == BH_PANO_FEATHER ? acc + wv : ((mode == BH_PANO_LAST || first) ? v : acc);
+                    num[p * 3 + c] = present[p] ? next : acc;
+                }
+                den[p] = present[p] ? den[p] + w : den[p];
+                cnt[p] += present[p] ? 1u : 0u;
+            }
+        }
+        unsigned q[PX * 3];
+#pragma unroll
+        for (int p = 0; p < PX; ++p)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float v = mode == BH_PANO_FEATHER ? (den[p] > 0.0f ? num[p * 3 + c] / den[p] : 0.0f) : num[p * 3 + c];
+                q[p * 3 + c] = u8_round(v);
+            }
+        const size_t at = ((size_t)b * Hc + y) * Wc + x;
+        u8_store_pixels<PX>(out + at * 3, q);
+        if (count) u8_store_flags<PX>(count + at, cnt, count_vec);
+    }
+}
+
+// what the entry points refuse as BH_E_BADARG apart from their NULL pointers: a negative batch, a frame count outside 1..255, an extent
+// below `least`
+static bool pano_counts_bad(int count, int frames) { return count < 0 || frames < 1 || frames > PANO_MAX_FRAMES; }
+static bool pano_extents_bad(int Hs, int Ws, int Hc, int Wc, int least) { return Hs < 1 || Ws < 1 || Hc < least || Wc < least; }
+
+extern "C" {
+
+int bh_pano_chain(const double* Hpair, const double* gain_pair, int B, int n, int ref, double* G, double* gain, void* stream) {
+    if (!G || pano_counts_bad(B, n) || (!Hpair && n > 1) || ref < 0 || ref >= n) return BH_E_BADARG;
+    if (B == 0) return BH_OK;
+    hipLaunchKernelGGL(pano_chain_kernel, dim3(((unsigned)B + PANO_THREADS - 1) / PANO_THREADS), dim3(PANO_THREADS), 0, bh_stream(stream), Hpair, gain_pair, B, n,
+                       ref, G, gain);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int Ws, int Hc, int Wc, double limit,
+                  double* T, double* bbox, uint8_t* fitted, double* M, void* stream) {
+    if (!G || !T || pano_counts_bad(B, n) || pano_extents_bad(Hs, Ws, Hc, Wc, 2) || !(limit > 0.0)) return BH_E_BADARG;
+    if (B == 0) return BH_OK;
+    hipLaunchKernelGGL(pano_frame_kernel, dim3((unsigned)B), dim3(PANO_THREADS), 0, bh_stream(stream), G, use, n, Hs, Ws, Hc, Wc, limit, T, bbox, fitted, M);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+int bh_pano_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* M, const double* gain,
+               const uint8_t* use, int B, int n, int Hc, int Wc, float feather, int mode, uint8_t* out, uint8_t* count, void* stream) {
+    if (!images || !M || !out || pano_counts_bad(B, n) || n_images < 1 || pano_extents_bad(Hs, Ws, Hc, Wc, 1)) return BH_E_BADARG;
+    if (!(feather >= 1.0f) || !(feather <= 3.402823466e+38f)) return BH_E_BADARG;                  // (NaN and infinity fail one of the two)
+    if (mode != BH_PANO_FEATHER && mode != BH_PANO_FIRST && mode != BH_PANO_LAST) return BH_E_BADARG;
+    // (bh_mosaic_u8's limits: tap_place's offsets, 32-bit byte offsets inside an image, the unit index of a thread)
+    if ((long long)Hs * Ws > (1ll << 29) || (long long)Hc * Wc > 0x7fffffffll) return BH_E_UNSUPPORTED;
+    if (B == 0) return BH_OK;
+    const bool vec = Wc % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0;
+    const int count_vec = count && reinterpret_cast<uintptr_t>(count) % 4 == 0;
+    const dim3 grid(pano_grid_x(Hc, Wc, vec ? 4 : 1), u8_grid_y(B));
+    hipStream_t st = bh_stream(stream);
+    const bool bytes = (long long)Hs * Ws < 2;                                 // a single-pixel frame: no room for 4-byte loads
+    u8_flags([&](auto four, auto by) {
+        hipLaunchKernelGGL((pano_kernel<four ? 4 : 1, by>), grid, dim3(PANO_THREADS), 0, st, images, idx, n_images, Hs, Ws, M, gain, use, B, n, Hc, Wc, feather,
+                           mode, out, count, count_vec);
+    }, vec, bytes);
+    BH_LAUNCH_CHECK();
+    return BH_OK;
+}
+
+}  // extern "C"

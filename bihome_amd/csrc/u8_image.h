@@ -1,4 +1,4 @@
-// The interleaved uint8 RGB bank image, spelled ONCE for the aligner (csrc/align.hip, ecc.hip, cascade.hip, mosaic.hip) and the bank
+// The interleaved uint8 RGB bank image, spelled ONCE for the aligner (csrc/align.hip, ecc.hip, cascade.hip, mosaic.hip, pano.hip) and the bank
 // (csrc/bank.hip): which image sample b reads, how a pixel is loaded, the bilinear sample of a pixel through a homography with its
 // validity, the rounding to a byte, the stores of pixels and flags, the patch epilogue and the grid clamp.  The reason is warp_tap.h's:
 // bh_warp_u8, bh_align_prep_warp_u8 and bh_mosaic_u8 promise ONE sample and ONE `valid` (include/bihome.h), and they agree bit for bit on
@@ -55,11 +55,19 @@ __device__ __forceinline__ unsigned ld_rgb_u8(const U8Image& im, unsigned pixel)
 // The bilinear sample of pixel (x, y) through H in a w x h image, xmax = (float)(w - 1), ymax = (float)(h - 1) (the caller's, computed
 // once per kernel and kept in registers it already has).  Taps outside the image contribute 0; under the guard c is unspecified.
 // valid: the projected point lies inside [0, w - 1] x [0, h - 1] and was divided.
+// The sample comes in two parts, for a kernel that decides from the validity whether it loads at all (csrc/pano.hip): u8_point, the
+// projection with the taps placed, and u8_valid are arithmetic only; u8_gather is the four loads and their blend.  u8_sample is the
+// composition, the only form every other kernel uses.  (The Tap4 goes by VALUE into both parts: with a reference the compiler schedules
+// the kernels that call u8_sample differently; like this their code is instruction for instruction what it was before the split.)
 struct U8Sample { float c[3], u, v; bool guard, valid; };
+__device__ __forceinline__ Tap4 u8_point(const Hf& H, int x, int y, int w, int h) { return make_tap4(H, x, y, w, h); }
+__device__ __forceinline__ bool u8_valid(const Tap4 t, float xmax, float ymax) {
+#pragma clang fp contract(off)      // (the comparisons decide validity)
+    return !t.guard && t.u >= 0.0f && t.u <= xmax && t.v >= 0.0f && t.v <= ymax;
+}
 template <bool BYTES>
-__device__ __forceinline__ U8Sample u8_sample(const U8Image& im, const Hf& H, int x, int y, int w, int h, float xmax, float ymax) {
-#pragma clang fp contract(off)      // (the comparisons below decide validity)
-    const Tap4 t = make_tap4(H, x, y, w, h);
+__device__ __forceinline__ U8Sample u8_gather(const U8Image& im, const Tap4 t, float xmax, float ymax) {
+#pragma clang fp contract(off)
     float w00, w01, w10, w11, wsum;
     tap_weights(t, w00, w01, w10, w11, wsum);
     // no branch around the loads: a tap outside the image reads pixel 0 and weighs 0
@@ -71,8 +79,13 @@ __device__ __forceinline__ U8Sample u8_sample(const U8Image& im, const Hf& H, in
         s.c[c] = tap_blend((float)((p00 >> (8 * c)) & 255u), (float)((p01 >> (8 * c)) & 255u), (float)((p10 >> (8 * c)) & 255u),
                            (float)((p11 >> (8 * c)) & 255u), w00, w01, w10, w11);
     s.u = t.u; s.v = t.v; s.guard = t.guard;
-    s.valid = !t.guard && t.u >= 0.0f && t.u <= xmax && t.v >= 0.0f && t.v <= ymax;
+    s.valid = u8_valid(t, xmax, ymax);
     return s;
+}
+template <bool BYTES>
+__device__ __forceinline__ U8Sample u8_sample(const U8Image& im, const Hf& H, int x, int y, int w, int h, float xmax, float ymax) {
+    const Tap4 t = u8_point(H, x, y, w, h);
+    return u8_gather<BYTES>(im, t, xmax, ymax);
 }
 
 // round half up into a byte (fmaxf drops a NaN: 0; the conversion truncates)

@@ -1787,3 +1787,89 @@ def mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=None, 
                            _p(Ma), _p(Mb), _p(gain), B, out.shape[1], out.shape[2], float(feather), int(mode), _p(out), _p(cover), _stream()),
           "bh_mosaic_u8")
     return out, cover
+
+
+# ------------------------------------------------------------------------------------------------
+# panorama: the n frames of a registered sequence on one canvas (bihome_amd/align.py; csrc/pano.hip).  Every buffer is the caller's.
+# ------------------------------------------------------------------------------------------------
+PANO_MODES = {"feather": 0, "first": 1, "last": 2}                    # include/bihome.h BH_PANO_*
+PANO_MAX_FRAMES = 255
+
+
+def _is_hn(M):
+    """M is [B,n,3,3] or [B,n,9] with 1 <= n <= 255: the homographies of a batch of sequences."""
+    return M.dim() >= 3 and 1 <= M.shape[1] <= PANO_MAX_FRAMES and M.numel() == 9 * M.shape[0] * M.shape[1]
+
+
+def _chk_frames_u8(images, idx, B, n, what):
+    """`_chk_images_u8` for a sequence: idx [B,n] int32 (None: frame k is image k)."""
+    _chk(images, torch.uint8); _chk(idx, torch.int32)
+    if images.dim() != 4 or images.shape[3] != 3 or min(images.shape) < 1:
+        raise ValueError("%s: images [N,H,W,3] uint8 with N, H, W >= 1, got %s" % (what, tuple(images.shape)))
+    if idx is not None and tuple(idx.shape) != (B, n):
+        raise ValueError("%s: idx [B,n] int32, got %s for B = %d, n = %d" % (what, tuple(idx.shape), B, n))
+
+
+def pano_chain(H_pairs, ref, G, gain_pairs=None, gain=None):
+    """G [B,n,3,3] float64 = the chain of H_pairs [B,n-1,3,3] float64 around frame `ref` (include/bihome.h bh_pano_chain;
+    bihome_amd.align.chain_host), and with gain_pairs [B,n-1,2] and gain [B,n,2] float64 both given the exposure lines along it.  The
+    outputs are the caller's (bihome_amd.align.chain_device allocates them)."""
+    _chk(H_pairs, torch.float64); _chk(G, torch.float64); _chk(gain_pairs, torch.float64); _chk(gain, torch.float64)
+    if not _is_hn(G):
+        raise ValueError("pano_chain: G [B,n,3,3] float64 with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, tuple(G.shape)))
+    B, n = G.shape[:2]
+    if H_pairs.dim() < 3 or tuple(H_pairs.shape[:2]) != (B, n - 1) or H_pairs.numel() != 9 * B * (n - 1):
+        raise ValueError("pano_chain: H_pairs [B,n-1,3,3] float64 with B = %d, n = %d, got %s" % (B, n, tuple(H_pairs.shape)))
+    if (gain_pairs is None) != (gain is None) or (gain is not None and (tuple(gain_pairs.shape) != (B, n - 1, 2) or tuple(gain.shape) != (B, n, 2))):
+        raise ValueError("pano_chain: gain_pairs [B,n-1,2] and gain [B,n,2] float64 come together, got %s and %s"
+                         % (None if gain_pairs is None else tuple(gain_pairs.shape), None if gain is None else tuple(gain.shape)))
+    if not 0 <= ref < n:
+        raise ValueError("pano_chain: ref in [0, %d), got %r" % (n, ref))
+    check(lib.bh_pano_chain(_p(H_pairs), _p(gain_pairs), B, n, int(ref), _p(G), _p(gain), _stream()), "bh_pano_chain")
+    return G, gain
+
+
+def pano_frame(G, size, canvas, limit, T, bbox=None, fitted=None, M=None, use=None):
+    """The canvas of a sequence (include/bihome.h bh_pano_frame; bihome_amd.align.pano_frame_host): G [B,n,3,3] float64, size = (Hs, Ws),
+    canvas = (Hc, Wc), use [B,n] uint8 or None -> T [B,3,3], bbox [B,4], M [B,n,3,3] float64 and fitted [B,n] uint8, the caller's
+    (bihome_amd.align.pano_frame_device allocates them; all but T may be None)."""
+    _chk(G, torch.float64); _chk(T, torch.float64); _chk(bbox, torch.float64); _chk(M, torch.float64); _chk(fitted, torch.uint8); _chk(use, torch.uint8)
+    if not _is_hn(G):
+        raise ValueError("pano_frame: G [B,n,3,3] float64 with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, tuple(G.shape)))
+    B, n = G.shape[:2]
+    if not _is_h(T) or T.shape[0] != B or (bbox is not None and tuple(bbox.shape) != (B, 4)) or (M is not None and tuple(M.shape) != tuple(G.shape)):
+        raise ValueError("pano_frame: T [B,3,3], bbox [B,4] and M like G, float64, with B = %d, got %s, %s and %s"
+                         % (B, tuple(T.shape), None if bbox is None else tuple(bbox.shape), None if M is None else tuple(M.shape)))
+    for t, what in ((fitted, "fitted"), (use, "use")):
+        if t is not None and tuple(t.shape) != (B, n):
+            raise ValueError("pano_frame: %s [B,n] uint8 with B = %d, n = %d, got %s" % (what, B, n, tuple(t.shape)))
+    (Hs, Ws), (Hc, Wc) = size, canvas
+    check(lib.bh_pano_frame(_p(G), _p(use), B, n, int(Hs), int(Ws), int(Hc), int(Wc), float(limit), _p(T), _p(bbox), _p(fitted), _p(M), _stream()),
+          "bh_pano_frame")
+    return T, bbox, fitted, M
+
+
+def pano_u8(images, idx, M, out, count, feather, mode, gain=None, use=None):
+    """out [B,Hc,Wc,3] uint8 = the n frames images[idx[b,k]] (one uint8 bank [N,Hs,Ws,3], idx [B,n] int32 or None: frame k is image k)
+    on a canvas whose index coordinates M [B,n,3,3] float64 map to frame k's, count [B,Hc,Wc] uint8 (may be None) the number of frames
+    present (include/bihome.h bh_pano_u8; bihome_amd.align.pano_host).  mode is 'feather', 'first' or 'last' (or its BH_PANO_* number);
+    gain [B,n,2] float64 (g, o) per frame and use [B,n] uint8 (0: the frame is left out) may be None.  Both outputs are the caller's
+    (bihome_amd.align.pano_u8 allocates them)."""
+    _chk(M, torch.float64); _chk(gain, torch.float64); _chk(use, torch.uint8); _chk(out, torch.uint8); _chk(count, torch.uint8)
+    if not _is_hn(M):
+        raise ValueError("pano_u8: M [B,n,3,3] float64 with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, tuple(M.shape)))
+    B, n = M.shape[:2]
+    if (gain is not None and tuple(gain.shape) != (B, n, 2)) or (use is not None and tuple(use.shape) != (B, n)):
+        raise ValueError("pano_u8: gain [B,n,2] float64 and use [B,n] uint8 with B = %d, n = %d, got %s and %s"
+                         % (B, n, None if gain is None else tuple(gain.shape), None if use is None else tuple(use.shape)))
+    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (count is not None and tuple(count.shape) != tuple(out.shape[:3])):
+        raise ValueError("pano_u8: out [B,Hc,Wc,3] uint8 and count [B,Hc,Wc] uint8 with B = %d, got %s and %s"
+                         % (B, tuple(out.shape), None if count is None else tuple(count.shape)))
+    if isinstance(mode, str):
+        if mode not in PANO_MODES:
+            raise ValueError("pano_u8: mode is one of %s, got %r" % (sorted(PANO_MODES), mode))
+        mode = PANO_MODES[mode]
+    _chk_frames_u8(images, idx, B, n, "pano_u8")
+    check(lib.bh_pano_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(M), _p(gain), _p(use), B, n,
+                         out.shape[1], out.shape[2], float(feather), int(mode), _p(out), _p(count), _stream()), "bh_pano_u8")
+    return out, count

@@ -987,6 +987,56 @@ int bh_mosaic_u8(const uint8_t* images_a, const int* idx_a, int n_a, int Ha, int
                  int B, int Hc, int Wc, float feather, int mode,
                  uint8_t* out, uint8_t* cover, void* stream);
 
+/* Panorama: the n frames of a registered SEQUENCE (a pan, a burst, an aerial strip) on one canvas - the mosaic beyond a pair.  Upstream has
+ * nothing like it.  The numpy float64 statements are bihome_amd/align.py's chain_host, pano_frame_host and pano_host.  Index coordinates
+ * throughout.  A sample is n frames (1 <= n <= 255) of ONE uint8 bank images[n_images,Hs,Ws,3], all of one size; frame r is the reference,
+ * and G[b,k] maps index coordinates of the reference to index coordinates of frame k (the pair convention "B's -> A's" with B = the
+ * reference): G[b,r] = I, every G scaled to G[2,2] = 1.
+ *
+ * bh_pano_chain: Hpair[B,n-1,9] double, pair j connects frames j and j + 1: for j >= ref it is (a, b) = (j + 1, j) and G[j+1] = Hpair[j] G[j],
+ * for j < ref it is (a, b) = (j, j + 1) and G[j] = Hpair[j] G[j+1] - Hpair[j] maps b's coordinates to a's; each product is divided by its
+ * [2,2] entry, unguarded.  With gain_pair[B,n-1,2] and gain[B,n,2] both given (either NULL: no gains; n = 1 has no pair and needs gain alone), a pair's (g, o) matches a to b,
+ * v_b ~ g v_a + o, and frame a's line to the reference is (g_b g, g_b o + o_b), the reference's (1, 0).  G[B,n,9] double.  One thread per
+ * sample, plain double arithmetic without contraction.
+ * BH_E_BADARG: NULL G, NULL Hpair with n > 1, a negative B, n outside 1..255, ref outside [0, n); then B == 0: BH_OK, nothing launched.
+ *
+ * bh_pano_frame: the canvas, bh_mosaic_u8's frame rule (mosaic_frame_host) per frame in ONE launch.  It starts from the reference's extent
+ * [0, Ws-1] x [0, Hs-1]; frame k takes part where it is usable - det G finite and not 0, the denominators of its four corners through G^-1
+ * (adjugate / determinant) finite, of one sign and above 1e-8 in magnitude, the projected corners finite - and use[b,k] != 0 (use[B,n]
+ * uint8, NULL: all): its corners, clamped to [-limit Ws, (1 + limit) Ws - 1] x [-limit Hs, (1 + limit) Hs - 1], are united into the box.
+ * s = max((x1 - x0) / (Wc - 1), (y1 - y0) / (Hc - 1)), 1 where that is 0; T[B,9] = (s 0 tx; 0 s ty; 0 0 1) maps canvas index coordinates to
+ * the reference's with the box centred; bbox[B,4] = (x0, y0, x1, y1) (NULL ok); fitted[B,n] uint8 (NULL ok): frame k took part;
+ * M[B,n,9] = G[b,k] T (NULL ok), what bh_pano_u8 takes.  One workgroup of 256 threads per sample, thread k is frame k, a min / max reduction;
+ * all double, no contraction.
+ * BH_E_BADARG: NULL G / T, a negative B, n outside 1..255, Hs or Ws < 1, Hc or Wc < 2, a limit that is not > 0; then B == 0: BH_OK.
+ *
+ * bh_pano_u8: idx[B,n] int32: frame k of sample b is image idx[b n + k], CLAMPED into the bank in the kernel (NULL: frame k is image k, for
+ * every sample).  M[B,n,9] double maps index coordinates of the canvas (Hc x Wc) to frame k's.  At canvas pixel (x, y) frame k's (u, v) and
+ * bilinear value are bh_warp_u8's (csrc/u8_image.h, float); the frame is PRESENT where bh_warp_u8's valid holds and use[b n + k] != 0 (use
+ * NULL: all); its value is fmaf(g_k, v, o_k) per channel with gain[B,n,2] double (NULL: (1, 0)), its weight bh_mosaic_u8's
+ * w = min(min(u, Ws - 1 - u, v, Hs - 1 - v) + 1, feather).  By mode, over the frames present in the order k = 0 .. n - 1,
+ *     BH_PANO_FEATHER  (sum_k w_k v_k) / (sum_k w_k), every product rounded before it is added,
+ *     BH_PANO_FIRST    the value of the lowest k present,
+ *     BH_PANO_LAST     the value of the highest k present,
+ * 0 where none is, and out[b,y,x,:] = round_half_up(clamp(., 0, 255)).  A frame that is not present is selected out, not multiplied by 0 -
+ * so a wavefront none of whose pixels has frame k present passes on to frame k + 1 without loading anything of it, and in a pan, where a
+ * canvas pixel sees a few of the n frames, that is most (wavefront, frame) pairs.  count[B,Hc,Wc] uint8 (NULL ok): the number of frames
+ * present.  For n = 2 with frames (A, B), gain ((g, o), (1, 0)) the result is bit for bit bh_mosaic_u8's: FEATHER = BH_MOSAIC_FEATHER,
+ * FIRST = BH_MOSAIC_A_OVER_B, LAST = BH_MOSAIC_B_OVER_A, count = the number of bits set in cover.  Stores, offsets and the two paths
+ * (Wc % 4 == 0 with out on a 4-byte boundary: four pixels per thread) are bh_mosaic_u8's; one pass, one writer per output element, no
+ * atomics, no scratch, no LDS: two calls are bitwise equal.
+ * BH_E_BADARG: NULL images / M / out, a negative B, n outside 1..255, n_images, Hs, Ws, Hc or Wc < 1, a feather that is NaN, infinite or
+ * below 1, an unknown mode; then BH_E_UNSUPPORTED: Hs * Ws > 2^29 or Hc * Wc > 2^31 - 1 pixels; then B == 0: BH_OK, nothing launched.
+ * Refusals return before any launch. */
+#define BH_PANO_FEATHER 0
+#define BH_PANO_FIRST 1
+#define BH_PANO_LAST 2
+int bh_pano_chain(const double* Hpair, const double* gain_pair, int B, int n, int ref, double* G, double* gain, void* stream);
+int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int Ws, int Hc, int Wc, double limit,
+                  double* T, double* bbox, uint8_t* fitted, double* M, void* stream);
+int bh_pano_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* M, const double* gain,
+               const uint8_t* use, int B, int n, int Hc, int Wc, float feather, int mode, uint8_t* out, uint8_t* count, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */
