@@ -47,9 +47,9 @@ Mosaic (optional, `aligner(..., mosaic="b")` / `mosaic=(Hc, Wc)` / `mosaic`; csr
 of A falls outside B's frame is lost and inside it the two are never combined.  bh_mosaic_u8 puts both on one canvas in one pass: with T
 from canvas index coordinates to B's (the identity for canvas "b"; else `mosaic_frame_host`: the bounding box of B's extent and of A's
 corners projected through H^-1 - clamped to `limit` image sizes around B, so that a garbage H cannot shrink B to a dot - scaled and centred
-onto the Hc x Wc canvas with the aspect ratio kept) each canvas pixel takes warp_u8_host's sample of A through H T and of B through T, and
-an image is PRESENT where warp_u8_host's `valid` holds.  Its weight is min(distance of the projected point to the border of the image, in
-its own pixels, + 1, feather); mode "feather" gives (wa a' + wb b) / (wa + wb) over the images present, "b_over_a" / "a_over_b" put one
+onto the Hc x Wc canvas with the aspect ratio kept; it is the panorama's frame rule for the single frame A) each canvas pixel takes
+warp_u8_host's sample of A through H T and of B through T, and an image is PRESENT where warp_u8_host's `valid` holds.  Its weight
+is min(distance of the projected point to the border of the image, in its own pixels, + 1, feather); mode "feather" gives (wa a' + wb b) / (wa + wb) over the images present, "b_over_a" / "a_over_b" put one
 image on top, nothing present gives 0, then round half up; cover = (A present) | (B present) << 1.  a' = g a + o is A after the optional
 gain / bias match: the ECC step is blind to both by design, so the blend handles them - `exposure_host` is the least-squares line of B's
 gray on A's through H from the sums ecc_sums_host already makes.  Stated below as mosaic_frame_host / mosaic_host / exposure_host.
@@ -58,11 +58,11 @@ Panorama (`aligner.sequence(images, idx, ..., canvas=...)` / `panorama`; csrc/pa
 one bank, chosen by idx [B,n].  Frame r is the reference and G[b,k] maps the reference's index coordinates to frame k's (the pair
 convention with B = the reference; G[b,r] = I).  The n - 1 neighbouring pairs (`pairs_of`: pair j connects frames j and j + 1, b the
 one nearer to the reference) go through the aligner in ONE call, `chain_host` composes them outwards from the reference - G[a] = H_pair
-G[b], divided by its [2,2] entry; the exposure lines compose alongside - `pano_frame_host` is the mosaic's frame rule per frame (the
-reference's extent united with the clamped corners of every usable frame), and `pano_host` the mosaic's blend over the frames present:
-'feather' sum w v / sum w in frame order, 'first' / 'last' the lowest / highest frame present, count = the number present.  For n = 2 all
-three equal the pair's definitions bit for bit.  bh_pano_u8 makes the canvas in one pass, and a wavefront none of whose pixels has a
-frame present takes no tap of it."""
+G[b], divided by its [2,2] entry; the exposure lines compose alongside - `pano_frame_host` is the frame rule (the reference's extent
+united with the clamped corners of every usable frame; `_corner_box` / `_fit_canvas`), and `pano_host` the blend over the frames present
+(`_blend_host`, the one statement `mosaic_host` is made of too): 'feather' sum w v / sum w in frame order, 'first' / 'last' the lowest /
+highest frame present, count = the number present.  For n = 2 both equal the pair's results bit for bit.  bh_pano_u8 makes the canvas
+in one pass, and a wavefront none of whose pixels has a frame present takes no tap of it."""
 import operator
 
 import numpy as np
@@ -182,7 +182,12 @@ def warp_u8_host(images, H, Ho, Wo):
     """images uint8 [B,Hs,Ws,3], H [B,3,3] (output index coordinates -> source index coordinates) -> (out uint8 [B,Ho,Wo,3],
     valid uint8 [B,Ho,Wo]): the uint8 warp of the module docstring."""
     values, valid, _ = _sample_host(images, H, Ho, Wo)
-    return np.floor(np.clip(values, 0.0, 255.0) + 0.5).astype(np.uint8), valid.astype(np.uint8)
+    return _round_u8(values), valid.astype(np.uint8)
+
+
+def _round_u8(values):
+    """round_half_up(clamp(values, 0, 255)) as uint8."""
+    return np.floor(np.clip(values, 0.0, 255.0) + 0.5).astype(np.uint8)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -194,7 +199,7 @@ MOSAIC_MODES = ("feather", "b_over_a", "a_over_b")
 def _corner_box(H, size_a, size_b, limit):
     """H [K,3,3] (B's index coordinates -> A's) -> (x0, x1, y0, y1 [K] float64, usable [K] bool): B's extent united with A's four corners
     through H^-1 (adjugate / determinant, written out) clamped to `limit` image sizes around B; B's extent alone where H is not usable.
-    What `mosaic_frame_host` and `pano_frame_host` share."""
+    `pano_frame_host`'s half of the frame rule per frame (A the frame, B the reference)."""
     (Ha, Wa), (Hb, Wb) = size_a, size_b
     a, b, c, d, e, f, g, h, i = (H[:, r, k] for r in range(3) for k in range(3))
     with np.errstate(all="ignore"):
@@ -235,47 +240,67 @@ def _frame_args(canvas, limit, who):
 def mosaic_frame_host(H, size_a, size_b, canvas, limit=2.0):
     """H [B,3,3] (B's index coordinates -> A's), size_a = (Ha, Wa), size_b = (Hb, Wb), canvas = (Hc, Wc) -> (T [B,3,3] float64: canvas
     index coordinates -> B's, a scale and a translation; bbox [B,4] = (xmin, ymin, xmax, ymax) in B's index coordinates; fitted [B]
-    uint8): the Mosaic frame of the module docstring.  H^-1 is adjugate / determinant, written out."""
-    H = np.asarray(H, np.float64).reshape(-1, 3, 3)
+    uint8): the Mosaic frame of the module docstring - `pano_frame_host` for the single frame A around the reference B."""
     _frame_args(canvas, limit, "mosaic_frame")
-    x0, x1, y0, y1, usable = _corner_box(H, size_a, size_b, limit)
-    return _fit_canvas(x0, x1, y0, y1, canvas), np.stack([x0, y0, x1, y1], 1), usable.astype(np.uint8)
+    T, bbox, fitted = pano_frame_host(np.asarray(H, np.float64).reshape(-1, 1, 3, 3), size_a, canvas, limit, ref_size=size_b)
+    return T, bbox, fitted[:, 0]
+
+
+def _blend_host(frames, feather, mode):
+    """The blend statement of the mosaic and the panorama.  frames yields, in order, (values float64 [B,Hc,Wc,3] (`_sample_host`), present
+    bool [B,Hc,Wc], M [B,3,3], (Hs, Ws), gain [B,2] = (g, o) or None) per frame; mode is 'feather', 'first' or 'last' -> (the values before
+    rounding [B,Hc,Wc,3], the list of the `present` planes).  A frame's value is g v + o and its weight min(distance of its projected point
+    to the border of the frame + 1, feather); 'feather' is sum w v / sum w over the frames present, accumulated in the order given, 'first'
+    / 'last' the value of the first / last frame present, nothing present 0.  A frame that is not present is selected out, never
+    multiplied by 0: under the projection guard its sample is unspecified."""
+    num = den = val = 0.0
+    seen, planes = False, []
+    for v, present, M, (Hs, Ws), gain in frames:
+        B, Hc, Wc = present.shape
+        P = present[..., None]
+        if gain is not None:
+            v = gain[:, 0, None, None, None] * v + gain[:, 1, None, None, None]
+        if mode == "feather":
+            w = np.empty((B, Hc, Wc))
+            for b in range(B):
+                with np.errstate(all="ignore"):
+                    pu, pv, _ = _project_host(M[b], Hc, Wc)
+                    w[b] = np.minimum(np.minimum(np.minimum(pu, Ws - 1 - pu), np.minimum(pv, Hs - 1 - pv)) + 1.0, feather)
+            w = np.where(present, w, 0.0)[..., None]
+            num = num + np.where(P, w * np.where(P, v, 0.0), 0.0)
+            den = den + w
+        elif mode == "first":
+            val = np.where(P & np.logical_not(seen), v, val)
+        else:
+            val = np.where(P, v, val)
+        seen = seen | P
+        planes.append(present)
+    if mode == "feather":
+        val = np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
+    return np.where(seen, val, 0.0), planes
+
+
+def _blend_args(feather, mode, modes, who):
+    if mode not in modes:
+        raise ValueError("%s: mode is one of %s, got %r" % (who, modes, mode))
+    if not (feather >= 1 and np.isfinite(feather)):
+        raise ValueError("%s: feather is finite and at least 1, got %r" % (who, feather))
 
 
 def mosaic_host(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather", gain=None):
     """images_a uint8 [B,Ha,Wa,3], images_b uint8 [B,Hb,Wb,3], Ma / Mb [B,3,3] (canvas index coordinates -> A's / B's; the caller passes
     Ma = H T, Mb = T), gain [B,2] = (g, o) or None -> (out uint8 [B,Hc,Wc,3], cover uint8 [B,Hc,Wc] = (A present) | (B present) << 1):
-    the Mosaic of the module docstring."""
-    if mode not in MOSAIC_MODES:
-        raise ValueError("mosaic_host: mode is one of %s, got %r" % (MOSAIC_MODES, mode))
-    if not (feather >= 1 and np.isfinite(feather)):
-        raise ValueError("mosaic_host: feather is finite and at least 1, got %r" % (feather,))
+    the Mosaic of the module docstring - `_blend_host` on the frames (A, B), 'b_over_a' the last present and 'a_over_b' the first."""
+    _blend_args(feather, mode, MOSAIC_MODES, "mosaic_host")
     Ma, Mb = np.asarray(Ma, np.float64).reshape(-1, 3, 3), np.asarray(Mb, np.float64).reshape(-1, 3, 3)
     B = Ma.shape[0]
     gain = np.tile(np.array([[1.0, 0.0]]), (B, 1)) if gain is None else np.asarray(gain, np.float64).reshape(B, 2)
-    va, pa, _ = _sample_host(images_a, Ma, Hc, Wc)
-    vb, pb, _ = _sample_host(images_b, Mb, Hc, Wc)
-    va = gain[:, 0, None, None, None] * va + gain[:, 1, None, None, None]
-    out = np.empty((B, Hc, Wc, 3), np.uint8)
-    for b in range(B):
-        w = []
-        for img, M in ((images_a, Ma[b]), (images_b, Mb[b])):
-            Hx, Wx = np.asarray(img).shape[1:3]
-            with np.errstate(all="ignore"):
-                u, v, _ = _project_host(M, Hc, Wc)
-                w.append(np.minimum(np.minimum(np.minimum(u, Wx - 1 - u), np.minimum(v, Hx - 1 - v)) + 1.0, feather))
-        a, t, A, T = va[b], vb[b], pa[b][..., None], pb[b][..., None]
-        if mode == "feather":
-            wa, wb = np.where(pa[b], w[0], 0.0)[..., None], np.where(pb[b], w[1], 0.0)[..., None]
-            num = np.where(A, wa * np.where(A, a, 0.0), 0.0) + np.where(T, wb * np.where(T, t, 0.0), 0.0)
-            den = wa + wb
-            val = np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
-        elif mode == "b_over_a":
-            val = np.where(T, t, np.where(A, a, 0.0))
-        else:
-            val = np.where(A, a, np.where(T, t, 0.0))
-        out[b] = np.floor(np.clip(np.where(A | T, val, 0.0), 0.0, 255.0) + 0.5).astype(np.uint8)
-    return out, (pa.astype(np.uint8) | (pb.astype(np.uint8) << 1)).astype(np.uint8)
+    frames = []
+    for images, M, g in ((images_a, Ma, gain), (images_b, Mb, None)):
+        v, present, _ = _sample_host(images, M, Hc, Wc)
+        frames.append((v, present, M, np.asarray(images).shape[1:3], g))
+    val, (pa, pb) = _blend_host(frames, feather, {"feather": "feather", "b_over_a": "last", "a_over_b": "first"}[mode])
+    return _round_u8(val), (pa.astype(np.uint8) | (pb.astype(np.uint8) << 1)).astype(np.uint8)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -318,34 +343,32 @@ def chain_host(H_pairs, ref, gain_pairs=None):
     return G if gp is None else (G, gain)
 
 
-def pano_frame_host(G, size, canvas, limit=2.0, use=None):
-    """G [B,n,3,3] (the reference's index coordinates -> frame k's), size = (Hs, Ws) of every frame, canvas = (Hc, Wc), use [B,n] or None
-    -> (T [B,3,3] float64: canvas index coordinates -> the reference's; bbox [B,4] = (xmin, ymin, xmax, ymax) in the reference's index
-    coordinates; fitted [B,n] uint8): `mosaic_frame_host`'s rule per frame - the reference's extent united with the clamped corners of
-    every frame that is usable and in use."""
+def pano_frame_host(G, size, canvas, limit=2.0, use=None, ref_size=None):
+    """G [B,n,3,3] (the reference's index coordinates -> frame k's), size = (Hs, Ws) of every frame, canvas = (Hc, Wc), use [B,n] or None,
+    ref_size = (Hr, Wr) of the reference (None: size) -> (T [B,3,3] float64: canvas index coordinates -> the reference's; bbox [B,4] =
+    (xmin, ymin, xmax, ymax) in the reference's index coordinates; fitted [B,n] uint8): the frame rule - the reference's extent united
+    with the corners of every frame that is usable and in use, clamped to `limit` reference sizes around it (`_corner_box`), then fitted to
+    the canvas (`_fit_canvas`)."""
     G = np.asarray(G, np.float64)
     if G.ndim != 4 or G.shape[2:] != (3, 3) or not 1 <= G.shape[1] <= PANO_MAX_FRAMES:
         raise ValueError("pano_frame: G [B,n,3,3] with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, G.shape))
     _frame_args(canvas, limit, "pano_frame")
     B, n = G.shape[:2]
-    Hs, Ws = size
-    x0, x1, y0, y1, usable = (v.reshape(B, n) for v in _corner_box(G.reshape(B * n, 3, 3), size, size, limit))
+    Hr, Wr = ref_size = size if ref_size is None else ref_size
+    x0, x1, y0, y1, usable = (v.reshape(B, n) for v in _corner_box(G.reshape(B * n, 3, 3), size, ref_size, limit))
     fitted = usable if use is None else usable & (np.asarray(use).reshape(B, n) != 0)
-    x0, x1 = np.where(fitted, x0, 0.0).min(1), np.where(fitted, x1, Ws - 1.0).max(1)
-    y0, y1 = np.where(fitted, y0, 0.0).min(1), np.where(fitted, y1, Hs - 1.0).max(1)
+    x0, x1 = np.where(fitted, x0, 0.0).min(1), np.where(fitted, x1, Wr - 1.0).max(1)
+    y0, y1 = np.where(fitted, y0, 0.0).min(1), np.where(fitted, y1, Hr - 1.0).max(1)
     return _fit_canvas(x0, x1, y0, y1, canvas), np.stack([x0, y0, x1, y1], 1), fitted.astype(np.uint8)
 
 
 def pano_host(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, use=None):
     """images uint8 [N,Hs,Ws,3], idx [B,n] (frame k of sample b is images[idx[b,k]]), M [B,n,3,3] (canvas index coordinates -> frame
     k's; the caller passes G T), gain [B,n,2] = (g, o) or None, use [B,n] or None -> (out uint8 [B,Hc,Wc,3], count uint8 [B,Hc,Wc]): frame
-    k is PRESENT at a canvas pixel where warp_u8_host's `valid` holds and use[b,k] != 0, its value is g v + o and its weight
-    `mosaic_host`'s; 'feather' is sum w v / sum w over the frames present, accumulated in the order k = 0..n-1, 'first' / 'last' the value
-    of the lowest / highest k present, nothing present 0; then round half up.  count is the number of frames present."""
-    if mode not in PANO_MODES:
-        raise ValueError("pano_host: mode is one of %s, got %r" % (PANO_MODES, mode))
-    if not (feather >= 1 and np.isfinite(feather)):
-        raise ValueError("pano_host: feather is finite and at least 1, got %r" % (feather,))
+    k is PRESENT at a canvas pixel where warp_u8_host's `valid` holds and use[b,k] != 0; `_blend_host` on the n frames in the order
+    k = 0..n-1 ('first' / 'last': the value of the lowest / highest k present), then round half up.  count is the number of frames
+    present."""
+    _blend_args(feather, mode, PANO_MODES, "pano_host")
     images, idx = np.asarray(images), np.asarray(idx)
     M = np.asarray(M, np.float64)
     if idx.ndim != 2 or not 1 <= idx.shape[1] <= PANO_MAX_FRAMES or M.shape != idx.shape + (3, 3):
@@ -353,32 +376,13 @@ def pano_host(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, u
     B, n = idx.shape
     gain = np.tile(np.array([1.0, 0.0]), (B, n, 1)) if gain is None else np.asarray(gain, np.float64).reshape(B, n, 2)
     use = np.ones((B, n), bool) if use is None else np.asarray(use).reshape(B, n) != 0
-    Hs, Ws = images.shape[1:3]
-    num, den, val = np.zeros((B, Hc, Wc, 3)), np.zeros((B, Hc, Wc, 1)), np.zeros((B, Hc, Wc, 3))
-    count = np.zeros((B, Hc, Wc), np.uint8)
-    for k in range(n):
-        v, present, _ = _sample_host(images[idx[:, k]], M[:, k], Hc, Wc)
-        present = present & use[:, k, None, None]
-        v = gain[:, k, 0, None, None, None] * v + gain[:, k, 1, None, None, None]
-        P = present[..., None]
-        if mode == "feather":
-            w = np.empty((B, Hc, Wc))
-            for b in range(B):
-                with np.errstate(all="ignore"):
-                    pu, pv, _ = _project_host(M[b, k], Hc, Wc)
-                    w[b] = np.minimum(np.minimum(np.minimum(pu, Ws - 1 - pu), np.minimum(pv, Hs - 1 - pv)) + 1.0, feather)
-            w = np.where(present, w, 0.0)[..., None]
-            num = num + np.where(P, w * np.where(P, v, 0.0), 0.0)
-            den = den + w
-        elif mode == "first":
-            val = np.where(P & (count == 0)[..., None], v, val)
-        else:
-            val = np.where(P, v, val)
-        count = count + present.astype(np.uint8)
-    if mode == "feather":
-        val = np.where(den > 0, num / np.where(den > 0, den, 1.0), 0.0)
-    out = np.floor(np.clip(np.where((count > 0)[..., None], val, 0.0), 0.0, 255.0) + 0.5).astype(np.uint8)
-    return out, count
+
+    def frames():
+        for k in range(n):
+            v, present, _ = _sample_host(images[idx[:, k]], M[:, k], Hc, Wc)
+            yield v, present & use[:, k, None, None], M[:, k], images.shape[1:3], gain[:, k]
+    val, planes = _blend_host(frames(), feather, mode)
+    return _round_u8(val), np.sum(planes, axis=0, dtype=np.uint8)
 
 
 def exposure_host(sums):
@@ -895,6 +899,18 @@ def _check_mask(mask, B, Hb, Wb, device):
     return mask.contiguous()
 
 
+def _refine_args(levels, iters, sizes, iters_label):
+    """The refinement's argument rules, checked before any launch: `pyramid_sizes` of every (label, (h, w)) of `sizes`, and iters >= 0; the
+    labels open the messages with the caller's name for the argument."""
+    for label, (h, w) in sizes:
+        try:
+            pyramid_sizes(h, w, levels)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (label, e)) from None
+    if not iters >= 0:
+        raise ValueError("%s >= 0, got %r" % (iters_label, iters))
+
+
 def ecc_refine(images_a, images_b, H, levels=3, iters=10, idx_a=None, idx_b=None, mask=None):
     """Coarse-to-fine ECC refinement on the device (`ecc_refine_host`): images_* uint8 [N,H*,W*,3] device tensors, H [B,3,3] float64 (B's
     index coordinates -> A's), idx_* [B] int32 DEVICE tensors or None, mask [B,Hb,Wb] uint8 or None (non-zero: the pixel of B may count)
@@ -902,14 +918,8 @@ def ecc_refine(images_a, images_b, H, levels=3, iters=10, idx_a=None, idx_b=None
     finest level).  ValueError, before any launch, for levels too deep for the images.  Nothing is copied to the host."""
     _need_device(images_a, images_b, H, name=False)
     _need_h(H, "ecc_refine")
-    if not iters >= 0:
-        raise ValueError("ecc_refine: iters >= 0, got %r" % (iters,))
     B, (Ha, Wa), (Hb, Wb) = H.shape[0], images_a.shape[1:3], images_b.shape[1:3]
-    for h, w, what in ((Ha, Wa, "images_a"), (Hb, Wb, "images_b")):
-        try:
-            pyramid_sizes(h, w, levels)
-        except ValueError as e:
-            raise ValueError("ecc_refine: %s: %s" % (what, e)) from None
+    _refine_args(levels, iters, (("ecc_refine: images_a", (Ha, Wa)), ("ecc_refine: images_b", (Hb, Wb))), "ecc_refine: iters")
     mask = _check_mask(mask, B, Hb, Wb, images_b.device)
     pa, pb = gray_pyramid(images_a, B, levels, idx=idx_a), gray_pyramid(images_b, B, levels, idx=idx_b)
     return ecc_refine_pyramids(pa, (Ha, Wa), pb, (Hb, Wb), H.contiguous(), levels, iters, mask_pyr=None if mask is None else mask_pyramid(mask, levels))
@@ -919,35 +929,11 @@ def ecc_refine(images_a, images_b, H, levels=3, iters=10, idx_a=None, idx_b=None
 # mosaic, the device path
 # ------------------------------------------------------------------------------------------------
 def mosaic_frame_device(H, size_a, size_b, canvas, limit=2.0):
-    """`mosaic_frame_host` on the device: H [B,3,3] float64 -> (T [B,3,3] float64, bbox [B,4] float64, fitted [B] uint8), batched double
-    tensor arithmetic with the adjugate written out - no solve, nothing copied to the host."""
-    (Ha, Wa), (Hb, Wb), (Hc, Wc) = size_a, size_b, canvas
-    if min(Hc, Wc) < 2:
-        raise ValueError("mosaic_frame: a canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (Hc, Wc))
-    if not limit > 0:
-        raise ValueError("mosaic_frame: limit > 0, got %r" % (limit,))
-    B = H.shape[0]
-    a, b, c, d, e, f, g, h, i = H.reshape(B, 9).unbind(1)
-    adj = ((e * i - f * h, c * h - b * i, b * f - c * e), (f * g - d * i, a * i - c * g, c * d - a * f), (d * h - e * g, b * g - a * h, a * e - b * d))
-    det = a * adj[0][0] + b * adj[1][0] + c * adj[2][0]
-    inv = [[adj[r][k] / det for k in range(3)] for r in range(3)]
-    corners = ((0.0, 0.0), (Wa - 1.0, 0.0), (Wa - 1.0, Ha - 1.0), (0.0, Ha - 1.0))
-    qx, qy, qz = (torch.stack([inv[r][0] * x + inv[r][1] * y + inv[r][2] for x, y in corners], 1) for r in range(3))              # [B,4]
-    px, py = qx / qz, qy / qz
-    usable = torch.isfinite(det) & (det != 0) & torch.isfinite(qz).all(1) & ((qz > 0).all(1) | (qz < 0).all(1)) & (qz.abs() > QZ_GUARD).all(1)
-    usable = usable & torch.isfinite(px).all(1) & torch.isfinite(py).all(1)
-    zero = torch.zeros_like(det)
-    x0 = torch.minimum(px.amin(1).clamp(-limit * Wb, (1 + limit) * Wb - 1), zero)
-    x1 = torch.maximum(px.amax(1).clamp(-limit * Wb, (1 + limit) * Wb - 1), zero + (Wb - 1.0))
-    y0 = torch.minimum(py.amin(1).clamp(-limit * Hb, (1 + limit) * Hb - 1), zero)
-    y1 = torch.maximum(py.amax(1).clamp(-limit * Hb, (1 + limit) * Hb - 1), zero + (Hb - 1.0))
-    x0, x1, y0, y1 = torch.where(usable, x0, zero), torch.where(usable, x1, zero + (Wb - 1.0)), torch.where(usable, y0, zero), torch.where(usable, y1, zero + (Hb - 1.0))
-    s = torch.maximum((x1 - x0) / (Wc - 1), (y1 - y0) / (Hc - 1))
-    s = torch.where(s == 0, zero + 1.0, s)
-    T = torch.zeros((B, 3, 3), dtype=torch.float64, device=H.device)
-    T[:, 0, 0], T[:, 1, 1], T[:, 2, 2] = s, s, 1.0
-    T[:, 0, 2], T[:, 1, 2] = (x0 + x1) * 0.5 - s * (0.5 * (Wc - 1)), (y0 + y1) * 0.5 - s * (0.5 * (Hc - 1))
-    return T, torch.stack([x0, y0, x1, y1], 1), usable.to(torch.uint8)
+    """`mosaic_frame_host` on the device: H [B,3,3] float64 -> (T [B,3,3] float64, bbox [B,4] float64, fitted [B] uint8) - bh_pano_frame
+    for the single frame A around the reference B (`pano_frame_device`): one launch, nothing copied to the host."""
+    _frame_args(canvas, limit, "mosaic_frame")
+    T, bbox, fitted, _ = pano_frame_device(H.reshape(-1, 1, 3, 3), size_a, canvas, limit, ref_size=size_b, want_M=False)
+    return T, bbox, fitted[:, 0].contiguous()
 
 
 def exposure_device(sums):
@@ -961,6 +947,15 @@ def exposure_device(sums):
     return torch.stack([torch.where(ok, g, torch.ones_like(g)), torch.where(ok, m_t - g * m_iw, torch.zeros_like(g))], 1)
 
 
+def measure_exposure(a, b, H, ia=None, ib=None, mask=None):
+    """The exposure 'gain' of B samples on the device: a, b uint8 banks, H [B,3,3] float64 (b's index coordinates -> a's), ia / ib [B]
+    int32 device tensors or None, mask uint8 [B,Hb,Wb] or None (non-zero: the pixel of b may count) -> [B,2] float64 (g, o), the
+    least-squares line of b's gray on a's through H - a one-level `gray_pyramid` of both, `ecc_sums`, `exposure_device`."""
+    B, (Ha, Wa), (Hb, Wb) = H.shape[0], a.shape[1:3], b.shape[1:3]
+    pa, pb = gray_pyramid(a, B, 1, idx=ia), gray_pyramid(b, B, 1, idx=ib)
+    return exposure_device(ecc_sums(pyramid_level(pa, Ha, Wa, 1, 0), pyramid_level(pb, Hb, Wb, 1, 0), H, mask=mask))
+
+
 def mosaic_u8(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather", gain=None, idx_a=None, idx_b=None, want_cover=True):
     """bh_mosaic_u8 on outputs allocated here: (out [B,Hc,Wc,3] uint8, cover [B,Hc,Wc] uint8 or None) (kernels.mosaic_u8; `mosaic_host`)."""
     _need_device(images_a, images_b)
@@ -970,30 +965,49 @@ def mosaic_u8(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather", 
     return K.mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=gain, idx_a=idx_a, idx_b=idx_b)
 
 
-def _mosaic_args(canvas, feather, mode, exposure, limit, size_a, size_b, who):
-    """The host-side argument rules of `mosaic` and Aligner(mosaic=), checked before any launch -> (Hc, Wc) or None for canvas 'b'."""
+# noun -> (the canvas keyword, what it names, the modes, what `limit` counts image sizes around)
+_CANVAS_KINDS = {"mosaic": ("b", "image B's grid", MOSAIC_MODES, "B"), "panorama": ("ref", "the reference frame's grid", PANO_MODES, "the reference")}
+
+
+def _canvas_args(noun, canvas, feather, mode, limit, who):
+    """The host-side rules of the canvas, feather, mode and limit of a mosaic (`mosaic`, Aligner(mosaic=)) or a panorama (`panorama`,
+    Aligner.sequence(canvas=)), checked before any launch -> (Hc, Wc), or None for the canvas keyword ('b' / 'ref')."""
+    keyword, grid, modes, around = _CANVAS_KINDS[noun]
     size = None
-    if not (isinstance(canvas, str) and canvas == "b"):
+    if not (isinstance(canvas, str) and canvas == keyword):
         try:
             size = tuple(operator.index(v) for v in canvas)
         except (TypeError, ValueError):
             size = ()
         if len(size) != 2:
-            raise ValueError("%s: the mosaic canvas is 'b' (image B's grid) or (Hc, Wc), got %r" % (who, canvas))
+            raise ValueError("%s: the %s canvas is %r (%s) or (Hc, Wc), got %r" % (who, noun, keyword, grid, canvas))
         if min(size) < 2:
-            raise ValueError("%s: a mosaic canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (who, size[0], size[1]))
+            raise ValueError("%s: a %s canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (who, noun, size[0], size[1]))
     try:
         feather_ok = bool(1.0 <= float(feather) < float("inf"))                # (False for a NaN too)
     except (TypeError, ValueError):
         feather_ok = False
     if not feather_ok:
-        raise ValueError("%s: the mosaic feather is finite and at least 1 (pixels), got %r" % (who, feather))
-    if not (isinstance(mode, str) and mode in MOSAIC_MODES):
-        raise ValueError("%s: the mosaic mode is one of %s, got %r" % (who, ", ".join(MOSAIC_MODES), mode))
+        raise ValueError("%s: the %s feather is finite and at least 1 (pixels), got %r" % (who, noun, feather))
+    if not (isinstance(mode, str) and mode in modes):
+        raise ValueError("%s: the %s mode is one of %s, got %r" % (who, noun, ", ".join(modes), mode))
+    try:
+        limit_ok = bool(float(limit) > 0)
+    except (TypeError, ValueError):
+        limit_ok = False
+    if not limit_ok:
+        raise ValueError("%s: the %s limit (image sizes around %s that the frame may reach) is > 0, got %r" % (who, noun, around, limit))
+    return size
+
+
+def _mosaic_exposure_args(exposure, B, size_a, size_b, who, name):
+    """The rules of the mosaic's exposure (`name`: what the caller calls the argument), checked before any launch."""
     if isinstance(exposure, torch.Tensor):
         if not exposure.is_cuda or exposure.dtype != torch.float64 or exposure.dim() != 2 or exposure.shape[1] != 2:
             raise ValueError("%s: the mosaic exposure as a tensor is [B,2] float64 (g, o) on the device, got %s %s on %s"
                              % (who, exposure.dtype, tuple(exposure.shape), exposure.device))
+        if exposure.shape[0] != B:
+            raise ValueError("%s: %s [B,2] with B = %d, got %s" % (who, name, B, tuple(exposure.shape)))
     elif exposure == "gain":
         for (h, w), what in ((size_a, "images_a"), (size_b, "images_b")):
             if min(h, w) < ECC_MIN_SIDE:
@@ -1001,13 +1015,15 @@ def _mosaic_args(canvas, feather, mode, exposure, limit, size_a, size_b, who):
                                  "%s is %d x %d (H x W)" % (who, ECC_MIN_SIDE, what, h, w))
     elif exposure is not None:
         raise ValueError("%s: the mosaic exposure is None, 'gain' or a [B,2] float64 device tensor (g, o), got %r" % (who, exposure))
-    try:
-        limit_ok = bool(float(limit) > 0)
-    except (TypeError, ValueError):
-        limit_ok = False
-    if not limit_ok:
-        raise ValueError("%s: the mosaic limit (image sizes around B that the frame may reach) is > 0, got %r" % (who, limit))
-    return size
+
+
+def _identity_canvas(B, H, W, fitted_shape, device):
+    """The canvas that is the reference's own H x W grid: (T = I [B,3,3], bbox = (0, 0, W - 1, H - 1) [B,4], fitted = 0 of fitted_shape)."""
+    T = torch.zeros((B, 3, 3), dtype=torch.float64, device=device)
+    T[:, 0, 0] = T[:, 1, 1] = T[:, 2, 2] = 1.0
+    bbox = torch.zeros((B, 4), dtype=torch.float64, device=device)
+    bbox[:, 2], bbox[:, 3] = W - 1.0, H - 1.0
+    return T, bbox, torch.zeros(fitted_shape, dtype=torch.uint8, device=device)
 
 
 def _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b):
@@ -1015,22 +1031,16 @@ def _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b):
     B, dev, (Ha, Wa), (Hb, Wb) = H.shape[0], H.device, a.shape[1:3], b.shape[1:3]
     H = H.reshape(B, 3, 3).contiguous()
     if size is None:
-        Hc, Wc = Hb, Wb
-        T = torch.zeros((B, 3, 3), dtype=torch.float64, device=dev)
-        T[:, 0, 0] = T[:, 1, 1] = T[:, 2, 2] = 1.0
-        bbox = torch.zeros((B, 4), dtype=torch.float64, device=dev)
-        bbox[:, 2], bbox[:, 3] = Wb - 1.0, Hb - 1.0
-        fitted = torch.zeros((B,), dtype=torch.uint8, device=dev)
-        Ma = H
+        Hc, Wc, Ma = Hb, Wb, H
+        T, bbox, fitted = _identity_canvas(B, Hb, Wb, (B,), dev)
     else:
         Hc, Wc = size
         T, bbox, fitted = mosaic_frame_device(H, (Ha, Wa), (Hb, Wb), (Hc, Wc), limit)
-        Ma = (H @ T).contiguous()
+        Ma = (H @ T).contiguous()                                              # (torch's product, not the frame kernel's M: other roundings)
     if isinstance(exposure, torch.Tensor):
         gain = exposure.contiguous()
     elif exposure == "gain":
-        pa, pb = gray_pyramid(a, B, 1, idx=ia), gray_pyramid(b, B, 1, idx=ib)
-        gain = exposure_device(ecc_sums(pyramid_level(pa, Ha, Wa, 1, 0), pyramid_level(pb, Hb, Wb, 1, 0), H, mask=mask_b)).contiguous()
+        gain = measure_exposure(a, b, H, ia, ib, mask_b).contiguous()
     else:
         gain = None
     out, cover = mosaic_u8(a, b, Ma, T, Hc, Wc, feather, mode, gain=gain, idx_a=ia, idx_b=ib)
@@ -1056,9 +1066,8 @@ def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", expo
         raise ValueError("mosaic: images_a is on %s, images_b on %s, H on %s" % (a.device, b.device, H.device))
     _need_h(H, "mosaic")
     B = H.shape[0]
-    size = _mosaic_args(canvas, feather, mode, exposure, limit, a.shape[1:3], b.shape[1:3], "mosaic")
-    if isinstance(exposure, torch.Tensor) and exposure.shape[0] != B:
-        raise ValueError("mosaic: exposure [B,2] with B = %d, got %s" % (B, tuple(exposure.shape)))
+    size = _canvas_args("mosaic", canvas, feather, mode, limit, "mosaic")
+    _mosaic_exposure_args(exposure, B, a.shape[1:3], b.shape[1:3], "mosaic", "exposure")
     ia, na = _index(idx_a, a.shape[0], a.device, "idx_a")
     ib, nb = _index(idx_b, b.shape[0], b.device, "idx_b")
     for n, what in ((a.shape[0] if na is None else na, "images_a"), (b.shape[0] if nb is None else nb, "images_b")):
@@ -1086,9 +1095,10 @@ def chain_device(H_pairs, ref, gain_pairs=None):
     return K.pano_chain(H_pairs.contiguous(), ref, G, None if gain_pairs is None else gain_pairs.contiguous(), gain)
 
 
-def pano_frame_device(G, size, canvas, limit=2.0, use=None):
-    """bh_pano_frame on outputs allocated here (`pano_frame_host`): G [B,n,3,3] float64, use [B,n] uint8 or None -> (T [B,3,3] float64,
-    bbox [B,4] float64, fitted [B,n] uint8, M [B,n,3,3] float64 = G T): one launch."""
+def pano_frame_device(G, size, canvas, limit=2.0, use=None, ref_size=None, want_M=True):
+    """bh_pano_frame on outputs allocated here (`pano_frame_host`): G [B,n,3,3] float64, use [B,n] uint8 or None, ref_size = (Hr, Wr) of
+    the reference (None: size) -> (T [B,3,3] float64, bbox [B,4] float64, fitted [B,n] uint8, M [B,n,3,3] float64 = G T or None): one
+    launch."""
     _need_device(G)
     _frame_args(canvas, limit, "pano_frame")
     if G.dim() != 4:
@@ -1097,8 +1107,8 @@ def pano_frame_device(G, size, canvas, limit=2.0, use=None):
     T = torch.empty((B, 3, 3), dtype=torch.float64, device=G.device)
     bbox = torch.empty((B, 4), dtype=torch.float64, device=G.device)
     fitted = torch.empty((B, n), dtype=torch.uint8, device=G.device)
-    M = torch.empty((B, n, 3, 3), dtype=torch.float64, device=G.device)
-    return K.pano_frame(G.contiguous(), size, canvas, limit, T, bbox, fitted, M, use=use)
+    M = torch.empty((B, n, 3, 3), dtype=torch.float64, device=G.device) if want_M else None
+    return K.pano_frame(G.contiguous(), size, canvas, limit, T, bbox, fitted, M, use=use, ref_size=ref_size)
 
 
 def pano_u8(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, use=None, want_count=True):
@@ -1131,35 +1141,6 @@ def _frames_index(idx, n_images, device, who):
     return torch.from_numpy(host.astype(np.int32)).to(device)
 
 
-def _pano_args(canvas, feather, mode, limit, who):
-    """The host-side argument rules of `panorama` and Aligner.sequence(canvas=), checked before any launch -> (Hc, Wc) or None for 'ref'."""
-    size = None
-    if not (isinstance(canvas, str) and canvas == "ref"):
-        try:
-            size = tuple(operator.index(v) for v in canvas)
-        except (TypeError, ValueError):
-            size = ()
-        if len(size) != 2:
-            raise ValueError("%s: the panorama canvas is 'ref' (the reference frame's grid) or (Hc, Wc), got %r" % (who, canvas))
-        if min(size) < 2:
-            raise ValueError("%s: a panorama canvas has at least 2 pixels on each side, got %d x %d (H x W)" % (who, size[0], size[1]))
-    try:
-        feather_ok = bool(1.0 <= float(feather) < float("inf"))                # (False for a NaN too)
-    except (TypeError, ValueError):
-        feather_ok = False
-    if not feather_ok:
-        raise ValueError("%s: the panorama feather is finite and at least 1 (pixels), got %r" % (who, feather))
-    if not (isinstance(mode, str) and mode in PANO_MODES):
-        raise ValueError("%s: the panorama mode is one of %s, got %r" % (who, ", ".join(PANO_MODES), mode))
-    try:
-        limit_ok = bool(float(limit) > 0)
-    except (TypeError, ValueError):
-        limit_ok = False
-    if not limit_ok:
-        raise ValueError("%s: the panorama limit (image sizes around the reference that the frame may reach) is > 0, got %r" % (who, limit))
-    return size
-
-
 def _pano_tensor(t, shape, dtype, what, who):
     if t is None:
         return None
@@ -1174,13 +1155,8 @@ def _panorama(images, idx, G, size, feather, mode, gain, use, limit):
     B, n = G.shape[:2]
     dev, (Hs, Ws) = G.device, images.shape[1:3]
     if size is None:
-        Hc, Wc = Hs, Ws
-        T = torch.zeros((B, 3, 3), dtype=torch.float64, device=dev)
-        T[:, 0, 0] = T[:, 1, 1] = T[:, 2, 2] = 1.0
-        bbox = torch.zeros((B, 4), dtype=torch.float64, device=dev)
-        bbox[:, 2], bbox[:, 3] = Ws - 1.0, Hs - 1.0
-        fitted = torch.zeros((B, n), dtype=torch.uint8, device=dev)
-        M = G
+        Hc, Wc, M = Hs, Ws, G
+        T, bbox, fitted = _identity_canvas(B, Hs, Ws, (B, n), dev)
     else:
         Hc, Wc = size
         T, bbox, fitted, M = pano_frame_device(G, (Hs, Ws), (Hc, Wc), limit, use=use)
@@ -1209,7 +1185,7 @@ def panorama(images, G, idx=None, canvas="ref", feather=32.0, mode="feather", ga
     if G.dtype != torch.float64 or G.dim() != 4 or tuple(G.shape[2:]) != (3, 3) or not 1 <= G.shape[1] <= PANO_MAX_FRAMES:
         raise ValueError("panorama: G [B,n,3,3] float64 with 1 <= n <= %d, got %s %s" % (PANO_MAX_FRAMES, G.dtype, tuple(G.shape)))
     B, n = G.shape[:2]
-    size = _pano_args(canvas, feather, mode, limit, "panorama")
+    size = _canvas_args("panorama", canvas, feather, mode, limit, "panorama")
     ix = _frames_index(idx, data.shape[0], data.device, "panorama")
     if tuple(ix.shape) != (B, n):
         raise ValueError("panorama: idx names %d samples of %d frames, G has %d of %d" % (ix.shape[0], ix.shape[1], B, n))
@@ -1362,21 +1338,15 @@ class Aligner:
         ra = _regions(roi_a, B, a.shape[1], a.shape[2], a.device, "roi_a")
         rb = _regions(roi_b, B, b.shape[1], b.shape[2], b.device, "roi_b")
         if refine is not None:
-            for img, what in ((a, "images_a"), (b, "images_b")):
-                try:
-                    pyramid_sizes(img.shape[1], img.shape[2], refine_levels)
-                except ValueError as e:
-                    raise ValueError("Aligner: refine_levels, %s: %s" % (what, e)) from None
-            if not refine_iters >= 0:
-                raise ValueError("Aligner: refine_iters >= 0, got %r" % (refine_iters,))
+            _refine_args(refine_levels, refine_iters, (("Aligner: refine_levels, images_a", a.shape[1:3]), ("Aligner: refine_levels, images_b", b.shape[1:3])),
+                         "Aligner: refine_iters")
             mask_b = _check_mask(mask_b, B, b.shape[1], b.shape[2], b.device)
         elif mask_b is not None:
             raise ValueError("Aligner: mask_b restricts the pixels the refinement counts; pass refine='ecc' with it")
         nx, ny = samples or _cascade_samples(None, roi_b, b.shape[1], b.shape[2], P)
         if mosaic is not None:
-            canvas = _mosaic_args(mosaic, mosaic_feather, mosaic_mode, mosaic_exposure, mosaic_limit, a.shape[1:3], b.shape[1:3], "Aligner")
-            if isinstance(mosaic_exposure, torch.Tensor) and mosaic_exposure.shape[0] != B:
-                raise ValueError("Aligner: mosaic_exposure [B,2] with B = %d, got %s" % (B, tuple(mosaic_exposure.shape)))
+            canvas = _canvas_args("mosaic", mosaic, mosaic_feather, mosaic_mode, mosaic_limit, "Aligner")
+            _mosaic_exposure_args(mosaic_exposure, B, a.shape[1:3], b.shape[1:3], "Aligner", "mosaic_exposure")
         with torch.cuda.device(a.device):
             p1, ga = prepare(a, B, P, self.channels, self.mean, self.std, idx=ia, roi=ra)
             p2, gb = prepare(b, B, P, self.channels, self.mean, self.std, idx=ib, roi=rb)
@@ -1440,18 +1410,13 @@ class Aligner:
                     roi = np.repeat(roi, n - 1, axis=0)                        # one region per sample -> one per pair
             _regions(roi, B * (n - 1), Hs, Ws, torch.device("cpu"), "roi")
         if refine is not None:
-            try:
-                pyramid_sizes(Hs, Ws, refine_levels)
-            except ValueError as e:
-                raise ValueError("%s: refine_levels: %s" % (who, e)) from None
-            if not refine_iters >= 0:
-                raise ValueError("%s: refine_iters >= 0, got %r" % (who, refine_iters))
+            _refine_args(refine_levels, refine_iters, (("%s: refine_levels" % who, (Hs, Ws)),), "%s: refine_iters" % who)
         if canvas is None:
             if exposure is not None or use is not None:
                 raise ValueError("%s: exposure and use belong to the panorama; pass canvas='ref' or (Hc, Wc) with them" % who)
             size = None
         else:
-            size = _pano_args(canvas, feather, mode, limit, who)
+            size = _canvas_args("panorama", canvas, feather, mode, limit, who)
         measure = isinstance(exposure, str) and exposure == "gain"
         if measure:
             if min(Hs, Ws) < ECC_MIN_SIDE:
@@ -1480,9 +1445,7 @@ class Aligner:
                 out["pair"] = r
                 H_pairs = r["H"].reshape(B, n - 1, 3, 3).contiguous()
                 if measure:
-                    pa, pb = gray_pyramid(data, B * (n - 1), 1, idx=ia), gray_pyramid(data, B * (n - 1), 1, idx=ib)
-                    sums = ecc_sums(pyramid_level(pa, Hs, Ws, 1, 0), pyramid_level(pb, Hs, Ws, 1, 0), r["H"], mask=mask_b)
-                    gain_pairs = exposure_device(sums).reshape(B, n - 1, 2).contiguous()
+                    gain_pairs = measure_exposure(data, data, r["H"], ia, ib, mask_b).reshape(B, n - 1, 2).contiguous()
             else:
                 H_pairs = torch.empty((B, 0, 3, 3), dtype=torch.float64, device=dev)
                 if measure:

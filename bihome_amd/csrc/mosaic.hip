@@ -6,7 +6,9 @@
 // gain / bias to A's value, weighs each image by the distance of its projected point to the border of the image plus 1, capped at
 // `feather`, blends (or, in the two "over" modes, selects), rounds half up and stores.  An image that is not present at a pixel is
 // selected out, never multiplied by 0: under the projection guard its sample is unspecified.  No full-size intermediate, no atomics, no
-// scratch, no LDS, one writer per output element.
+// scratch, no LDS, one writer per output element.  The weight (u8_border_weight), the feather rule and the choice between the two store
+// paths are u8_image.h's, shared with pano.hip; the fitted canvas itself is pano.hip's bh_pano_frame with A as its single frame
+// (align.py mosaic_frame_device).
 //
 // Wc % 4 == 0 and out on a 4-byte boundary: a thread makes four pixels and stores three dwords (consecutive lanes on consecutive
 // 12 bytes, u8_store_pixels) and, with cover on a 4-byte boundary, one dword of cover codes (u8_store_flags); anything else: one pixel,
@@ -15,12 +17,6 @@
 #include "u8_image.h"
 
 #define MOSAIC_THREADS 256
-
-// min(distance of the sample's projected point to the border of its image + 1, feather); meaningful where the sample is valid
-__device__ __forceinline__ float mosaic_weight(const U8Sample& s, float xmax, float ymax, float feather) {
-#pragma clang fp contract(off)
-    return fminf(fminf(fminf(s.u, xmax - s.u), fminf(s.v, ymax - s.v)) + 1.0f, feather);
-}
 
 // the value of one channel before rounding: a is A's value after the gain
 __device__ __forceinline__ float mosaic_value(float a, float b, float wa, float wb, bool pa, bool pb, int mode) {
@@ -55,7 +51,7 @@ __global__ void __launch_bounds__(MOSAIC_THREADS) mosaic_kernel(const unsigned c
         for (int p = 0; p < PX; ++p) {
             const U8Sample sa = u8_sample<BYTES_A>(im_a, Ma, x + p, y, Wa, Ha, xmax_a, ymax_a);
             const U8Sample sb = u8_sample<BYTES_B>(im_b, Mb, x + p, y, Wb, Hb, xmax_b, ymax_b);
-            const float wa = mosaic_weight(sa, xmax_a, ymax_a, feather), wb = mosaic_weight(sb, xmax_b, ymax_b, feather);
+            const float wa = u8_border_weight(sa, xmax_a, ymax_a, feather), wb = u8_border_weight(sb, xmax_b, ymax_b, feather);
 #pragma unroll
             for (int c = 0; c < 3; ++c)
                 q[p * 3 + c] = u8_round(mosaic_value(__builtin_fmaf(g, sa.c[c], o), sb.c[c], wa, wb, sa.valid, sb.valid, mode));
@@ -80,21 +76,20 @@ int bh_mosaic_u8(const uint8_t* images_a, const int* idx_a, int n_a, int Ha, int
                  int B, int Hc, int Wc, float feather, int mode,
                  uint8_t* out, uint8_t* cover, void* stream) {
     if (!images_a || !images_b || !Ma || !Mb || !out || mosaic_extents_bad(B, n_a, Ha, Wa, n_b, Hb, Wb, Hc, Wc)) return BH_E_BADARG;
-    if (!(feather >= 1.0f) || !(feather <= 3.402823466e+38f)) return BH_E_BADARG;                  // (NaN and infinity fail one of the two)
+    if (u8_feather_bad(feather)) return BH_E_BADARG;
     if (mode != BH_MOSAIC_FEATHER && mode != BH_MOSAIC_B_OVER_A && mode != BH_MOSAIC_A_OVER_B) return BH_E_BADARG;
     // (tap_place's offsets are ints of 4 bytes per pixel, byte offsets inside an image 32-bit; the unit index of a thread is an unsigned)
     if ((long long)Ha * Wa > (1ll << 29) || (long long)Hb * Wb > (1ll << 29) || (long long)Hc * Wc > 0x7fffffffll) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
-    const bool vec = Wc % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0;
-    const int cover_vec = cover && reinterpret_cast<uintptr_t>(cover) % 4 == 0;
-    const unsigned units = (unsigned)Hc * ((unsigned)Wc / (vec ? 4 : 1));
+    const U8Stores stores = u8_stores(Wc, out, cover);
+    const unsigned units = (unsigned)Hc * ((unsigned)Wc / (stores.vec ? 4 : 1));
     const dim3 grid((units + MOSAIC_THREADS - 1) / MOSAIC_THREADS, u8_grid_y(B));
     hipStream_t st = bh_stream(stream);
     const bool ba = (long long)Ha * Wa < 2, bb = (long long)Hb * Wb < 2;       // a single-pixel image: no room for 4-byte loads
     u8_flags([&](auto four, auto by_a, auto by_b) {
         hipLaunchKernelGGL((mosaic_kernel<four ? 4 : 1, by_a, by_b>), grid, dim3(MOSAIC_THREADS), 0, st, images_a, idx_a, n_a, Ha, Wa, images_b, idx_b, n_b, Hb, Wb,
-                           Ma, Mb, gain, B, Hc, Wc, feather, mode, out, cover, cover_vec);
-    }, vec, ba, bb);
+                           Ma, Mb, gain, B, Hc, Wc, feather, mode, out, cover, stores.flag_vec);
+    }, stores.vec, ba, bb);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

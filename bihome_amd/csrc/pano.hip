@@ -5,7 +5,7 @@
 // from the reference; one thread per sample, double.
 // bh_pano_frame: the canvas around the reference's extent and every frame's projected corners - adjugate, corners, the usable test and
 // the clamp per frame (thread k), a min / max reduction over the workgroup, then T, the box and M[k] = G[k] T; one workgroup per sample,
-// one launch where mosaic_frame_device spends some sixty tensor launches per pair.
+// one launch.  The reference has a size of its own, so the pair's frame (align.py mosaic_frame_device) is this kernel with n = 1.
 // bh_pano_u8: mosaic.hip's kernel with a run-time loop over the frames.  Per frame a thread first projects its pixels (u8_image.h's
 // u8_point / u8_valid: arithmetic only), and when no lane of the wavefront has the frame present the wavefront goes on to the next frame
 // without a single load (PANO_SKIP) - in a pan most canvas pixels see 0 to 3 of the n frames.  That cannot change a result: a frame
@@ -69,17 +69,18 @@ __device__ __forceinline__ double pano_wave_min(double v) {
 }
 __device__ __forceinline__ double pano_clip(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
-// grid B, PANO_THREADS threads: thread k is frame k (n <= PANO_MAX_FRAMES)
+// grid B, PANO_THREADS threads: thread k is frame k (n <= PANO_MAX_FRAMES).  Hs x Ws: the frames, whose corners are projected; Hr x Wr: the
+// reference, whose extent starts the box and scales the clamp
 __global__ void __launch_bounds__(PANO_THREADS) pano_frame_kernel(const double* __restrict__ G, const unsigned char* __restrict__ use, int n, int Hs, int Ws,
-                                                                  int Hc, int Wc, double limit, double* __restrict__ T, double* __restrict__ bbox,
-                                                                  unsigned char* __restrict__ fitted, double* __restrict__ M) {
+                                                                  int Hr, int Wr, int Hc, int Wc, double limit, double* __restrict__ T,
+                                                                  double* __restrict__ bbox, unsigned char* __restrict__ fitted, double* __restrict__ M) {
 #pragma clang fp contract(off)
     __shared__ double red[4][PANO_THREADS / 64];
     __shared__ double Ts[3];                                                   // s, tx, ty
     const size_t b = blockIdx.x;
     const int k = threadIdx.x;
-    const double W1 = (double)Ws - 1.0, H1 = (double)Hs - 1.0;
-    double x0 = 0.0, x1 = W1, y0 = 0.0, y1 = H1, g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const double W1 = (double)Ws - 1.0, H1 = (double)Hs - 1.0, Wr1 = (double)Wr - 1.0, Hr1 = (double)Hr - 1.0;
+    double x0 = 0.0, x1 = Wr1, y0 = 0.0, y1 = Hr1, g[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (k < n) {
         const double* Gk = G + 9 * (b * n + k);
         for (int i = 0; i < 9; ++i) g[i] = Gk[i];
@@ -102,11 +103,11 @@ __global__ void __launch_bounds__(PANO_THREADS) pano_frame_kernel(const double* 
         }
         usable = usable && (pos || neg) && !(use && use[b * n + k] == 0);
         if (usable) {
-            const double W = (double)Ws, H = (double)Hs;
+            const double W = (double)Wr, H = (double)Hr;
             x0 = fmin(pano_clip(pxmin, -limit * W, (1.0 + limit) * W - 1.0), 0.0);
-            x1 = fmax(pano_clip(pxmax, -limit * W, (1.0 + limit) * W - 1.0), W1);
+            x1 = fmax(pano_clip(pxmax, -limit * W, (1.0 + limit) * W - 1.0), Wr1);
             y0 = fmin(pano_clip(pymin, -limit * H, (1.0 + limit) * H - 1.0), 0.0);
-            y1 = fmax(pano_clip(pymax, -limit * H, (1.0 + limit) * H - 1.0), H1);
+            y1 = fmax(pano_clip(pymax, -limit * H, (1.0 + limit) * H - 1.0), Hr1);
         }
         if (fitted) fitted[b * n + k] = usable ? 1 : 0;
     }
@@ -139,12 +140,6 @@ __global__ void __launch_bounds__(PANO_THREADS) pano_frame_kernel(const double* 
 // ------------------------------------------------------------------------------------------------
 // the blend
 // ------------------------------------------------------------------------------------------------
-// mosaic.hip's mosaic_weight: min(distance of the projected point to the border of the frame + 1, feather); meaningful where present
-__device__ __forceinline__ float pano_weight(const U8Sample& s, float xmax, float ymax, float feather) {
-#pragma clang fp contract(off)
-    return fminf(fminf(fminf(s.u, xmax - s.u), fminf(s.v, ymax - s.v)) + 1.0f, feather);
-}
-
 // the thread's unit of PX pixels -> (x, y) of its first pixel; false: outside the canvas
 template <int PX>
 __device__ __forceinline__ bool pano_unit(int Hc, int Wc, int& x, int& y) {
@@ -206,7 +201,7 @@ __global__ void __launch_bounds__(PANO_THREADS) pano_kernel(const unsigned char*
 #pragma unroll
             for (int p = 0; p < PX; ++p) {
                 const U8Sample s = u8_gather<BYTES>(im, t[p], xmax, ymax);
-                const float w = pano_weight(s, xmax, ymax, feather);
+                const float w = u8_border_weight(s, xmax, ymax, feather);
                 const bool first = cnt[p] == 0u;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
@@ -248,11 +243,12 @@ int bh_pano_chain(const double* Hpair, const double* gain_pair, int B, int n, in
     return BH_OK;
 }
 
-int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int Ws, int Hc, int Wc, double limit,
+int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int Ws, int Hr, int Wr, int Hc, int Wc, double limit,
                   double* T, double* bbox, uint8_t* fitted, double* M, void* stream) {
-    if (!G || !T || pano_counts_bad(B, n) || pano_extents_bad(Hs, Ws, Hc, Wc, 2) || !(limit > 0.0)) return BH_E_BADARG;
+    if (!G || !T || pano_counts_bad(B, n) || pano_extents_bad(Hs, Ws, Hc, Wc, 2) || Hr < 1 || Wr < 1 || !(limit > 0.0)) return BH_E_BADARG;
     if (B == 0) return BH_OK;
-    hipLaunchKernelGGL(pano_frame_kernel, dim3((unsigned)B), dim3(PANO_THREADS), 0, bh_stream(stream), G, use, n, Hs, Ws, Hc, Wc, limit, T, bbox, fitted, M);
+    hipLaunchKernelGGL(pano_frame_kernel, dim3((unsigned)B), dim3(PANO_THREADS), 0, bh_stream(stream), G, use, n, Hs, Ws, Hr, Wr, Hc, Wc, limit, T, bbox,
+                       fitted, M);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }
@@ -260,20 +256,19 @@ int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int
 int bh_pano_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* M, const double* gain,
                const uint8_t* use, int B, int n, int Hc, int Wc, float feather, int mode, uint8_t* out, uint8_t* count, void* stream) {
     if (!images || !M || !out || pano_counts_bad(B, n) || n_images < 1 || pano_extents_bad(Hs, Ws, Hc, Wc, 1)) return BH_E_BADARG;
-    if (!(feather >= 1.0f) || !(feather <= 3.402823466e+38f)) return BH_E_BADARG;                  // (NaN and infinity fail one of the two)
+    if (u8_feather_bad(feather)) return BH_E_BADARG;
     if (mode != BH_PANO_FEATHER && mode != BH_PANO_FIRST && mode != BH_PANO_LAST) return BH_E_BADARG;
     // (bh_mosaic_u8's limits: tap_place's offsets, 32-bit byte offsets inside an image, the unit index of a thread)
     if ((long long)Hs * Ws > (1ll << 29) || (long long)Hc * Wc > 0x7fffffffll) return BH_E_UNSUPPORTED;
     if (B == 0) return BH_OK;
-    const bool vec = Wc % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0;
-    const int count_vec = count && reinterpret_cast<uintptr_t>(count) % 4 == 0;
-    const dim3 grid(pano_grid_x(Hc, Wc, vec ? 4 : 1), u8_grid_y(B));
+    const U8Stores stores = u8_stores(Wc, out, count);
+    const dim3 grid(pano_grid_x(Hc, Wc, stores.vec ? 4 : 1), u8_grid_y(B));
     hipStream_t st = bh_stream(stream);
     const bool bytes = (long long)Hs * Ws < 2;                                 // a single-pixel frame: no room for 4-byte loads
     u8_flags([&](auto four, auto by) {
         hipLaunchKernelGGL((pano_kernel<four ? 4 : 1, by>), grid, dim3(PANO_THREADS), 0, st, images, idx, n_images, Hs, Ws, M, gain, use, B, n, Hc, Wc, feather,
-                           mode, out, count, count_vec);
-    }, vec, bytes);
+                           mode, out, count, stores.flag_vec);
+    }, stores.vec, bytes);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

@@ -1,8 +1,8 @@
 // The interleaved uint8 RGB bank image, spelled ONCE for the aligner (csrc/align.hip, ecc.hip, cascade.hip, mosaic.hip, pano.hip) and the bank
 // (csrc/bank.hip): which image sample b reads, how a pixel is loaded, the bilinear sample of a pixel through a homography with its
-// validity, the rounding to a byte, the stores of pixels and flags, the patch epilogue and the grid clamp.  The reason is warp_tap.h's:
-// bh_warp_u8, bh_align_prep_warp_u8 and bh_mosaic_u8 promise ONE sample and ONE `valid` (include/bihome.h), and they agree bit for bit on
-// which side of a border a pixel falls because they call one function.
+// validity, the border weight of a blend, the rounding to a byte, the stores of pixels and flags, the patch epilogue and the grid clamp.
+// The reason is warp_tap.h's: bh_warp_u8, bh_align_prep_warp_u8 and bh_mosaic_u8 promise ONE sample and ONE `valid` (include/bihome.h),
+// and they agree bit for bit on which side of a border a pixel falls because they call one function.
 #pragma once
 #include <type_traits>
 #include "warp_tap.h"
@@ -88,6 +88,15 @@ __device__ __forceinline__ U8Sample u8_sample(const U8Image& im, const Hf& H, in
     return u8_gather<BYTES>(im, t, xmax, ymax);
 }
 
+// The weight of a sample in a blend (bh_mosaic_u8, bh_pano_u8): min(distance of its projected point to the border of its image + 1,
+// feather); meaningful where the sample is valid
+__device__ __forceinline__ float u8_border_weight(const U8Sample& s, float xmax, float ymax, float feather) {
+#pragma clang fp contract(off)
+    return fminf(fminf(fminf(s.u, xmax - s.u), fminf(s.v, ymax - s.v)) + 1.0f, feather);
+}
+// a feather the blends refuse: NaN, infinite (both fail one of the two comparisons) or below 1
+static inline bool u8_feather_bad(float feather) { return !(feather >= 1.0f) || !(feather <= 3.402823466e+38f); }
+
 // round half up into a byte (fmaxf drops a NaN: 0; the conversion truncates)
 __device__ __forceinline__ unsigned u8_round(float v) { return (unsigned)(fminf(fmaxf(v, 0.0f), 255.0f) + 0.5f); }
 
@@ -114,6 +123,13 @@ __device__ __forceinline__ void u8_store_flags(unsigned char* __restrict__ dst, 
     }
 #pragma unroll
     for (int p = 0; p < PX; ++p) dst[p] = (unsigned char)f[p];
+}
+
+// How a blend stores its canvas: vec - Wc % 4 == 0 and out on a 4-byte boundary, a thread makes four pixels (u8_store_pixels<4>), else
+// one; flag_vec - the flag plane (NULL ok) is on a 4-byte boundary too (u8_store_flags' vec)
+struct U8Stores { bool vec; int flag_vec; };
+static inline U8Stores u8_stores(int Wc, const void* out, const void* flags) {
+    return {Wc % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0, flags && reinterpret_cast<uintptr_t>(flags) % 4 == 0};
 }
 
 // The patch epilogue: channel sums (r, g, b) times inv as gray (C = 1) or per channel (C = 3) in planes pp floats apart, standardised.

@@ -1586,12 +1586,31 @@ def _is_h(M):
     return M.dim() >= 2 and M.numel() == 9 * M.shape[0]
 
 
-def _chk_images_u8(images, idx, B, what):
+def _chk_images_u8(images, idx, idx_shape, what):
+    """A uint8 bank and its index list idx (None: the images in order) of shape idx_shape: (B,), or (B, n) for sequences."""
     _chk(images, torch.uint8); _chk(idx, torch.int32)
     if images.dim() != 4 or images.shape[3] != 3 or min(images.shape) < 1:
         raise ValueError("%s: images [N,H,W,3] uint8 with N, H, W >= 1, got %s" % (what, tuple(images.shape)))
-    if idx is not None and tuple(idx.shape) != (B,):
-        raise ValueError("%s: idx [B] int32, got %s for B = %d" % (what, tuple(idx.shape), B))
+    if idx is not None and tuple(idx.shape) != tuple(idx_shape):
+        names = "Bn"[:len(idx_shape)]
+        raise ValueError("%s: idx [%s] int32, got %s for %s" % (what, ",".join(names), tuple(idx.shape), ", ".join("%s = %d" % p for p in zip(names, idx_shape))))
+
+
+def _chk_canvas_u8(out, flags, B, what, names):
+    """The shapes of an output image out [B,H,W,3] and its flag plane [B,H,W] or None; names = (the plane's name, "H,W" as the message
+    spells them)."""
+    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (flags is not None and tuple(flags.shape) != tuple(out.shape[:3])):
+        raise ValueError("%s: out [B,%s,3] uint8 and %s [B,%s] uint8 with B = %d, got %s and %s"
+                         % (what, names[1], names[0], names[1], B, tuple(out.shape), None if flags is None else tuple(flags.shape)))
+
+
+def _mode_number(mode, modes, what):
+    """A blend mode by name, or already its number in include/bihome.h."""
+    if isinstance(mode, str):
+        if mode not in modes:
+            raise ValueError("%s: mode is one of %s, got %r" % (what, sorted(modes), mode))
+        mode = modes[mode]
+    return int(mode)
 
 
 def align_prep_u8(images, patch, geom, mean, std, idx=None, roi=None):
@@ -1604,7 +1623,7 @@ def align_prep_u8(images, patch, geom, mean, std, idx=None, roi=None):
     if patch.dim() != 4 or patch.shape[2] != patch.shape[3] or tuple(geom.shape) != (patch.shape[0], 4):
         raise ValueError("align_prep_u8: patch [B,C,P,P] float32 and geom [B,4] float64, got %s and %s" % (tuple(patch.shape), tuple(geom.shape)))
     B, C, P = patch.shape[:3]
-    _chk_images_u8(images, idx, B, "align_prep_u8")
+    _chk_images_u8(images, idx, (B,), "align_prep_u8")
     if roi is not None and tuple(roi.shape) != (B, 4):
         raise ValueError("align_prep_u8: roi [B,4] float64, got %s" % (tuple(roi.shape),))
     check(lib.bh_align_prep_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(roi), B, P, C,
@@ -1620,10 +1639,8 @@ def warp_u8(images, H64, out, valid=None, idx=None):
     if not _is_h(H64):
         raise ValueError("warp_u8: H64 [B,3,3] float64, got %s" % (tuple(H64.shape),))
     B = H64.shape[0]
-    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (valid is not None and tuple(valid.shape) != tuple(out.shape[:3])):
-        raise ValueError("warp_u8: out [B,Ho,Wo,3] uint8 and valid [B,Ho,Wo] uint8 with B = %d, got %s and %s"
-                         % (B, tuple(out.shape), None if valid is None else tuple(valid.shape)))
-    _chk_images_u8(images, idx, B, "warp_u8")
+    _chk_canvas_u8(out, valid, B, "warp_u8", ("valid", "Ho,Wo"))
+    _chk_images_u8(images, idx, (B,), "warp_u8")
     check(lib.bh_warp_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(H64), B, out.shape[1], out.shape[2],
                          _p(out), _p(valid), _stream()), "bh_warp_u8")
     return out, valid
@@ -1660,7 +1677,7 @@ def gray_pyramid_u8(images, pyr, levels, idx=None):
     if pyr.dim() != 2:
         raise ValueError("gray_pyramid_u8: pyr [B,total] float32, got %s" % (tuple(pyr.shape),))
     B = pyr.shape[0]
-    _chk_images_u8(images, idx, B, "gray_pyramid_u8")
+    _chk_images_u8(images, idx, (B,), "gray_pyramid_u8")
     total = gray_pyramid_layout(images.shape[1], images.shape[2], levels)[-1]
     if pyr.shape[1] != total:
         raise ValueError("gray_pyramid_u8: %d levels of %d x %d take %d floats per sample, pyr has %d" % (levels, images.shape[1], images.shape[2], total, pyr.shape[1]))
@@ -1733,7 +1750,7 @@ def align_prep_warp_u8(images, Hg, patch, cover, nx, ny, mean, std, idx=None):
     B, C, P = patch.shape[:3]
     if cover is not None and tuple(cover.shape) != (B, P, P):
         raise ValueError("align_prep_warp_u8: cover [B,P,P] float32 = [%d,%d,%d], got %s" % (B, P, P, tuple(cover.shape)))
-    _chk_images_u8(images, idx, B, "align_prep_warp_u8")
+    _chk_images_u8(images, idx, (B,), "align_prep_warp_u8")
     check(lib.bh_align_prep_warp_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(Hg), B, P, C, int(nx), int(ny),
                                     float(mean), float(std), _p(patch), _p(cover), _stream()), "bh_align_prep_warp_u8")
     return patch, cover
@@ -1773,18 +1790,13 @@ def mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=None, 
     if Mb.shape[0] != B or (gain is not None and tuple(gain.shape) != (B, 2)):
         raise ValueError("mosaic_u8: Ma and Mb [B,3,3] and gain [B,2] float64 with one B, got %s, %s and %s"
                          % (tuple(Ma.shape), tuple(Mb.shape), None if gain is None else tuple(gain.shape)))
-    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (cover is not None and tuple(cover.shape) != tuple(out.shape[:3])):
-        raise ValueError("mosaic_u8: out [B,Hc,Wc,3] uint8 and cover [B,Hc,Wc] uint8 with B = %d, got %s and %s"
-                         % (B, tuple(out.shape), None if cover is None else tuple(cover.shape)))
-    if isinstance(mode, str):
-        if mode not in MOSAIC_MODES:
-            raise ValueError("mosaic_u8: mode is one of %s, got %r" % (sorted(MOSAIC_MODES), mode))
-        mode = MOSAIC_MODES[mode]
-    _chk_images_u8(images_a, idx_a, B, "mosaic_u8")
-    _chk_images_u8(images_b, idx_b, B, "mosaic_u8")
+    _chk_canvas_u8(out, cover, B, "mosaic_u8", ("cover", "Hc,Wc"))
+    mode = _mode_number(mode, MOSAIC_MODES, "mosaic_u8")
+    _chk_images_u8(images_a, idx_a, (B,), "mosaic_u8")
+    _chk_images_u8(images_b, idx_b, (B,), "mosaic_u8")
     check(lib.bh_mosaic_u8(_p(images_a), _p(idx_a), images_a.shape[0], images_a.shape[1], images_a.shape[2],
                            _p(images_b), _p(idx_b), images_b.shape[0], images_b.shape[1], images_b.shape[2],
-                           _p(Ma), _p(Mb), _p(gain), B, out.shape[1], out.shape[2], float(feather), int(mode), _p(out), _p(cover), _stream()),
+                           _p(Ma), _p(Mb), _p(gain), B, out.shape[1], out.shape[2], float(feather), mode, _p(out), _p(cover), _stream()),
           "bh_mosaic_u8")
     return out, cover
 
@@ -1799,15 +1811,6 @@ PANO_MAX_FRAMES = 255
 def _is_hn(M):
     """M is [B,n,3,3] or [B,n,9] with 1 <= n <= 255: the homographies of a batch of sequences."""
     return M.dim() >= 3 and 1 <= M.shape[1] <= PANO_MAX_FRAMES and M.numel() == 9 * M.shape[0] * M.shape[1]
-
-
-def _chk_frames_u8(images, idx, B, n, what):
-    """`_chk_images_u8` for a sequence: idx [B,n] int32 (None: frame k is image k)."""
-    _chk(images, torch.uint8); _chk(idx, torch.int32)
-    if images.dim() != 4 or images.shape[3] != 3 or min(images.shape) < 1:
-        raise ValueError("%s: images [N,H,W,3] uint8 with N, H, W >= 1, got %s" % (what, tuple(images.shape)))
-    if idx is not None and tuple(idx.shape) != (B, n):
-        raise ValueError("%s: idx [B,n] int32, got %s for B = %d, n = %d" % (what, tuple(idx.shape), B, n))
 
 
 def pano_chain(H_pairs, ref, G, gain_pairs=None, gain=None):
@@ -1829,10 +1832,10 @@ def pano_chain(H_pairs, ref, G, gain_pairs=None, gain=None):
     return G, gain
 
 
-def pano_frame(G, size, canvas, limit, T, bbox=None, fitted=None, M=None, use=None):
-    """The canvas of a sequence (include/bihome.h bh_pano_frame; bihome_amd.align.pano_frame_host): G [B,n,3,3] float64, size = (Hs, Ws),
-    canvas = (Hc, Wc), use [B,n] uint8 or None -> T [B,3,3], bbox [B,4], M [B,n,3,3] float64 and fitted [B,n] uint8, the caller's
-    (bihome_amd.align.pano_frame_device allocates them; all but T may be None)."""
+def pano_frame(G, size, canvas, limit, T, bbox=None, fitted=None, M=None, use=None, ref_size=None):
+    """The canvas of a sequence (include/bihome.h bh_pano_frame; bihome_amd.align.pano_frame_host): G [B,n,3,3] float64, size = (Hs, Ws)
+    of the frames, ref_size = (Hr, Wr) of the reference (None: size), canvas = (Hc, Wc), use [B,n] uint8 or None -> T [B,3,3], bbox [B,4],
+    M [B,n,3,3] float64 and fitted [B,n] uint8, the caller's (bihome_amd.align.pano_frame_device allocates them; all but T may be None)."""
     _chk(G, torch.float64); _chk(T, torch.float64); _chk(bbox, torch.float64); _chk(M, torch.float64); _chk(fitted, torch.uint8); _chk(use, torch.uint8)
     if not _is_hn(G):
         raise ValueError("pano_frame: G [B,n,3,3] float64 with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, tuple(G.shape)))
@@ -1843,9 +1846,9 @@ def pano_frame(G, size, canvas, limit, T, bbox=None, fitted=None, M=None, use=No
     for t, what in ((fitted, "fitted"), (use, "use")):
         if t is not None and tuple(t.shape) != (B, n):
             raise ValueError("pano_frame: %s [B,n] uint8 with B = %d, n = %d, got %s" % (what, B, n, tuple(t.shape)))
-    (Hs, Ws), (Hc, Wc) = size, canvas
-    check(lib.bh_pano_frame(_p(G), _p(use), B, n, int(Hs), int(Ws), int(Hc), int(Wc), float(limit), _p(T), _p(bbox), _p(fitted), _p(M), _stream()),
-          "bh_pano_frame")
+    (Hs, Ws), (Hr, Wr), (Hc, Wc) = size, size if ref_size is None else ref_size, canvas
+    check(lib.bh_pano_frame(_p(G), _p(use), B, n, int(Hs), int(Ws), int(Hr), int(Wr), int(Hc), int(Wc), float(limit), _p(T), _p(bbox), _p(fitted),
+                            _p(M), _stream()), "bh_pano_frame")
     return T, bbox, fitted, M
 
 
@@ -1862,14 +1865,9 @@ def pano_u8(images, idx, M, out, count, feather, mode, gain=None, use=None):
     if (gain is not None and tuple(gain.shape) != (B, n, 2)) or (use is not None and tuple(use.shape) != (B, n)):
         raise ValueError("pano_u8: gain [B,n,2] float64 and use [B,n] uint8 with B = %d, n = %d, got %s and %s"
                          % (B, n, None if gain is None else tuple(gain.shape), None if use is None else tuple(use.shape)))
-    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (count is not None and tuple(count.shape) != tuple(out.shape[:3])):
-        raise ValueError("pano_u8: out [B,Hc,Wc,3] uint8 and count [B,Hc,Wc] uint8 with B = %d, got %s and %s"
-                         % (B, tuple(out.shape), None if count is None else tuple(count.shape)))
-    if isinstance(mode, str):
-        if mode not in PANO_MODES:
-            raise ValueError("pano_u8: mode is one of %s, got %r" % (sorted(PANO_MODES), mode))
-        mode = PANO_MODES[mode]
-    _chk_frames_u8(images, idx, B, n, "pano_u8")
+    _chk_canvas_u8(out, count, B, "pano_u8", ("count", "Hc,Wc"))
+    mode = _mode_number(mode, PANO_MODES, "pano_u8")
+    _chk_images_u8(images, idx, (B, n), "pano_u8")
     check(lib.bh_pano_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(M), _p(gain), _p(use), B, n,
-                         out.shape[1], out.shape[2], float(feather), int(mode), _p(out), _p(count), _stream()), "bh_pano_u8")
+                         out.shape[1], out.shape[2], float(feather), mode, _p(out), _p(count), _stream()), "bh_pano_u8")
     return out, count

@@ -956,7 +956,7 @@ int bh_patch_ncc(const float* w, const float* t, const float* cover, int B, int 
 
 /* Mosaic: both images of an aligned pair on one canvas, combined in one pass - what an inter-image homography is usually computed for
  * (panoramas, frame stacks, before / after composites).  The numpy float64 statement is bihome_amd/align.py's mosaic_host
- * (mosaic_frame_host places the canvas, exposure_host gives the gain / bias).  Index coordinates throughout.
+ * (mosaic_frame_host places the canvas - bh_pano_frame with n = 1 - and exposure_host gives the gain / bias).  Index coordinates throughout.
  *
  * images_a[n_a,Ha,Wa,3], images_b[n_b,Hb,Wb,3] uint8 interleaved RGB banks, idx_a / idx_b[B] int32 as in bh_align_prep_u8 (NULL: sample b
  * is image b; CLAMPED into the bank in the kernel).  Ma[B,9], Mb[B,9] double map index coordinates of the CANVAS (Hc x Wc) to index
@@ -1000,15 +1000,17 @@ int bh_mosaic_u8(const uint8_t* images_a, const int* idx_a, int n_a, int Ha, int
  * sample, plain double arithmetic without contraction.
  * BH_E_BADARG: NULL G, NULL Hpair with n > 1, a negative B, n outside 1..255, ref outside [0, n); then B == 0: BH_OK, nothing launched.
  *
- * bh_pano_frame: the canvas, bh_mosaic_u8's frame rule (mosaic_frame_host) per frame in ONE launch.  It starts from the reference's extent
- * [0, Ws-1] x [0, Hs-1]; frame k takes part where it is usable - det G finite and not 0, the denominators of its four corners through G^-1
+ * bh_pano_frame: the canvas, the ONE frame rule of the mosaic and the panorama (pano_frame_host) for all n frames in one launch.  Hs x Ws is
+ * the size of every frame, whose corners (0, 0), (Ws-1, 0), (Ws-1, Hs-1), (0, Hs-1) are projected; Hr x Wr is the size of the reference -
+ * the frames' own in a sequence, image B's for a pair, where n = 1, G = H and the frame is image A.  It starts from the reference's extent
+ * [0, Wr-1] x [0, Hr-1]; frame k takes part where it is usable - det G finite and not 0, the denominators of its four corners through G^-1
  * (adjugate / determinant) finite, of one sign and above 1e-8 in magnitude, the projected corners finite - and use[b,k] != 0 (use[B,n]
- * uint8, NULL: all): its corners, clamped to [-limit Ws, (1 + limit) Ws - 1] x [-limit Hs, (1 + limit) Hs - 1], are united into the box.
+ * uint8, NULL: all): its corners, clamped to [-limit Wr, (1 + limit) Wr - 1] x [-limit Hr, (1 + limit) Hr - 1], are united into the box.
  * s = max((x1 - x0) / (Wc - 1), (y1 - y0) / (Hc - 1)), 1 where that is 0; T[B,9] = (s 0 tx; 0 s ty; 0 0 1) maps canvas index coordinates to
  * the reference's with the box centred; bbox[B,4] = (x0, y0, x1, y1) (NULL ok); fitted[B,n] uint8 (NULL ok): frame k took part;
  * M[B,n,9] = G[b,k] T (NULL ok), what bh_pano_u8 takes.  One workgroup of 256 threads per sample, thread k is frame k, a min / max reduction;
  * all double, no contraction.
- * BH_E_BADARG: NULL G / T, a negative B, n outside 1..255, Hs or Ws < 1, Hc or Wc < 2, a limit that is not > 0; then B == 0: BH_OK.
+ * BH_E_BADARG: NULL G / T, a negative B, n outside 1..255, Hs, Ws, Hr or Wr < 1, Hc or Wc < 2, a limit that is not > 0; then B == 0: BH_OK.
  *
  * bh_pano_u8: idx[B,n] int32: frame k of sample b is image idx[b n + k], CLAMPED into the bank in the kernel (NULL: frame k is image k, for
  * every sample).  M[B,n,9] double maps index coordinates of the canvas (Hc x Wc) to frame k's.  At canvas pixel (x, y) frame k's (u, v) and
@@ -1032,7 +1034,7 @@ int bh_mosaic_u8(const uint8_t* images_a, const int* idx_a, int n_a, int Ha, int
 #define BH_PANO_FIRST 1
 #define BH_PANO_LAST 2
 int bh_pano_chain(const double* Hpair, const double* gain_pair, int B, int n, int ref, double* G, double* gain, void* stream);
-int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int Ws, int Hc, int Wc, double limit,
+int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int Ws, int Hr, int Wr, int Hc, int Wc, double limit,
                   double* T, double* bbox, uint8_t* fitted, double* M, void* stream);
 int bh_pano_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* M, const double* gain,
                const uint8_t* use, int B, int n, int Hc, int Wc, float feather, int mode, uint8_t* out, uint8_t* count, void* stream);

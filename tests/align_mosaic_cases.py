@@ -69,7 +69,7 @@ def differing_share(got, want):
 # ------------------------------------------------------------------------------------------------
 def sample_f32(image, M, Ho, Wo, feather):
     """What csrc/mosaic.hip mosaic_kernel takes of one image, in float32 numpy: csrc/u8_image.h's u8_sample (align_cases.sample_f32),
-    whose `valid` is the presence, and the border weight mosaic_weight.  -> (value float32 [Ho,Wo,3], weight, present)"""
+    whose `valid` is the presence, and the border weight u8_border_weight.  -> (value float32 [Ho,Wo,3], weight, present)"""
     f = np.float32
     Hs, Ws = image.shape[:2]
     val, u, v, _, present = align_cases.sample_f32(image, M, Ho, Wo)

@@ -70,6 +70,17 @@ def test_mosaic_host_equals_the_pixel_loop(h, w, mode, gain):
     assert d <= 1 and share <= 1e-3, (d, share)
 
 
+def test_mosaic_host_returns_the_recorded_bytes():
+    """tests/golden/align_mosaic_host.npz holds mosaic_host's output on this case as it stood before the blend statement was shared with
+    pano_host (`_blend_host`): the statement is the reference of every device test, so it moves by no byte."""
+    A, B, Ma, Mb, Hc, Wc = Mc.case("48x80-and-40x56-fitted-64x96-vector")
+    want = np.load(os.path.join(ROOT, "tests", "golden", "align_mosaic_host.npz"))
+    for i, (mode, feather, gain) in enumerate(Mc.COMBOS):
+        out, cover = align.mosaic_host(A, B, Ma, Mb, Hc, Wc, feather, mode, Mc.gain_of(gain, len(A)))
+        assert np.array_equal(out, want["out%d" % i]) and np.array_equal(cover, want["cover%d" % i]), (mode, feather, gain)
+        assert out.dtype == np.uint8 and cover.dtype == np.uint8
+
+
 def test_mosaic_host_refuses_what_it_does_not_define():
     A = Mc.pixels(1, 17, 23)
     for kw in (dict(mode="over"), dict(feather=0.5), dict(feather=float("nan")), dict(feather=float("inf"))):
@@ -153,6 +164,23 @@ def test_frame_contains_both_and_fits_the_canvas():
         c = project(T[b], np.array([[0, 0], [Wc - 1, Hc - 1]], np.float64))              # the canvas covers the box, one axis with equality
         assert c[0, 0] <= x0 + 1e-9 and c[0, 1] <= y0 + 1e-9 and c[1, 0] >= x1 - 1e-9 and c[1, 1] >= y1 - 1e-9
         assert min(abs(c[1, 0] - c[0, 0] - (x1 - x0)), abs(c[1, 1] - c[0, 1] - (y1 - y0))) <= 1e-9
+
+
+def test_single_frame_with_a_reference_size_is_the_recorded_mosaic_frame():
+    """The pair's frame is the sequence's frame rule for the single frame A around a reference of B's size: bitwise what
+    mosaic_frame_host returned while it was a statement of its own (tests/golden/align_mosaic_frame_host.npz), on the matrices, sizes and
+    canvases of test_align_mosaic_gpu.py's test_frame_device_equals_the_host_statement."""
+    sizes = ((48, 80), (40, 56))
+    H = np.stack([Mc.corner_homography(11 + b, 48, 80, 40, 56) for b in range(3)]
+                 + [HORIZON, GARBAGE, np.zeros((3, 3)), np.full((3, 3), np.nan), np.array([[1.0, 0, 1e6], [0, 1, -1e6], [0, 0, 1]]), np.eye(3)])
+    want = np.load(os.path.join(ROOT, "tests", "golden", "align_mosaic_frame_host.npz"))
+    for i, (canvas, limit) in enumerate((((64, 96), 2.0), ((37, 53), 0.5), ((2, 2), 2.0))):
+        T, bbox, fitted = align.pano_frame_host(H[:, None], sizes[0], canvas, limit, ref_size=sizes[1])
+        assert fitted.shape == (9, 1) and fitted.dtype == np.uint8 and fitted[:, 0].tolist() == [1, 1, 1, 0, 1, 0, 0, 1, 1]
+        for got, name in ((T, "T"), (bbox, "bbox"), (fitted[:, 0], "fitted")):
+            assert got.dtype == want["%s%d" % (name, i)].dtype and got.tobytes() == want["%s%d" % (name, i)].tobytes(), (name, canvas)
+        for got, mine in zip(align.mosaic_frame_host(H, *sizes, canvas, limit), (T, bbox, fitted[:, 0])):
+            assert got.tobytes() == mine.tobytes()
 
 
 def test_frame_of_a_horizon_and_of_garbage():

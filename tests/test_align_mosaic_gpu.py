@@ -177,8 +177,9 @@ def test_wild_indices_are_clamped():
 # ------------------------------------------------------------------------------------------------
 # the frame and the exposure, device twins
 # ------------------------------------------------------------------------------------------------
-def test_frame_device_equals_the_host_statement():
+def test_frame_device_equals_the_host_statement(monkeypatch):
     from test_align_mosaic_cpu import GARBAGE, HORIZON
+    p = poisoned_alloc.poison(monkeypatch, align)
     sizes = ((48, 80), (40, 56))
     H = np.stack([Mc.corner_homography(11 + b, 48, 80, 40, 56) for b in range(3)]
                  + [HORIZON, GARBAGE, np.zeros((3, 3)), np.full((3, 3), np.nan), np.array([[1.0, 0, 1e6], [0, 1, -1e6], [0, 0, 1]]), np.eye(3)])
@@ -190,6 +191,7 @@ def test_frame_device_equals_the_host_statement():
         assert host(fitted).tolist() == wfitted.tolist() == [1, 1, 1, 0, 1, 0, 0, 1, 1]
         for got, want in ((host(T), wT), (host(bbox), wbbox)):
             assert np.isfinite(got).all() and np.all(np.abs(got - want) <= 1e-12 * np.abs(want).max(axis=tuple(range(1, want.ndim)), keepdims=True))
+    assert p.verify() == 9                                                 # T, bbox and fitted of each of the three launches
     with pytest.raises(ValueError):
         align.mosaic_frame_device(cuda(H), *sizes, (1, 96))
 

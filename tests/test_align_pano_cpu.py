@@ -84,6 +84,17 @@ def test_two_frames_are_the_mosaic_bit_for_bit(name):
         assert np.array_equal(count, (cover & 1) + (cover >> 1))
 
 
+def test_pano_host_returns_the_recorded_bytes():
+    """tests/golden/align_pano_host.npz holds pano_host's output on this case as it stood before the blend statement was shared with
+    mosaic_host (`_blend_host`): the statement is the reference of every device test, so it moves by no byte."""
+    bank, idx, _, M, Hc, Wc = Pc.case("n5-40x56-on-48x160")
+    want = np.load(os.path.join(ROOT, "tests", "golden", "align_pano_host.npz"))
+    for i, (mode, feather, gain) in enumerate(Pc.COMBOS):
+        out, count = align.pano_host(bank, idx, M, Hc, Wc, feather, mode, Pc.gain_of(*idx.shape[::-1]) if gain else None)
+        assert np.array_equal(out, want["out%d" % i]) and np.array_equal(count, want["count%d" % i]), (mode, feather, gain)
+        assert out.dtype == np.uint8 and count.dtype == np.uint8
+
+
 def test_pano_host_refuses_what_it_does_not_define():
     bank, idx, _, M, Hc, Wc = Pc.case("n3-17x23-on-24x53")
     for kw in (dict(mode="b_over_a"), dict(mode="median"), dict(feather=0.5), dict(feather=float("nan")), dict(feather=float("inf"))):
@@ -249,8 +260,8 @@ def test_float32_restatement_stays_within_the_measured_shares(name):
 # ------------------------------------------------------------------------------------------------
 ARGS = {
     "bh_pano_chain": ["const double* Hpair", "const double* gain_pair", "int B", "int n", "int ref", "double* G", "double* gain", "void* stream"],
-    "bh_pano_frame": ["const double* G", "const uint8_t* use", "int B", "int n", "int Hs", "int Ws", "int Hc", "int Wc", "double limit", "double* T",
-                      "double* bbox", "uint8_t* fitted", "double* M", "void* stream"],
+    "bh_pano_frame": ["const double* G", "const uint8_t* use", "int B", "int n", "int Hs", "int Ws", "int Hr", "int Wr", "int Hc", "int Wc", "double limit",
+                      "double* T", "double* bbox", "uint8_t* fitted", "double* M", "void* stream"],
     "bh_pano_u8": ["const uint8_t* images", "const int* idx", "int n_images", "int Hs", "int Ws", "const double* M", "const double* gain",
                    "const uint8_t* use", "int B", "int n", "int Hc", "int Wc", "float feather", "int mode", "uint8_t* out", "uint8_t* count", "void* stream"],
 }
@@ -262,7 +273,7 @@ def test_header_declares_what_ctypes_binds():
     raw = open(os.path.join(ROOT, "include", "bihome.h")).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
     P, I, F, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
-    sigs = {"bh_pano_chain": [P, P, I, I, I, P, P, P], "bh_pano_frame": [P, P, I, I, I, I, I, I, D, P, P, P, P, P],
+    sigs = {"bh_pano_chain": [P, P, I, I, I, P, P, P], "bh_pano_frame": [P, P, I, I, I, I, I, I, I, I, D, P, P, P, P, P],
             "bh_pano_u8": [P, P, I, I, I, P, P, P, I, I, I, I, F, I, P, P, P]}
     for name, args in ARGS.items():
         m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
@@ -282,8 +293,8 @@ def test_entry_point_argument_rules():
     def chain(Hpair=p, gain_pair=p, B=2, n=4, ref=1, G=p, gain=p):
         return _lib.lib.bh_pano_chain(Hpair, gain_pair, B, n, ref, G, gain, None)
 
-    def frame(G=p, use=p, B=2, n=4, Hs=24, Ws=32, Hc=30, Wc=40, limit=2.0, T=p, bbox=p, fitted=p, M=p):
-        return _lib.lib.bh_pano_frame(G, use, B, n, Hs, Ws, Hc, Wc, limit, T, bbox, fitted, M, None)
+    def frame(G=p, use=p, B=2, n=4, Hs=24, Ws=32, Hr=24, Wr=32, Hc=30, Wc=40, limit=2.0, T=p, bbox=p, fitted=p, M=p):
+        return _lib.lib.bh_pano_frame(G, use, B, n, Hs, Ws, Hr, Wr, Hc, Wc, limit, T, bbox, fitted, M, None)
 
     def pano(images=p, idx=p, n_images=5, Hs=24, Ws=32, M=p, gain=p, use=p, B=2, n=4, Hc=30, Wc=40, feather=32.0, mode=0, out=p, count=p):
         return _lib.lib.bh_pano_u8(images, idx, n_images, Hs, Ws, M, gain, use, B, n, Hc, Wc, feather, mode, out, count, None)
@@ -291,10 +302,10 @@ def test_entry_point_argument_rules():
         assert chain(**bad) == BH_E_BADARG, bad
     for ok in (dict(B=0), dict(B=0, n=1, ref=0, Hpair=None, gain_pair=None, gain=None), dict(B=0, n=255, ref=254)):
         assert chain(**ok) == BH_OK, ok
-    for bad in (dict(G=None), dict(T=None), dict(B=-1), dict(n=0), dict(n=256), dict(Hs=0), dict(Ws=0), dict(Hc=1), dict(Wc=1), dict(Wc=-5),
-                dict(limit=0.0), dict(limit=-1.0), dict(limit=float("nan")), dict(B=0, T=None), dict(B=0, n=0)):
+    for bad in (dict(G=None), dict(T=None), dict(B=-1), dict(n=0), dict(n=256), dict(Hs=0), dict(Ws=0), dict(Hr=0), dict(Wr=0), dict(Wr=-1), dict(Hc=1),
+                dict(Wc=1), dict(Wc=-5), dict(limit=0.0), dict(limit=-1.0), dict(limit=float("nan")), dict(B=0, T=None), dict(B=0, n=0)):
         assert frame(**bad) == BH_E_BADARG, bad
-    for ok in (dict(B=0), dict(B=0, use=None, bbox=None, fitted=None, M=None, n=255, Hs=1, Ws=1, Hc=2, Wc=2)):
+    for ok in (dict(B=0), dict(B=0, use=None, bbox=None, fitted=None, M=None, n=255, Hs=1, Ws=1, Hr=1, Wr=1, Hc=2, Wc=2)):
         assert frame(**ok) == BH_OK, ok
     for bad in (dict(images=None), dict(M=None), dict(out=None), dict(B=-1), dict(n=0), dict(n=256), dict(n=-1), dict(n_images=0), dict(Hs=0), dict(Ws=-1),
                 dict(Hc=0), dict(Wc=0), dict(Hc=-3), dict(feather=float("nan")), dict(feather=float("inf")), dict(feather=0.999), dict(feather=0.0),

@@ -232,6 +232,15 @@ def test_frame_device_equals_the_host_statement(monkeypatch):
         ok = np.isfinite(G).all((2, 3))                                    # (M of a frame that is not finite is not)
         close(host(M)[ok], (G @ wT[:, None])[ok], "M")
     assert p.verify() == 12
+    ref_size = (48, 80)                                                    # a reference of another size than the frames: one launch of seven workgroups
+    T, bbox, fitted, M = align.pano_frame_device(cuda(G), size, (48, 160), 2.0, use=cuda(use), ref_size=ref_size)
+    wT, wbbox, wfitted = align.pano_frame_host(G, size, (48, 160), 2.0, use=use, ref_size=ref_size)
+    assert host(fitted).tolist() == wfitted.tolist() and wfitted[2:, 1].tolist() == [0, 1, 0, 0, 1]
+    assert np.all(wbbox[:, 2] >= 79) and np.all(wbbox[:, 3] >= 47) and wbbox[3].tolist()[2:] == [3 * 80 - 1, 3 * 48 - 1]      # the reference's extent and clamp
+    close(host(T), wT, "T")
+    close(host(bbox), wbbox, "bbox")
+    close(host(M)[ok], (G @ wT[:, None])[ok], "M")
+    assert p.verify() == 4
     for n in (1, 255):                                                     # the fewest and the most frames a workgroup takes
         Gn = np.stack([np.eye(3) if k == n // 2 else Mc.corner_homography(k, 40, 56, 40, 56, 0.3) for k in range(n)])[None]
         T, bbox, fitted, M = align.pano_frame_device(cuda(Gn), size, (48, 160))

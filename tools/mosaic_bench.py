@@ -109,10 +109,7 @@ def main():
     del wa_img, wb_img, va, vb, src, dst
 
     # the exposure measurement alone
-    def exposure():
-        pa, pb = align.gray_pyramid(images_a, B, 1), align.gray_pyramid(images_b, B, 1)
-        return align.exposure_device(align.ecc_sums(align.pyramid_level(pa, h, w, 1, 0), align.pyramid_level(pb, h, w, 1, 0), H))
-    r = device_rounds({"exposure": exposure}, a.reps, a.rounds, a.warmup)
+    r = device_rounds({"exposure": lambda: align.measure_exposure(images_a, images_b, H)}, a.reps, a.rounds, a.warmup)
     out("exposure: two gray pyramids of one level, bh_ecc_sums, exposure_device", exposure=r["exposure"], **shape)
 
     if a.skip_model:

@@ -11,7 +11,8 @@ One JSON line per row:
               bits; (b) the route without the kernel: n bh_warp_u8 calls onto the canvas with their validity masks, then the weights,
               products, sums, division and rounding as torch tensor operations; (c) a Tensor.copy_ of the bytes read and written.  The
               share of canvas pixels with 0, 1, 2, 3+ frames is printed with it.
-    frame     bh_pano_frame (one launch) against n - 1 `mosaic_frame_device` calls
+    frame     bh_pano_frame, one launch for the n frames, against n - 1 launches of it for a single frame each (`mosaic_frame_device`, the
+              pair's frame, which is the same kernel with n = 1)
     n2        bh_pano_u8 with n = 2 against bh_mosaic_u8 on tools/mosaic_bench.py's workload (64 pairs on a fitted 640 x 960 canvas), and
               whether the two outputs are the same bits
     sequence  Aligner.sequence end to end without and with canvas=(Hc, Wc), zeng-bihome at random initialisation
@@ -87,13 +88,13 @@ def main():
     idx = torch.arange(B * n, dtype=torch.int32, device="cuda").reshape(B, n)
     G = torch.from_numpy(pan(rng, B, n, h, w, a.step)).cuda()
 
-    # the frame: one launch against n - 1 pair frames
+    # the frame: one launch for n frames against n - 1 single-frame launches
     T, bbox, fitted, M = align.pano_frame_device(G, (h, w), (Hc, Wc))
-    frame = raw_call("bh_pano_frame", G, None, B, n, h, w, Hc, Wc, 2.0, T, bbox, fitted, M)
+    frame = raw_call("bh_pano_frame", G, None, B, n, h, w, h, w, Hc, Wc, 2.0, T, bbox, fitted, M)
     others = [G[:, k].contiguous() for k in range(n) if k != n // 2]
-    r = device_rounds({"pano_frame": frame, "pair_frames": lambda: [align.mosaic_frame_device(H, (h, w), (h, w), (Hc, Wc)) for H in others]},
+    r = device_rounds({"pano_frame": frame, "single_frames": lambda: [align.mosaic_frame_device(H, (h, w), (h, w), (Hc, Wc)) for H in others]},
                       a.reps, a.rounds, a.warmup)
-    out("bh_pano_frame against n - 1 mosaic_frame_device calls", pano_frame=r["pano_frame"], pair_frames=r["pair_frames"],
+    out("bh_pano_frame for n frames against n - 1 single-frame launches (mosaic_frame_device)", pano_frame=r["pano_frame"], single_frames=r["single_frames"],
         fitted=int(fitted.sum().item()), **shape)
 
     # the blend
