@@ -147,6 +147,9 @@ SIGNATURES = {
     "bh_pano_chain": [P, P, c_int, c_int, c_int, P, P, P],
     "bh_pano_frame": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, P, P, P, P, P],
     "bh_pano_u8": [P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P],
+    "bh_blur_u8": [P, P, c_int, c_int, c_int, c_int, P, c_int, P, P],
+    "bh_pano_bands_u8": [P, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P],
+    "bh_mosaic_bands_u8": [P, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_gap_fwd": [P, P, c_int, c_int, c_int, P],

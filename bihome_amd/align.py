@@ -62,7 +62,16 @@ G[b], divided by its [2,2] entry; the exposure lines compose alongside - `pano_f
 united with the clamped corners of every usable frame; `_corner_box` / `_fit_canvas`), and `pano_host` the blend over the frames present
 (`_blend_host`, the one statement `mosaic_host` is made of too): 'feather' sum w v / sum w in frame order, 'first' / 'last' the lowest /
 highest frame present, count = the number present.  For n = 2 both equal the pair's results bit for bit.  bh_pano_u8 makes the canvas
-in one pass, and a wavefront none of whose pixels has a frame present takes no tap of it."""
+in one pass, and a wavefront none of whose pixels has a frame present takes no tap of it.
+
+Two-band blend (mode "two_band" of `mosaic`, `panorama`, the aligner's mosaic and `Aligner.sequence`; csrc/blur.hip, csrc/bands.hip):
+wherever two frames disagree by a pixel or two a feather doubles edges over the whole overlap, and a narrow feather shows the exposure
+step instead.  So every frame is split into a LOW band - `blur_host`, a Gaussian of `band_sigma` frame pixels in integer arithmetic
+with the taps of `blur_taps`, bit for bit what bh_blur_u8 makes - and a HIGH band, frame minus low (Burt & Adelson; two bands as in Brown
+& Lowe).  The low bands are blended with the feather; the high band comes from ONE frame per pixel, the one with the largest weight
+(ties: the lowest k): value = v_winner + (sum w l / sum w - l_winner), the frame's own value where one frame is present, `winner` the
+frame chosen.  Stated below as blur_taps / blur_host / bands_host / mosaic_bands_host; bh_pano_bands_u8 and bh_mosaic_bands_u8 gather the
+frame and its low band at the same taps, eight loads per present frame."""
 import operator
 
 import numpy as np
@@ -383,6 +392,138 @@ def pano_host(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, u
             yield v, present & use[:, k, None, None], M[:, k], images.shape[1:3], gain[:, k]
     val, planes = _blend_host(frames(), feather, mode)
     return _round_u8(val), np.sum(planes, axis=0, dtype=np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------
+# two-band blend, the definitions (numpy; include/bihome.h "Two-band blend" states the same in C terms)
+# ------------------------------------------------------------------------------------------------
+BAND_MODES = ("two_band",)         # the mode of `mosaic` / `panorama` that has no BH_MOSAIC_* / BH_PANO_* number: entry points of its own
+BAND_SIGMA_MIN, BAND_SIGMA_MAX = 0.5, 10.5
+BAND_NONE = 255                    # winner where nothing is present
+
+
+def blur_taps(sigma):
+    """The integer taps of the low band: int64 [r + 1] = (w_0 .. w_r), r = ceil(3 sigma) (0.5 <= sigma <= 10.5, so 1 <= r <= 32).
+    g_i = exp(-i^2 / (2 sigma^2)) normalised over i = -r .. r, w_i = floor(2048 g_i + 0.5) for i >= 1 and w_0 = 2048 - 2 sum_{i>=1} w_i: the
+    taps sum to 2048 exactly, whatever the rounding did.  Pure numpy float64."""
+    sigma = float(sigma)
+    if not BAND_SIGMA_MIN <= sigma <= BAND_SIGMA_MAX:                          # (False for a NaN too)
+        raise ValueError("blur_taps: %g <= sigma <= %g, got %r" % (BAND_SIGMA_MIN, BAND_SIGMA_MAX, sigma))
+    r = int(np.ceil(3.0 * sigma))
+    i = np.arange(r + 1, dtype=np.float64)
+    g = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    g = g / (g[0] + 2.0 * g[1:].sum())
+    w = np.floor(2048.0 * g + 0.5).astype(np.int64)
+    w[0] = 2048 - 2 * int(w[1:].sum())
+    return w
+
+
+def blur_host(images, sigma, order="rows"):
+    """images uint8 [...,H,W,3] -> the low band, uint8 of the same shape:
+    L[y,x,c] = (sum_j sum_i w|j| w|i| I[clamp(y + j), clamp(x + i), c] + 2^21) >> 22 with `blur_taps(sigma)`, the border replicated.
+    Integer arithmetic (the sum stays below 2^31), so order = 'rows' (rows first) and 'cols' give the same bits, and bh_blur_u8 too."""
+    images = np.asarray(images)
+    if images.dtype != np.uint8 or images.ndim < 3 or images.shape[-1] != 3:
+        raise ValueError("blur_host: images uint8 [...,H,W,3], got %s %s" % (images.dtype, images.shape))
+    if order not in ("rows", "cols"):
+        raise ValueError("blur_host: order is 'rows' or 'cols', got %r" % (order,))
+    w = blur_taps(sigma)
+    r = len(w) - 1
+
+    def along(v, axis):
+        n = v.shape[axis]
+        at = np.clip(np.arange(-r, n + r), 0, n - 1)
+        acc = np.zeros(v.shape, np.int64)
+        for d in range(-r, r + 1):
+            acc += int(w[abs(d)]) * np.take(v, at[r + d:r + d + n], axis=axis)
+        return acc
+    v = images.astype(np.int64)
+    H_axis, W_axis = images.ndim - 3, images.ndim - 2
+    v = along(along(v, W_axis), H_axis) if order == "rows" else along(along(v, H_axis), W_axis)
+    return ((v + (1 << 21)) >> 22).astype(np.uint8)
+
+
+def _bands_blend_host(frames, feather):
+    """The two-band statement of the mosaic and the panorama.  frames yields, in order, (v, l float64 [B,Hc,Wc,3]: `_sample_host` of the
+    frame and of its low band, present bool [B,Hc,Wc], M [B,3,3], (Hs, Ws), gain [B,2] or None) per frame -> (the values before rounding
+    [B,Hc,Wc,3], the list of the `present` planes, winner uint8 [B,Hc,Wc]).  Both bands take the gain, the weight is `_blend_host`'s;
+    num += w l and den += w over the frames present, and the frame becomes the winner if it is the first present or its weight is
+    strictly larger than the winner's (ties: the lowest k).  Nothing present: 0; one frame present: its value; else
+    v_winner + (num / den - l_winner)."""
+    num = den = 0.0
+    v_best = l_best = w_best = cnt = winner = None
+    planes = []
+    for k, (v, l, present, M, (Hs, Ws), gain) in enumerate(frames):
+        B, Hc, Wc = present.shape
+        if cnt is None:
+            v_best, l_best = np.zeros((B, Hc, Wc, 3)), np.zeros((B, Hc, Wc, 3))
+            w_best, cnt, winner = np.zeros((B, Hc, Wc)), np.zeros((B, Hc, Wc), np.int64), np.full((B, Hc, Wc), BAND_NONE, np.uint8)
+        P = present[..., None]
+        if gain is not None:
+            g, o = gain[:, 0, None, None, None], gain[:, 1, None, None, None]
+            v, l = g * v + o, g * l + o
+        w = np.empty((B, Hc, Wc))
+        for b in range(B):
+            with np.errstate(all="ignore"):
+                pu, pv, _ = _project_host(M[b], Hc, Wc)
+                w[b] = np.minimum(np.minimum(np.minimum(pu, Ws - 1 - pu), np.minimum(pv, Hs - 1 - pv)) + 1.0, feather)
+        w = np.where(present, w, 0.0)
+        num = num + np.where(P, w[..., None] * np.where(P, l, 0.0), 0.0)
+        den = den + w
+        take = present & ((cnt == 0) | (w > w_best))
+        v_best, l_best = np.where(take[..., None], v, v_best), np.where(take[..., None], l, l_best)
+        w_best, winner = np.where(take, w, w_best), np.where(take, np.uint8(k), winner).astype(np.uint8)
+        cnt = cnt + present
+        planes.append(present)
+    mixed = v_best + (num / np.where(den > 0, den, 1.0)[..., None] - l_best)
+    val = np.where((cnt == 0)[..., None], 0.0, np.where((cnt == 1)[..., None], v_best, mixed))
+    return val, planes, winner
+
+
+def bands_host(images, low, idx, M, Hc, Wc, feather=32.0, gain=None, use=None):
+    """`pano_host`'s arguments without a mode, plus low uint8 [B,n,Hs,Ws,3] (or [B n,Hs,Ws,3]): the low band of frame k of sample b
+    (`blur_host(images[idx])`) -> (out uint8 [B,Hc,Wc,3], count uint8 [B,Hc,Wc], winner uint8 [B,Hc,Wc]: the frame whose high band the
+    pixel takes, 255 for none): the two-band blend, `_bands_blend_host` on the n frames in the order k = 0..n-1, presence as in
+    `pano_host`, then round half up."""
+    _blend_args(feather, "feather", PANO_MODES, "bands_host")
+    images, idx = np.asarray(images), np.asarray(idx)
+    M = np.asarray(M, np.float64)
+    if idx.ndim != 2 or not 1 <= idx.shape[1] <= PANO_MAX_FRAMES or M.shape != idx.shape + (3, 3):
+        raise ValueError("bands_host: idx [B,n] with 1 <= n <= %d and M [B,n,3,3], got %s and %s" % (PANO_MAX_FRAMES, idx.shape, M.shape))
+    B, n = idx.shape
+    low = np.asarray(low)
+    if low.dtype != np.uint8 or low.size != B * n * images[0].size or low.shape[-3:] != images.shape[1:]:
+        raise ValueError("bands_host: low uint8 [B,n,Hs,Ws,3] with B = %d, n = %d, got %s %s" % (B, n, low.dtype, low.shape))
+    low = low.reshape((B, n) + images.shape[1:])
+    gain = np.tile(np.array([1.0, 0.0]), (B, n, 1)) if gain is None else np.asarray(gain, np.float64).reshape(B, n, 2)
+    use = np.ones((B, n), bool) if use is None else np.asarray(use).reshape(B, n) != 0
+
+    def frames():
+        for k in range(n):
+            v, present, _ = _sample_host(images[idx[:, k]], M[:, k], Hc, Wc)
+            l, _, _ = _sample_host(low[:, k], M[:, k], Hc, Wc)
+            yield v, l, present & use[:, k, None, None], M[:, k], images.shape[1:3], gain[:, k]
+    val, planes, winner = _bands_blend_host(frames(), feather)
+    return _round_u8(val), np.sum(planes, axis=0, dtype=np.uint8), winner
+
+
+def mosaic_bands_host(images_a, low_a, images_b, low_b, Ma, Mb, Hc, Wc, feather=32.0, gain=None):
+    """`mosaic_host`'s arguments without a mode, plus the low bands low_a uint8 [B,Ha,Wa,3] and low_b uint8 [B,Hb,Wb,3] -> (out uint8
+    [B,Hc,Wc,3], cover uint8 [B,Hc,Wc] as `mosaic_host`'s, winner uint8 [B,Hc,Wc]: 0 for A, 1 for B, 255 for none):
+    `_bands_blend_host` on the frames (A, B); the gain applies to A."""
+    _blend_args(feather, "feather", MOSAIC_MODES, "mosaic_bands_host")
+    Ma, Mb = np.asarray(Ma, np.float64).reshape(-1, 3, 3), np.asarray(Mb, np.float64).reshape(-1, 3, 3)
+    B = Ma.shape[0]
+    gain = np.tile(np.array([[1.0, 0.0]]), (B, 1)) if gain is None else np.asarray(gain, np.float64).reshape(B, 2)
+    frames = []
+    for images, low, M, g in ((images_a, low_a, Ma, gain), (images_b, low_b, Mb, None)):
+        if np.asarray(low).shape != np.asarray(images).shape or np.asarray(low).dtype != np.uint8:
+            raise ValueError("mosaic_bands_host: a low band is uint8 of its images' shape %s, got %s" % (np.asarray(images).shape, np.asarray(low).shape))
+        v, present, _ = _sample_host(images, M, Hc, Wc)
+        l, _, _ = _sample_host(low, M, Hc, Wc)
+        frames.append((v, l, present, M, np.asarray(images).shape[1:3], g))
+    val, (pa, pb), winner = _bands_blend_host(frames, feather)
+    return _round_u8(val), (pa.astype(np.uint8) | (pb.astype(np.uint8) << 1)).astype(np.uint8), winner
 
 
 def exposure_host(sums):
@@ -989,8 +1130,8 @@ def _canvas_args(noun, canvas, feather, mode, limit, who):
         feather_ok = False
     if not feather_ok:
         raise ValueError("%s: the %s feather is finite and at least 1 (pixels), got %r" % (who, noun, feather))
-    if not (isinstance(mode, str) and mode in modes):
-        raise ValueError("%s: the %s mode is one of %s, got %r" % (who, noun, ", ".join(modes), mode))
+    if not (isinstance(mode, str) and mode in modes + BAND_MODES):
+        raise ValueError("%s: the %s mode is one of %s, got %r" % (who, noun, ", ".join(modes + BAND_MODES), mode))
     try:
         limit_ok = bool(float(limit) > 0)
     except (TypeError, ValueError):
@@ -1026,8 +1167,9 @@ def _identity_canvas(B, H, W, fitted_shape, device):
     return T, bbox, torch.zeros(fitted_shape, dtype=torch.uint8, device=device)
 
 
-def _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b):
-    """The mosaic stage on checked arguments (a, b: uint8 banks on the device, ia / ib: int32 device tensors or None) -> its six keys."""
+def _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b, band_sigma=None):
+    """The mosaic stage on checked arguments (a, b: uint8 banks on the device, ia / ib: int32 device tensors or None) -> its six keys (in
+    the two-band mode, whose low bands of sigma band_sigma are made here with one launch per image: seven, with 'mosaic_winner')."""
     B, dev, (Ha, Wa), (Hb, Wb) = H.shape[0], H.device, a.shape[1:3], b.shape[1:3]
     H = H.reshape(B, 3, 3).contiguous()
     if size is None:
@@ -1043,14 +1185,20 @@ def _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b):
         gain = measure_exposure(a, b, H, ia, ib, mask_b).contiguous()
     else:
         gain = None
-    out, cover = mosaic_u8(a, b, Ma, T, Hc, Wc, feather, mode, gain=gain, idx_a=ia, idx_b=ib)
+    extra = {}
+    if mode in BAND_MODES:
+        out, cover, extra["mosaic_winner"] = mosaic_bands_u8(a, blur_u8(a, band_sigma, ia), b, blur_u8(b, band_sigma, ib), Ma, T, Hc, Wc, feather,
+                                                             gain=gain, idx_a=ia, idx_b=ib)
+    else:
+        out, cover = mosaic_u8(a, b, Ma, T, Hc, Wc, feather, mode, gain=gain, idx_a=ia, idx_b=ib)
     if gain is None:
         gain = torch.zeros((B, 2), dtype=torch.float64, device=dev)
         gain[:, 0] = 1.0
-    return {"mosaic": out, "mosaic_cover": cover, "mosaic_T": T, "mosaic_bbox": bbox, "mosaic_fitted": fitted, "mosaic_gain": gain}
+    return {"mosaic": out, "mosaic_cover": cover, "mosaic_T": T, "mosaic_bbox": bbox, "mosaic_fitted": fitted, "mosaic_gain": gain, **extra}
 
 
-def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", exposure=None, limit=2.0, idx_a=None, idx_b=None, mask_b=None):
+def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", exposure=None, limit=2.0, idx_a=None, idx_b=None, mask_b=None,
+           band_sigma=4.0):
     """Both images on one canvas, for a caller who has H [B,3,3] float64 (B's index coordinates -> A's) from anywhere: images_* uint8
     [N,H*,W*,3] device tensors or ImageBanks, idx_* as in `Aligner`.  canvas="b": the canvas is B's grid (T the identity);
     canvas=(Hc, Wc): the frame `mosaic_frame_device` fits around B and A's projected corners, `limit` image sizes around B at most.
@@ -1059,7 +1207,10 @@ def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", expo
     count), `exposure_device`) or a [B,2] float64 device tensor (g, o).  -> dict: 'mosaic' [B,Hc,Wc,3] uint8, 'mosaic_cover'
     [B,Hc,Wc] uint8 (0 empty, 1 only A, 2 only B, 3 both), 'mosaic_T' [B,3,3] float64 (canvas -> B), 'mosaic_bbox' [B,4] float64
     (xmin, ymin, xmax, ymax in B's coordinates), 'mosaic_fitted' [B] uint8 (A's corners took part in the frame), 'mosaic_gain' [B,2]
-    float64.  ValueError before any launch for arguments outside these; nothing is copied to the host."""
+    float64.  mode="two_band" (`mosaic_bands_host`; band_sigma in [0.5, 10.5], a default and not a tuned value, in each image's own
+    pixels; the other modes do not look at it): each image is split by `blur_u8` into a low band, blended with the feather, and a high
+    band, taken per pixel from the image with the larger weight - and 'mosaic_winner' [B,Hc,Wc] uint8 (0: A, 1: B, 255: neither) is
+    added; the exposure applies to both bands.  ValueError before any launch for arguments outside these; nothing is copied to the host."""
     a, b = _images(images_a, "images_a"), _images(images_b, "images_b")
     _need_device(H, name=False)
     if a.device != b.device or H.device != a.device:
@@ -1067,6 +1218,7 @@ def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", expo
     _need_h(H, "mosaic")
     B = H.shape[0]
     size = _canvas_args("mosaic", canvas, feather, mode, limit, "mosaic")
+    _band_args(mode, band_sigma, "mosaic", "mosaic")
     _mosaic_exposure_args(exposure, B, a.shape[1:3], b.shape[1:3], "mosaic", "exposure")
     ia, na = _index(idx_a, a.shape[0], a.device, "idx_a")
     ib, nb = _index(idx_b, b.shape[0], b.device, "idx_b")
@@ -1077,7 +1229,7 @@ def mosaic(images_a, images_b, H, canvas="b", feather=32.0, mode="feather", expo
         raise ValueError("mosaic: mask_b restricts the pixels the exposure measurement counts; pass exposure='gain' with it")
     mask_b = _check_mask(mask_b, B, b.shape[1], b.shape[2], b.device)
     with torch.cuda.device(a.device):
-        return _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b)
+        return _mosaic(a, b, H, size, feather, mode, exposure, limit, ia, ib, mask_b, band_sigma)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1120,6 +1272,54 @@ def pano_u8(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, use
     return K.pano_u8(images, idx, M, out, count, feather, mode, gain=gain, use=use)
 
 
+# ------------------------------------------------------------------------------------------------
+# two-band blend, the device path
+# ------------------------------------------------------------------------------------------------
+def blur_u8(images, sigma, idx=None):
+    """bh_blur_u8 on an output allocated here (`blur_host`): images a uint8 [N,H,W,3] device tensor, idx an int32 device tensor of any
+    shape S (clamped by the kernel) or None (S = [N]) -> the low bands, uint8 [*S,H,W,3]: one launch."""
+    _need_device(images)
+    shape = (images.shape[0],) if idx is None else tuple(idx.shape)
+    out = torch.empty((int(np.prod(shape)),) + tuple(images.shape[1:]), dtype=torch.uint8, device=images.device)
+    return K.blur_u8(images, out, blur_taps(sigma).tolist(), idx=idx).view(shape + tuple(images.shape[1:]))
+
+
+def pano_bands_u8(images, low, idx, M, Hc, Wc, feather=32.0, gain=None, use=None, want_count=True, want_winner=True):
+    """bh_pano_bands_u8 on outputs allocated here: (out [B,Hc,Wc,3], count [B,Hc,Wc] or None, winner [B,Hc,Wc] or None), uint8
+    (kernels.pano_bands_u8; `bands_host`)."""
+    _need_device(images, low)
+    B = M.shape[0]
+    out = torch.empty((B, Hc, Wc, 3), dtype=torch.uint8, device=images.device)
+    count = torch.empty((B, Hc, Wc), dtype=torch.uint8, device=images.device) if want_count else None
+    winner = torch.empty((B, Hc, Wc), dtype=torch.uint8, device=images.device) if want_winner else None
+    return K.pano_bands_u8(images, low, idx, M, out, count, winner, feather, gain=gain, use=use)
+
+
+def mosaic_bands_u8(images_a, low_a, images_b, low_b, Ma, Mb, Hc, Wc, feather=32.0, gain=None, idx_a=None, idx_b=None, want_cover=True,
+                    want_winner=True):
+    """bh_mosaic_bands_u8 on outputs allocated here: (out [B,Hc,Wc,3], cover [B,Hc,Wc] or None, winner [B,Hc,Wc] or None), uint8
+    (kernels.mosaic_bands_u8; `mosaic_bands_host`)."""
+    _need_device(images_a, low_a, images_b, low_b)
+    B = Ma.shape[0]
+    out = torch.empty((B, Hc, Wc, 3), dtype=torch.uint8, device=images_a.device)
+    cover = torch.empty((B, Hc, Wc), dtype=torch.uint8, device=images_a.device) if want_cover else None
+    winner = torch.empty((B, Hc, Wc), dtype=torch.uint8, device=images_a.device) if want_winner else None
+    return K.mosaic_bands_u8(images_a, low_a, images_b, low_b, Ma, Mb, out, cover, winner, feather, gain=gain, idx_a=idx_a, idx_b=idx_b)
+
+
+def _band_args(mode, band_sigma, noun, who, name="band_sigma"):
+    """The rule of the low band's sigma in the two-band mode, checked before any launch (the other modes do not look at it)."""
+    if not (isinstance(mode, str) and mode in BAND_MODES):
+        return
+    try:
+        ok = not isinstance(band_sigma, (str, bytes)) and bool(BAND_SIGMA_MIN <= float(band_sigma) <= BAND_SIGMA_MAX)      # (False for a NaN too)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("%s: the %s %s (the low band's Gaussian, in the frame's own pixels) is in [%g, %g], got %r"
+                         % (who, noun, name, BAND_SIGMA_MIN, BAND_SIGMA_MAX, band_sigma))
+
+
 def _frames_index(idx, n_images, device, who):
     """idx -> int32 [B,n] device tensor.  None: one sample of all the bank's images in order; host values are range-checked here, a
     device tensor is the kernel's to clamp."""
@@ -1150,8 +1350,22 @@ def _pano_tensor(t, shape, dtype, what, who):
     return t.contiguous()
 
 
-def _panorama(images, idx, G, size, feather, mode, gain, use, limit):
-    """The panorama stage on checked arguments -> its seven keys."""
+def _low_arg(low, mode, shape, device, who):
+    """The rules of a precomputed low bank, checked before any launch: it belongs to the two-band mode and is a uint8 device tensor of
+    `shape` on the images' device."""
+    if low is None:
+        return None
+    if not (isinstance(mode, str) and mode in BAND_MODES):
+        raise ValueError("%s: low is the two-band mode's low bank; pass mode='two_band' with it (got mode %r)" % (who, mode))
+    if not isinstance(low, torch.Tensor) or not low.is_cuda or low.device != device or low.dtype != torch.uint8 or tuple(low.shape) != shape:
+        got = "%s %s on %s" % (low.dtype, tuple(low.shape), low.device) if isinstance(low, torch.Tensor) else repr(low)
+        raise ValueError("%s: low is a uint8 %s tensor on %s (`blur_u8(images, band_sigma, idx)`), got %s" % (who, list(shape), device, got))
+    return low.contiguous()
+
+
+def _panorama(images, idx, G, size, feather, mode, gain, use, limit, band_sigma=None, low=None):
+    """The panorama stage on checked arguments -> its seven keys (in the two-band mode, whose low bank is `low` or made here with one
+    launch: eight, with 'panorama_winner')."""
     B, n = G.shape[:2]
     dev, (Hs, Ws) = G.device, images.shape[1:3]
     if size is None:
@@ -1160,15 +1374,20 @@ def _panorama(images, idx, G, size, feather, mode, gain, use, limit):
     else:
         Hc, Wc = size
         T, bbox, fitted, M = pano_frame_device(G, (Hs, Ws), (Hc, Wc), limit, use=use)
-    out, count = pano_u8(images, idx, M, Hc, Wc, feather, mode, gain=gain, use=use)
+    extra = {}
+    if mode in BAND_MODES:
+        low = blur_u8(images, band_sigma, idx) if low is None else low
+        out, count, extra["panorama_winner"] = pano_bands_u8(images, low, idx, M, Hc, Wc, feather, gain=gain, use=use)
+    else:
+        out, count = pano_u8(images, idx, M, Hc, Wc, feather, mode, gain=gain, use=use)
     if gain is None:
         gain = torch.zeros((B, n, 2), dtype=torch.float64, device=dev)
         gain[:, :, 0] = 1.0
     return {"panorama": out, "panorama_count": count, "panorama_T": T, "panorama_bbox": bbox, "panorama_fitted": fitted, "panorama_M": M,
-            "panorama_gain": gain}
+            "panorama_gain": gain, **extra}
 
 
-def panorama(images, G, idx=None, canvas="ref", feather=32.0, mode="feather", gain=None, use=None, limit=2.0):
+def panorama(images, G, idx=None, canvas="ref", feather=32.0, mode="feather", gain=None, use=None, limit=2.0, band_sigma=4.0, low=None):
     """The n frames of a sequence on one canvas, for a caller who has G [B,n,3,3] float64 (the reference's index coordinates -> frame
     k's, the identity for the reference) from anywhere: images a uint8 [N,Hs,Ws,3] device tensor or an ImageBank, idx [B,n] (host values:
     range-checked; int32 device tensor: clamped by the kernel; None: one sample of all N images in order).  canvas="ref": the canvas is
@@ -1177,7 +1396,12 @@ def panorama(images, G, idx=None, canvas="ref", feather=32.0, mode="feather", ga
     gain [B,n,2] float64 device tensor (g, o) per frame, use [B,n] uint8 device tensor (0: the frame is left out), or None.  -> dict:
     'panorama' [B,Hc,Wc,3] uint8, 'panorama_count' [B,Hc,Wc] uint8 (frames present), 'panorama_T' [B,3,3] float64 (canvas -> reference),
     'panorama_bbox' [B,4] float64, 'panorama_fitted' [B,n] uint8, 'panorama_M' [B,n,3,3] float64 (canvas -> frame k), 'panorama_gain'
-    [B,n,2] float64.  ValueError before any launch for arguments outside these; nothing is copied to the host."""
+    [B,n,2] float64.  mode="two_band" (`bands_host`; band_sigma in [0.5, 10.5], a default and not a tuned value, in the frames' own
+    pixels; the other modes do not look at it): every frame is split into a low band, blended with the feather, and a high band, taken
+    per pixel from the frame with the largest weight - and 'panorama_winner' [B,Hc,Wc] uint8 (that frame's k, 255 for none) is added;
+    the gain applies to both bands.  low: the low bank, a uint8 [B,n,Hs,Ws,3] device tensor from an earlier `blur_u8(images, band_sigma,
+    idx)`, or None: made here with one launch.  ValueError before any launch for arguments outside these (a low bank with another mode
+    among them); nothing is copied to the host."""
     data = _images(images, "images")
     _need_device(G, name=False)
     if G.device != data.device:
@@ -1186,13 +1410,15 @@ def panorama(images, G, idx=None, canvas="ref", feather=32.0, mode="feather", ga
         raise ValueError("panorama: G [B,n,3,3] float64 with 1 <= n <= %d, got %s %s" % (PANO_MAX_FRAMES, G.dtype, tuple(G.shape)))
     B, n = G.shape[:2]
     size = _canvas_args("panorama", canvas, feather, mode, limit, "panorama")
+    _band_args(mode, band_sigma, "panorama", "panorama")
+    low = _low_arg(low, mode, (B, n) + tuple(data.shape[1:]), data.device, "panorama")
     ix = _frames_index(idx, data.shape[0], data.device, "panorama")
     if tuple(ix.shape) != (B, n):
         raise ValueError("panorama: idx names %d samples of %d frames, G has %d of %d" % (ix.shape[0], ix.shape[1], B, n))
     gain = _pano_tensor(gain, (B, n, 2), torch.float64, "gain", "panorama")
     use = _pano_tensor(use, (B, n), torch.uint8, "use", "panorama")
     with torch.cuda.device(data.device):
-        return _panorama(data, ix, G.contiguous(), size, feather, mode, gain, use, limit)
+        return _panorama(data, ix, G.contiguous(), size, feather, mode, gain, use, limit, band_sigma, low)
 
 
 def _stage_args(refine, cascade, cascade_min_cover, cascade_samples):
@@ -1217,7 +1443,7 @@ class Aligner:
 
     aligner(images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
             refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25, mosaic=None, mosaic_feather=32.0,
-            mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0) -> dict
+            mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0, mosaic_band_sigma=4.0) -> dict
         images_*: uint8 [N,H,W,3] device tensors or ImageBanks; the two may differ in size.
         idx_*: which image each of the B samples uses (host list: range-checked; int32 device tensor: clamped by the kernel;
                None: sample b is image b, so B = N).
@@ -1256,6 +1482,9 @@ class Aligner:
         (canvas index coordinates -> B's), 'mosaic_bbox' [B,4] float64, 'mosaic_fitted' [B] uint8, 'mosaic_gain' [B,2] float64.  A
         mosaic that is neither of the two, a canvas side below 2, a feather that is NaN, infinite or below 1, an unknown mode or
         exposure, 'gain' on an image side below 8 and a limit that is not > 0 raise a ValueError before any launch.
+        mosaic_mode "two_band" with mosaic_band_sigma=4.0 (in [0.5, 10.5], in each image's own pixels; a default, not a tuned value) is
+        `mosaic`'s two-band blend - the low bands blended with the feather, the high band from the image with the larger weight - and
+        adds 'mosaic_winner' [B,Hc,Wc] uint8 (0: A, 1: B, 255: neither); the other modes do not look at mosaic_band_sigma.
     aligner.sequence(images, idx=None, ref=None, ..., canvas=None) registers n frames of one bank to a reference frame through this
         call and blends them on one canvas (`chain_device`, `pano_frame_device`, `pano_u8`): see its docstring.
     The aligner copies nothing from the device to the host (host-given idx / roi values are uploaded).  What a model's own
@@ -1323,7 +1552,7 @@ class Aligner:
 
     def __call__(self, images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
                  refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25, mosaic=None, mosaic_feather=32.0,
-                 mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0):
+                 mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0, mosaic_band_sigma=4.0):
         from .step import predict
         stages, samples = _stage_args(refine, cascade, cascade_min_cover, cascade_samples)
         a, b = _images(images_a, "images_a"), _images(images_b, "images_b")
@@ -1346,6 +1575,7 @@ class Aligner:
         nx, ny = samples or _cascade_samples(None, roi_b, b.shape[1], b.shape[2], P)
         if mosaic is not None:
             canvas = _canvas_args("mosaic", mosaic, mosaic_feather, mosaic_mode, mosaic_limit, "Aligner")
+            _band_args(mosaic_mode, mosaic_band_sigma, "mosaic", "Aligner", "mosaic_band_sigma")
             _mosaic_exposure_args(mosaic_exposure, B, a.shape[1:3], b.shape[1:3], "Aligner", "mosaic_exposure")
         with torch.cuda.device(a.device):
             p1, ga = prepare(a, B, P, self.channels, self.mean, self.std, idx=ia, roi=ra)
@@ -1364,11 +1594,12 @@ class Aligner:
             if warp:
                 out["aligned"], out["valid"] = warp_u8(a, H, b.shape[1], b.shape[2], idx=ia)
             if mosaic is not None:
-                out.update(_mosaic(a, b, H, canvas, mosaic_feather, mosaic_mode, mosaic_exposure, mosaic_limit, ia, ib, mask_b))
+                out.update(_mosaic(a, b, H, canvas, mosaic_feather, mosaic_mode, mosaic_exposure, mosaic_limit, ia, ib, mask_b, mosaic_band_sigma))
         return out
 
     def sequence(self, images, idx=None, ref=None, roi=None, refine=None, refine_levels=3, refine_iters=10, mask=None, cascade=0,
-                 cascade_samples=None, cascade_min_cover=0.25, canvas=None, feather=32.0, mode="feather", exposure=None, limit=2.0, use=None):
+                 cascade_samples=None, cascade_min_cover=0.25, canvas=None, feather=32.0, mode="feather", exposure=None, limit=2.0, use=None,
+                 band_sigma=4.0):
         """Register a sequence of n frames (1 <= n <= 255) to one of them and, with a canvas, blend them all on it.
             images: one uint8 [N,Hs,Ws,3] device tensor or ImageBank; every frame has this size.
             idx: [B,n], frame k of sample b (host values: range-checked; int32 device tensor: clamped by the kernels; None: one sample
@@ -1383,7 +1614,8 @@ class Aligner:
         canvas="ref" or (Hc, Wc) (default None: no further launch) adds `panorama`'s keys with feather, mode, limit and use [B,n] uint8 on
         the device (0: the frame is left out of the blend and of the frame fit); exposure=None, "gain" (each pair's least-squares line of
         b's gray on a's through its H - one-level `gray_pyramid`, `ecc_sums`, `exposure_device`, counting the pixels `mask` allows -
-        composed along the chain) or a [B,n,2] float64 device tensor (g, o) per frame.  The chain accumulates every pair's error: it
+        composed along the chain) or a [B,n,2] float64 device tensor (g, o) per frame.  mode="two_band" with band_sigma=4.0 is
+        `panorama`'s two-band blend (the low bank is made here, one launch) and adds 'panorama_winner'.  The chain accumulates every pair's error: it
         drifts with n, and nothing here closes a loop.  Arguments outside these rules raise a ValueError before any launch; nothing is
         copied to the host."""
         who = "Aligner.sequence"
@@ -1417,6 +1649,7 @@ class Aligner:
             size = None
         else:
             size = _canvas_args("panorama", canvas, feather, mode, limit, who)
+            _band_args(mode, band_sigma, "panorama", who)
         measure = isinstance(exposure, str) and exposure == "gain"
         if measure:
             if min(Hs, Ws) < ECC_MIN_SIDE:
@@ -1453,5 +1686,5 @@ class Aligner:
             G, gain = chain_device(H_pairs, ref, gain_pairs)
             out.update({"G": G, "H_pairs": H_pairs})
             if canvas is not None:
-                out.update(_panorama(data, ix, G, size, feather, mode, exposure if isinstance(exposure, torch.Tensor) else gain, use, limit))
+                out.update(_panorama(data, ix, G, size, feather, mode, exposure if isinstance(exposure, torch.Tensor) else gain, use, limit, band_sigma))
         return out

@@ -15,16 +15,13 @@
 // are a compact tile, not a run of one row, because a tile is absent from more frames (PANO_TILE).  No LDS, no atomics, no scratch, one
 // writer per output element.
 #include "u8_image.h"
+#include "pano_tile.h"      // PANO_THREADS, PANO_TILE, pano_unit, pano_grid_x: shared with bands.hip
 
-#define PANO_THREADS 256
 #define PANO_MAX_FRAMES 255
 // A/B switches for tools/pano_bench.py (make ab ABFLAGS=-DPANO_SKIP=0 / -DPANO_TILE=0); DESIGN.md section 8 "Panorama" has the figures
 #ifndef PANO_SKIP
 #define PANO_SKIP 1        // 0: every frame takes its taps at every pixel
 #endif
-#ifndef PANO_TILE
-#define PANO_TILE 1        // 1: a wavefront makes 8 units x 8 rows of the canvas (a unit: 4 pixels, or 1), a workgroup 32 units x 8 rows - the
-#endif                     // compact tile is absent from more frames; 0: mosaic.hip's 64 consecutive units of one row (longer store runs)
 
 // ------------------------------------------------------------------------------------------------
 // the chain
@@ -140,31 +137,6 @@ __global__ void __launch_bounds__(PANO_THREADS) pano_frame_kernel(const double* 
 // ------------------------------------------------------------------------------------------------
 // the blend
 // ------------------------------------------------------------------------------------------------
-// the thread's unit of PX pixels -> (x, y) of its first pixel; false: outside the canvas
-template <int PX>
-__device__ __forceinline__ bool pano_unit(int Hc, int Wc, int& x, int& y) {
-    const unsigned upr = (unsigned)Wc / PX;                                    // units per canvas row
-#if PANO_TILE
-    const unsigned tiles_x = (upr + 31u) / 32u, by = blockIdx.x / tiles_x, bx = blockIdx.x - by * tiles_x;
-    const unsigned ux = bx * 32u + (threadIdx.x >> 6) * 8u + (threadIdx.x & 7u), uy = by * 8u + ((threadIdx.x >> 3) & 7u);
-    if (ux >= upr || uy >= (unsigned)Hc) return false;
-    x = (int)ux * PX; y = (int)uy;
-#else
-    const unsigned u = blockIdx.x * PANO_THREADS + threadIdx.x;
-    if (u >= upr * (unsigned)Hc) return false;
-    y = (int)(u / upr); x = (int)(u - (unsigned)y * upr) * PX;
-#endif
-    return true;
-}
-static unsigned pano_grid_x(int Hc, int Wc, int px) {
-    const unsigned upr = (unsigned)Wc / px;
-#if PANO_TILE
-    return ((upr + 31u) / 32u) * (((unsigned)Hc + 7u) / 8u);
-#else
-    return (upr * (unsigned)Hc + PANO_THREADS - 1) / PANO_THREADS;
-#endif
-}
-
 // grid (pano_grid_x, u8_grid_y(B)); PX = 4: Wc % 4 == 0 and out % 4 == 0 (count_vec: count % 4 == 0 too)
 template <int PX, bool BYTES>
 __global__ void __launch_bounds__(PANO_THREADS) pano_kernel(const unsigned char* __restrict__ images, const int* __restrict__ idx, int n_images, int Hs, int Ws,

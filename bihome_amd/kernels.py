@@ -1871,3 +1871,86 @@ def pano_u8(images, idx, M, out, count, feather, mode, gain=None, use=None):
     check(lib.bh_pano_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(M), _p(gain), _p(use), B, n,
                          out.shape[1], out.shape[2], float(feather), mode, _p(out), _p(count), _stream()), "bh_pano_u8")
     return out, count
+
+
+# ------------------------------------------------------------------------------------------------
+# two-band blend: the low band of uint8 frames, and the mosaic / panorama that blends it with the feather and takes the high band from one
+# frame per pixel (bihome_amd/align.py; csrc/blur.hip, csrc/bands.hip).  Every buffer is the caller's.
+# ------------------------------------------------------------------------------------------------
+BLUR_MAX_RADIUS = 32
+
+
+def blur_u8(images, out, taps, idx=None):
+    """out [count,H,W,3] uint8 = the integer Gaussian low-pass of images[idx[s]] (one uint8 bank [N,H,W,3]; idx int32 of count elements in
+    any shape, or None: sample s is image s and count <= N is out's) with the HOST taps w_0 .. w_r (bihome_amd.align.blur_taps), border
+    replicated (include/bihome.h bh_blur_u8; bihome_amd.align.blur_host).  out is the caller's (bihome_amd.align.blur_u8 allocates it)."""
+    _chk(out, torch.uint8)
+    if out.dim() != 4 or out.shape[3] != 3:
+        raise ValueError("blur_u8: out [count,H,W,3] uint8, got %s" % (tuple(out.shape),))
+    count = out.shape[0]
+    _chk_images_u8(images, None if idx is None else idx.reshape(-1), (count,), "blur_u8")
+    if tuple(out.shape[1:]) != tuple(images.shape[1:]):
+        raise ValueError("blur_u8: out [count,H,W,3] of the images' size %s, got %s" % (tuple(images.shape[1:3]), tuple(out.shape)))
+    w = [int(t) for t in taps]
+    if not 2 <= len(w) <= BLUR_MAX_RADIUS + 1 or min(w) < 0 or w[0] + 2 * sum(w[1:]) != 2048:
+        raise ValueError("blur_u8: taps are w_0 .. w_r, 1 <= r <= %d, none negative, w_0 + 2 sum w_i = 2048, got %r" % (BLUR_MAX_RADIUS, w))
+    check(lib.bh_blur_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], count, (ctypes.c_int * len(w))(*w), len(w) - 1,
+                         _p(out), _stream()), "bh_blur_u8")
+    return out
+
+
+def _chk_flag_plane(plane, out, what, name):
+    _chk(plane, torch.uint8)
+    if plane is not None and tuple(plane.shape) != tuple(out.shape[:3]):
+        raise ValueError("%s: %s [B,Hc,Wc] uint8 like out, got %s" % (what, name, tuple(plane.shape)))
+
+
+def pano_bands_u8(images, low, idx, M, out, count, winner, feather, gain=None, use=None):
+    """out [B,Hc,Wc,3] uint8 = the two-band blend of the n frames images[idx[b,k]] with their low bands low [B,n,Hs,Ws,3] (or [B n,Hs,Ws,3])
+    uint8 on a canvas whose index coordinates M [B,n,3,3] float64 map to frame k's; count [B,Hc,Wc] uint8 the number of frames present and
+    winner [B,Hc,Wc] uint8 the frame the high band comes from, 255 for none (either may be None) (include/bihome.h bh_pano_bands_u8;
+    bihome_amd.align.bands_host).  gain and use as in pano_u8.  The outputs are the caller's (bihome_amd.align.pano_bands_u8 allocates)."""
+    _chk(M, torch.float64); _chk(gain, torch.float64); _chk(use, torch.uint8); _chk(out, torch.uint8); _chk(low, torch.uint8)
+    if not _is_hn(M):
+        raise ValueError("pano_bands_u8: M [B,n,3,3] float64 with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, tuple(M.shape)))
+    B, n = M.shape[:2]
+    if (gain is not None and tuple(gain.shape) != (B, n, 2)) or (use is not None and tuple(use.shape) != (B, n)):
+        raise ValueError("pano_bands_u8: gain [B,n,2] float64 and use [B,n] uint8 with B = %d, n = %d, got %s and %s"
+                         % (B, n, None if gain is None else tuple(gain.shape), None if use is None else tuple(use.shape)))
+    _chk_canvas_u8(out, count, B, "pano_bands_u8", ("count", "Hc,Wc"))
+    _chk_flag_plane(count, out, "pano_bands_u8", "count")
+    _chk_flag_plane(winner, out, "pano_bands_u8", "winner")
+    _chk_images_u8(images, idx, (B, n), "pano_bands_u8")
+    if low.numel() != B * n * images[0].numel() or tuple(low.shape[-3:]) != tuple(images.shape[1:]) or tuple(low.shape[:-3]) not in ((B, n), (B * n,)):
+        raise ValueError("pano_bands_u8: low [B,n,Hs,Ws,3] uint8 with B = %d, n = %d and the frames' size %s, got %s"
+                         % (B, n, tuple(images.shape[1:3]), tuple(low.shape)))
+    check(lib.bh_pano_bands_u8(_p(images), _p(low), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(M), _p(gain), _p(use), B, n,
+                               out.shape[1], out.shape[2], float(feather), _p(out), _p(count), _p(winner), _stream()), "bh_pano_bands_u8")
+    return out, count, winner
+
+
+def mosaic_bands_u8(images_a, low_a, images_b, low_b, Ma, Mb, out, cover, winner, feather, gain=None, idx_a=None, idx_b=None):
+    """out [B,Hc,Wc,3] uint8 = the two-band blend of images_a[idx_a[b]] and images_b[idx_b[b]] with their low bands low_a [B,Ha,Wa,3] and
+    low_b [B,Hb,Wb,3] uint8 (in sample order); cover as in mosaic_u8, winner [B,Hc,Wc] uint8 = 0 for A, 1 for B, 255 for none (either may be
+    None) (include/bihome.h bh_mosaic_bands_u8; bihome_amd.align.mosaic_bands_host).  The outputs are the caller's."""
+    _chk(Ma, torch.float64); _chk(Mb, torch.float64); _chk(gain, torch.float64); _chk(out, torch.uint8); _chk(low_a, torch.uint8); _chk(low_b, torch.uint8)
+    for M, what in ((Ma, "Ma"), (Mb, "Mb")):
+        if not _is_h(M):
+            raise ValueError("mosaic_bands_u8: %s [B,3,3] float64, got %s" % (what, tuple(M.shape)))
+    B = Ma.shape[0]
+    if Mb.shape[0] != B or (gain is not None and tuple(gain.shape) != (B, 2)):
+        raise ValueError("mosaic_bands_u8: Ma and Mb [B,3,3] and gain [B,2] float64 with one B, got %s, %s and %s"
+                         % (tuple(Ma.shape), tuple(Mb.shape), None if gain is None else tuple(gain.shape)))
+    _chk_canvas_u8(out, cover, B, "mosaic_bands_u8", ("cover", "Hc,Wc"))
+    _chk_flag_plane(cover, out, "mosaic_bands_u8", "cover")
+    _chk_flag_plane(winner, out, "mosaic_bands_u8", "winner")
+    _chk_images_u8(images_a, idx_a, (B,), "mosaic_bands_u8")
+    _chk_images_u8(images_b, idx_b, (B,), "mosaic_bands_u8")
+    for low, images, what in ((low_a, images_a, "low_a"), (low_b, images_b, "low_b")):
+        if tuple(low.shape) != (B,) + tuple(images.shape[1:]):
+            raise ValueError("mosaic_bands_u8: %s [B,H,W,3] uint8 with B = %d and its images' size %s, got %s" % (what, B, tuple(images.shape[1:3]), tuple(low.shape)))
+    check(lib.bh_mosaic_bands_u8(_p(images_a), _p(low_a), _p(idx_a), images_a.shape[0], images_a.shape[1], images_a.shape[2],
+                                 _p(images_b), _p(low_b), _p(idx_b), images_b.shape[0], images_b.shape[1], images_b.shape[2],
+                                 _p(Ma), _p(Mb), _p(gain), B, out.shape[1], out.shape[2], float(feather), _p(out), _p(cover), _p(winner), _stream()),
+          "bh_mosaic_bands_u8")
+    return out, cover, winner

@@ -1039,6 +1039,53 @@ int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int
 int bh_pano_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* M, const double* gain,
                const uint8_t* use, int B, int n, int Hc, int Wc, float feather, int mode, uint8_t* out, uint8_t* count, void* stream);
 
+/* Two-band blend: the mosaic and the panorama without the feather's doubled edges.  Every frame is split into a LOW band, a Gaussian
+ * low-pass of the frame in its own pixels, and a HIGH band, frame minus low (Burt & Adelson; two bands as in Brown & Lowe).  The low bands
+ * are blended with the wide feather, so exposure and vignetting fade over the whole overlap; the high band is taken from ONE frame per
+ * pixel, so frames that disagree by a pixel or two double nothing.  The numpy statements are bihome_amd/align.py's blur_taps, blur_host,
+ * bands_host and mosaic_bands_host.
+ *
+ * bh_blur_u8: out[count,H,W,3] uint8, sample s the low band of image idx[s] of images[n_images,H,W,3] (NULL: image s; CLAMPED into the
+ * bank in the kernel).  taps is a HOST pointer to radius + 1 ints w_0 .. w_radius, 1 <= radius <= 32, every w >= 0 and
+ * w_0 + 2 sum_{i >= 1} w_i = 2048 (align.blur_taps(sigma): radius = ceil(3 sigma), w_i = floor(2048 g_i + 0.5) of the normalised Gaussian
+ * for i >= 1, w_0 the rest); they are read before the call returns and go to the kernel by value.
+ *     L[y,x,c] = (sum_j sum_i w_|j| w_|i| I[clamp(y + j, 0, H - 1), clamp(x + i, 0, W - 1), c] + 2^21) >> 22,  -radius <= i, j <= radius,
+ * the border replicated.  The sum is exact in 32-bit unsigned integers (255 * 2048 * 2048 < 2^31): its order does not show, the kernel
+ * equals the statement bit for bit, and a constant image comes back unchanged.  One launch for all samples; a workgroup stages a 32 x 24
+ * tile with its halo in LDS, sums along the rows into 32-bit LDS words, then along the columns, and stores; no atomics, one writer per
+ * output byte: two calls are bitwise equal.
+ * BH_E_BADARG: NULL images / taps / out, count < 0, n_images, H or W < 1, a radius outside 1..32, a negative tap, taps that do not sum to
+ * 2048; then BH_E_UNSUPPORTED: H * W > 2^29 pixels; then count == 0: BH_OK, nothing launched.
+ *
+ * bh_pano_bands_u8: bh_pano_u8's arguments without a mode, plus low[B n,Hs,Ws,3] uint8: low image b n + k is the low band of frame k of
+ * sample b (what bh_blur_u8 writes for idx[B,n] flattened).  Frame k is PRESENT exactly where bh_pano_u8 has it present.  Over the frames
+ * present, in the order k = 0 .. n - 1, all in float without contraction, with I_k(p) bh_warp_u8's bilinear value and L_k(p) the same
+ * bilinear sample of the low image at the SAME taps (one projection, eight loads):
+ *     v = fmaf(g_k, I_k(p), o_k),  l = fmaf(g_k, L_k(p), o_k),  w = bh_mosaic_u8's weight min(border distance + 1, feather),
+ *     num_c += w l_c (the product rounded before it is added),  den += w,
+ *     the frame becomes the WINNER if it is the first present or w > w_best, strictly (ties: the lowest k): w_best, v_best, l_best, winner = k.
+ * Before rounding the value is 0 where nothing is present, v_best where exactly one frame is, else v_best + (num / den - l_best); then
+ * out[b,y,x,:] = round_half_up(clamp(., 0, 255)).  So where one frame is present the result is BH_PANO_FIRST's bit for bit, and with an
+ * all-zero low bank it is the winner's own sample bit for bit.  count[B,Hc,Wc] uint8 (NULL ok): the number of frames present;
+ * winner[B,Hc,Wc] uint8 (NULL ok): the winner's k, 255 where nothing is present.  The wavefront skip, the 32 x 8 tile, the two store paths
+ * and their alignment rules are bh_pano_u8's; no LDS, no atomics, no scratch, one writer per output element.
+ * Refusals: bh_pano_u8's (and a NULL low), without the mode.
+ *
+ * bh_mosaic_bands_u8: bh_mosaic_u8's arguments without a mode, plus low_a[B,Ha,Wa,3] and low_b[B,Hb,Wb,3] uint8, the low bands of the
+ * B samples' images in sample order.  The frames are (A, B), the gain applies to A (both bands), and the rule is bh_pano_bands_u8's - one
+ * device function: for same-size frames bh_pano_bands_u8 with n = 2 and gain ((g, o), (1, 0)) gives out and winner bit for bit, and count
+ * equals the number of bits set in cover.  cover as in bh_mosaic_u8; winner[B,Hc,Wc] uint8 (NULL ok): 0 for A, 1 for B, 255 for none.
+ * Refusals: bh_mosaic_u8's (and a NULL low_a / low_b), without the mode. */
+int bh_blur_u8(const uint8_t* images, const int* idx, int n_images, int H, int W, int count, const int* taps, int radius, uint8_t* out,
+               void* stream);
+int bh_pano_bands_u8(const uint8_t* images, const uint8_t* low, const int* idx, int n_images, int Hs, int Ws, const double* M, const double* gain,
+                     const uint8_t* use, int B, int n, int Hc, int Wc, float feather, uint8_t* out, uint8_t* count, uint8_t* winner, void* stream);
+int bh_mosaic_bands_u8(const uint8_t* images_a, const uint8_t* low_a, const int* idx_a, int n_a, int Ha, int Wa,
+                       const uint8_t* images_b, const uint8_t* low_b, const int* idx_b, int n_b, int Hb, int Wb,
+                       const double* Ma, const double* Mb, const double* gain,
+                       int B, int Hc, int Wc, float feather,
+                       uint8_t* out, uint8_t* cover, uint8_t* winner, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */

@@ -1,0 +1,404 @@
+"""The two-band blend on the device (csrc/blur.hip: bh_blur_u8; csrc/bands.hip: bh_pano_bands_u8, bh_mosaic_bands_u8; bihome_amd/align.py
+blur_u8 / pano_bands_u8 / mosaic_bands_u8 and mode "two_band" of panorama / mosaic / Aligner) against the numpy statements of
+bihome_amd/align.py, which tests/test_align_bands_cpu.py holds to independent restatements.
+
+The low band is integer arithmetic: bh_blur_u8 equals blur_host bit for bit, everywhere.
+
+The blend is compared with bands_host on the pixels that are DECIDED (tests/align_bands_cases.py: in float64 no second frame's weight
+comes within 1e-3 of the winner's, unless the cap makes the tie exact) and at least 1e-3 px from every border line of every frame; at
+most 1e-3 of a canvas is undecided (test_align_bands_cpu.py asserts it per case).  There winner and count are bitwise equal, no colour is
+off by more than one grey level, and the share of pixels that differ at all is capped at three times what a float32 numpy restatement of
+the kernel's arithmetic (align_bands_cases.bands_f32) shows against the float64 statement on exactly these inputs, rounded up to one
+significant digit (three times, as in test_align_pano_gpu.py: the kernel's reciprocal and its compiler's instruction selection are not
+the restatement's).  Measured on the host (test_align_bands_cpu.py asserts the figures), without the gain / with it:
+    n = 3, 17 x 23 on 24 x 53, sigma 3        0       / 1.57e-3
+    n = 5, 40 x 56 on 48 x 160, sigma 3       1.30e-4 / 3.26e-4
+    n = 5, 40 x 56 on 48 x 160, sigma 1       2.61e-4 / 2.61e-4
+    n = 5, 40 x 56 on 37 x 131, sigma 3       0       / 3.10e-4
+    n = 8, 120 x 160 on 160 x 640, sigma 3    1.37e-4 / 5.47e-4
+    burst n = 6, 40 x 56 on "ref", sigma 3    0       / 0
+so CAP = 9e-4 without the gain and CAP_GAIN = 5e-3 with it."""
+import numpy as np
+import pytest
+import torch
+
+import align_bands_cases as Bc
+import align_mosaic_cases as Mc
+import align_pano_cases as Pc
+import poisoned_alloc
+from bihome_amd import align
+from bihome_amd import kernels as K
+from test_align_bands_cpu import MEASURED, SAME_SIZE
+
+pytestmark = pytest.mark.gpu
+
+CAP, CAP_GAIN = 9e-4, 5e-3
+N_BIG = 9400        # 240 x 320 x 3 bytes per image: image 9,321 is the first that starts past 2^31 bytes (tests/test_align_gpu.py)
+
+
+def test_caps_are_three_times_the_measured_shares():
+    def up(x):                                                             # rounded up to one significant digit
+        e = 10.0 ** np.floor(np.log10(x))
+        return float(np.ceil(x / e - 1e-9) * e)
+    want = up(3 * max(m[0] for m in MEASURED.values())), up(3 * max(m[1] for m in MEASURED.values()))
+    assert np.allclose((CAP, CAP_GAIN), want, rtol=1e-12, atol=0.0)        # (9 * 1e-4 is not the double 9e-4)
+
+
+def cuda(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+    return t if dtype is None else t.to(dtype)
+
+
+def host(t):
+    return t.cpu().numpy()
+
+
+def run(bank, low, idx, M, Hc, Wc, feather=8.0, gain=None, use=None, **kw):
+    out, count, winner = align.pano_bands_u8(cuda(bank), cuda(low), None if idx is None else cuda(idx, torch.int32), cuda(M), Hc, Wc, feather,
+                                             gain=None if gain is None else cuda(gain), use=None if use is None else cuda(use), **kw)
+    return host(out), None if count is None else host(count), None if winner is None else host(winner)
+
+
+# ------------------------------------------------------------------------------------------------
+# bh_blur_u8 against blur_host: bit for bit
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("h,w,sigma", [(1, 1, 0.5), (5, 7, 3.0), (17, 23, 0.5), (40, 56, 3.0), (33, 130, 1.0), (120, 160, 10.5)])
+def test_blur_equals_the_host_statement_bit_for_bit(monkeypatch, h, w, sigma):
+    p = poisoned_alloc.poison(monkeypatch, align)          # the output handed out 1-filled between red zones
+    bank = Mc.pixels(2, h, w, seed=6) if h * w < 100 else np.concatenate([Mc.textures(2, h, w, seed=1), Mc.pixels(1, h, w, seed=6)])
+    want = align.blur_host(bank, sigma)
+    assert len(align.blur_taps(sigma)) - 1 == {0.5: 2, 1.0: 3, 3.0: 9, 10.5: 32}[sigma]
+    dbank = cuda(bank)
+    low = align.blur_u8(dbank, sigma)                                      # without an index list
+    assert low.shape == dbank.shape and low.dtype == torch.uint8 and np.array_equal(host(low), want)
+    n = len(bank)
+    wild = torch.tensor([[n - 1, 0, -7], [2 ** 30, -2147483648, n - 1]], dtype=torch.int32, device="cuda")      # the last image, and values that are clamped
+    low = align.blur_u8(dbank, sigma, wild)
+    assert low.shape == (2, 3, h, w, 3) and np.array_equal(host(low), want[[n - 1, 0, 0, n - 1, 0, n - 1]].reshape(2, 3, h, w, 3))
+    assert torch.equal(align.blur_u8(dbank, sigma, wild), low)             # two calls, equal bits
+    assert "blur_u8" in p.callers() and p.verify() == 3                    # nothing written outside the output
+    for off in (1, 3):                                                     # an output at any byte offset
+        big = torch.full((off + want.size + 16,), 0xAB, dtype=torch.uint8, device="cuda")
+        K.blur_u8(dbank, big[off:off + want.size].view(want.shape), align.blur_taps(sigma).tolist())
+        assert np.array_equal(host(big[off:off + want.size]).reshape(want.shape), want)
+        assert (big[:off] == 0xAB).all() and (big[off + want.size:] == 0xAB).all()
+
+
+def test_blur_offsets_are_64_bit():
+    """One bank whose last images start past 2^31 bytes: a 32-bit byte offset reads image 9,321 from the wrong place."""
+    data = torch.randint(0, 256, (N_BIG, 240, 320, 3), dtype=torch.uint8, device="cuda")
+    assert data.numel() > 2 ** 31 and 9320 * 230400 < 2 ** 31 <= 9321 * 230400
+    idx = [0, 9320, 9321, N_BIG - 1]
+    low = align.blur_u8(data, 1.0, torch.tensor(idx, dtype=torch.int32, device="cuda"))
+    want = align.blur_host(host(data[idx]), 1.0)
+    assert np.array_equal(host(low), want) and len({want[i].tobytes() for i in range(4)}) == 4
+
+
+def test_blur_wrapper_refuses_bad_taps_and_shapes():
+    img = torch.zeros(3, 8, 8, 3, dtype=torch.uint8, device="cuda")
+    good = align.blur_taps(1.0).tolist()
+    for taps in ([2048], good[:-1], [g + 1 for g in good], [good[0] + 2 * good[1] + 2, -1] + good[2:], [2048] + [0] * 33):
+        with pytest.raises(ValueError):
+            K.blur_u8(img, torch.empty_like(img), taps)
+    for out in (torch.empty(3, 8, 9, 3, dtype=torch.uint8, device="cuda"), torch.empty(4, 8, 8, 3, dtype=torch.uint8, device="cuda")[:, :, :, :2]):
+        with pytest.raises(ValueError):
+            K.blur_u8(img, out, good)
+    with pytest.raises(ValueError):
+        K.blur_u8(img, torch.empty_like(img), good, idx=torch.zeros(2, dtype=torch.int32, device="cuda"))      # 2 indices, 3 outputs
+    with pytest.raises(ValueError):
+        align.blur_u8(img, 11.0)
+
+
+# ------------------------------------------------------------------------------------------------
+# bh_pano_bands_u8 against bands_host
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,sigma", list(MEASURED), ids=["%s-sigma%g" % k for k in MEASURED])
+def test_bands_match_the_host_statement(monkeypatch, name, sigma):
+    p = poisoned_alloc.poison(monkeypatch, align)
+    bank, idx, _, M, Hc, Wc = Pc.case(name)
+    nb, n = idx.shape
+    dbank, didx, dM, dgain = cuda(bank), cuda(idx, torch.int32), cuda(M), cuda(Pc.gain_of(n, nb))
+    low = align.blur_u8(dbank, sigma, didx)
+    assert np.array_equal(host(low), Bc.low_of(name, sigma))               # the bank the statement blends, bit for bit
+    runs = [(f, g) for nm, f, g, s in Bc.RUNS if (nm, s) == (name, sigma)]
+    assert len(runs) == 4
+    for feather, gain in runs:
+        keep = Bc.compared(name, feather)
+        want, want_count, want_winner = Bc.reference(name, feather, gain, sigma)
+        out, count, winner = align.pano_bands_u8(dbank, low, didx, dM, Hc, Wc, feather, gain=dgain if gain else None)
+        assert out.shape == (nb, Hc, Wc, 3) and count.shape == winner.shape == (nb, Hc, Wc) and out.dtype == count.dtype == winner.dtype == torch.uint8
+        d, share = Mc.differing_share(host(out)[keep], want[keep])
+        cap = CAP_GAIN if gain else CAP
+        print("%s, sigma %g, feather %g, gain %s: max |difference| %d grey levels, %.2e of the compared pixels differ (cap %.0e); %.2e of the canvas "
+              "is not compared" % (name, sigma, feather, gain, d, share, cap, 1.0 - keep.mean()))
+        assert 1.0 - keep.mean() <= 6e-3                                   # 1e-3 undecided and 5e-3 near a border line at the most
+        assert np.array_equal(host(winner)[keep], want_winner[keep]) and np.array_equal(host(count)[keep], want_count[keep])
+        assert d <= 1 and share <= cap, (feather, gain, d, share)
+        assert host(count).max() <= n and np.array_equal(host(winner) == 255, host(count) == 0) and host(winner)[host(count) > 0].max() < n
+    again = align.pano_bands_u8(dbank, low, didx, dM, Hc, Wc, feather, gain=dgain if gain else None)
+    assert all(torch.equal(x, y) for x, y in zip(again, (out, count, winner)))          # two calls, equal bits
+    only, no_count, no_winner = align.pano_bands_u8(dbank, low, didx, dM, Hc, Wc, feather, gain=dgain if gain else None, want_count=False, want_winner=False)
+    assert no_count is None and no_winner is None and torch.equal(only, out)
+    assert "pano_bands_u8" in p.callers() and p.verify() == 1 + 3 * len(runs) + 3 + 1      # nothing written outside any output
+    # one frame present: mode 'first', bit for bit (the last run's feather and gain)
+    first, first_count = align.pano_u8(dbank, didx, dM, Hc, Wc, feather, "first", gain=dgain if gain else None)
+    assert torch.equal(count, first_count) and torch.equal(out[count == 1], first[count == 1]) and (count == 1).any()
+
+
+@pytest.mark.parametrize("name", ["n5-40x56-on-48x160", "n5-40x56-on-37x131", "burst-n6-40x56-on-ref"])
+def test_a_zero_low_bank_gives_the_winners_own_sample_everywhere(name):
+    """At EVERY pixel, near-ties and border lines included: the kernel's own winner names the frame whose bh_warp_u8 sample the pixel is."""
+    bank, idx, _, M, Hc, Wc = Pc.case(name)
+    nb, n = idx.shape
+    dbank, didx, dM = cuda(bank), cuda(idx, torch.int32), cuda(M)
+    zero = torch.zeros((nb, n) + bank.shape[1:], dtype=torch.uint8, device="cuda")
+    for feather in Bc.FEATHERS[name]:
+        out, count, winner = align.pano_bands_u8(dbank, zero, didx, dM, Hc, Wc, feather)
+        want = torch.zeros_like(out)
+        for k in range(n):
+            own, valid = align.warp_u8(dbank, dM[:, k].contiguous(), Hc, Wc, idx=didx[:, k].contiguous())
+            want = torch.where((winner == k)[..., None], own, want)
+            assert valid[winner == k].all()
+        assert torch.equal(out, want) and not out[winner == 255].any() and len(torch.unique(winner)) >= 3
+
+
+# ------------------------------------------------------------------------------------------------
+# exact cases, bitwise
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("h,w", [(17, 23), (48, 80)], ids=["17x23-scalar", "48x80-vector"])
+def test_exact_cases_are_bitwise(h, w):
+    A = Mc.textures(2, h, w, seed=1)
+    low = align.blur_host(A, Bc.SIGMA)
+    eye = np.stack([np.eye(3)] * 2)[:, None]
+    for feather in (1.0, 8.0, 64.0):
+        out, count, winner = run(A, low[:, None], np.arange(2).reshape(2, 1), eye, h, w, feather)          # n = 1, M = I: the image
+        assert np.array_equal(out, A) and np.all(count == 1) and np.all(winner == 0), feather
+    out, count, winner = run(A[:1], low[:1, None], None, eye[:1], h, w)   # no index list: frame k is image k
+    assert np.array_equal(out, A[:1]) and np.all(count == 1) and np.all(winner == 0)
+    # integer translations: integer taps and integer weights, so no near-tie and every pixel is compared
+    bank, idx, M = Pc.translation_case(h, w)
+    low = align.blur_host(bank, Bc.SIGMA)[None]
+    use = np.array([[1, 0, 1]], np.uint8)
+    for feather in (1.0, 4.0):
+        out, count, winner = run(bank, low, idx, M, h, w, feather)
+        want, want_count, want_winner = align.bands_host(bank, low, idx, M, h, w, feather)
+        assert np.array_equal(out, want) and np.array_equal(count, want_count) and np.array_equal(winner, want_winner), feather
+        assert set(np.unique(count)) == {0, 1, 2, 3} and not out[count == 0].any()
+        out, count, winner = run(bank, low, idx, M, h, w, feather, use=use)          # one frame zeroed: the call without it
+        want, want_count, want_winner = run(bank, low[:, [0, 2]], idx[:, [0, 2]], M[:, [0, 2]], h, w, feather)
+        assert np.array_equal(out, want) and np.array_equal(count, want_count) and count.max() == 2
+        assert np.array_equal(winner, np.where(want_winner == 1, 2, want_winner))
+
+
+def test_a_single_pixel_frame_and_a_vanishing_denominator():
+    A = np.array([[[[200, 100, 50]]], [[[10, 20, 30]]]], np.uint8)        # two frames of one pixel each
+    low = align.blur_host(A, 0.5)[None]
+    assert np.array_equal(low[0], A)
+    M = np.array([[[[0.5, 0, -1], [0, 0.5, -1], [0, 0, 1]], [[1.0, 0, -3], [0, 1, -2], [0, 0, 1]]]])      # at canvas (2, 2) and (3, 2)
+    for Hc, Wc in ((5, 7), (4, 8)):
+        out, count, winner = run(A, low, np.array([[0, 1]]), M, Hc, Wc, 8.0)
+        want, want_count, want_winner = align.bands_host(A, low, [[0, 1]], M, Hc, Wc, 8.0)
+        assert np.array_equal(out, want) and np.array_equal(count, want_count) and np.array_equal(winner, want_winner) and count.sum() == 2
+        assert out[0, 2, 2].tolist() == [200, 100, 50] and out[0, 2, 3].tolist() == [10, 20, 30] and winner[0, 2, 2] == 0 and winner[0, 2, 3] == 1
+    bank = Mc.textures(2, 48, 80, seed=1)
+    low = align.blur_host(bank, Bc.SIGMA)[None]
+    M = np.stack([np.array([[1.0, 0, 0], [0, 1, 0], [-0.125, 0, 1]]), np.eye(3)])[None]          # qz = 1 - x / 8: exactly 0 on the column x = 8
+    out, count, winner = run(bank, low, np.array([[0, 1]]), M, 48, 80, 8.0)
+    assert (count[0, :, 8] == 1).all() and (winner[0, :, 8] == 1).all() and (count[0, :, 0] == 2).all() and np.array_equal(out[0, :, 8], bank[1, :, 8])
+    assert np.array_equal(count, align.bands_host(bank, low, [[0, 1]], M, 48, 80, 8.0)[1])
+
+
+# ------------------------------------------------------------------------------------------------
+# the pair
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", SAME_SIZE)
+def test_two_frames_are_bh_mosaic_bands_u8_bit_for_bit(name):
+    A, B, Ma, Mb, Hc, Wc = Mc.case(name)
+    n = len(A)
+    bank = cuda(np.concatenate([A, B]))
+    idx = cuda(np.stack([np.arange(n), n + np.arange(n)], 1), torch.int32)
+    M, dMa, dMb = cuda(np.stack([Ma, Mb], 1)), cuda(Ma), cuda(Mb)
+    ia, ib = idx[:, 0].contiguous(), idx[:, 1].contiguous()
+    low = align.blur_u8(bank, Bc.SIGMA, idx)
+    la, lb = low[:, 0].contiguous(), low[:, 1].contiguous()
+    for feather in (1.0, 8.0, 64.0):
+        for gain in (None, Mc.GAIN):
+            want, cover, want_winner = align.mosaic_bands_u8(bank, la, bank, lb, dMa, dMb, Hc, Wc, feather, gain=None if gain is None else cuda(Mc.gain_of(gain, n)),
+                                                             idx_a=ia, idx_b=ib)
+            g = None if gain is None else cuda(np.tile(np.array([gain, (1.0, 0.0)]), (n, 1, 1)))
+            out, count, winner = align.pano_bands_u8(bank, low, idx, M, Hc, Wc, feather, gain=g)
+            assert torch.equal(out, want) and torch.equal(winner, want_winner), (feather, gain)
+            assert torch.equal(count, (cover & 1) + (cover >> 1))
+            assert torch.equal(cover, align.mosaic_u8(bank, bank, dMa, dMb, Hc, Wc, feather, "feather", idx_a=ia, idx_b=ib)[1])
+
+
+def test_the_pair_with_images_of_two_sizes_matches_the_host_statement(monkeypatch):
+    p = poisoned_alloc.poison(monkeypatch, align)
+    for name in ("48x80-and-40x56-fitted-64x96-vector", "48x80-and-40x56-fitted-37x53-scalar"):
+        A, B, Ma, Mb, Hc, Wc = Mc.case(name)
+        n = len(A)
+        la, lb = align.blur_host(A, Bc.SIGMA), align.blur_host(B, Bc.SIGMA)
+        near = Mc.near_border(Ma, Hc, Wc, *A.shape[1:3]) | Mc.near_border(Mb, Hc, Wc, *B.shape[1:3])
+        (wa, pa), (wb, pb) = Bc.frame_weights(Ma, *A.shape[1:3], Hc, Wc), Bc.frame_weights(Mb, *B.shape[1:3], Hc, Wc)
+        keep = Bc.decided_of(np.stack([wa, wb]), np.stack([pa, pb]), 8.0) & ~near
+        for gain in (None, Mc.GAIN):
+            want, want_cover, want_winner = align.mosaic_bands_host(A, la, B, lb, Ma, Mb, Hc, Wc, 8.0, Mc.gain_of(gain, n))
+            out, cover, winner = align.mosaic_bands_u8(cuda(A), cuda(la), cuda(B), cuda(lb), cuda(Ma), cuda(Mb), Hc, Wc, 8.0,
+                                                       gain=None if gain is None else cuda(Mc.gain_of(gain, n)))
+            d, share = Mc.differing_share(host(out)[keep], want[keep])
+            print("%s, gain %s: max |difference| %d, %.2e of the compared pixels differ; %.2e of the canvas not compared" % (name, gain, d, share, 1 - keep.mean()))
+            assert 1 - keep.mean() <= 6e-3 and np.array_equal(host(cover)[keep], want_cover[keep]) and np.array_equal(host(winner)[keep], want_winner[keep])
+            assert d <= 1 and share <= (CAP_GAIN if gain else CAP)
+            assert set(np.unique(host(winner))) == {0, 1, 255}
+    assert p.verify() == 12
+
+
+# ------------------------------------------------------------------------------------------------
+# buffer contracts
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("out_off,flag_off", [(3, 1), (4, 1), (4, 8), (3, 4)],
+                         ids=["out+3-flags+1-scalar", "out+4-flags+1-vector-byte-flags", "out+4-flags+8-vector", "out+3-flags+4-scalar"])
+def test_outputs_at_any_byte_offset_leave_their_surroundings_alone(out_off, flag_off):
+    name = "n5-40x56-on-48x160"
+    bank, idx, _, M, Hc, Wc = Pc.case(name)
+    dbank, didx, dM, low = cuda(bank), cuda(idx, torch.int32), cuda(M), cuda(Bc.low_of(name))
+    want, want_count, want_winner = align.pano_bands_u8(dbank, low, didx, dM, Hc, Wc, 8.0)
+    n_out, n_flag, tail = want.numel(), want_count.numel(), 16
+    big_out = torch.full((out_off + n_out + tail,), 0xAB, dtype=torch.uint8, device="cuda")
+    big_count = torch.full((flag_off + n_flag + tail,), 0xCD, dtype=torch.uint8, device="cuda")
+    win_off = 2 if flag_off % 4 == 0 else 4                                # the winner plane on the other alignment than count
+    big_winner = torch.full((win_off + n_flag + tail,), 0xEF, dtype=torch.uint8, device="cuda")
+    assert big_out.data_ptr() % 4 == 0 and big_count.data_ptr() % 4 == 0 and big_winner.data_ptr() % 4 == 0
+    out, count = big_out[out_off:out_off + n_out].view(want.shape), big_count[flag_off:flag_off + n_flag].view(want_count.shape)
+    winner = big_winner[win_off:win_off + n_flag].view(want_winner.shape)
+    K.pano_bands_u8(dbank, low, didx, dM, out, count, winner, 8.0)
+    assert torch.equal(out, want) and torch.equal(count, want_count) and torch.equal(winner, want_winner)
+    assert (big_out[:out_off] == 0xAB).all() and (big_out[out_off + n_out:] == 0xAB).all()
+    assert (big_count[:flag_off] == 0xCD).all() and (big_count[flag_off + n_flag:] == 0xCD).all()
+    assert (big_winner[:win_off] == 0xEF).all() and (big_winner[win_off + n_flag:] == 0xEF).all()
+
+
+def test_wild_indices_are_clamped():
+    bank, _, M = Pc.translation_case()
+    wild = torch.tensor([[-7, 1, 2 ** 30], [2, -2147483648, 2147483647]], dtype=torch.int32, device="cuda")
+    M2 = np.concatenate([M, M])
+    low = align.blur_u8(cuda(bank), Bc.SIGMA, wild)
+    out, count, winner = align.pano_bands_u8(cuda(bank), low, wild, cuda(M2), 17, 23, 4.0)
+    clamped = np.array([[0, 1, 2], [2, 0, 2]])
+    assert np.array_equal(host(low), align.blur_host(bank[clamped], Bc.SIGMA))
+    want, want_count, want_winner = align.bands_host(bank, host(low), clamped, M2, 17, 23, 4.0)
+    assert np.array_equal(host(out), want) and np.array_equal(host(count), want_count) and np.array_equal(host(winner), want_winner)
+
+
+# ------------------------------------------------------------------------------------------------
+# panorama(), mosaic() and the Aligner in mode "two_band"
+# ------------------------------------------------------------------------------------------------
+PANO_KEYS = {"panorama", "panorama_count", "panorama_T", "panorama_bbox", "panorama_fitted", "panorama_M", "panorama_gain"}
+MOSAIC_KEYS = {"mosaic", "mosaic_cover", "mosaic_T", "mosaic_bbox", "mosaic_fitted", "mosaic_gain"}
+SEQ_KEYS = {"G", "H_pairs", "pairs", "pair"}
+PLAIN_KEYS = {"delta_hat", "H", "patch_1", "patch_2", "geom_a", "geom_b", "aligned", "valid"}
+
+
+def stub_aligner(delta, P=32):
+    return align.Aligner(torch.nn.Sequential(Mc.StubHead(cuda(delta, torch.float32))), patch=P)
+
+
+def test_panorama_two_band_adds_the_winner_and_takes_a_precomputed_low_bank(monkeypatch):
+    calls = []
+    for fname in ("blur_u8", "pano_bands_u8", "pano_u8"):
+        fn = getattr(K, fname)
+        monkeypatch.setattr(K, fname, lambda *a, _fn=fn, _n=fname, **k: calls.append(_n) or _fn(*a, **k))
+    name = "n5-40x56-on-48x160"
+    bank, idx, G, M, Hc, Wc = Pc.case(name)
+    dbank, dG, didx = cuda(bank), cuda(G), cuda(idx, torch.int32)
+    r = align.panorama(dbank, dG, idx=idx, canvas=(Hc, Wc), feather=8.0, mode="two_band", band_sigma=Bc.SIGMA)
+    assert set(r) == PANO_KEYS | {"panorama_winner"} and calls == ["blur_u8", "pano_bands_u8"]
+    assert r["panorama_winner"].shape == (2, Hc, Wc) and r["panorama_winner"].dtype == torch.uint8
+    low = align.blur_u8(dbank, Bc.SIGMA, didx)
+    del calls[:]
+    again = align.panorama(dbank, dG, idx=idx, canvas=(Hc, Wc), feather=8.0, mode="two_band", band_sigma=Bc.SIGMA, low=low)
+    assert calls == ["pano_bands_u8"] and all(torch.equal(again[k], r[k]) for k in r)          # the internal bank's bits
+    keep = Bc.compared(name, 8.0)
+    want, want_count, want_winner = Bc.reference(name, 8.0, False)
+    d, share = Mc.differing_share(host(r["panorama"])[keep], want[keep])
+    assert d <= 1 and share <= CAP and np.array_equal(host(r["panorama_winner"])[keep], want_winner[keep])
+    # the default sigma is 4; a gain runs; the other modes keep their keys and their launches
+    assert set(align.panorama(dbank, dG, idx=idx, canvas="ref", mode="two_band", gain=cuda(Pc.gain_of(5, 2)))) == PANO_KEYS | {"panorama_winner"}
+    del calls[:]
+    plain = align.panorama(dbank, dG, idx=idx, canvas=(Hc, Wc), feather=8.0, band_sigma=99.0)
+    assert set(plain) == PANO_KEYS and calls == ["pano_u8"] and torch.equal(plain["panorama_count"], r["panorama_count"])
+
+
+def test_mosaic_two_band():
+    name = "48x80-and-40x56-fitted-64x96-vector"
+    A, B, Ma, Mb, Hc, Wc = Mc.case(name)
+    H = cuda(np.stack([Mc.corner_homography(11 + b, 48, 80, 40, 56) for b in range(2)]))
+    a, b = cuda(A), cuda(B)
+    r = align.mosaic(a, b, H, canvas=(Hc, Wc), feather=8.0, mode="two_band", band_sigma=Bc.SIGMA)
+    plain = align.mosaic(a, b, H, canvas=(Hc, Wc), feather=8.0)
+    assert set(plain) == MOSAIC_KEYS and set(r) == MOSAIC_KEYS | {"mosaic_winner"}
+    assert all(torch.equal(r[k], plain[k]) for k in MOSAIC_KEYS - {"mosaic"})
+    Ma_dev = (H @ r["mosaic_T"]).contiguous()
+    want = align.mosaic_bands_u8(a, align.blur_u8(a, Bc.SIGMA), b, align.blur_u8(b, Bc.SIGMA), Ma_dev, r["mosaic_T"], Hc, Wc, 8.0)
+    assert torch.equal(r["mosaic"], want[0]) and torch.equal(r["mosaic_cover"], want[1]) and torch.equal(r["mosaic_winner"], want[2])
+    single = (r["mosaic_cover"] == 1) | (r["mosaic_cover"] == 2)
+    assert torch.equal(r["mosaic"][single], plain["mosaic"][single]) and single.any()          # one image present: every mode's value
+    g = align.mosaic(a, b, H, canvas="b", mode="two_band", exposure="gain")
+    assert set(g) == MOSAIC_KEYS | {"mosaic_winner"} and g["mosaic_gain"].shape == (2, 2)
+
+
+def test_the_aligner_in_two_band_mode_with_a_stub_model():
+    frames, deltas, _, _ = Pc.aligner_sequence()
+    aligner, bank = stub_aligner(deltas), cuda(frames)
+    Hc, Wc = 120, 320
+    s = aligner.sequence(bank, ref=1, canvas=(Hc, Wc), feather=16.0, mode="two_band", band_sigma=2.0)
+    assert set(s) == SEQ_KEYS | PANO_KEYS | {"panorama_winner"}
+    m = align.panorama(bank, s["G"], canvas=(Hc, Wc), feather=16.0, mode="two_band", band_sigma=2.0)
+    assert all(torch.equal(m[k], s[k]) for k in PANO_KEYS | {"panorama_winner"})
+    f = aligner.sequence(bank, ref=1, canvas=(Hc, Wc), feather=16.0)
+    assert set(f) == SEQ_KEYS | PANO_KEYS and torch.equal(f["panorama_count"], s["panorama_count"])
+    # the frames come from one texture: where they overlap they agree, so the two-band canvas is close to the feathered one
+    both = s["panorama_count"] >= 2
+    assert both.any() and (s["panorama"].int() - f["panorama"].int()).abs()[both].float().mean().item() < 3.0
+    one = s["panorama_count"] == 1
+    assert torch.equal(s["panorama"][one], f["panorama"][one])
+    e = aligner.sequence(bank, ref=1, canvas="ref", mode="two_band", exposure="gain")
+    assert set(e) == SEQ_KEYS | PANO_KEYS | {"panorama_winner"} and e["panorama_gain"].shape == (1, 4, 2)
+    A, B, delta, _ = Mc.aligner_pair()
+    pair = stub_aligner(delta)
+    r = pair(cuda(A), cuda(B), mosaic="b", mosaic_mode="two_band", mosaic_band_sigma=2.0)
+    assert set(r) == PLAIN_KEYS | MOSAIC_KEYS | {"mosaic_winner"}
+    m = align.mosaic(cuda(A), cuda(B), r["H"], mode="two_band", band_sigma=2.0)
+    assert all(torch.equal(m[k], r[k]) for k in MOSAIC_KEYS | {"mosaic_winner"})
+    assert set(pair(cuda(A), cuda(B), mosaic="b")) == PLAIN_KEYS | MOSAIC_KEYS
+
+
+def test_arguments_are_refused_before_any_launch(monkeypatch):
+    launches = []
+    for name in ("align_prep_u8", "pano_u8", "pano_chain", "pano_frame", "gray_pyramid_u8", "mosaic_u8", "blur_u8", "pano_bands_u8", "mosaic_bands_u8"):
+        fn = getattr(K, name)
+        monkeypatch.setattr(K, name, lambda *a, _fn=fn, **k: launches.append(1) or _fn(*a, **k))
+    frames, deltas, _, _ = Pc.aligner_sequence()
+    aligner, bank = stub_aligner(deltas), cuda(frames)
+    G = torch.eye(3, dtype=torch.float64, device="cuda").repeat(1, 4, 1, 1)
+    low = torch.zeros((1, 4) + tuple(bank.shape[1:]), dtype=torch.uint8, device="cuda")
+    sigmas = [dict(band_sigma=s) for s in (float("nan"), 0.49, 10.6, 0.0, -1.0, float("inf"), None, "4")]
+    for kw in sigmas:
+        with pytest.raises(ValueError, match="band_sigma"):
+            aligner.sequence(bank, canvas="ref", mode="two_band", **kw)
+        with pytest.raises(ValueError, match="band_sigma"):
+            align.panorama(bank, G, mode="two_band", **kw)
+        with pytest.raises(ValueError, match="band_sigma"):
+            align.mosaic(bank, bank, G[0], mode="two_band", **kw)
+        with pytest.raises(ValueError, match="mosaic_band_sigma"):
+            aligner(bank, bank, mosaic="b", mosaic_mode="two_band", mosaic_band_sigma=kw["band_sigma"])
+    for kw in (dict(low=low), dict(low=low, mode="first"),                                     # a low bank with another mode
+               dict(mode="two_band", low=low[:, :3]), dict(mode="two_band", low=low[0]), dict(mode="two_band", low=low.cpu()),
+               dict(mode="two_band", low=low.float()), dict(mode="two_band", low=host(low)), dict(mode="two_band", low=low[:, :, :, :-1]),
+               dict(mode="two_band", feather=0.5), dict(mode="two_bands"), dict(mode="two_band", canvas=(1, 96))):
+        with pytest.raises(ValueError):
+            align.panorama(bank, G, **kw)
+    with pytest.raises(TypeError):
+        aligner.sequence(bank, canvas="ref", mode="two_band", low=low)    # the sequence makes its own bank
+    assert not launches                                                    # every refusal came before any launch
+    assert set(align.panorama(bank, G, mode="two_band", low=low)) == PANO_KEYS | {"panorama_winner"} and launches
