@@ -43,7 +43,7 @@ patch_1 is A's coordinate H_prev A_b q, hence H_k = H_prev A_b H_p(delta_k) A_b^
 only where it raises the zero-mean normalised correlation of the two patches over the fully covered pixels (bh_patch_ncc), decided per
 sample on the device.  Stated below as sample_host / grid_map / prep_warp_host / patch_ncc_host / cascade_compose.
 
-Mosaic (optional, `aligner(..., mosaic="b")` / `mosaic=(Hc, Wc)` / `mosaic`; csrc/mosaic.hip): the warp alone gives "A on B's grid" - what
+Mosaic (optional, `aligner(..., mosaic="b")` / `mosaic=(Hc, Wc)` / `mosaic`; csrc/blend.hip): the warp alone gives "A on B's grid" - what
 of A falls outside B's frame is lost and inside it the two are never combined.  bh_mosaic_u8 puts both on one canvas in one pass: with T
 from canvas index coordinates to B's (the identity for canvas "b"; else `mosaic_frame_host`: the bounding box of B's extent and of A's
 corners projected through H^-1 - clamped to `limit` image sizes around B, so that a garbage H cannot shrink B to a dot - scaled and centred
@@ -64,7 +64,7 @@ united with the clamped corners of every usable frame; `_corner_box` / `_fit_can
 highest frame present, count = the number present.  For n = 2 both equal the pair's results bit for bit.  bh_pano_u8 makes the canvas
 in one pass, and a wavefront none of whose pixels has a frame present takes no tap of it.
 
-Two-band blend (mode "two_band" of `mosaic`, `panorama`, the aligner's mosaic and `Aligner.sequence`; csrc/blur.hip, csrc/bands.hip):
+Two-band blend (mode "two_band" of `mosaic`, `panorama`, the aligner's mosaic and `Aligner.sequence`; csrc/blur.hip, csrc/blend.hip):
 wherever two frames disagree by a pixel or two a feather doubles edges over the whole overlap, and a narrow feather shows the exposure
 step instead.  So every frame is split into a LOW band - `blur_host`, a Gaussian of `band_sigma` frame pixels in integer arithmetic
 with the taps of `blur_taps`, bit for bit what bh_blur_u8 makes - and a HIGH band, frame minus low (Burt & Adelson; two bands as in Brown
@@ -202,7 +202,7 @@ def _round_u8(values):
 # ------------------------------------------------------------------------------------------------
 # mosaic, the definitions (numpy float64; include/bihome.h "Mosaic" states the same in C terms)
 # ------------------------------------------------------------------------------------------------
-MOSAIC_MODES = ("feather", "b_over_a", "a_over_b")
+MOSAIC_MODES = tuple(K.MOSAIC_MODES)          # ("feather", "b_over_a", "a_over_b"): kernels.py has the BH_MOSAIC_* numbers
 
 
 def _corner_box(H, size_a, size_b, limit):
@@ -255,6 +255,16 @@ def mosaic_frame_host(H, size_a, size_b, canvas, limit=2.0):
     return T, bbox, fitted[:, 0]
 
 
+def _border_weight_host(M, size, present, feather, Hc, Wc):
+    """The weight of a frame of size = (Hs, Ws) on a canvas it is projected to through M [B,3,3]: min(distance of the projected point to
+    the border of the frame + 1, feather) where present [B,Hc,Wc] holds, else 0 -> [B,Hc,Wc] float64."""
+    Hs, Ws = size
+    with np.errstate(all="ignore"):
+        points = [_project_host(M[b], Hc, Wc) for b in range(present.shape[0])]
+        w = np.stack([np.minimum(np.minimum(np.minimum(pu, Ws - 1 - pu), np.minimum(pv, Hs - 1 - pv)) + 1.0, feather) for pu, pv, _ in points])
+    return np.where(present, w, 0.0)
+
+
 def _blend_host(frames, feather, mode):
     """The blend statement of the mosaic and the panorama.  frames yields, in order, (values float64 [B,Hc,Wc,3] (`_sample_host`), present
     bool [B,Hc,Wc], M [B,3,3], (Hs, Ws), gain [B,2] = (g, o) or None) per frame; mode is 'feather', 'first' or 'last' -> (the values before
@@ -264,18 +274,12 @@ def _blend_host(frames, feather, mode):
     multiplied by 0: under the projection guard its sample is unspecified."""
     num = den = val = 0.0
     seen, planes = False, []
-    for v, present, M, (Hs, Ws), gain in frames:
-        B, Hc, Wc = present.shape
+    for v, present, M, size, gain in frames:
         P = present[..., None]
         if gain is not None:
             v = gain[:, 0, None, None, None] * v + gain[:, 1, None, None, None]
         if mode == "feather":
-            w = np.empty((B, Hc, Wc))
-            for b in range(B):
-                with np.errstate(all="ignore"):
-                    pu, pv, _ = _project_host(M[b], Hc, Wc)
-                    w[b] = np.minimum(np.minimum(np.minimum(pu, Ws - 1 - pu), np.minimum(pv, Hs - 1 - pv)) + 1.0, feather)
-            w = np.where(present, w, 0.0)[..., None]
+            w = _border_weight_host(M, size, present, feather, *present.shape[1:])[..., None]
             num = num + np.where(P, w * np.where(P, v, 0.0), 0.0)
             den = den + w
         elif mode == "first":
@@ -315,8 +319,8 @@ def mosaic_host(images_a, images_b, Ma, Mb, Hc, Wc, feather=32.0, mode="feather"
 # ------------------------------------------------------------------------------------------------
 # panorama, the definitions (numpy float64; include/bihome.h "Panorama" states the same in C terms)
 # ------------------------------------------------------------------------------------------------
-PANO_MODES = ("feather", "first", "last")
-PANO_MAX_FRAMES = 255              # count is a byte
+PANO_MODES = tuple(K.PANO_MODES)              # ("feather", "first", "last"): kernels.py has the BH_PANO_* numbers
+PANO_MAX_FRAMES = K.PANO_MAX_FRAMES           # 255: count is a byte
 
 
 def pairs_of(n, ref):
@@ -453,7 +457,7 @@ def _bands_blend_host(frames, feather):
     num = den = 0.0
     v_best = l_best = w_best = cnt = winner = None
     planes = []
-    for k, (v, l, present, M, (Hs, Ws), gain) in enumerate(frames):
+    for k, (v, l, present, M, size, gain) in enumerate(frames):
         B, Hc, Wc = present.shape
         if cnt is None:
             v_best, l_best = np.zeros((B, Hc, Wc, 3)), np.zeros((B, Hc, Wc, 3))
@@ -462,12 +466,7 @@ def _bands_blend_host(frames, feather):
         if gain is not None:
             g, o = gain[:, 0, None, None, None], gain[:, 1, None, None, None]
             v, l = g * v + o, g * l + o
-        w = np.empty((B, Hc, Wc))
-        for b in range(B):
-            with np.errstate(all="ignore"):
-                pu, pv, _ = _project_host(M[b], Hc, Wc)
-                w[b] = np.minimum(np.minimum(np.minimum(pu, Ws - 1 - pu), np.minimum(pv, Hs - 1 - pv)) + 1.0, feather)
-        w = np.where(present, w, 0.0)
+        w = _border_weight_host(M, size, present, feather, Hc, Wc)
         num = num + np.where(P, w[..., None] * np.where(P, l, 0.0), 0.0)
         den = den + w
         take = present & ((cnt == 0) | (w > w_best))

@@ -1,27 +1,16 @@
-// Panorama: the n frames of a registered sequence on one canvas, in one pass (include/bihome.h "Panorama"; bihome_amd/align.py holds the
-// numpy float64 statements chain_host / pano_frame_host / pano_host the kernels are tested against).  Upstream has nothing like it.
+// Panorama, the geometry: the chain and the canvas of a registered sequence (include/bihome.h "Panorama"; bihome_amd/align.py holds the
+// numpy float64 statements chain_host / pano_frame_host the kernels are tested against).  Upstream has nothing like it.  The blend of
+// the frames on that canvas, bh_pano_u8, is csrc/blend.hip's.
 //
 // bh_pano_chain: the n - 1 pair homographies of a sequence composed into G[k], the reference's index coordinates -> frame k's, outwards
 // from the reference; one thread per sample, double.
 // bh_pano_frame: the canvas around the reference's extent and every frame's projected corners - adjugate, corners, the usable test and
 // the clamp per frame (thread k), a min / max reduction over the workgroup, then T, the box and M[k] = G[k] T; one workgroup per sample,
 // one launch.  The reference has a size of its own, so the pair's frame (align.py mosaic_frame_device) is this kernel with n = 1.
-// bh_pano_u8: mosaic.hip's kernel with a run-time loop over the frames.  Per frame a thread first projects its pixels (u8_image.h's
-// u8_point / u8_valid: arithmetic only), and when no lane of the wavefront has the frame present the wavefront goes on to the next frame
-// without a single load (PANO_SKIP) - in a pan most canvas pixels see 0 to 3 of the n frames.  That cannot change a result: a frame
-// that is not present at a pixel is selected out, never multiplied by 0.  Else the four taps of each pixel (u8_gather), the gain, the
-// border weight and num += w v, den += w (or first / last) in registers, in the order k = 0..n-1 with every product rounded before it
-// is added: for n = 2 the result is bit for bit bh_mosaic_u8's.  Stores, offsets and clamps are mosaic.hip's; the pixels of a wavefront
-// are a compact tile, not a run of one row, because a tile is absent from more frames (PANO_TILE).  No LDS, no atomics, no scratch, one
-// writer per output element.
-#include "u8_image.h"
-#include "pano_tile.h"      // PANO_THREADS, PANO_TILE, pano_unit, pano_grid_x: shared with bands.hip
+#include "common.h"
 
+#define PANO_THREADS 256
 #define PANO_MAX_FRAMES 255
-// A/B switches for tools/pano_bench.py (make ab ABFLAGS=-DPANO_SKIP=0 / -DPANO_TILE=0); DESIGN.md section 8 "Panorama" has the figures
-#ifndef PANO_SKIP
-#define PANO_SKIP 1        // 0: every frame takes its taps at every pixel
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // the chain
@@ -134,71 +123,6 @@ __global__ void __launch_bounds__(PANO_THREADS) pano_frame_kernel(const double* 
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// the blend
-// ------------------------------------------------------------------------------------------------
-// grid (pano_grid_x, u8_grid_y(B)); PX = 4: Wc % 4 == 0 and out % 4 == 0 (count_vec: count % 4 == 0 too)
-template <int PX, bool BYTES>
-__global__ void __launch_bounds__(PANO_THREADS) pano_kernel(const unsigned char* __restrict__ images, const int* __restrict__ idx, int n_images, int Hs, int Ws,
-                                                            const double* __restrict__ M64, const double* __restrict__ gain, const unsigned char* __restrict__ use,
-                                                            int B, int n, int Hc, int Wc, float feather, int mode,
-                                                            unsigned char* __restrict__ out, unsigned char* __restrict__ count, int count_vec) {
-#pragma clang fp contract(off)
-    int x, y;
-    if (!pano_unit<PX>(Hc, Wc, x, y)) return;
-    const unsigned npix = (unsigned)Hs * (unsigned)Ws;
-    const float xmax = (float)(Ws - 1), ymax = (float)(Hs - 1);
-    for (int b = blockIdx.y; b < B; b += gridDim.y) {
-        float num[PX * 3], den[PX];
-        unsigned cnt[PX];
-#pragma unroll
-        for (int p = 0; p < PX; ++p) { num[p * 3] = num[p * 3 + 1] = num[p * 3 + 2] = den[p] = 0.0f; cnt[p] = 0u; }
-        for (int k = 0; k < n; ++k) {
-            const size_t f = (size_t)b * n + k;
-            if (use && use[f] == 0) continue;                                  // (the same for every lane)
-            const Hf M = load_h(M64 + 9 * f);
-            Tap4 t[PX];
-            bool present[PX], any = false;
-#pragma unroll
-            for (int p = 0; p < PX; ++p) {
-                t[p] = u8_point(M, x + p, y, Ws, Hs);
-                present[p] = u8_valid(t[p], xmax, ymax);
-                any = any || present[p];
-            }
-#if PANO_SKIP
-            if (!__any(any)) continue;                                         // absent from the whole wavefront: no load at all
-#endif
-            const float g = gain ? (float)gain[2 * f] : 1.0f, o = gain ? (float)gain[2 * f + 1] : 0.0f;
-            const U8Image im = u8_image(images, idx ? idx + (size_t)b * n : nullptr, k, n_images, npix);
-#pragma unroll
-            for (int p = 0; p < PX; ++p) {
-                const U8Sample s = u8_gather<BYTES>(im, t[p], xmax, ymax);
-                const float w = u8_border_weight(s, xmax, ymax, feather);
-                const bool first = cnt[p] == 0u;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float v = __builtin_fmaf(g, s.c[c], o), wv = w * v, acc = num[p * 3 + c];
-                    const float next = mode == BH_PANO_FEATHER ? acc + wv : ((mode == BH_PANO_LAST || first) ? v : acc);
-                    num[p * 3 + c] = present[p] ? next : acc;
-                }
-                den[p] = present[p] ? den[p] + w : den[p];
-                cnt[p] += present[p] ? 1u : 0u;
-            }
-        }
-        unsigned q[PX * 3];
-#pragma unroll
-        for (int p = 0; p < PX; ++p)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float v = mode == BH_PANO_FEATHER ? (den[p] > 0.0f ? num[p * 3 + c] / den[p] : 0.0f) : num[p * 3 + c];
-                q[p * 3 + c] = u8_round(v);
-            }
-        const size_t at = ((size_t)b * Hc + y) * Wc + x;
-        u8_store_pixels<PX>(out + at * 3, q);
-        if (count) u8_store_flags<PX>(count + at, cnt, count_vec);
-    }
-}
-
 // what the entry points refuse as BH_E_BADARG apart from their NULL pointers: a negative batch, a frame count outside 1..255, an extent
 // below `least`
 static bool pano_counts_bad(int count, int frames) { return count < 0 || frames < 1 || frames > PANO_MAX_FRAMES; }
@@ -221,26 +145,6 @@ int bh_pano_frame(const double* G, const uint8_t* use, int B, int n, int Hs, int
     if (B == 0) return BH_OK;
     hipLaunchKernelGGL(pano_frame_kernel, dim3((unsigned)B), dim3(PANO_THREADS), 0, bh_stream(stream), G, use, n, Hs, Ws, Hr, Wr, Hc, Wc, limit, T, bbox,
                        fitted, M);
-    BH_LAUNCH_CHECK();
-    return BH_OK;
-}
-
-int bh_pano_u8(const uint8_t* images, const int* idx, int n_images, int Hs, int Ws, const double* M, const double* gain,
-               const uint8_t* use, int B, int n, int Hc, int Wc, float feather, int mode, uint8_t* out, uint8_t* count, void* stream) {
-    if (!images || !M || !out || pano_counts_bad(B, n) || n_images < 1 || pano_extents_bad(Hs, Ws, Hc, Wc, 1)) return BH_E_BADARG;
-    if (u8_feather_bad(feather)) return BH_E_BADARG;
-    if (mode != BH_PANO_FEATHER && mode != BH_PANO_FIRST && mode != BH_PANO_LAST) return BH_E_BADARG;
-    // (bh_mosaic_u8's limits: tap_place's offsets, 32-bit byte offsets inside an image, the unit index of a thread)
-    if ((long long)Hs * Ws > (1ll << 29) || (long long)Hc * Wc > 0x7fffffffll) return BH_E_UNSUPPORTED;
-    if (B == 0) return BH_OK;
-    const U8Stores stores = u8_stores(Wc, out, count);
-    const dim3 grid(pano_grid_x(Hc, Wc, stores.vec ? 4 : 1), u8_grid_y(B));
-    hipStream_t st = bh_stream(stream);
-    const bool bytes = (long long)Hs * Ws < 2;                                 // a single-pixel frame: no room for 4-byte loads
-    u8_flags([&](auto four, auto by) {
-        hipLaunchKernelGGL((pano_kernel<four ? 4 : 1, by>), grid, dim3(PANO_THREADS), 0, st, images, idx, n_images, Hs, Ws, M, gain, use, B, n, Hc, Wc, feather,
-                           mode, out, count, stores.flag_vec);
-    }, stores.vec, bytes);
     BH_LAUNCH_CHECK();
     return BH_OK;
 }

@@ -1,4 +1,4 @@
-// The interleaved uint8 RGB bank image, spelled ONCE for the aligner (csrc/align.hip, ecc.hip, cascade.hip, mosaic.hip, pano.hip) and the bank
+// The interleaved uint8 RGB bank image, spelled ONCE for the aligner (csrc/align.hip, ecc.hip, cascade.hip, blend.hip) and the bank
 // (csrc/bank.hip): which image sample b reads, how a pixel is loaded, the bilinear sample of a pixel through a homography with its
 // validity, the border weight of a blend, the rounding to a byte, the stores of pixels and flags, the patch epilogue and the grid clamp.
 // The reason is warp_tap.h's: bh_warp_u8, bh_align_prep_warp_u8 and bh_mosaic_u8 promise ONE sample and ONE `valid` (include/bihome.h),
@@ -55,7 +55,7 @@ __device__ __forceinline__ unsigned ld_rgb_u8(const U8Image& im, unsigned pixel)
 // The bilinear sample of pixel (x, y) through H in a w x h image, xmax = (float)(w - 1), ymax = (float)(h - 1) (the caller's, computed
 // once per kernel and kept in registers it already has).  Taps outside the image contribute 0; under the guard c is unspecified.
 // valid: the projected point lies inside [0, w - 1] x [0, h - 1] and was divided.
-// The sample comes in two parts, for a kernel that decides from the validity whether it loads at all (csrc/pano.hip): u8_point, the
+// The sample comes in two parts, for a kernel that decides from the validity whether it loads at all (csrc/blend.hip): u8_point, the
 // projection with the taps placed, and u8_valid are arithmetic only; u8_gather is the four loads and their blend.  u8_sample is the
 // composition, the only form every other kernel uses.  (The Tap4 goes by VALUE into both parts: with a reference the compiler schedules
 // the kernels that call u8_sample differently; like this their code is instruction for instruction what it was before the split.)

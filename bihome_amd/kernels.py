@@ -1596,12 +1596,19 @@ def _chk_images_u8(images, idx, idx_shape, what):
         raise ValueError("%s: idx [%s] int32, got %s for %s" % (what, ",".join(names), tuple(idx.shape), ", ".join("%s = %d" % p for p in zip(names, idx_shape))))
 
 
-def _chk_canvas_u8(out, flags, B, what, names):
-    """The shapes of an output image out [B,H,W,3] and its flag plane [B,H,W] or None; names = (the plane's name, "H,W" as the message
-    spells them)."""
-    if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (flags is not None and tuple(flags.shape) != tuple(out.shape[:3])):
-        raise ValueError("%s: out [B,%s,3] uint8 and %s [B,%s] uint8 with B = %d, got %s and %s"
-                         % (what, names[1], names[0], names[1], B, tuple(out.shape), None if flags is None else tuple(flags.shape)))
+def _chk_u8(out, planes):
+    """An output image and its flag planes are uint8 device tensors."""
+    for t in [out] + [plane for _, plane in planes]:
+        _chk(t, torch.uint8)
+
+
+def _chk_canvas_u8(out, planes, B, what, hw):
+    """The shapes of an output image out [B,H,W,3] and its uint8 flag planes [B,H,W]: planes = [(name, plane or None), ...]; hw = "H,W" as
+    the message spells them.  Device and dtype are `_chk_u8`'s, which the callers run before any shape check."""
+    for name, plane in planes or [("the flag plane", None)]:
+        if out.dim() != 4 or out.shape[0] != B or out.shape[3] != 3 or (plane is not None and tuple(plane.shape) != tuple(out.shape[:3])):
+            raise ValueError("%s: out [B,%s,3] uint8 and %s [B,%s] uint8 with B = %d, got %s and %s"
+                             % (what, hw, name, hw, B, tuple(out.shape), None if plane is None else tuple(plane.shape)))
 
 
 def _mode_number(mode, modes, what):
@@ -1635,11 +1642,11 @@ def warp_u8(images, H64, out, valid=None, idx=None):
     """out [B,Ho,Wo,3] uint8 = round_half_up(bilinear images[idx[b]](H64[b] (x, y, 1))) with zero padding, and valid [B,Ho,Wo] uint8
     (may be None) (include/bihome.h bh_warp_u8).  Both outputs are the caller's (bihome_amd.align.warp_u8 allocates them).  H64 [B,3,3]
     or [B,9] float64: output index coordinates -> source index coordinates."""
-    _chk(H64, torch.float64); _chk(out, torch.uint8); _chk(valid, torch.uint8)
+    _chk(H64, torch.float64); _chk_u8(out, [("valid", valid)])
     if not _is_h(H64):
         raise ValueError("warp_u8: H64 [B,3,3] float64, got %s" % (tuple(H64.shape),))
     B = H64.shape[0]
-    _chk_canvas_u8(out, valid, B, "warp_u8", ("valid", "Ho,Wo"))
+    _chk_canvas_u8(out, [("valid", valid)], B, "warp_u8", "Ho,Wo")
     _chk_images_u8(images, idx, (B,), "warp_u8")
     check(lib.bh_warp_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(H64), B, out.shape[1], out.shape[2],
                          _p(out), _p(valid), _stream()), "bh_warp_u8")
@@ -1771,9 +1778,25 @@ def patch_ncc(w, t, cover, out):
 
 
 # ------------------------------------------------------------------------------------------------
-# mosaic: both images of an aligned pair on one canvas, feathered, in one pass (bihome_amd/align.py; csrc/mosaic.hip)
+# mosaic: both images of an aligned pair on one canvas, feathered, in one pass (bihome_amd/align.py; csrc/blend.hip, the pair walk)
 # ------------------------------------------------------------------------------------------------
 MOSAIC_MODES = {"feather": 0, "b_over_a": 1, "a_over_b": 2}          # include/bihome.h BH_MOSAIC_*
+
+
+def _chk_pair_blend(what, images_a, images_b, Ma, Mb, gain, out, planes, idx_a, idx_b):
+    """What mosaic_u8 and mosaic_bands_u8 check in common -> B."""
+    _chk(Ma, torch.float64); _chk(Mb, torch.float64); _chk(gain, torch.float64); _chk_u8(out, planes)
+    for M, name in ((Ma, "Ma"), (Mb, "Mb")):
+        if not _is_h(M):
+            raise ValueError("%s: %s [B,3,3] float64, got %s" % (what, name, tuple(M.shape)))
+    B = Ma.shape[0]
+    if Mb.shape[0] != B or (gain is not None and tuple(gain.shape) != (B, 2)):
+        raise ValueError("%s: Ma and Mb [B,3,3] and gain [B,2] float64 with one B, got %s, %s and %s"
+                         % (what, tuple(Ma.shape), tuple(Mb.shape), None if gain is None else tuple(gain.shape)))
+    _chk_canvas_u8(out, planes, B, what, "Hc,Wc")
+    _chk_images_u8(images_a, idx_a, (B,), what)
+    _chk_images_u8(images_b, idx_b, (B,), what)
+    return B
 
 
 def mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=None, idx_a=None, idx_b=None):
@@ -1782,18 +1805,8 @@ def mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=None, 
     (include/bihome.h bh_mosaic_u8).  feather >= 1 caps the border-distance weights; mode is 'feather', 'b_over_a' or 'a_over_b' (or
     its BH_MOSAIC_* number); gain [B,2] float64 (g, o) turns A's value into g a + o (None: unchanged).  Both outputs are the caller's
     (bihome_amd.align.mosaic_u8 allocates them)."""
-    _chk(Ma, torch.float64); _chk(Mb, torch.float64); _chk(gain, torch.float64); _chk(out, torch.uint8); _chk(cover, torch.uint8)
-    for M, what in ((Ma, "Ma"), (Mb, "Mb")):
-        if not _is_h(M):
-            raise ValueError("mosaic_u8: %s [B,3,3] float64, got %s" % (what, tuple(M.shape)))
-    B = Ma.shape[0]
-    if Mb.shape[0] != B or (gain is not None and tuple(gain.shape) != (B, 2)):
-        raise ValueError("mosaic_u8: Ma and Mb [B,3,3] and gain [B,2] float64 with one B, got %s, %s and %s"
-                         % (tuple(Ma.shape), tuple(Mb.shape), None if gain is None else tuple(gain.shape)))
-    _chk_canvas_u8(out, cover, B, "mosaic_u8", ("cover", "Hc,Wc"))
+    B = _chk_pair_blend("mosaic_u8", images_a, images_b, Ma, Mb, gain, out, [("cover", cover)], idx_a, idx_b)
     mode = _mode_number(mode, MOSAIC_MODES, "mosaic_u8")
-    _chk_images_u8(images_a, idx_a, (B,), "mosaic_u8")
-    _chk_images_u8(images_b, idx_b, (B,), "mosaic_u8")
     check(lib.bh_mosaic_u8(_p(images_a), _p(idx_a), images_a.shape[0], images_a.shape[1], images_a.shape[2],
                            _p(images_b), _p(idx_b), images_b.shape[0], images_b.shape[1], images_b.shape[2],
                            _p(Ma), _p(Mb), _p(gain), B, out.shape[1], out.shape[2], float(feather), mode, _p(out), _p(cover), _stream()),
@@ -1802,7 +1815,8 @@ def mosaic_u8(images_a, images_b, Ma, Mb, out, cover, feather, mode, gain=None, 
 
 
 # ------------------------------------------------------------------------------------------------
-# panorama: the n frames of a registered sequence on one canvas (bihome_amd/align.py; csrc/pano.hip).  Every buffer is the caller's.
+# panorama: the n frames of a registered sequence on one canvas (bihome_amd/align.py; csrc/pano.hip, and csrc/blend.hip's sequence walk).
+# Every buffer is the caller's.
 # ------------------------------------------------------------------------------------------------
 PANO_MODES = {"feather": 0, "first": 1, "last": 2}                    # include/bihome.h BH_PANO_*
 PANO_MAX_FRAMES = 255
@@ -1852,22 +1866,28 @@ def pano_frame(G, size, canvas, limit, T, bbox=None, fitted=None, M=None, use=No
     return T, bbox, fitted, M
 
 
+def _chk_seq_blend(what, images, idx, M, gain, use, out, planes):
+    """What pano_u8 and pano_bands_u8 check in common -> (B, n)."""
+    _chk(M, torch.float64); _chk(gain, torch.float64); _chk(use, torch.uint8); _chk_u8(out, planes)
+    if not _is_hn(M):
+        raise ValueError("%s: M [B,n,3,3] float64 with 1 <= n <= %d, got %s" % (what, PANO_MAX_FRAMES, tuple(M.shape)))
+    B, n = M.shape[:2]
+    if (gain is not None and tuple(gain.shape) != (B, n, 2)) or (use is not None and tuple(use.shape) != (B, n)):
+        raise ValueError("%s: gain [B,n,2] float64 and use [B,n] uint8 with B = %d, n = %d, got %s and %s"
+                         % (what, B, n, None if gain is None else tuple(gain.shape), None if use is None else tuple(use.shape)))
+    _chk_canvas_u8(out, planes, B, what, "Hc,Wc")
+    _chk_images_u8(images, idx, (B, n), what)
+    return B, n
+
+
 def pano_u8(images, idx, M, out, count, feather, mode, gain=None, use=None):
     """out [B,Hc,Wc,3] uint8 = the n frames images[idx[b,k]] (one uint8 bank [N,Hs,Ws,3], idx [B,n] int32 or None: frame k is image k)
     on a canvas whose index coordinates M [B,n,3,3] float64 map to frame k's, count [B,Hc,Wc] uint8 (may be None) the number of frames
     present (include/bihome.h bh_pano_u8; bihome_amd.align.pano_host).  mode is 'feather', 'first' or 'last' (or its BH_PANO_* number);
     gain [B,n,2] float64 (g, o) per frame and use [B,n] uint8 (0: the frame is left out) may be None.  Both outputs are the caller's
     (bihome_amd.align.pano_u8 allocates them)."""
-    _chk(M, torch.float64); _chk(gain, torch.float64); _chk(use, torch.uint8); _chk(out, torch.uint8); _chk(count, torch.uint8)
-    if not _is_hn(M):
-        raise ValueError("pano_u8: M [B,n,3,3] float64 with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, tuple(M.shape)))
-    B, n = M.shape[:2]
-    if (gain is not None and tuple(gain.shape) != (B, n, 2)) or (use is not None and tuple(use.shape) != (B, n)):
-        raise ValueError("pano_u8: gain [B,n,2] float64 and use [B,n] uint8 with B = %d, n = %d, got %s and %s"
-                         % (B, n, None if gain is None else tuple(gain.shape), None if use is None else tuple(use.shape)))
-    _chk_canvas_u8(out, count, B, "pano_u8", ("count", "Hc,Wc"))
+    B, n = _chk_seq_blend("pano_u8", images, idx, M, gain, use, out, [("count", count)])
     mode = _mode_number(mode, PANO_MODES, "pano_u8")
-    _chk_images_u8(images, idx, (B, n), "pano_u8")
     check(lib.bh_pano_u8(_p(images), _p(idx), images.shape[0], images.shape[1], images.shape[2], _p(M), _p(gain), _p(use), B, n,
                          out.shape[1], out.shape[2], float(feather), mode, _p(out), _p(count), _stream()), "bh_pano_u8")
     return out, count
@@ -1875,7 +1895,7 @@ def pano_u8(images, idx, M, out, count, feather, mode, gain=None, use=None):
 
 # ------------------------------------------------------------------------------------------------
 # two-band blend: the low band of uint8 frames, and the mosaic / panorama that blends it with the feather and takes the high band from one
-# frame per pixel (bihome_amd/align.py; csrc/blur.hip, csrc/bands.hip).  Every buffer is the caller's.
+# frame per pixel (bihome_amd/align.py; csrc/blur.hip, and csrc/blend.hip's two walks with its band rule).  Every buffer is the caller's.
 # ------------------------------------------------------------------------------------------------
 BLUR_MAX_RADIUS = 32
 
@@ -1899,28 +1919,13 @@ def blur_u8(images, out, taps, idx=None):
     return out
 
 
-def _chk_flag_plane(plane, out, what, name):
-    _chk(plane, torch.uint8)
-    if plane is not None and tuple(plane.shape) != tuple(out.shape[:3]):
-        raise ValueError("%s: %s [B,Hc,Wc] uint8 like out, got %s" % (what, name, tuple(plane.shape)))
-
-
 def pano_bands_u8(images, low, idx, M, out, count, winner, feather, gain=None, use=None):
     """out [B,Hc,Wc,3] uint8 = the two-band blend of the n frames images[idx[b,k]] with their low bands low [B,n,Hs,Ws,3] (or [B n,Hs,Ws,3])
     uint8 on a canvas whose index coordinates M [B,n,3,3] float64 map to frame k's; count [B,Hc,Wc] uint8 the number of frames present and
     winner [B,Hc,Wc] uint8 the frame the high band comes from, 255 for none (either may be None) (include/bihome.h bh_pano_bands_u8;
     bihome_amd.align.bands_host).  gain and use as in pano_u8.  The outputs are the caller's (bihome_amd.align.pano_bands_u8 allocates)."""
-    _chk(M, torch.float64); _chk(gain, torch.float64); _chk(use, torch.uint8); _chk(out, torch.uint8); _chk(low, torch.uint8)
-    if not _is_hn(M):
-        raise ValueError("pano_bands_u8: M [B,n,3,3] float64 with 1 <= n <= %d, got %s" % (PANO_MAX_FRAMES, tuple(M.shape)))
-    B, n = M.shape[:2]
-    if (gain is not None and tuple(gain.shape) != (B, n, 2)) or (use is not None and tuple(use.shape) != (B, n)):
-        raise ValueError("pano_bands_u8: gain [B,n,2] float64 and use [B,n] uint8 with B = %d, n = %d, got %s and %s"
-                         % (B, n, None if gain is None else tuple(gain.shape), None if use is None else tuple(use.shape)))
-    _chk_canvas_u8(out, count, B, "pano_bands_u8", ("count", "Hc,Wc"))
-    _chk_flag_plane(count, out, "pano_bands_u8", "count")
-    _chk_flag_plane(winner, out, "pano_bands_u8", "winner")
-    _chk_images_u8(images, idx, (B, n), "pano_bands_u8")
+    _chk(low, torch.uint8)
+    B, n = _chk_seq_blend("pano_bands_u8", images, idx, M, gain, use, out, [("count", count), ("winner", winner)])
     if low.numel() != B * n * images[0].numel() or tuple(low.shape[-3:]) != tuple(images.shape[1:]) or tuple(low.shape[:-3]) not in ((B, n), (B * n,)):
         raise ValueError("pano_bands_u8: low [B,n,Hs,Ws,3] uint8 with B = %d, n = %d and the frames' size %s, got %s"
                          % (B, n, tuple(images.shape[1:3]), tuple(low.shape)))
@@ -1933,19 +1938,8 @@ def mosaic_bands_u8(images_a, low_a, images_b, low_b, Ma, Mb, out, cover, winner
     """out [B,Hc,Wc,3] uint8 = the two-band blend of images_a[idx_a[b]] and images_b[idx_b[b]] with their low bands low_a [B,Ha,Wa,3] and
     low_b [B,Hb,Wb,3] uint8 (in sample order); cover as in mosaic_u8, winner [B,Hc,Wc] uint8 = 0 for A, 1 for B, 255 for none (either may be
     None) (include/bihome.h bh_mosaic_bands_u8; bihome_amd.align.mosaic_bands_host).  The outputs are the caller's."""
-    _chk(Ma, torch.float64); _chk(Mb, torch.float64); _chk(gain, torch.float64); _chk(out, torch.uint8); _chk(low_a, torch.uint8); _chk(low_b, torch.uint8)
-    for M, what in ((Ma, "Ma"), (Mb, "Mb")):
-        if not _is_h(M):
-            raise ValueError("mosaic_bands_u8: %s [B,3,3] float64, got %s" % (what, tuple(M.shape)))
-    B = Ma.shape[0]
-    if Mb.shape[0] != B or (gain is not None and tuple(gain.shape) != (B, 2)):
-        raise ValueError("mosaic_bands_u8: Ma and Mb [B,3,3] and gain [B,2] float64 with one B, got %s, %s and %s"
-                         % (tuple(Ma.shape), tuple(Mb.shape), None if gain is None else tuple(gain.shape)))
-    _chk_canvas_u8(out, cover, B, "mosaic_bands_u8", ("cover", "Hc,Wc"))
-    _chk_flag_plane(cover, out, "mosaic_bands_u8", "cover")
-    _chk_flag_plane(winner, out, "mosaic_bands_u8", "winner")
-    _chk_images_u8(images_a, idx_a, (B,), "mosaic_bands_u8")
-    _chk_images_u8(images_b, idx_b, (B,), "mosaic_bands_u8")
+    _chk(low_a, torch.uint8); _chk(low_b, torch.uint8)
+    B = _chk_pair_blend("mosaic_bands_u8", images_a, images_b, Ma, Mb, gain, out, [("cover", cover), ("winner", winner)], idx_a, idx_b)
     for low, images, what in ((low_a, images_a, "low_a"), (low_b, images_b, "low_b")):
         if tuple(low.shape) != (B,) + tuple(images.shape[1:]):
             raise ValueError("mosaic_bands_u8: %s [B,H,W,3] uint8 with B = %d and its images' size %s, got %s" % (what, B, tuple(images.shape[1:3]), tuple(low.shape)))

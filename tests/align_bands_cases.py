@@ -80,8 +80,8 @@ def compared(name, feather):
 # the kernel's arithmetic in float32 numpy
 # ------------------------------------------------------------------------------------------------
 def bands_f32(images, low, idx, M, Hc, Wc, feather, gain=None, use=None):
-    """csrc/bands.hip pano_bands_kernel in float32 numpy (align_mosaic_cases.sample_f32 for the frame and, at the same taps, its low band;
-    band_add / band_value) -> (out uint8 [B,Hc,Wc,3], count uint8 [B,Hc,Wc], winner uint8 [B,Hc,Wc])."""
+    """csrc/blend.hip blend_seq_kernel<BandRule> in float32 numpy (align_mosaic_cases.sample_f32 for the frame and, at the same taps, its low band;
+    BandRule's add / value) -> (out uint8 [B,Hc,Wc,3], count uint8 [B,Hc,Wc], winner uint8 [B,Hc,Wc])."""
     f = np.float32
     B, n = idx.shape
     low = np.asarray(low).reshape((B, n) + images.shape[1:])

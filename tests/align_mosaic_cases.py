@@ -68,7 +68,7 @@ def differing_share(got, want):
 # the kernel's arithmetic in float32 numpy
 # ------------------------------------------------------------------------------------------------
 def sample_f32(image, M, Ho, Wo, feather):
-    """What csrc/mosaic.hip mosaic_kernel takes of one image, in float32 numpy: csrc/u8_image.h's u8_sample (align_cases.sample_f32),
+    """What csrc/blend.hip mosaic_kernel takes of one image, in float32 numpy: csrc/u8_image.h's u8_sample (align_cases.sample_f32),
     whose `valid` is the presence, and the border weight u8_border_weight.  -> (value float32 [Ho,Wo,3], weight, present)"""
     f = np.float32
     Hs, Ws = image.shape[:2]
@@ -80,7 +80,7 @@ def sample_f32(image, M, Ho, Wo, feather):
 
 
 def mosaic_f32(images_a, images_b, Ma, Mb, Hc, Wc, feather, mode, gain=None):
-    """csrc/mosaic.hip mosaic_kernel in float32 numpy -> (out uint8 [B,Hc,Wc,3], cover uint8 [B,Hc,Wc])."""
+    """csrc/blend.hip mosaic_kernel in float32 numpy -> (out uint8 [B,Hc,Wc,3], cover uint8 [B,Hc,Wc])."""
     f = np.float32
     B = len(Ma)
     out, cover = np.empty((B, Hc, Wc, 3), np.uint8), np.empty((B, Hc, Wc), np.uint8)
@@ -135,6 +135,27 @@ def translation_want(mode, feather, gain, pa, pb, a, b, da, db):
         val = np.where(pa[..., None], a, b)
     val = np.where((pa | pb)[..., None], val, 0.0)
     return np.floor(np.clip(val, 0, 255) + 0.5).astype(np.uint8), (pa.astype(np.uint8) | (pb.astype(np.uint8) << 1))
+
+
+# ------------------------------------------------------------------------------------------------
+# single-pixel images in a pair: the byte-load instances of the pair kernels on both store paths
+# ------------------------------------------------------------------------------------------------
+EXACT_FEATHER, EXACT_GAIN = 2.0, (0.5, 4.0)
+
+
+@functools.lru_cache(maxsize=None)
+def single_pixel_pairs():
+    """[(A, Ma, B, Mb, Hc, Wc)] with two samples each: a 1 x 1 image as A, as B and as both, next to a 6 x 9 image, on an 8 x 8 canvas (four
+    pixels per thread) and a 5 x 7 one (one pixel per thread, odd width).  The single pixel lies on canvas pixel (2, 2) of sample 0 and
+    (3, 2) of sample 1, the 6 x 9 image is shifted down by one row, so every sample is a pixel; with EXACT_FEATHER the weights are 1 or 2
+    (2 for the 6 x 9 image where it meets the single pixel) and with EXACT_GAIN every value is a multiple of 1/2: sums and quotients are
+    exact or thirds, never within rounding of a half, and float32 gives the float64 statement's bits at EVERY pixel."""
+    one, big = np.array([[[[200, 100, 50]]], [[[10, 20, 31]]]], np.uint8), pixels(2, 6, 9, seed=7)
+    M1 = np.array([[[0.5, 0, -1], [0, 0.5, -1], [0, 0, 1]], [[0.5, 0, -1.5], [0, 0.5, -1], [0, 0, 1]]])
+    Mt = np.array([[[1.0, 0, 0], [0, 1, -1], [0, 0, 1]]] * 2)
+    for x in (one, M1, Mt):
+        x.setflags(write=False)
+    return [(A, Ma, B, Mb, Hc, Wc) for Hc, Wc in ((8, 8), (5, 7)) for (A, Ma), (B, Mb) in (((one, M1), (big, Mt)), ((big, Mt), (one, M1)), ((one, M1), (one[::-1], M1)))]
 
 
 # ------------------------------------------------------------------------------------------------

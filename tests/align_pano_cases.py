@@ -83,7 +83,7 @@ def near_border(name):
 # the kernel's arithmetic in float32 numpy
 # ------------------------------------------------------------------------------------------------
 def pano_f32(images, idx, M, Hc, Wc, feather, mode, gain=None, use=None):
-    """csrc/pano.hip pano_kernel in float32 numpy (align_mosaic_cases.sample_f32 per frame) -> (out uint8 [B,Hc,Wc,3], count uint8 [B,Hc,Wc])."""
+    """csrc/blend.hip pano_kernel in float32 numpy (align_mosaic_cases.sample_f32 per frame) -> (out uint8 [B,Hc,Wc,3], count uint8 [B,Hc,Wc])."""
     f = np.float32
     B, n = idx.shape
     out, count = np.empty((B, Hc, Wc, 3), np.uint8), np.zeros((B, Hc, Wc), np.uint8)

@@ -1,4 +1,4 @@
-"""The two-band blend on the device (csrc/blur.hip: bh_blur_u8; csrc/bands.hip: bh_pano_bands_u8, bh_mosaic_bands_u8; bihome_amd/align.py
+"""The two-band blend on the device (csrc/blur.hip: bh_blur_u8; csrc/blend.hip: bh_pano_bands_u8, bh_mosaic_bands_u8; bihome_amd/align.py
 blur_u8 / pano_bands_u8 / mosaic_bands_u8 and mode "two_band" of panorama / mosaic / Aligner) against the numpy statements of
 bihome_amd/align.py, which tests/test_align_bands_cpu.py holds to independent restatements.
 
@@ -250,7 +250,16 @@ def test_the_pair_with_images_of_two_sizes_matches_the_host_statement(monkeypatc
             assert 1 - keep.mean() <= 6e-3 and np.array_equal(host(cover)[keep], want_cover[keep]) and np.array_equal(host(winner)[keep], want_winner[keep])
             assert d <= 1 and share <= (CAP_GAIN if gain else CAP)
             assert set(np.unique(host(winner))) == {0, 1, 255}
-    assert p.verify() == 12
+    # a single pixel as A, as B and as both, on either store path: integer maps and weights, so EVERY pixel is compared, bit for bit
+    pairs = Mc.single_pixel_pairs()
+    for A, Ma, B, Mb, Hc, Wc in pairs:
+        la, lb = (align.blur_host(x, Bc.SIGMA) if x.shape[1] > 1 else 255 - x for x in (A, B))          # (a low band is any uint8 bank)
+        for gain in (None, Mc.gain_of(Mc.EXACT_GAIN, 2)):
+            want = align.mosaic_bands_host(A, la, B, lb, Ma, Mb, Hc, Wc, Mc.EXACT_FEATHER, gain)
+            got = align.mosaic_bands_u8(cuda(A), cuda(la), cuda(B), cuda(lb), cuda(Ma), cuda(Mb), Hc, Wc, Mc.EXACT_FEATHER, gain=None if gain is None else cuda(gain))
+            assert all(np.array_equal(host(x), y) for x, y in zip(got, want)), (A.shape, B.shape, Hc, Wc, gain is not None)
+            assert (want[1] == 3).sum() == 2 and (want[2][want[1] == 3] == (1 if A.shape[1] < B.shape[1] else 0)).all()          # 2 > 1: the 6 x 9 image wins
+    assert p.verify() == 12 + 6 * len(pairs)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The mosaic on the device (csrc/mosaic.hip: bh_mosaic_u8; bihome_amd/align.py mosaic_frame_device / exposure_device / mosaic /
+"""The mosaic on the device (csrc/blend.hip: bh_mosaic_u8; bihome_amd/align.py mosaic_frame_device / exposure_device / mosaic /
 Aligner(mosaic=)) against the numpy float64 statements of bihome_amd/align.py, which tests/test_align_mosaic_cpu.py holds to independent
 restatements.
 
@@ -117,6 +117,12 @@ def test_a_single_pixel_image_and_a_vanishing_denominator():
     assert out[0, 2, 2].tolist() == [200, 100, 50] and cover[0, 2, 2] == 3 and (cover == 1).sum() == 34
     out, cover = run(A, A, I3, I3, 4, 4, 8.0, "feather")                   # both single pixels, the vector path
     assert out[0, 0, 0].tolist() == [200, 100, 50] and not out[0].reshape(-1, 3)[1:].any() and cover.reshape(-1).tolist() == [3] + [0] * 15
+    for A, Ma, B, Mb, Hc, Wc in Mc.single_pixel_pairs():                   # a single pixel as A, as B and as both on either store path
+        for mode in align.MOSAIC_MODES:
+            for gain in (None, Mc.gain_of(Mc.EXACT_GAIN, 2)):
+                out, cover = run(A, B, Ma, Mb, Hc, Wc, Mc.EXACT_FEATHER, mode, gain=gain)
+                want, want_cover = align.mosaic_host(A, B, Ma, Mb, Hc, Wc, Mc.EXACT_FEATHER, mode, gain)
+                assert np.array_equal(out, want) and np.array_equal(cover, want_cover) and (cover == 3).sum() == 2, (A.shape, B.shape, Hc, Wc, mode)
     A, B = Mc.textures(1, 48, 80, seed=1), Mc.textures(1, 48, 80, seed=2)
     Ma = np.array([[[1.0, 0, 0], [0, 1, 0], [-0.125, 0, 1]]])              # qz = 1 - x / 8: exactly 0 on the column x = 8
     for mode in align.MOSAIC_MODES:

@@ -1,16 +1,19 @@
 """Device time of the two-band blend (bihome_amd/align.py blur_u8 / pano_bands_u8 / panorama(mode="two_band"); csrc/blur.hip,
-csrc/bands.hip) on tools/pano_bench.py's workload: B samples of n frames of 480 x 640 uint8, a pan of 0.45 frame widths per step, on a
+csrc/blend.hip's band rule) on tools/pano_bench.py's workload: B samples of n frames of 480 x 640 uint8, a pan of 0.45 frame widths per step, on a
 fitted 720 x 2560 canvas with feather 32.
 
     python tools/bands_bench.py [--batch 8] [--frames 8] [--height 480] [--width 640] [--canvas-height 720] [--canvas-width 2560] [--step 0.45]
-                                [--feather 32] [--rounds 21] [--reps 10] [--warmup 5]
+                                [--feather 32] [--rounds 21] [--reps 10] [--warmup 5] [--other-lib LABEL=PATH ...]
 
 One JSON line per row:
     blur      bh_blur_u8 of the B n frames at sigma 4 (radius 12) and 10.5 (radius 32) against (a) a Tensor.copy_ of the bytes read and
               written and (b) the torch formulation: the frames as a float NCHW copy, replicate padding and two conv2d calls with the
               real-valued taps (its conversion from and to uint8 is timed apart)
     bands     bh_pano_bands_u8 against bh_pano_u8 in feather mode, alternating in this one process, and the share of canvas pixels with
-              0, 1, 2, 3+ frames
+              0, 1, 2, 3+ frames.  --other-lib LABEL=PATH times bh_pano_bands_u8 of another build of the library in the same rounds
+              (tools/pano_bench.py's other_call) and reports whether its outputs are the same bits
+    pair      bh_mosaic_bands_u8 against bh_mosaic_u8 in feather mode on tools/mosaic_bench.py's workload (64 pairs on a fitted
+              640 x 960 canvas), and with --other-lib the same of the other build
     panorama  panorama(mode="two_band") end to end with and without a precomputed low bank, and panorama(mode="feather")
 
 The method is tools/pano_bench.py's: the callables of a row alternate in this one process, `--rounds` rounds (at least 20) of `--reps`
@@ -28,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bihome_amd import align, synth  # noqa: E402
 from align_bench import copy_pair, raw_call  # noqa: E402
 from datagen_bench import device_rounds  # noqa: E402
-from pano_bench import pan  # noqa: E402
+from pano_bench import other_call, pan  # noqa: E402
 
 
 def out(case, **kw):
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=21)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--other-lib", action="append", default=[], metavar="LABEL=PATH", help="another build of libbihome_hip.so whose two-band blends are timed too")
     a = ap.parse_args()
     if a.rounds < 20:
         ap.error("--rounds is at least 20: the medians compared come from that many alternating repetitions")
@@ -100,16 +104,48 @@ def main():
     low = align.blur_u8(bank, 4.0, idx).view(B * n, h, w, 3)               # (what the blend reads: sigma 4)
     res, res_f = (torch.empty((B, Hc, Wc, 3), dtype=torch.uint8, device="cuda") for _ in range(2))
     count, count_f, winner = (torch.empty((B, Hc, Wc), dtype=torch.uint8, device="cuda") for _ in range(3))
-    fns = {"bands": raw_call("bh_pano_bands_u8", bank, low, idx, B * n, h, w, M, None, None, B, n, Hc, Wc, feather, res, count, winner),
+    args = (bank, low, idx, B * n, h, w, M, None, None, B, n, Hc, Wc, feather)
+    fns = {"bands": raw_call("bh_pano_bands_u8", *args, res, count, winner),
            "pano_feather": raw_call("bh_pano_u8", bank, idx, B * n, h, w, M, None, None, B, n, Hc, Wc, feather, 0, res_f, count_f)}
+    other_libs = dict(spec.split("=", 1) for spec in a.other_lib)
+    other_out = {label: (torch.empty_like(res), torch.empty_like(count), torch.empty_like(winner)) for label in other_libs}
+    fns.update({label: other_call(path, "bh_pano_bands_u8", *args, *other_out[label]) for label, path in other_libs.items()})
     r = device_rounds(fns, a.reps, a.rounds, a.warmup)
     for fn in fns.values():
         fn()
     diff = (res.to(torch.int16) - res_f.to(torch.int16)).abs()
-    out("bh_pano_bands_u8 against bh_pano_u8 in feather mode", bands=r["bands"], pano_feather=r["pano_feather"],
+    out("bh_pano_bands_u8 against bh_pano_u8 in feather mode", **r, bands_over_other={k: round(r["bands"]["median_us"] / r[k]["median_us"], 3) for k in other_libs},
+        other_same_bits={k: all(torch.equal(x, y) for x, y in zip(o, (res, count, winner))) for k, o in other_out.items()},
         bands_over_pano_feather=round(r["bands"]["median_us"] / r["pano_feather"]["median_us"], 3), same_count=bool(torch.equal(count, count_f)),
         mean_difference_from_feather_grey_levels=round(float(diff.float().mean().item()), 3), largest_difference_from_feather_grey_levels=int(diff.max().item()),
         count_shares=[round(float((count == k).float().mean().item()), 3) for k in range(3)] + [round(float((count >= 3).float().mean().item()), 3)], **shape)
+
+    # the pair, on tools/mosaic_bench.py's workload
+    B2, Hc2, Wc2 = 64, 640, 960
+    images = torch.from_numpy(few).cuda().repeat(B2 // 4, 1, 1, 1).contiguous()
+    c = np.array([[0, 0], [w - 1, 0], [w - 1, h - 1], [0, h - 1]], np.float64)
+    H = torch.from_numpy(np.stack([synth.four_point_homography(c, c + rng.uniform(-0.2, 0.2, (4, 2)) * np.array([w, h])) for _ in range(B2)])).cuda()
+    T2 = align.mosaic_frame_device(H, (h, w), (h, w), (Hc2, Wc2))[0]
+    Ma, Mb = (H @ T2).contiguous(), T2.contiguous()
+    ia = torch.arange(B2, dtype=torch.int32, device="cuda")
+    ib = ia.flip(0).contiguous()
+    low_a, low_b = align.blur_u8(images, 4.0, ia), align.blur_u8(images, 4.0, ib)
+    res2, res2_f = (torch.empty((B2, Hc2, Wc2, 3), dtype=torch.uint8, device="cuda") for _ in range(2))
+    cover2, cover2_f, winner2 = (torch.empty((B2, Hc2, Wc2), dtype=torch.uint8, device="cuda") for _ in range(3))
+    args = (images, low_a, ia, B2, h, w, images, low_b, ib, B2, h, w, Ma, Mb, None, B2, Hc2, Wc2, feather)
+    fns = {"mosaic_bands": raw_call("bh_mosaic_bands_u8", *args, res2, cover2, winner2),
+           "mosaic_feather": raw_call("bh_mosaic_u8", images, ia, B2, h, w, images, ib, B2, h, w, Ma, Mb, None, B2, Hc2, Wc2, feather, 0, res2_f, cover2_f)}
+    other_out = {label: (torch.empty_like(res2), torch.empty_like(cover2), torch.empty_like(winner2)) for label in other_libs}
+    fns.update({label: other_call(path, "bh_mosaic_bands_u8", *args, *other_out[label]) for label, path in other_libs.items()})
+    r = device_rounds(fns, a.reps, a.rounds, a.warmup)
+    for fn in fns.values():
+        fn()
+    out("bh_mosaic_bands_u8 against bh_mosaic_u8 in feather mode, tools/mosaic_bench.py's workload", **r,
+        bands_over_mosaic_feather=round(r["mosaic_bands"]["median_us"] / r["mosaic_feather"]["median_us"], 3), same_cover=bool(torch.equal(cover2, cover2_f)),
+        bands_over_other={k: round(r["mosaic_bands"]["median_us"] / r[k]["median_us"], 3) for k in other_libs},
+        other_same_bits={k: all(torch.equal(x, y) for x, y in zip(o, (res2, cover2, winner2))) for k, o in other_out.items()},
+        **dict(shape, batch=B2, frames=2, canvas_height=Hc2, canvas_width=Wc2))
+    del res2, res2_f, cover2, cover2_f, winner2, other_out, images, low_a, low_b
 
     # the public function
     low5 = low.view(B, n, h, w, 3)

@@ -1,8 +1,8 @@
-"""Device time of the mosaic (bihome_amd/align.py mosaic / Aligner(mosaic=); csrc/mosaic.hip), B pairs of 480 x 640 uint8 images on a
+"""Device time of the mosaic (bihome_amd/align.py mosaic / Aligner(mosaic=); csrc/blend.hip, the pair walk), B pairs of 480 x 640 uint8 images on a
 fitted 640 x 960 canvas.
 
     python tools/mosaic_bench.py [--batch 64] [--height 480] [--width 640] [--canvas-height 640] [--canvas-width 960] [--rounds 21] [--reps 10]
-                                 [--warmup 5] [--skip-model]
+                                 [--warmup 5] [--other-lib LABEL=PATH ...] [--skip-model]
 
 One JSON line per row:
     mosaic    bh_mosaic_u8 (one launch: eight taps, weights, blend, rounding, cover) against the two-call route - bh_warp_u8 of A and of B
@@ -10,7 +10,9 @@ One JSON line per row:
               rounding as torch tensor operations - and against a Tensor.copy_ of the same bytes (A + B read, the canvas written);
               `fused_not_above_two_call` is the condition the fused kernel is kept on (its median over the rounds is not above the
               two-call route's in this run); the share of pixels on which the two results differ and the largest difference are reported
-              next to it (the two-call route rounds both warped images to uint8 before it blends them)
+              next to it (the two-call route rounds both warped images to uint8 before it blends them).  --other-lib LABEL=PATH times
+              the same entry point of another build of the library in the same rounds (tools/pano_bench.py's other_call) and reports
+              whether its output is the same bits
     exposure  the gain / bias measurement alone: two one-level gray pyramids, bh_ecc_sums, exposure_device
     aligner   Aligner end to end without and with mosaic=(Hc, Wc), zeng-bihome at random initialisation: the cost of the stage
 
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=21)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--other-lib", action="append", default=[], metavar="LABEL=PATH", help="another build of libbihome_hip.so whose bh_mosaic_u8 is timed too")
     ap.add_argument("--skip-model", action="store_true", help="kernel rows only")
     a = ap.parse_args()
     if a.rounds < 20:
@@ -73,7 +76,15 @@ def main():
     # the mosaic: one launch against two warps and the torch formulation of the blend
     res = torch.empty((B, Hc, Wc, 3), dtype=torch.uint8, device="cuda")
     cover = torch.empty((B, Hc, Wc), dtype=torch.uint8, device="cuda")
-    fused = raw_call("bh_mosaic_u8", images_a, None, B, h, w, images_b, None, B, h, w, Ma, Mb, None, B, Hc, Wc, feather, 0, res, cover)
+    args = (images_a, None, B, h, w, images_b, None, B, h, w, Ma, Mb, None, B, Hc, Wc, feather, 0)
+    fused = raw_call("bh_mosaic_u8", *args, res, cover)
+    other_out, others = {}, {}
+    if a.other_lib:
+        from pano_bench import other_call                                 # (not at the top: pano_bench imports this module's border_weight)
+    for spec in a.other_lib:
+        label, path = spec.split("=", 1)
+        other_out[label] = (torch.empty_like(res), torch.empty_like(cover))
+        others[label] = other_call(path, "bh_mosaic_u8", *args, *other_out[label])
     wa_img, wb_img = torch.empty_like(res), torch.empty_like(res)
     va, vb = torch.empty_like(cover), torch.empty_like(cover)
     warp_a = raw_call("bh_warp_u8", images_a, None, B, h, w, Ma, B, Hc, Wc, wa_img, va)
@@ -92,13 +103,15 @@ def main():
         two["cover"] = va | (vb << 1)
     moved = 2 * B * h * w * 3 + B * Hc * Wc * 4
     src, dst = copy_pair(moved)
-    r = device_rounds({"fused": fused, "two_call": two_call, "copy": lambda: dst.copy_(src)}, a.reps, a.rounds, a.warmup)
-    fused()
-    two_call()
+    r = device_rounds({"fused": fused, **others, "two_call": two_call, "copy": lambda: dst.copy_(src)}, a.reps, a.rounds, a.warmup)
+    for fn in (fused, two_call, *others.values()):
+        fn()
     differ = float((res != two["out"]).any(-1).float().mean().item())
     largest = int((res.to(torch.int16) - two["out"].to(torch.int16)).abs().max().item())
     out("bh_mosaic_u8 against two bh_warp_u8 + the torch formulation of weights and blend", fused=r["fused"], two_call=r["two_call"],
-        device_copy_same_bytes=r["copy"], bytes_moved=moved,
+        device_copy_same_bytes=r["copy"], bytes_moved=moved, **{k: r[k] for k in others},
+        fused_over_other={k: round(r["fused"]["median_us"] / r[k]["median_us"], 3) for k in others},
+        other_same_bits={k: bool(torch.equal(o, res) and torch.equal(c, cover)) for k, (o, c) in other_out.items()},
         fused_GBps=round(moved / (r["fused"]["median_us"] * 1e-6) / 1e9, 1), copy_GBps=round(moved / (r["copy"]["median_us"] * 1e-6) / 1e9, 1),
         share_of_copy_rate=round(r["copy"]["median_us"] / r["fused"]["median_us"], 3),
         fused_over_two_call=round(r["fused"]["median_us"] / r["two_call"]["median_us"], 3),
@@ -106,7 +119,7 @@ def main():
         share_of_pixels_that_differ=differ, largest_difference_grey_levels=largest, cover_differs=float((cover != two["cover"]).float().mean().item()),
         fitted=int(fitted.sum().item()), cover_shares=[round(float((cover == k).float().mean().item()), 3) for k in range(4)], **shape)
     two.clear()
-    del wa_img, wb_img, va, vb, src, dst
+    del wa_img, wb_img, va, vb, src, dst, other_out, others
 
     # the exposure measurement alone
     r = device_rounds({"exposure": lambda: align.measure_exposure(images_a, images_b, H)}, a.reps, a.rounds, a.warmup)

@@ -1,4 +1,4 @@
-"""Device time of the panorama (bihome_amd/align.py panorama / Aligner.sequence; csrc/pano.hip): B samples of n frames of 480 x 640 uint8,
+"""Device time of the panorama (bihome_amd/align.py panorama / Aligner.sequence; csrc/pano.hip, csrc/blend.hip): B samples of n frames of 480 x 640 uint8,
 a pan of 0.45 frame widths per step, on a fitted 720 x 2560 canvas.
 
     python tools/pano_bench.py [--batch 8] [--frames 8] [--height 480] [--width 640] [--canvas-height 720] [--canvas-width 2560] [--step 0.45]
