@@ -150,6 +150,8 @@ SIGNATURES = {
     "bh_blur_u8": [P, P, c_int, c_int, c_int, c_int, P, c_int, P, P],
     "bh_pano_bands_u8": [P, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P, P, P],
     "bh_mosaic_bands_u8": [P, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, c_float, P, P, P, P],
+    "bh_pano_adjust_ws_doubles": [c_int, c_int, c_int, P],
+    "bh_pano_adjust": [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P],
     "bh_maxpool3s2_fwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_maxpool3s2_bwd": [P, P, P, c_int, c_int, c_int, c_int, P],
     "bh_gap_fwd": [P, P, c_int, c_int, c_int, P],

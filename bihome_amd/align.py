@@ -71,7 +71,17 @@ with the taps of `blur_taps`, bit for bit what bh_blur_u8 makes - and a HIGH ban
 & Lowe).  The low bands are blended with the feather; the high band comes from ONE frame per pixel, the one with the largest weight
 (ties: the lowest k): value = v_winner + (sum w l / sum w - l_winner), the frame's own value where one frame is present, `winner` the
 frame chosen.  Stated below as blur_taps / blur_host / bands_host / mosaic_bands_host; bh_pano_bands_u8 and bh_mosaic_bands_u8 gather the
-frame and its low band at the same taps, eight loads per present frame."""
+frame and its low band at the same taps, eight loads per present frame.
+
+Global adjustment (`aligner.sequence(..., links=[(a, b), ...])` / `adjust`; csrc/adjust.hip): the chain composes neighbouring pairs, so
+its error grows with n and a pan that comes back, an out-and-back sweep or a raster scan does not close.  With further EDGES between
+frames that overlap - each link predicted through the chain's own estimate, `Aligner(..., init=)`, and kept only where the two frames
+correlate through it - all frames are solved jointly: the unknowns are W_k = G_k^-1 (frame k -> reference, W[2,2] = 1, the reference
+fixed), the residual of an edge (a, b) with H (b's index coordinates -> a's) at a control point y of a g x g lattice over the frame is
+proj(W_a proj(H y)) - proj(W_b y), where the two frames put one scene point in the reference's pixels, and Levenberg-Marquardt with
+bh_homography_refine_lm's rules (lambda from 1e-3 by factors of 10, a step accepted iff the cost falls with every denominator positive)
+solves the dense 8 (n - 1) system by Cholesky, one workgroup per sample, a fixed number of steps.  A sample that cannot be evaluated
+or solved keeps its start bit for bit.  Stated below as adjust_points / adjust_system_host / adjust_host."""
 import operator
 
 import numpy as np
@@ -396,6 +406,152 @@ def pano_host(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, u
             yield v, present & use[:, k, None, None], M[:, k], images.shape[1:3], gain[:, k]
     val, planes = _blend_host(frames(), feather, mode)
     return _round_u8(val), np.sum(planes, axis=0, dtype=np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------
+# global adjustment, the definitions (numpy float64; include/bihome.h "Global adjustment" states the same in C terms)
+# ------------------------------------------------------------------------------------------------
+ADJUST_MAX_FRAMES, ADJUST_MAX_EDGES = K.ADJUST_MAX_FRAMES, K.ADJUST_MAX_EDGES          # 64 frames (N = 504 unknowns), 1024 edges
+ADJUST_LAMBDA = (1e-3, 1e-12, 1e12)                                                    # the start, the floor, the ceiling
+
+
+def _adjugate(M):
+    """M [...,3,3] -> (adj [...,3,3], det [...]): the adjugate written out and the determinant by its first column."""
+    a, b, c, d, e, f, g, h, i = (M[..., r, k] for r in range(3) for k in range(3))
+    adj = np.stack([np.stack([e * i - f * h, c * h - b * i, b * f - c * e], -1), np.stack([f * g - d * i, a * i - c * g, c * d - a * f], -1),
+                    np.stack([d * h - e * g, b * g - a * h, a * e - b * d], -1)], -2)
+    return adj, (a * adj[..., 0, 0] + b * adj[..., 1, 0]) + c * adj[..., 2, 0]
+
+
+def adjust_points(size, grid):
+    """[g g,2] float64: the control points, the g x g lattice over a frame of size = (Hs, Ws), p = j g + i at
+    ((i (Ws - 1)) / (g - 1), (j (Hs - 1)) / (g - 1))."""
+    Hs, Ws = size
+    j, i = np.divmod(np.arange(grid * grid), grid)
+    return np.stack([(i * (Ws - 1)) / (grid - 1.0), (j * (Hs - 1)) / (grid - 1.0)], 1)
+
+
+def _proj(M, pts):
+    """M [3,3], pts [P,2] -> ((u, v) [P,2], qz [P])."""
+    q = pts @ M[:, :2].T + M[:, 2]
+    return q[:, :2] / q[:, 2:3], q[:, 2]
+
+
+def _adjust_jacobian(W, pts):
+    """d proj(W pts) / d W[0..7] -> [P,2,8]: (x, y, 1) / qz for the row of the coordinate, -(x, y) (u or v) / qz in columns 6, 7."""
+    uv, qz = _proj(W, pts)
+    x, y, iz = pts[:, 0] / qz, pts[:, 1] / qz, 1.0 / qz
+    J = np.zeros((len(pts), 2, 8))
+    J[:, 0, 0], J[:, 0, 1], J[:, 0, 2], J[:, 0, 6], J[:, 0, 7] = x, y, iz, -x * uv[:, 0], -y * uv[:, 0]
+    J[:, 1, 3], J[:, 1, 4], J[:, 1, 5], J[:, 1, 6], J[:, 1, 7] = x, y, iz, -x * uv[:, 1], -y * uv[:, 1]
+    return J
+
+
+def adjust_system_host(W, edges, ref, want_J=True):
+    """W [n,3,3] (frame k -> reference), edges = [(a, b, w, y [P,2], z [P,2])] of the counting edges -> (r [2 P E'], sw [2 P E'] the
+    weight of each residual, J [2 P E', N] dense or None, ok: every qz > 0): the residuals proj(W_a z_p) - proj(W_b y_p), edge after edge,
+    point after point, x before y, and their Jacobian with respect to the 8 (n - 1) unknowns (frame k's at 8 (k < ref ? k : k - 1))."""
+    n = W.shape[0]
+    N, rows = 8 * (n - 1), sum(2 * len(e[3]) for e in edges)
+    r, sw, J, ok, at = np.empty(rows), np.empty(rows), np.zeros((rows, N)) if want_J else None, True, 0
+    for a, b, w, y, z in edges:
+        m = 2 * len(y)
+        (pa, qa), (pb, qb) = _proj(W[a], z), _proj(W[b], y)
+        ok = ok and bool((qa > 0).all() and (qb > 0).all())
+        r[at:at + m], sw[at:at + m] = (pa - pb).reshape(m), w
+        if want_J:
+            for k, pts, sign in ((a, z, 1.0), (b, y, -1.0)):
+                if k != ref:
+                    c = 8 * (k if k < ref else k - 1)
+                    J[at:at + m, c:c + 8] = sign * _adjust_jacobian(W[k], pts).reshape(m, 8)
+        at += m
+    return r, sw, J, ok
+
+
+def adjust_host(G0, links, H_links, weight, ref, size, grid=4, iters=10, solver="cholesky"):
+    """The global adjustment: G0 [B,n,3,3] (the reference's index coordinates -> frame k's, `chain_host`'s), links [E,2] the edges (a, b),
+    H_links [B,E,3,3] (b's index coordinates -> a's, used as H / H[2,2]), weight [B,E] or None (all 1), size = (Hs, Ws) of the frames ->
+    (G [B,n,3,3] float64, work [B,4] = (cost at the start, cost at the result, accepted steps, final lambda)).
+    An edge COUNTS iff a != b, both are frames of the sequence and its weight is finite and > 0.  The unknowns are W_k = G_k^-1 =
+    adj(G_k) / adj(G_k)[2,2] for k != ref (8 entries each, W[2,2] = 1), W_ref = I; with y_p `adjust_points` and z_p = proj(H_e y_p) the
+    residual of edge e at p is proj(W_a z_p) - proj(W_b y_p) and cost = sum_e w_e sum_p |r|^2.  One Levenberg-Marquardt step solves
+    (J^T w J + lambda diag(J^T w J)) d = -J^T w r with the dense J of `adjust_system_host` (a frame no counting edge touches gets unit
+    rows) by Cholesky (solver="solve": np.linalg.solve, what the device bound is measured with) and is accepted iff the cost of W + d is
+    finite, every qz is > 0 and the cost fell; lambda starts at 1e-3 and moves by factors of 10 inside [1e-12, 1e12].  The sample keeps its
+    start bit for bit (both costs the start's - NaN where it cannot be evaluated -, zero accepted steps) for an entry of G0 or of a
+    counting H that is not finite, a singular G0, a qz <= 0 or a cost that is not finite at the start, a failed factorisation or a d that
+    is not finite in any step, no accepted step, or a result that is not finite.  Otherwise G_k = adj(W_k) / adj(W_k)[2,2], G_ref = I."""
+    G0 = np.asarray(G0, np.float64)
+    links = np.asarray(links, np.int64).reshape(-1, 2)
+    B, n, E = G0.shape[0], G0.shape[1], links.shape[0]
+    if G0.ndim != 4 or G0.shape[2:] != (3, 3) or not 2 <= n <= ADJUST_MAX_FRAMES or not 1 <= E <= ADJUST_MAX_EDGES or not 0 <= ref < n:
+        raise ValueError("adjust_host: G0 [B,n,3,3] with 2 <= n <= %d, 1 <= E <= %d edges and 0 <= ref < n, got %s, E = %d, ref = %r"
+                         % (ADJUST_MAX_FRAMES, ADJUST_MAX_EDGES, G0.shape, E, ref))
+    if not 2 <= grid <= 8 or iters < 0 or min(size) < 2 or solver not in ("cholesky", "solve"):
+        raise ValueError("adjust_host: grid in 2..8, iters >= 0, a frame of at least 2 x 2 and solver 'cholesky' or 'solve', got %r, %r, %r, %r" % (grid, iters, size, solver))
+    Hl = np.asarray(H_links, np.float64).reshape(B, E, 3, 3)
+    weight = np.ones((B, E)) if weight is None else np.asarray(weight, np.float64).reshape(B, E)
+    y = adjust_points(size, grid)
+    N, lam0, lam_min, lam_max = 8 * (n - 1), *ADJUST_LAMBDA
+    G, work = G0.copy(), np.empty((B, 4))
+    for s in range(B):
+        with np.errstate(all="ignore"):
+            work[s] = np.nan, np.nan, 0.0, lam0
+            counts = [e for e, (a, b) in enumerate(links.tolist()) if a != b and 0 <= a < n and 0 <= b < n and np.isfinite(weight[s, e]) and weight[s, e] > 0]
+            adj, det = _adjugate(G0[s])
+            W = adj / adj[:, 2:3, 2:3]
+            W[ref] = np.eye(3)
+            others = np.arange(n) != ref
+            if not (np.isfinite(G0[s]).all() and np.isfinite(Hl[s, counts]).all() and np.isfinite(det[others]).all() and (det[others] != 0).all() and np.isfinite(W).all()):
+                continue
+            edges, ok = [], True
+            for e in counts:
+                z, qz = _proj(Hl[s, e] / Hl[s, e, 2, 2], y)
+                ok = ok and bool((qz > 0).all())
+                edges.append((int(links[e, 0]), int(links[e, 1]), weight[s, e], y, z))
+            r, sw, _, ok_w = adjust_system_host(W, edges, ref, want_J=False)
+            cost = float((sw * r * r).sum())
+            work[s, :2] = cost
+            if not (ok and ok_w and np.isfinite(cost)):
+                continue
+            touched = np.zeros(n, bool)
+            for a, b, *_ in edges:
+                touched[a] = touched[b] = True
+            free = np.repeat(touched[others], 8)
+            lam, accepted, failed = lam0, 0, False
+            for _ in range(iters):
+                r, sw, J, _ = adjust_system_host(W, edges, ref)
+                A, g = J.T @ (sw[:, None] * J), J.T @ (sw * r)
+                A[np.diag_indices(N)] = np.where(free, np.diag(A) + lam * np.diag(A), 1.0)
+                try:
+                    if solver == "cholesky":
+                        L = np.linalg.cholesky(A)
+                        d = np.linalg.solve(L.T, np.linalg.solve(L, -g))
+                    else:
+                        d = np.linalg.solve(A, -g)
+                except np.linalg.LinAlgError:
+                    failed = True
+                    break
+                if not np.isfinite(d).all():
+                    failed = True
+                    break
+                trial = W.copy()
+                trial[others] = (W[others].reshape(-1, 9) + np.concatenate([d.reshape(n - 1, 8), np.zeros((n - 1, 1))], 1)).reshape(-1, 3, 3)
+                rt, _, _, ok_t = adjust_system_host(trial, edges, ref, want_J=False)
+                cost_t = float((sw * rt * rt).sum())
+                if np.isfinite(cost_t) and ok_t and cost_t < cost:
+                    W, cost, accepted, lam = trial, cost_t, accepted + 1, max(lam / 10.0, lam_min)
+                else:
+                    lam = min(lam * 10.0, lam_max)
+            work[s, 3] = lam
+            if failed or accepted == 0:
+                continue
+            adj, _ = _adjugate(W)
+            out = adj / adj[:, 2:3, 2:3]
+            out[ref] = np.eye(3)
+            if np.isfinite(out).all():
+                G[s], work[s, 1], work[s, 2] = out, cost, accepted
+    return G, work
 
 
 # ------------------------------------------------------------------------------------------------
@@ -889,6 +1045,15 @@ def _affine_dev(geom, inverse=False):
     return A
 
 
+def _inverse_device(M):
+    """M [...,3,3] float64 device tensor -> M^-1, the adjugate written out over the determinant, unguarded (torch.linalg.inv would
+    synchronise with the host)."""
+    a, b, c, d, e, f, g, h, i = (M[..., r, k] for r in range(3) for k in range(3))
+    adj = torch.stack([e * i - f * h, c * h - b * i, b * f - c * e, f * g - d * i, a * i - c * g, c * d - a * f, d * h - e * g, b * g - a * h, a * e - b * d], -1)
+    det = (a * adj[..., 0] + b * adj[..., 3]) + c * adj[..., 6]
+    return (adj / det[..., None]).reshape(M.shape)
+
+
 def _compose_device(left, delta, P, geom_b):
     """`_compose` on the device: left [B,3,3] float64, delta [B,4,2] float32, geom_b [B,4] float64 -> H [B,3,3] float64.  The 8 x 8 solve
     is bh_h4pt_fwd's (double), the rest batched [B,3,3] double arithmetic; nothing is copied to the host."""
@@ -943,6 +1108,17 @@ def cascade_compose_device(H_prev, delta, P, geom_b):
     """`cascade_compose` on the device: H_prev [B,3,3] float64, delta [B,4,2] float32, geom_b [B,4] float64 -> H [B,3,3] float64
     (`_compose_device`, left = H_prev A_b)."""
     return _compose_device(H_prev @ _affine_dev(geom_b), delta, P, geom_b)
+
+
+def _grid_map_device(gb, nx, ny):
+    """`grid_map` on the device, A_b S written out (no upload): geom_b [B,4] float64 -> [B,3,3], the sub-sample grid -> B's index
+    coordinates."""
+    G = _affine_dev(gb)
+    G[:, 0, 2] += G[:, 0, 0] * (0.5 / nx - 0.5)
+    G[:, 1, 2] += G[:, 1, 1] * (0.5 / ny - 0.5)
+    G[:, 0, 0] *= 1.0 / nx
+    G[:, 1, 1] *= 1.0 / ny
+    return G
 
 
 def _cascade_samples(samples, roi_b, Hb, Wb, P):
@@ -1272,6 +1448,81 @@ def pano_u8(images, idx, M, Hc, Wc, feather=32.0, mode="feather", gain=None, use
 
 
 # ------------------------------------------------------------------------------------------------
+# global adjustment, the device path
+# ------------------------------------------------------------------------------------------------
+def adjust_device(G0, links, H_links, weight, ref, size, grid=4, iters=10):
+    """bh_pano_adjust on G, work and a workspace allocated here (`adjust_host`): G0 [B,n,3,3] float64, links [E,2] int32 ON THE DEVICE,
+    H_links [B,E,3,3] float64, weight [B,E] float64 or None -> (G [B,n,3,3] float64, work [B,4] float64): one launch."""
+    _need_device(G0, links, H_links)
+    if G0.dim() != 4 or links.dim() != 2:
+        raise ValueError("adjust_device: G0 [B,n,3,3] float64 and links [E,2] int32, got %s and %s" % (tuple(G0.shape), tuple(links.shape)))
+    B, n, E = G0.shape[0], G0.shape[1], links.shape[0]
+    G = torch.empty((B, n, 3, 3), dtype=torch.float64, device=G0.device)
+    work = torch.empty((B, 4), dtype=torch.float64, device=G0.device)
+    ws = torch.empty((K.pano_adjust_ws_doubles(n, E, B),), dtype=torch.float64, device=G0.device)
+    return K.pano_adjust(G0.contiguous(), links.contiguous(), H_links.contiguous(), None if weight is None else weight.contiguous(), ref, size, grid, iters,
+                         G, work, ws)
+
+
+def _adjust_args(links, n, ref, grid, iters, who, pairs=()):
+    """The host-side rules of the adjustment, checked before any launch -> the links as a list of (a, b): every link is two distinct
+    frames of the sequence and none repeats one of `pairs` (in either order); 2 <= n <= 64, at most 1024 edges with the pairs, the grid in
+    2..8, iters >= 0."""
+    try:
+        out = [(operator.index(a), operator.index(b)) for a, b in links]
+    except (TypeError, ValueError):
+        raise ValueError("%s: links is a host list of (a, b) frame pairs, got %r" % (who, links)) from None
+    if not 2 <= n <= ADJUST_MAX_FRAMES:
+        raise ValueError("%s: the adjustment takes 2 <= n <= %d frames, got %d" % (who, ADJUST_MAX_FRAMES, n))
+    if not 1 <= len(out) + len(pairs) <= ADJUST_MAX_EDGES:
+        raise ValueError("%s: the adjustment takes 1..%d edges, got %d" % (who, ADJUST_MAX_EDGES, len(out) + len(pairs)))
+    taken = {frozenset(p) for p in pairs}
+    for a, b in out:
+        if not (0 <= a < n and 0 <= b < n and a != b):
+            raise ValueError("%s: a link is two distinct frames of the sequence, indices in [0, %d), got (%d, %d)" % (who, n, a, b))
+        if frozenset((a, b)) in taken:
+            raise ValueError("%s: the link (%d, %d) repeats a pair of the chain" % (who, a, b))
+    try:
+        ok = 2 <= operator.index(grid) <= 8 and operator.index(iters) >= 0 and 0 <= operator.index(ref) < n
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("%s: the adjustment's grid is an integer in 2..8, its iters an integer >= 0 and ref a frame in [0, %d), got %r, %r and %r"
+                         % (who, n, grid, iters, ref))
+    return out
+
+
+def adjust(G, links, H_links, size, ref, weight=None, grid=4, iters=10):
+    """The global adjustment for a caller who has the chain and the links from anywhere: G [B,n,3,3] float64 device tensor (the reference's
+    index coordinates -> frame k's, 2 <= n <= 64), links a HOST list of 1..1024 edges (a, b), two distinct frames each (range-checked here
+    and uploaded), H_links [B,E,3,3] float64 device tensor (b's index coordinates -> a's), size = (Hs, Ws) of the frames, ref the
+    reference frame, weight [B,E] float64 device tensor or None (an edge counts iff its weight is finite and > 0), grid the side of the
+    control lattice, iters the Levenberg-Marquardt steps (`adjust_host`) -> dict: 'G' [B,n,3,3] float64, 'adjust_stats' [B,4] float64
+    (cost at the start, cost at the result, accepted steps, final lambda).  ValueError before any launch for arguments outside these;
+    nothing is copied to the host."""
+    _need_device(G, H_links, name=False)
+    if G.dtype != torch.float64 or G.dim() != 4 or tuple(G.shape[2:]) != (3, 3):
+        raise ValueError("adjust: G [B,n,3,3] float64, got %s %s" % (G.dtype, tuple(G.shape)))
+    B, n = G.shape[:2]
+    edges = _adjust_args(links, n, ref, grid, iters, "adjust")
+    E = len(edges)
+    if H_links.dtype != torch.float64 or H_links.device != G.device or H_links.dim() < 3 or tuple(H_links.shape[:2]) != (B, E) or H_links.numel() != 9 * B * E:
+        raise ValueError("adjust: H_links [B,E,3,3] float64 on G's device with B = %d, E = %d, got %s %s" % (B, E, H_links.dtype, tuple(H_links.shape)))
+    if weight is not None and not (isinstance(weight, torch.Tensor) and weight.is_cuda and weight.dtype == torch.float64 and tuple(weight.shape) == (B, E)):
+        raise ValueError("adjust: weight is a [B,E] = [%d,%d] float64 device tensor or None" % (B, E))
+    try:
+        size_ok = len(size) == 2 and min(operator.index(v) for v in size) >= 2
+    except TypeError:
+        size_ok = False
+    if not size_ok:
+        raise ValueError("adjust: size is (Hs, Ws), at least 2 pixels on each side, got %r" % (size,))
+    with torch.cuda.device(G.device):
+        link = torch.tensor(edges, dtype=torch.int32).to(G.device)
+        out, work = adjust_device(G, link, H_links, weight, operator.index(ref), (int(size[0]), int(size[1])), operator.index(grid), operator.index(iters))
+    return {"G": out, "adjust_stats": work}
+
+
+# ------------------------------------------------------------------------------------------------
 # two-band blend, the device path
 # ------------------------------------------------------------------------------------------------
 def blur_u8(images, sigma, idx=None):
@@ -1442,7 +1693,7 @@ class Aligner:
 
     aligner(images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
             refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25, mosaic=None, mosaic_feather=32.0,
-            mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0, mosaic_band_sigma=4.0) -> dict
+            mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0, mosaic_band_sigma=4.0, init=None) -> dict
         images_*: uint8 [N,H,W,3] device tensors or ImageBanks; the two may differ in size.
         idx_*: which image each of the B samples uses (host list: range-checked; int32 device tensor: clamped by the kernel;
                None: sample b is image b, so B = N).
@@ -1470,6 +1721,12 @@ class Aligner:
         through 'H' as the model last saw it; 'delta_hat', 'patch_1', 'geom_*' stay stage 0's.  With refine="ecc" the refinement starts
         from the cascade's 'H', and 'H_model' is that matrix.  A cascade that is no integer >= 0, samples outside 1..8 and a
         cascade_min_cover outside [0, 1] raise a ValueError before any launch.
+    init=None (nothing below happens, the result is key for key and bit for bit the one above) or a [B,3,3] float64 device tensor, B's
+        index coordinates -> A's: the cascade (cascade >= 1 is required) starts from init instead of from the lift, and the model is not
+        run on the unwarped patches - for two images too far apart for the model (it is trained on displacements up to P / 4), whose
+        homography is known roughly from elsewhere, as a sequence's link between distant frames is from its chain.  Stage 0 of
+        'H_stages', 'score' and 'accepted' is init itself, 'delta_stages'[:, 0] and 'delta_hat' are zero, 'patch_1' is A seen through
+        init, and 'geom_a' is absent: A is not prepared on its own, so roi_a is refused.
     mosaic="b" or (Hc, Wc) (default None: nothing below happens, no further launch, the result is key for key and bit for bit the one
         above), mosaic_feather=32.0, mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0: from the final 'H' - after the cascade
         and the refinement - both images are put on one canvas by `mosaic` (bh_mosaic_u8, one pass): "b" is image B's grid, (Hc, Wc) the
@@ -1520,13 +1777,10 @@ class Aligner:
 
     def _cascade(self, predict, a, ia, p2, gb, H0, delta0, stages, nx, ny, min_cover):
         """The stages after the lift, all on the device: every sample runs every stage, a candidate replaces the best so far where its
-        score is higher on enough elements (torch.where; False for a NaN or -inf score).  -> the keys the cascade adds or replaces."""
+        score is higher on enough elements (torch.where; False for a NaN or -inf score).  -> (the keys the cascade adds or replaces, A
+        through H0 as the model's patch)."""
         B, P, dev = H0.shape[0], self.patch, H0.device
-        G = _affine_dev(gb)                                                    # `grid_map`, A_b S written out (no upload): sub-sample grid ->
-        G[:, 0, 2] += G[:, 0, 0] * (0.5 / nx - 0.5)                            # B's index coordinates
-        G[:, 1, 2] += G[:, 1, 1] * (0.5 / ny - 0.5)
-        G[:, 0, 0] *= 1.0 / nx
-        G[:, 1, 1] *= 1.0 / ny
+        G = _grid_map_device(gb, nx, ny)
         need = float(min_cover) * self.channels * P * P
 
         def seen(Hc):                                                          # A through Hc as the model's patch, and its score
@@ -1534,6 +1788,7 @@ class Aligner:
             return W, patch_ncc(W, p2, cov)
         H_best = H0
         W_best, o = seen(H_best)
+        W0 = W_best                                                            # (A through H0: `init=`'s patch_1)
         s_best = o[:, 6]
         Hs, deltas, scores, accepted = [H0], [delta0], [s_best], [torch.ones(B, dtype=torch.uint8, device=dev)]
         for _ in range(stages):
@@ -1547,13 +1802,18 @@ class Aligner:
             s_best = torch.where(take, o[:, 6], s_best)
             Hs.append(H_c); deltas.append(d); scores.append(o[:, 6]); accepted.append(take.to(torch.uint8))
         return {"H": H_best, "H_stages": torch.stack(Hs, 1), "delta_stages": torch.stack(deltas, 1), "score": torch.stack(scores, 1),
-                "accepted": torch.stack(accepted, 1), "patch_1_warped": W_best}
+                "accepted": torch.stack(accepted, 1), "patch_1_warped": W_best}, W0
 
     def __call__(self, images_a, images_b, idx_a=None, idx_b=None, roi_a=None, roi_b=None, warp=True, refine=None, refine_levels=3,
                  refine_iters=10, mask_b=None, cascade=0, cascade_samples=None, cascade_min_cover=0.25, mosaic=None, mosaic_feather=32.0,
-                 mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0, mosaic_band_sigma=4.0):
+                 mosaic_mode="feather", mosaic_exposure=None, mosaic_limit=2.0, mosaic_band_sigma=4.0, init=None):
         from .step import predict
         stages, samples = _stage_args(refine, cascade, cascade_min_cover, cascade_samples)
+        if init is not None:
+            if stages < 1:
+                raise ValueError("Aligner: init is where the cascade starts; pass cascade >= 1 with it")
+            if roi_a is not None:
+                raise ValueError("Aligner: with init image A is only seen through the homography; roi_a does not apply")
         a, b = _images(images_a, "images_a"), _images(images_b, "images_b")
         if a.device != b.device:
             raise ValueError("Aligner: images_a is on %s, images_b on %s" % (a.device, b.device))
@@ -1576,16 +1836,29 @@ class Aligner:
             canvas = _canvas_args("mosaic", mosaic, mosaic_feather, mosaic_mode, mosaic_limit, "Aligner")
             _band_args(mosaic_mode, mosaic_band_sigma, "mosaic", "Aligner", "mosaic_band_sigma")
             _mosaic_exposure_args(mosaic_exposure, B, a.shape[1:3], b.shape[1:3], "Aligner", "mosaic_exposure")
+        if init is not None and not (isinstance(init, torch.Tensor) and init.is_cuda and init.device == a.device and init.dtype == torch.float64
+                                     and tuple(init.shape) == (B, 3, 3)):
+            got = "%s %s on %s" % (init.dtype, tuple(init.shape), init.device) if isinstance(init, torch.Tensor) else repr(init)
+            raise ValueError("Aligner: init is a [B,3,3] = [%d,3,3] float64 tensor on the images' device (B's index coordinates -> A's), got %s" % (B, got))
         with torch.cuda.device(a.device):
-            p1, ga = prepare(a, B, P, self.channels, self.mean, self.std, idx=ia, roi=ra)
+            if init is None:
+                p1, ga = prepare(a, B, P, self.channels, self.mean, self.std, idx=ia, roi=ra)
             p2, gb = prepare(b, B, P, self.channels, self.mean, self.std, idx=ib, roi=rb)
-            # the patch square, for the heads that ask for it (NoOpHead '4_points', PhotometricHead.predict_homography)
-            delta_hat = predict(self.model, {self.patch_keys[0]: p1, self.patch_keys[1]: p2, "corners": self._corners(B, a.device)})
-            delta_hat = delta_hat.detach().reshape(B, 4, 2)
-            H = lift_device(delta_hat, P, ga, gb)
-            out = {"delta_hat": delta_hat, "H": H, "patch_1": p1, "patch_2": p2, "geom_a": ga, "geom_b": gb}
+            if init is None:
+                # the patch square, for the heads that ask for it (NoOpHead '4_points', PhotometricHead.predict_homography)
+                delta_hat = predict(self.model, {self.patch_keys[0]: p1, self.patch_keys[1]: p2, "corners": self._corners(B, a.device)})
+                delta_hat = delta_hat.detach().reshape(B, 4, 2)
+                H = lift_device(delta_hat, P, ga, gb)
+                out = {"delta_hat": delta_hat, "H": H, "patch_1": p1, "patch_2": p2, "geom_a": ga, "geom_b": gb}
+            else:                                                              # the cascade starts from init: no prediction on the unwarped patches
+                delta_hat = torch.zeros((B, 4, 2), dtype=torch.float32, device=a.device)
+                H = init.contiguous()
+                out = {"delta_hat": delta_hat, "H": H, "patch_2": p2, "geom_b": gb}
             if stages:
-                out.update(self._cascade(predict, a, ia, p2, gb, H, delta_hat, stages, nx, ny, cascade_min_cover))
+                added, seen_0 = self._cascade(predict, a, ia, p2, gb, H, delta_hat, stages, nx, ny, cascade_min_cover)
+                out.update(added)
+                if init is not None:
+                    out["patch_1"] = seen_0
                 H = out["H"]
             if refine is not None:
                 H, stats = ecc_refine(a, b, H, refine_levels, refine_iters, idx_a=ia, idx_b=ib, mask=mask_b)
@@ -1598,7 +1871,7 @@ class Aligner:
 
     def sequence(self, images, idx=None, ref=None, roi=None, refine=None, refine_levels=3, refine_iters=10, mask=None, cascade=0,
                  cascade_samples=None, cascade_min_cover=0.25, canvas=None, feather=32.0, mode="feather", exposure=None, limit=2.0, use=None,
-                 band_sigma=4.0):
+                 band_sigma=4.0, links=None, link_min_score=0.5, adjust_iters=10, adjust_grid=4):
         """Register a sequence of n frames (1 <= n <= 255) to one of them and, with a canvas, blend them all on it.
             images: one uint8 [N,Hs,Ws,3] device tensor or ImageBank; every frame has this size.
             idx: [B,n], frame k of sample b (host values: range-checked; int32 device tensor: clamped by the kernels; None: one sample
@@ -1614,11 +1887,25 @@ class Aligner:
         the device (0: the frame is left out of the blend and of the frame fit); exposure=None, "gain" (each pair's least-squares line of
         b's gray on a's through its H - one-level `gray_pyramid`, `ecc_sums`, `exposure_device`, counting the pixels `mask` allows -
         composed along the chain) or a [B,n,2] float64 device tensor (g, o) per frame.  mode="two_band" with band_sigma=4.0 is
-        `panorama`'s two-band blend (the low bank is made here, one launch) and adds 'panorama_winner'.  The chain accumulates every pair's error: it
-        drifts with n, and nothing here closes a loop.  Arguments outside these rules raise a ValueError before any launch; nothing is
-        copied to the host."""
+        `panorama`'s two-band blend (the low bank is made here, one launch) and adds 'panorama_winner'.
+        links=None, link_min_score=0.5, adjust_iters=10, adjust_grid=4: the chain accumulates every pair's error and drifts with n, so a
+        pan that comes back, an out-and-back sweep or a raster scan does not close.  links is a HOST list of further frame pairs (a, b)
+        that overlap (None or empty: nothing below happens, no further launch, the result is key for key and bit for bit the one above;
+        2 <= n <= 64 with links).  After the chain each link is predicted THROUGH the chain's own estimate - all B L links go through the
+        aligner in ONE call with init = G_a G_b^-1 (the 3 x 3 inverse written out as an adjugate), cascade=max(1, cascade), the same
+        refine arguments and warp=False - and a link COUNTS (weight 1) iff the correlation of A seen through its final H against
+        patch_2 (`prepare_warped` + `patch_ncc`) is at least link_min_score on at least cascade_min_cover C P P elements, decided on the
+        device by torch.where: two frames that do not overlap fail the cover test and simply drop out.  0.5 is a default, not a tuned
+        value.  Then `adjust_device` solves all frames jointly (`adjust_host`: adjust_iters Levenberg-Marquardt steps on an adjust_grid x
+        adjust_grid lattice of control points) from the edges - the chain's pairs with weight 1 followed by the links.  'G' is then the
+        adjusted one and the canvas and panorama keys follow from it; added: 'G_chain' (the chain's G), 'links' (the host list),
+        'link' (the link call's dict), 'H_links' [B,L,3,3] float64, 'link_score' [B,L] float64, 'link_weight' [B,L] float64,
+        'adjust_stats' [B,4] float64 (cost at the start, cost at the result, accepted steps, final lambda).  The exposure lines stay the
+        chain's: adjusting the gains over the links is out of scope.  Refused: links with n > 64, a link that is not two distinct
+        frames of the sequence or that repeats a pair of the chain, a link_min_score outside [-1, 1], adjust_iters < 0, a grid outside 2..8.
+        Arguments outside these rules raise a ValueError before any launch; nothing is copied to the host."""
         who = "Aligner.sequence"
-        _stage_args(refine, cascade, cascade_min_cover, cascade_samples)
+        stages, _ = _stage_args(refine, cascade, cascade_min_cover, cascade_samples)
         data = _images(images, "images")
         dev, (Hs, Ws) = data.device, data.shape[1:3]
         ix = _frames_index(idx, data.shape[0], dev, who)
@@ -1632,11 +1919,25 @@ class Aligner:
         if not 0 <= ref < n:
             raise ValueError("%s: ref is a frame of the sequence, an integer in [0, %d), got %r" % (who, n, ref))
         pairs = pairs_of(n, ref)
+        try:
+            links = [] if links is None else list(links)
+        except TypeError:
+            raise ValueError("%s: links is a host list of (a, b) frame pairs, got %r" % (who, links)) from None
+        if links:
+            links = _adjust_args(links, n, ref, adjust_grid, adjust_iters, who, pairs=pairs)
+            try:
+                score_ok = bool(-1.0 <= float(link_min_score) <= 1.0)          # (False for a NaN too)
+            except (TypeError, ValueError):
+                score_ok = False
+            if not score_ok:
+                raise ValueError("%s: link_min_score is a correlation in [-1, 1], got %r" % (who, link_min_score))
+        roi_links = roi
         if roi is not None:
             if not (isinstance(roi, torch.Tensor) and roi.is_cuda):           # (a device tensor is `_regions`' to refuse)
                 roi = np.asarray(roi.numpy() if isinstance(roi, torch.Tensor) else roi, np.float64)
                 if roi.shape not in ((4,), (B, 4)):
                     raise ValueError("%s: roi is (x0, y0, rw, rh) or [B,4] of them with B = %d, got shape %s" % (who, B, roi.shape))
+                roi_links = np.repeat(roi, len(links), axis=0) if roi.ndim == 2 else roi
                 if roi.ndim == 2:
                     roi = np.repeat(roi, n - 1, axis=0)                        # one region per sample -> one per pair
             _regions(roi, B * (n - 1), Hs, Ws, torch.device("cpu"), "roi")
@@ -1684,6 +1985,29 @@ class Aligner:
                     gain_pairs = torch.empty((B, 0, 2), dtype=torch.float64, device=dev)
             G, gain = chain_device(H_pairs, ref, gain_pairs)
             out.update({"G": G, "H_pairs": H_pairs})
+            if links:
+                L, la, lb = len(links), [a for a, _ in links], [b for _, b in links]
+                init = (G[:, la] @ _inverse_device(G[:, lb])).reshape(B * L, 3, 3)          # b's index coordinates -> a's, through the chain
+                init = (init / init[:, 2:3, 2:3]).contiguous()
+                ia, ib = ix[:, la].reshape(-1).contiguous(), ix[:, lb].reshape(-1).contiguous()
+                mask_b = None if mask is None or refine is None else mask[:, lb].reshape(B * L, Hs, Ws).contiguous()
+                r = self(data, data, idx_a=ia, idx_b=ib, roi_b=roi_links, warp=False, refine=refine, refine_levels=refine_levels,
+                         refine_iters=refine_iters, mask_b=mask_b, cascade=max(1, stages), cascade_samples=cascade_samples,
+                         cascade_min_cover=cascade_min_cover, init=init)
+                H_links = r["H"].reshape(B, L, 3, 3).contiguous()
+                # the link's score: A through its final H against patch_2, on the grid the cascade samples
+                nx, ny = _cascade_samples(cascade_samples, roi_links, Hs, Ws, self.patch)
+                seen, cover = prepare_warped(data, (r["H"] @ _grid_map_device(r["geom_b"], nx, ny)).contiguous(), B * L, self.patch, self.channels, nx, ny,
+                                             self.mean, self.std, idx=ia)
+                o = patch_ncc(seen, r["patch_2"], cover)
+                counts = (o[:, 6] >= float(link_min_score)) & (o[:, 0] >= float(cascade_min_cover) * self.channels * self.patch * self.patch)
+                link_weight = torch.where(counts, torch.ones_like(o[:, 6]), torch.zeros_like(o[:, 6])).reshape(B, L)
+                edges = torch.tensor(pairs + links, dtype=torch.int32).to(dev)
+                weight = torch.cat([torch.ones((B, n - 1), dtype=torch.float64, device=dev), link_weight], 1).contiguous()
+                G_adj, stats = adjust_device(G, edges, torch.cat([H_pairs, H_links], 1).contiguous(), weight, ref, (Hs, Ws), adjust_grid, adjust_iters)
+                out.update({"G_chain": G, "G": G_adj, "links": links, "link": r, "H_links": H_links, "link_score": o[:, 6].reshape(B, L).contiguous(),
+                            "link_weight": link_weight, "adjust_stats": stats})
+                G = G_adj
             if canvas is not None:
                 out.update(_panorama(data, ix, G, size, feather, mode, exposure if isinstance(exposure, torch.Tensor) else gain, use, limit, band_sigma))
         return out

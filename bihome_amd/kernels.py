@@ -1894,6 +1894,44 @@ def pano_u8(images, idx, M, out, count, feather, mode, gain=None, use=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# global adjustment: all frames of a sequence solved jointly from its edges (bihome_amd/align.py; csrc/adjust.hip).  Every buffer is the
+# caller's.
+# ------------------------------------------------------------------------------------------------
+ADJUST_MAX_FRAMES = 64                                                # include/bihome.h BH_ADJUST_MAX_FRAMES
+ADJUST_MAX_EDGES = 1024                                               # include/bihome.h BH_ADJUST_MAX_EDGES
+
+
+def pano_adjust_ws_doubles(n, E, B):
+    return _size_query(lib.bh_pano_adjust_ws_doubles, "bh_pano_adjust_ws_doubles", int(n), int(E), int(B))
+
+
+def pano_adjust(G0, link, H_links, weight, ref, size, grid, iters, G, work, ws):
+    """G [B,n,3,3] float64 = G0 [B,n,3,3] float64 after `iters` Levenberg-Marquardt steps on the edges link [E,2] int32 (a, b) with
+    H_links [B,E,3,3] float64 (b's index coordinates -> a's) and weight [B,E] float64 or None; size = (Hs, Ws) of the frames, grid the
+    control lattice's side; work [B,4] float64 = (cost at the start, cost at the result, accepted steps, final lambda); ws float64 with
+    pano_adjust_ws_doubles(n, E, B) elements (include/bihome.h bh_pano_adjust; bihome_amd.align.adjust_host).  G, work and ws are the
+    caller's (bihome_amd.align.adjust_device allocates them)."""
+    _chk(G0, torch.float64); _chk(H_links, torch.float64); _chk(weight, torch.float64); _chk(G, torch.float64); _chk(work, torch.float64)
+    _chk(ws, torch.float64); _chk(link, torch.int32)
+    if G0.dim() < 3 or not 2 <= G0.shape[1] <= ADJUST_MAX_FRAMES or G0.numel() != 9 * G0.shape[0] * G0.shape[1] or tuple(G.shape) != tuple(G0.shape):
+        raise ValueError("pano_adjust: G0 and G [B,n,3,3] float64 with 2 <= n <= %d, got %s and %s" % (ADJUST_MAX_FRAMES, tuple(G0.shape), tuple(G.shape)))
+    B, n = G0.shape[:2]
+    if link.dim() != 2 or link.shape[1] != 2 or not 1 <= link.shape[0] <= ADJUST_MAX_EDGES:
+        raise ValueError("pano_adjust: link [E,2] int32 with 1 <= E <= %d, got %s" % (ADJUST_MAX_EDGES, tuple(link.shape)))
+    E = link.shape[0]
+    if H_links.dim() < 3 or tuple(H_links.shape[:2]) != (B, E) or H_links.numel() != 9 * B * E or (weight is not None and tuple(weight.shape) != (B, E)):
+        raise ValueError("pano_adjust: H_links [B,E,3,3] and weight [B,E] float64 with B = %d, E = %d, got %s and %s"
+                         % (B, E, tuple(H_links.shape), None if weight is None else tuple(weight.shape)))
+    if tuple(work.shape) != (B, 4) or ws.numel() < pano_adjust_ws_doubles(n, E, B):
+        raise ValueError("pano_adjust: work [B,4] and ws of pano_adjust_ws_doubles() float64, got %s and %d elements" % (tuple(work.shape), ws.numel()))
+    if not 0 <= ref < n:
+        raise ValueError("pano_adjust: ref in [0, %d), got %r" % (n, ref))
+    check(lib.bh_pano_adjust(_p(G0), _p(link), _p(H_links), _p(weight), B, n, E, int(ref), int(size[0]), int(size[1]), int(grid), int(iters), _p(G),
+                             _p(work), _p(ws), _stream()), "bh_pano_adjust")
+    return G, work
+
+
+# ------------------------------------------------------------------------------------------------
 # two-band blend: the low band of uint8 frames, and the mosaic / panorama that blends it with the feather and takes the high band from one
 # frame per pixel (bihome_amd/align.py; csrc/blur.hip, and csrc/blend.hip's two walks with its band rule).  Every buffer is the caller's.
 # ------------------------------------------------------------------------------------------------

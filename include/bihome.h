@@ -1086,6 +1086,55 @@ int bh_mosaic_bands_u8(const uint8_t* images_a, const uint8_t* low_a, const int*
                        int B, int Hc, int Wc, float feather,
                        uint8_t* out, uint8_t* cover, uint8_t* winner, void* stream);
 
+/* Global adjustment: bh_pano_chain composes neighbouring pairs, so its error grows along the chain and a sequence that comes back to where it
+ * started does not close.  bh_pano_adjust solves all frames' homographies JOINTLY from a list of EDGES - the chain's pairs and any further
+ * links between frames that overlap - by Levenberg-Marquardt on the disagreement of the edges in the reference's pixels (the "global
+ * alignment" / "bundle adjustment of the homographies" step of stitching pipelines).  The numpy float64 statement is bihome_amd/align.py's
+ * adjust_host.  All arithmetic is double; one workgroup of 256 threads per sample, one launch, nothing read back by the host, no atomics.
+ *   G0[B,n,9]      the start: the reference's index coordinates -> frame k's, as bh_pano_chain makes it (2 <= n <= BH_ADJUST_MAX_FRAMES)
+ *   link[E,2]      int32 in DEVICE memory, the edges (a, b), one list for all samples (1 <= E <= BH_ADJUST_MAX_EDGES); an edge with
+ *                  a == b or an index outside [0, n) counts for nothing
+ *   Hlink[B,E,9]   b's index coordinates -> a's, used as H / H[8] (the pair convention)
+ *   weight[B,E]    NULL: all 1.  An edge COUNTS iff its weight is finite and > 0 (and its indices are two distinct frames)
+ *   Hs, Ws         the frame size (2 .. 2^24 each); grid: g in 2..8; iters >= 0 steps, every sample that starts runs all of them
+ *   G[B,n,9]       out; work[B,4] out: cost at the start, cost at the result, accepted steps, final lambda
+ *   ws             scratch of bh_pano_adjust_ws_doubles() doubles (written to HOST memory by that query): B (N + 1) N, the normal matrix
+ *                  with the right-hand side as its last row
+ * Unknowns: W_k = G_k^-1 (frame k -> reference) scaled to W[2,2] = 1; the 8 leading entries of every k != ref are free, W_ref = I is fixed:
+ * N = 8 (n - 1), frame k's columns at 8 (k < ref ? k : k - 1).  W_k of the start is adj(G0_k) / adj(G0_k)[2,2] with the adjugate written
+ * out.  Control points: y_p, p = j g + i, the g x g lattice x = (i (Ws - 1)) / (g - 1), y = (j (Hs - 1)) / (g - 1); for edge e,
+ * z_p = proj(H_e y_p).  Residual of edge e at point p: r = proj(W_a z_p) - proj(W_b y_p), where the two frames put one scene point in the
+ * reference; cost = sum_e w_e sum_p |r|^2.  With q = W (x, y, 1), (u, v) = (qx, qy) / qz the Jacobian of proj(W (x, y)) with respect to
+ * W[0..7] is bh_homography_refine_lm's: d u / d W0..2 = (x, y, 1) / qz, d u / d W6,7 = -(x, y) u / qz, zero for W3..5; d v likewise with
+ * W3..5 and v - taken at z_p for W_a and, negated, at y_p for W_b.  Columns of the reference do not exist.
+ * One step (bh_homography_refine_lm's rules and constants): solve (J^T W J + lambda diag(J^T W J)) d = -J^T W r, a dense N x N system, by
+ * Cholesky; a frame that no counting edge touches has a zero diagonal and gets unit rows (diagonal 1, right-hand side 0), so it does not
+ * move; trial = W + d.  The trial is ACCEPTED iff its cost is finite, every point of every counting edge has qz > 0 under the link and
+ * under both of its matrices at the trial, and cost(trial) < cost - then W = trial and lambda = max(lambda / 10, 1e-12); otherwise W stays
+ * and lambda = min(10 lambda, 1e12).  lambda starts at 1e-3.
+ * A sample KEEPS ITS START - G = G0 copied bit for bit, both costs the start's, zero accepted steps - when
+ *   - an entry of G0 or of a counting Hlink is not finite; a G0_k, k != ref, is singular: the determinant by the adjugate's first column,
+ *     (a adj00 + b adj10) + c adj20, is 0 or not finite, or an entry of adj / adj[2,2] is not finite (then both costs are NaN and no step is
+ *     tried);
+ *   - a counting point has qz <= 0 at the start, or the start's cost is not finite (both costs are that sum, and no step is tried);
+ *   - a Cholesky pivot of any of its steps is not > 0, or a component of d is not finite (the steps end there);
+ *   - no step is accepted, or an entry of the result is not finite.
+ * Otherwise G_k = adj(W_k) / adj(W_k)[2,2] and G_ref = I exactly.
+ * Orders of summation.  A matrix entry: over the counting edges in index order, each edge's term w_e t, t = sum over p ascending of
+ * (jx_r jx_c + jy_r jy_c), products rounded before they are added; the right-hand side likewise with (jx_r rx + jy_r ry).  The cost: thread
+ * t sums w_e s_e over its edges e = t, t + 256, .. with s_e = sum over p ascending of (rx^2 + ry^2), and the 256 partial sums are added
+ * pairwise, [i] += [i + h] for h = 128, 64, .. 1.  The factorisation is a right-looking Cholesky in blocks of 8 with the right-hand side as row
+ * N (the forward substitution), then L^T d = y backwards in blocks of 8; an entry takes its subtractions as fused multiply-adds, the
+ * columns of a block ascending, block after block.  One workgroup per sample, no atomics: two calls agree bit for bit, and a sample's
+ * result does not depend on its neighbours.
+ * BH_E_BADARG: NULL G0 / link / Hlink / G / work / ws (doubles for the query), a negative B, n outside 2..64, E outside 1..1024, ref outside
+ * [0, n), Hs or Ws outside 2..2^24, grid outside 2..8, iters < 0; then B == 0: BH_OK, nothing launched.  Refusals come before any launch. */
+#define BH_ADJUST_MAX_FRAMES 64
+#define BH_ADJUST_MAX_EDGES 1024
+int bh_pano_adjust_ws_doubles(int n, int E, int B, int64_t* doubles);
+int bh_pano_adjust(const double* G0, const int* link, const double* Hlink, const double* weight, int B, int n, int E, int ref, int Hs, int Ws,
+                   int grid, int iters, double* G, double* work, double* ws, void* stream);
+
 /* MaxPool2d(3, 2, 1) NHWC. argmax[N,Ho,Wo,C] (uint8, NULL ok in inference): window position 0..8 of the first
  * maximum (ATen's tie rule); the adjoint gathers through it (no atomics, no recomputation).
  * BH_E_BADARG: a NULL x / y (gy / gx / argmax in the adjoint), N < 0, Hi < 1, Wi < 1, C < 4; BH_E_UNSUPPORTED: C % 4; N == 0: BH_OK, nothing launched. */
